@@ -28,8 +28,10 @@ No collective on the data path.  At N=1 the same shard workload (with a world-si
 as the `batched_c4_shard` sub-object (detail file; `side.c4_*` on the line), the like-for-like base of the 1 -> 8 curve: the N=1 line
 carries it at top level as `scale_base` {workload, value, ms_per_step}, the N>1 lines carry `per_gpu_value` (= value / N).
 
-Timed region: K steps bracketed by barrier + torch.cuda.synchronize() on both sides, `--blocks` (5) times over; every block's time is
-the MAX over ranks; ms_per_step is the MEDIAN block (min / max / first block ride along).
+Timed region: exactly K steps, split into `--blocks` (5, at most K) blocks, each bracketed by barrier + torch.cuda.synchronize() on both
+sides; every block's time is the MAX over ranks; ms_per_step is the MEDIAN block's time per step (min / max / first block ride along).
+--dump-outputs DIR writes what the last timed step returned (N=1: the pose and summary of clc_solve; N>1: the gathered result records)
+as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 `roofline` is the dominant kernel of the timed region.  Both whole-solve kernels (coop_solve_kernel at C2, resident_solve_kernel
 at C4) read the data from HBM once per SOLVE and are bound by FP64 VALU issue / latency: their object has "bound": "valu_f64"
@@ -146,13 +148,44 @@ def parse():
                          "with torch.distributed instead of clc_gather_results)")
     ap.add_argument("--detail-file", default=None, help="where the full result goes (default: bench_detail.json beside bench.py)")
     ap.add_argument("--blocks", type=int, default=5,
-                    help="the K-step timed region is repeated this many times (each bracketed by barrier + synchronize, max over ranks); "
-                         "ms_per_step is the median block")
+                    help="the K timed steps are split into this many blocks (at most K; each bracketed by barrier + synchronize, max over "
+                         "ranks); ms_per_step is the median block's time per step")
     ap.add_argument("--two-call-step", action="store_true",
                     help="C4 step as clc_solve_batched + clc_gather_results (the round-4 form) instead of the one-call clc_solve_batched_gather")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="testing only: map ranks onto the visible GPUs modulo their count (with --backend gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): N=1 pose.npy [7] "
+                         "and summary.npy [termination, iterations, successful steps, unsuccessful steps, evaluations, initial cost, "
+                         "final cost]; N>1 records.npy [problems, 12] (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def block_sizes(steps, blocks):
+    """The timed region runs exactly `steps` steps, split into min(blocks, steps) blocks whose sizes differ by at most one."""
+    n = max(1, min(blocks, steps))
+    return [steps // n + (1 if b < steps % n else 0) for b in range(n)]
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy in float64.  An array past the 64 MB budget is replaced by a fixed, seeded sample of its
+    rows, and the sampled row indices go to <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        budget = DUMP_LIMIT_BYTES // len(arrays)
+        if a.nbytes > budget:
+            keep = max(1, budget // (a.nbytes // a.shape[0] + 8))  # (8 bytes: the row's index)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 C4_SEED = 65536
@@ -290,10 +323,10 @@ def coop_kernel_report(clc, solver, x0, n_obs, n_scans):
     return rep
 
 
-def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_rccl=True):
+def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_rccl=True, outputs=None):
     """BASELINE.json configs[3] on this rank: generate problems [lo, hi) of the 8 192 x world batch, keep them resident,
     then time `steps` x (clc_solve_batched + RCCL all-gather of every rank's result records).
-    Returns the dict rank 0 reports (None on other ranks)."""
+    Returns the dict rank 0 reports (None on other ranks); on rank 0, `outputs` (a dict) receives the last step's records."""
     import camlasercalibratool_amd as clc
     from camlasercalibratool_amd import dist as cdist, simdata as sd
 
@@ -346,17 +379,18 @@ def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_
     for _ in range(warmup):
         step()
     finish(None)
-    # the timed region: `steps` steps bracketed by barrier + synchronize on both sides, `blocks` times over; every block's time is
-    # the MAX over ranks, ms_per_step the median block
+    # the timed region: `steps` steps in blocks (block_sizes), each bracketed by barrier + synchronize on both sides; every block's
+    # time is the MAX over ranks, ms_per_step the median block's time per step
+    sizes = block_sizes(steps, args.blocks)
     block_s = []
-    for _ in range(max(1, args.blocks)):
+    for n in sizes:
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(n):
             out = step()
         out = finish(out)
         barrier()
-        block_s.append(time.perf_counter() - t0)
+        block_s.append((time.perf_counter() - t0) / n)
     per = args.shard_poses * args.shard_pts
     if fused:  # the shard's totals came back with the records (clc_batch_stats)
         evals_step, iters_step = float(ss.last_stats.evaluations) * per, float(ss.last_stats.iterations)
@@ -372,13 +406,14 @@ def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         block_s, evals_step, iters_step = [float(v) for v in tmax], float(t[0]), float(t[1])
-    elapsed = float(np.median(block_s))
+    dt = float(np.median(block_s))  # seconds per step
     res = None
     ci = ss.comm.info() if ss.comm is not None else None
     if rank == 0:
         raw = np.array(out).reshape(-1, 12)
         full = cdist.order_records(raw, n_total)
-        dt = elapsed / steps
+        if outputs is not None:
+            outputs["records"] = full
         shards = [list(cdist.shard_problems(n_total, r, world)) for r in range(world)]
         its = full[:, 9]
         res = {
@@ -387,7 +422,7 @@ def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_
                         f"x{world} GPUs = {n_total} problems; step = solve of the shard + RCCL all-gather of all {n_total} result records",
             "problems": n_total, "problems_per_gpu": args.problems_per_gpu, "observations_per_gpu": n_obs_local,
             "record_bytes_per_gpu": 64 * n_obs_local,
-            "ms_per_step": 1e3 * dt, "ms_per_step_blocks": [1e3 * b / steps for b in block_s],
+            "ms_per_step": 1e3 * dt, "ms_per_step_blocks": [1e3 * b for b in block_s], "timed_steps": steps,
             "problems_per_s": n_total / dt, "evals_per_s": evals_step / dt,
             "lm_iters_per_s": iters_step / dt,
             "lm_iterations_min_max": [int(its.min()), int(its.max())],
@@ -662,8 +697,11 @@ def main():
 
     if world > 1:
         # ---- N>1: the C4 workload (sharded batch + RCCL gather); see run_c4_shard ----
-        c4 = run_c4_shard(args, torch, dist, rank, world, local_rank, args.steps, args.warmup, use_rccl=(args.backend == "nccl"))
+        dumped = {}
+        c4 = run_c4_shard(args, torch, dist, rank, world, local_rank, args.steps, args.warmup, use_rccl=(args.backend == "nccl"), outputs=dumped)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, dumped)
             out = {
                 "metric": "residual+Jacobian evals/s (batched LM solves, 8192 independent 1e4-obs point-to-plane problems per GPU, RCCL gather)",
                 "value": c4["evals_per_s"], "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -707,20 +745,23 @@ def main():
 
     for _ in range(args.warmup):
         res = solver.solve(x0, opt, trace_cap=0)
-    # the timed region: K solves bracketed by barrier + synchronize on both sides, `blocks` times over (at the driver's --steps 20
-    # one block is under 2 ms of wall time: a single scheduler hiccup would move it by percent); ms_per_step = the median block
+    # the timed region: K solves in blocks (block_sizes), each bracketed by barrier + synchronize on both sides (a short block is a
+    # few ms of wall time: a single scheduler hiccup would move it by percent); ms_per_step = the median block's time per solve
     block_ms, evals, iters = [], 0, 0
-    for _ in range(max(1, args.blocks)):
+    for n in block_sizes(args.steps, args.blocks):
         barrier()
         t0 = time.perf_counter()
-        evals = iters = 0
-        for _ in range(args.steps):
+        for _ in range(n):
             res = solver.solve(x0, opt, trace_cap=0)  # no iteration trace: nothing forces a stream sync
             evals += res.summary.num_evaluations * n_obs
             iters += res.summary.num_iterations
         barrier()
-        block_ms.append(1e3 * (time.perf_counter() - t0) / args.steps)
+        block_ms.append(1e3 * (time.perf_counter() - t0) / n)
     elapsed_max, evals_total, iters_total = 1e-3 * float(np.median(block_ms)) * args.steps, float(evals), float(iters)  # one rank
+    if rank == 0 and args.dump_outputs:  # what the caller of clc_solve received from the last timed step (solve_ms etc. are timings: left out)
+        sm = res.summary
+        dump_outputs(args.dump_outputs, {"pose": res.pose, "summary": [sm.termination, sm.num_iterations, sm.num_successful_steps,
+                                                                      sm.num_unsuccessful_steps, sm.num_evaluations, sm.initial_cost, sm.final_cost]})
 
     out = None
     hs = None

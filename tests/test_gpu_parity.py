@@ -803,38 +803,68 @@ def test_bench_two_rank_path_dry_run(tmp_path):
     assert "scale_base" in full["scale_base_field"]
 
 
-def test_bench_eight_rank_path_uneven_shards_dry_run(tmp_path):
-    """What C4 looks like on 8 ranks, through bench.py's own N>1 path: 8 processes (oversubscribing the one visible GPU, gloo
-    process group), a problem count that 8 does not divide — shards of 13 and 12 problems, padding records in the gather —
-    and the rank-major gathered buffer put back into global order by bench.py (order_records).  Launched the way the driver launches
-    N>1: python -m torch.distributed.run ... bench.py --gpus 8."""
+def test_bench_one_gpu_dump_outputs(tmp_path, oracle_mod):
+    """bench.py --gpus 1 runs exactly --steps timed solves and --dump-outputs writes what the last one returned: the same seeded
+    problem gives the same outputs in two runs, and they are the oracle's solve of that problem."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for k in range(2):
+        dump = tmp_path / f"outputs{k}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--poses", "40", "--pts", "100",
+               "--no-cpu-baseline", "--no-cold-start", "--no-c4-shard", "--no-batched", "--large-obs", "0",
+               "--detail-file", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert json.load(open(tmp_path / "detail.json"))["timed_blocks"] == 3  # 3 steps in all: blocks of one
+        outs.append({n: np.load(dump / f"{n}.npy") for n in ("pose", "summary")})
+    assert outs[0]["pose"].shape == (7,) and outs[0]["summary"].shape == (7,) and outs[0]["pose"].dtype == np.float64
+    assert all(np.array_equal(outs[0][n], outs[1][n]) for n in ("pose", "summary"))
+    rec = clc.flatten_observations(sd.sim_fixed_count(1000, 40, 100, noise_sigma=0.01), use_linefitting_data=False)
+    ref = oracle_mod.solve(rec, sd.pose7_from_T(np.eye(4)), linear_solver="qr")
+    assert _dT(outs[0]["pose"], ref.pose) <= T_TOL and abs(outs[0]["summary"][6] - ref.summary.final_cost) <= COST_TOL
+    assert outs[0]["summary"][1] == ref.summary.num_iterations
+
+
+def test_bench_four_rank_path_uneven_shards_dry_run(tmp_path):
+    """What C4 looks like on several ranks, through bench.py's own N>1 path: 4 processes (oversubscribing the one visible GPU, gloo
+    process group; with this test's own process that is 5 processes holding the GPU, fewer than a shared machine allows), a problem
+    count that 4 does not divide — shards of 13 and 12 problems, padding records in the gather — and the rank-major gathered buffer
+    put back into global order by bench.py (order_records).  Launched the way the driver launches N>1: python -m torch.distributed.run
+    ... bench.py --gpus 4.  --dump-outputs writes the ordered records of the last timed step."""
     import json, os, socket, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     detail = str(tmp_path / "detail.json")
+    dump = tmp_path / "outputs"
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--blocks", "1",
-           "--backend", "gloo", "--oversubscribe", "--problems-total", "100", "--problems-per-gpu", "13", "--shard-poses", "6",
-           "--shard-pts", "100", "--detail-file", detail]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--blocks", "1",
+           "--backend", "gloo", "--oversubscribe", "--problems-total", "50", "--problems-per-gpu", "13", "--shard-poses", "6",
+           "--shard-pts", "100", "--detail-file", detail, "--dump-outputs", str(dump)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 4096
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["value"] > 0
+    assert d["n_gpus"] == 4 and d["scaling"] == "weak" and d["value"] > 0
     c4 = json.load(open(detail))["batched_c4_shard"]
     g = c4["gather"]
-    assert c4["problems"] == 100
-    assert g["shard_sizes"] == [13, 13, 13, 13, 12, 12, 12, 12] and g["records_per_rank"] == 13
-    assert g["first_global_index_per_rank"] == [0, 13, 26, 39, 52, 64, 76, 88]
-    assert g["padding_records"] == 8 * 13 - 100
-    assert g["first_record_index_of_each_rank_block"] == [0.0, 13.0, 26.0, 39.0, 52.0, 64.0, 76.0, 88.0]
+    assert c4["problems"] == 50 and c4["timed_steps"] == 2
+    assert g["shard_sizes"] == [13, 13, 12, 12] and g["records_per_rank"] == 13
+    assert g["first_global_index_per_rank"] == [0, 13, 26, 38]
+    assert g["padding_records"] == 4 * 13 - 50
+    assert g["first_record_index_of_each_rank_block"] == [0.0, 13.0, 26.0, 38.0]
     first, last = c4["first_and_last_record"]
-    assert first[11] == 0.0 and last[11] == 99.0
+    assert first[11] == 0.0 and last[11] == 49.0
     assert c4["max_abs_T_err_vs_ground_truth_sampled"] < 0.05 and c4["T_cl_max_abs_err_vs_oracle_sample"] <= T_TOL
     assert g["rccl_ranks"] is None  # (gloo dry run; with --backend nccl bench.py asserts rccl_ranks == WORLD_SIZE)
+    rec = np.load(dump / "records.npy")
+    assert rec.dtype == np.float64 and rec.shape == (50, 12) and np.array_equal(rec[:, 11], np.arange(50))
+    assert rec[0].tolist() == first and rec[-1].tolist() == last
 
 
 def test_rccl_world1_sharded_solve_through_the_c_abi(sv, oracle_mod):

@@ -6,8 +6,8 @@ tests/golden/ref_vectors.json holds outputs of the reference's translation units
 the build container (tests/golden/make_ref_golden.py).  Three layers:
 
   * oracle  vs the committed vectors     (CPU, always)           — pins the checker;
-  * oracle  vs libref.so live            (CPU, when oracle/_ref/libref.so exists or can be built:
-                                          fresh random inputs, not just the frozen ones);
+  * oracle  vs libref.so live            (CPU: the frozen cases of golden/ref_live_vectors.npz always, and fresh random
+                                          inputs too when oracle/_ref/libref.so exists or can be built);
   * HIP path vs the committed vectors    (-m gpu, through the C-ABI) — no oracle in the loop.
 
 What this pins: the factor + Jacobian, Plus, pi_from_ppp, TranScanToPoints (exact code paths), the
@@ -143,18 +143,41 @@ def test_sim_generator_and_whole_reference_program(oracle_mod, case):
 
 
 # ------------------------------------------------------------------------------------------
-# oracle vs the reference library, live (fresh inputs)
+# oracle vs the reference library: the frozen cases of tests/golden/ref_live_vectors.npz (make_ref_live_golden.py) always,
+# and fresh random inputs too when the library is at hand
 # ------------------------------------------------------------------------------------------
+LIVE = np.load(os.path.join(HERE, "golden", "ref_live_vectors.npz"))
+
+
 @pytest.fixture(scope="module")
 def ref_mod():
+    """oracle.ref when oracle/_ref/libref.so exists or can be built, else None (the frozen cases alone)."""
     import oracle.ref as ref
 
-    if not ref.available():
-        pytest.skip("oracle/_ref/libref.so not present and /root/reference not available to build it")
-    return ref
+    return ref if ref.available() else None
+
+
+def _raises(fn):
+    try:
+        fn()
+    except IndexError:
+        return True
+    return False
+
+
+def _check_elementwise(oracle_mod, plane, pt, s, pose, d, abc, r1, j1, plus1, pi1):
+    r0, j0 = oracle_mod.factor_evaluate(plane, pt, s, pose)
+    assert abs(r0 - r1) <= 1e-14 * max(1.0, abs(r1)) and np.allclose(j0, j1, rtol=1e-14, atol=1e-15)
+    assert np.allclose(oracle_mod.pose_plus(pose, d), plus1, rtol=1e-15, atol=1e-16)
+    assert np.allclose(oracle_mod.pi_from_ppp(*abc), pi1, rtol=1e-15, atol=1e-16)
 
 
 def test_live_reference_elementwise(oracle_mod, ref_mod):
+    for i in range(LIVE["el_plane"].shape[0]):
+        _check_elementwise(oracle_mod, *(LIVE["el_" + k][i] for k in ("plane", "point", "scale", "pose", "delta", "abc", "residual", "jacobian",
+                                                                      "plus", "pi")))
+    if ref_mod is None:
+        return
     rng = np.random.default_rng(int.from_bytes(os.urandom(4), "little"))
     for _ in range(300):
         n = rng.normal(size=3)
@@ -163,54 +186,72 @@ def test_live_reference_elementwise(oracle_mod, ref_mod):
         s = rng.uniform(0.02, 1.0)
         q = rng.normal(size=4)
         pose = np.r_[rng.normal(size=3), q / np.linalg.norm(q)]
-        r0, j0 = oracle_mod.factor_evaluate(plane, pt, s, pose)
-        r1, j1 = ref_mod.factor_evaluate(plane, pt, s, pose)
-        assert abs(r0 - r1) <= 1e-14 * max(1.0, abs(r1)) and np.allclose(j0, j1, rtol=1e-14, atol=1e-15)
         d = rng.normal(size=6) * 10.0 ** rng.uniform(-8, 0)
-        assert np.allclose(oracle_mod.pose_plus(pose, d), ref_mod.pose_plus(pose, d), rtol=1e-15, atol=1e-16)
-        a, b, c = rng.normal(size=(3, 3))
-        assert np.allclose(oracle_mod.pi_from_ppp(a, b, c), ref_mod.pi_from_ppp(a, b, c), rtol=1e-15, atol=1e-16)
+        abc = rng.normal(size=(3, 3))
+        r1, j1 = ref_mod.factor_evaluate(plane, pt, s, pose)
+        _check_elementwise(oracle_mod, plane, pt, s, pose, d, abc, r1, j1, ref_mod.pose_plus(pose, d), ref_mod.pi_from_ppp(*abc))
 
 
-def test_live_reference_whole_functions(oracle_mod, ref_mod):
-    seed = int.from_bytes(os.urandom(2), "little")
+def _check_whole_functions(oracle_mod, seed, Tcl, iterations, blocks, Tlc_closed, boundary_raises, Tcl_edges, iterations_edges, blocks_edges):
     S = sd.GenerateSimData(seed, noise_sigma=0.01)
     rec = oracle_mod.flatten(S, False, False)
     r = oracle_mod.solve(rec, sd.pose7_from_T(np.eye(4)))
-    Tcl, record, nb = ref_mod.calibration(S, np.eye(4), False, False)
-    assert nb == rec.shape[0] and record["num_iterations"] == r.summary.num_iterations, f"seed {seed}"
+    assert blocks == rec.shape[0] and iterations == r.summary.num_iterations, f"seed {seed}"
     assert np.abs(Tcl - sd.T_from_pose7(r.pose)).max() < 1e-12, f"seed {seed}"
     T, _, _ = oracle_mod.closed_form(oracle_mod.flatten(S, True, False))
-    assert np.abs(T - ref_mod.closed_solution(S)).max() < 1e-10, f"seed {seed}"
+    assert np.abs(T - Tlc_closed).max() < 1e-10, f"seed {seed}"
     # boundary mode on the raw simulation: a pose with an empty scan makes the reference throw
     # std::out_of_range at obi.points.at(0) (:278); the oracle must fail on exactly the same inputs
-    def raises(fn):
-        try:
-            fn()
-        except IndexError:
-            return True
-        return False
-    assert raises(lambda: ref_mod.calibration(S, np.eye(4), True, True)) == raises(lambda: oracle_mod.flatten(S, True, True)), f"seed {seed}"
-    S0 = sd.GenerateSimData(0, noise_sigma=0.0)  # known to contain empty scans
-    assert raises(lambda: ref_mod.calibration(S0, np.eye(4), True, True)) and raises(lambda: oracle_mod.flatten(S0, True, True))
+    assert bool(boundary_raises) == _raises(lambda: oracle_mod.flatten(S, True, True)), f"seed {seed}"
     Sb = sd.sim_board_edges(seed, 30, 40, noise_sigma=0.002)
-    x0 = oracle_mod.pose_plus(sd.pose7_from_T(sd.tlc_to_tcl(sd.GT_RLC, sd.GT_TLC)), np.array([0.03, -0.02, 0.03, 0.04, -0.03, 0.02]))
     recb = oracle_mod.flatten(Sb, True, True)
-    rb = oracle_mod.solve(recb, x0)
-    Tb, recordb, nbb = ref_mod.calibration(Sb, sd.T_from_pose7(x0), True, True)
-    assert nbb == recb.shape[0] and recordb["num_iterations"] == rb.summary.num_iterations, f"seed {seed}"
-    assert np.abs(Tb - sd.T_from_pose7(rb.pose)).max() < 1e-12, f"seed {seed}"
+    rb = oracle_mod.solve(recb, _edges_x0(oracle_mod))
+    assert blocks_edges == recb.shape[0] and iterations_edges == rb.summary.num_iterations, f"seed {seed}"
+    assert np.abs(Tcl_edges - sd.T_from_pose7(rb.pose)).max() < 1e-12, f"seed {seed}"
 
 
-def test_live_reference_simulation_program(oracle_mod, ref_mod):
-    seed = int.from_bytes(os.urandom(3), "little") + 1
-    q, t, cnt, pts = ref_mod.generate_sim_data(seed)
+def _edges_x0(oracle_mod):
+    return oracle_mod.pose_plus(sd.pose7_from_T(sd.tlc_to_tcl(sd.GT_RLC, sd.GT_TLC)), np.array([0.03, -0.02, 0.03, 0.04, -0.03, 0.02]))
+
+
+def test_live_reference_whole_functions(oracle_mod, ref_mod):
+    keys = ("seed", "Tcl", "iterations", "blocks", "Tlc_closed", "boundary_raises", "Tcl_edges", "iterations_edges", "blocks_edges")
+    for i in range(LIVE["wf_seed"].shape[0]):
+        c = {k: LIVE["wf_" + k][i] for k in keys}
+        c.update(seed=int(c["seed"]), iterations=int(c["iterations"]), blocks=int(c["blocks"]), iterations_edges=int(c["iterations_edges"]),
+                 blocks_edges=int(c["blocks_edges"]))
+        _check_whole_functions(oracle_mod, **c)
+    S0 = sd.GenerateSimData(0, noise_sigma=0.0)  # known to contain empty scans
+    assert LIVE["wf_s0_boundary_raises"] == 1.0 and _raises(lambda: oracle_mod.flatten(S0, True, True))
+    if ref_mod is None:
+        return
+    seed = int.from_bytes(os.urandom(2), "little")
+    S = sd.GenerateSimData(seed, noise_sigma=0.01)
+    Tcl, record, nb = ref_mod.calibration(S, np.eye(4), False, False)
+    Tb, recordb, nbb = ref_mod.calibration(sd.sim_board_edges(seed, 30, 40, noise_sigma=0.002), sd.T_from_pose7(_edges_x0(oracle_mod)), True, True)
+    _check_whole_functions(oracle_mod, seed, Tcl, record["num_iterations"], nb, ref_mod.closed_solution(S),
+                           _raises(lambda: ref_mod.calibration(S, np.eye(4), True, True)), Tb, recordb["num_iterations"], nbb)
+    assert _raises(lambda: ref_mod.calibration(S0, np.eye(4), True, True))
+
+
+def _check_simulation_program(oracle_mod, seed, q, t, cnt, pts, P):
     S = sd.points_from_tag_poses(sd.quat_wxyz_to_rot(q), t)
     assert np.array_equal(np.diff(S.pts_off), cnt), f"seed {seed}"
     assert np.abs(S.pts - pts).max() < 1e-12, f"seed {seed}"
-    P = ref_mod.parse_simulation_tlc(ref_mod.simulation_program(seed))
     r = oracle_mod.solve(oracle_mod.flatten(S, False, False), sd.pose7_from_T(np.eye(4)))
     assert np.abs(np.linalg.inv(sd.T_from_pose7(r.pose)) - P).max() < 1e-5, f"seed {seed}"
+
+
+def test_live_reference_simulation_program(oracle_mod, ref_mod):
+    off = np.r_[0, np.cumsum(LIVE["sim_counts"].sum(axis=1))].astype(np.int64)
+    for i in range(LIVE["sim_seed"].shape[0]):
+        _check_simulation_program(oracle_mod, int(LIVE["sim_seed"][i]), LIVE["sim_tag_q_wxyz"][i], LIVE["sim_tag_t"][i],
+                                  LIVE["sim_counts"][i].astype(np.int64), LIVE["sim_points"][off[i]:off[i + 1]], LIVE["sim_Tlc_printed"][i])
+    if ref_mod is None:
+        return
+    seed = int.from_bytes(os.urandom(3), "little") + 1
+    q, t, cnt, pts = ref_mod.generate_sim_data(seed)
+    _check_simulation_program(oracle_mod, seed, q, t, cnt, pts, ref_mod.parse_simulation_tlc(ref_mod.simulation_program(seed)))
 
 
 # ------------------------------------------------------------------------------------------
