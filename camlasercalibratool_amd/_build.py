@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("CLC_LIBRARY") or PRODUCT_LIB_PATH  # CLC_LIBRARY: run
 UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_comm.hip", "abi_debug.hip"]
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp"]
-SOURCES = UNITS + HEADERS
+HOST_HEADERS = ["abi_drive.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
+SOURCES = UNITS + HEADERS + HOST_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the
 # same device functions — the step kernel and the [eval, lm] launch pair then differed in the last bits on 1 of 60
@@ -36,7 +37,8 @@ def csrc_sha16() -> str:
     """Identity of what the KERNELS are built from: sha256 over the bytes of every csrc header (HEADERS order: all device code lives in
     the .hpp files; the abi_*.hip units are the host side — launchers, checks, RCCL calls) and the compiler flags.  Constants that were
     measured on a build (the VALU instruction counts bench.py prices the whole-solve kernels with, profiles/valu_counts.json) carry
-    it, and bench.py refuses them when it differs from the sources in the tree."""
+    it, and bench.py refuses them when it differs from the sources in the tree.  HOST_HEADERS are left out: they hold host code only
+    (launch drivers), which no kernel is built from, so editing them leaves the measured constants valid."""
     import hashlib
     h = hashlib.sha256()
     for s in HEADERS:

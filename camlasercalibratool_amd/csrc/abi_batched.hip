@@ -1,6 +1,6 @@
 // abi_batched.hip — clc_solve_batched: many independent problems per launch (resident kernel, whole-solve kernel, lockstep launches).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "clc_abi_internal.hpp"
+#include "abi_drive.hpp"
 
 using namespace clc_abi;
 
@@ -69,59 +69,24 @@ int batched_launch_setup(clc_handle* h, const clc_options& /*opt*/, BatchedLaunc
 }
 
 void launch_batched_eval(clc_handle* h, const clc_options& opt, const BatchedLaunch& bl) {
-  const size_t n_blocks = bl.n_blocks;
+  const unsigned n_blocks = (unsigned)bl.n_blocks;
   const int bpp = bl.bpp;
-  if (bl.rows) {
-#define CLC_LAUNCH_BR(LOSS, NT, BT)                                                                            \
-  hipLaunchKernelGGL((clc::batched_rows_eval_kernel<LOSS, NT, BT>), dim3((unsigned)n_blocks), dim3(BT), 0, h->stream,   \
-                     h->d_brxy, reinterpret_cast<const clc::RowDesc*>(h->d_brdesc), h->d_prob_row, h->d_states, bpp,     \
-                     opt.loss_scale_factor, h->d_bpartials)
-    if (h->brows_z) {
-#define CLC_LAUNCH_BRZ(LOSS, NT, BT)                                                                           \
-  hipLaunchKernelGGL((clc::batched_rows_eval_kernel<LOSS, NT, BT, true>), dim3((unsigned)n_blocks), dim3(BT), 0, h->stream, \
-                     h->d_brxy, reinterpret_cast<const clc::RowDesc*>(h->d_brdesc), h->d_prob_row, h->d_states, bpp,     \
-                     opt.loss_scale_factor, h->d_bpartials)
-      if (bl.rows_wave) {
-        if (opt.use_loss) { if (bl.rows_nt) CLC_LAUNCH_BRZ(true, true, 64); else CLC_LAUNCH_BRZ(true, false, 64); }
-        else { if (bl.rows_nt) CLC_LAUNCH_BRZ(false, true, 64); else CLC_LAUNCH_BRZ(false, false, 64); }
-      } else {
-        if (opt.use_loss) { if (bl.rows_nt) CLC_LAUNCH_BRZ(true, true, 256); else CLC_LAUNCH_BRZ(true, false, 256); }
-        else { if (bl.rows_nt) CLC_LAUNCH_BRZ(false, true, 256); else CLC_LAUNCH_BRZ(false, false, 256); }
-      }
-#undef CLC_LAUNCH_BRZ
-      return;
-    }
-    if (bl.rows_wave) {
-      if (opt.use_loss) { if (bl.rows_nt) CLC_LAUNCH_BR(true, true, 64); else CLC_LAUNCH_BR(true, false, 64); }
-      else { if (bl.rows_nt) CLC_LAUNCH_BR(false, true, 64); else CLC_LAUNCH_BR(false, false, 64); }
-    } else {
-      if (opt.use_loss) { if (bl.rows_nt) CLC_LAUNCH_BR(true, true, 256); else CLC_LAUNCH_BR(true, false, 256); }
-      else { if (bl.rows_nt) CLC_LAUNCH_BR(false, true, 256); else CLC_LAUNCH_BR(false, false, 256); }
-    }
-#undef CLC_LAUNCH_BR
+  if (bl.rows) {  // WAVE: one wave per workgroup
+    with_flags([&](auto Z, auto WAVE, auto LOSS, auto NT) {
+      constexpr int BT = WAVE ? 64 : 256;
+      hipLaunchKernelGGL((clc::batched_rows_eval_kernel<LOSS, NT, BT, Z>), dim3(n_blocks), dim3(BT), 0, h->stream, h->d_brxy,
+                         reinterpret_cast<const clc::RowDesc*>(h->d_brdesc), h->d_prob_row, h->d_states, bpp, opt.loss_scale_factor,
+                         h->d_bpartials);
+    }, h->brows_z, bl.rows_wave, opt.use_loss != 0, bl.rows_nt);
     return;
   }
-  const bool bcompact = bl.compact, bdeep = bl.deep, bnt = bl.nt;
-#define CLC_LAUNCH_B(LOSS, CP, NT)                                                                          \
-  hipLaunchKernelGGL((clc::batched_eval_kernel<LOSS, CP, NT, false>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, \
-                     h->stream, (CP) ? h->d_bctiles : h->d_btiles, h->d_bgroups, h->d_tile_off, h->d_nobs,    \
-                     h->d_states, bpp, opt.loss_scale_factor, h->d_bpartials)
-#define CLC_LAUNCH_BD(LOSS, NT)                                                                             \
-  hipLaunchKernelGGL((clc::batched_eval_kernel<LOSS, true, NT, true>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, \
-                     h->stream, h->d_bctiles, h->d_bgroups, h->d_tile_off, h->d_nobs, h->d_states, bpp,           \
-                     opt.loss_scale_factor, h->d_bpartials)
-  if (bcompact && bdeep) {
-    if (opt.use_loss) { if (bnt) CLC_LAUNCH_BD(true, true); else CLC_LAUNCH_BD(true, false); }
-    else { if (bnt) CLC_LAUNCH_BD(false, true); else CLC_LAUNCH_BD(false, false); }
-  } else if (bcompact) {
-    if (opt.use_loss) { if (bnt) CLC_LAUNCH_B(true, true, true); else CLC_LAUNCH_B(true, true, false); }
-    else { if (bnt) CLC_LAUNCH_B(false, true, true); else CLC_LAUNCH_B(false, true, false); }
-  } else {
-    if (opt.use_loss) { if (bnt) CLC_LAUNCH_B(true, false, true); else CLC_LAUNCH_B(true, false, false); }
-    else { if (bnt) CLC_LAUNCH_B(false, false, true); else CLC_LAUNCH_B(false, false, false); }
-  }
-#undef CLC_LAUNCH_B
-#undef CLC_LAUNCH_BD
+  const auto launch = [&](auto CP, auto DEEP, auto LOSS, auto NT) {
+    hipLaunchKernelGGL((clc::batched_eval_kernel<LOSS, CP, NT, DEEP>), dim3(n_blocks), dim3(clc::BLOCK), 0, h->stream,
+                       CP ? h->d_bctiles : h->d_btiles, h->d_bgroups, h->d_tile_off, h->d_nobs, h->d_states, bpp, opt.loss_scale_factor,
+                       h->d_bpartials);
+  };
+  if (bl.compact) with_flags(launch, std::true_type{}, bl.deep, opt.use_loss != 0, bl.nt);
+  else with_flags(launch, std::false_type{}, std::false_type{}, opt.use_loss != 0, bl.nt);
 }
 
 void launch_resident_batch(clc_handle* h, const clc_options& opt, const BatchedLaunch& bl, clc_summary* d_summaries, double* d_results,
@@ -133,27 +98,16 @@ void launch_resident_batch(clc_handle* h, const clc_options& opt, const BatchedL
   const int uni_ppl = multistart ? -2 - h->bres.max_ppl : h->bres.uni_ppl;
   const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->bres.d_row);
   const clc::ResLane* d_desc = reinterpret_cast<const clc::ResLane*>(h->bres.d_desc);
-#define CLC_LAUNCH_RES(LOSS, NT, NW, PR, PL)                                                                                  \
-  hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, kResCtrl##NW>), dim3((unsigned)P), dim3(NW * 64), 0, h->stream, \
-                     h->bres.d_xy, d_row, d_desc, h->d_bgroups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results, nullptr, nullptr, \
-                     rec_base, rec_host, seg_off, goal)
-#define CLC_LAUNCH_RES_V(NW, PR, PL)                                                                                          \
-  do {                                                                                                                        \
-    if (opt.use_loss) { if (bl.res_nt) CLC_LAUNCH_RES(true, true, NW, PR, PL); else CLC_LAUNCH_RES(true, false, NW, PR, PL); } \
-    else { if (bl.res_nt) CLC_LAUNCH_RES(false, true, NW, PR, PL); else CLC_LAUNCH_RES(false, false, NW, PR, PL); }            \
-  } while (0)
-#define CLC_LAUNCH_RESZ(LOSS, NT)                                                                                              \
-  hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, 8, kResPRz, kResPLz, kResCtrl8, true>), dim3((unsigned)P), dim3(512), 0, h->stream, \
-                     h->bres.d_xy, d_row, d_desc, h->d_bgroups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results, nullptr, nullptr, \
-                     rec_base, rec_host, seg_off, goal, h->bres.d_z)
-  if (h->bres.with_z) {  // 24-byte slots (p.z != 0 in some record of the batch)
-    if (opt.use_loss) { if (bl.res_nt) CLC_LAUNCH_RESZ(true, true); else CLC_LAUNCH_RESZ(true, false); }
-    else { if (bl.res_nt) CLC_LAUNCH_RESZ(false, true); else CLC_LAUNCH_RESZ(false, false); }
-  } else if (h->bres.lanes == 256) CLC_LAUNCH_RES_V(4, kResPR256, kResPL256);
-  else CLC_LAUNCH_RES_V(8, kResPR512, kResPL512);
-#undef CLC_LAUNCH_RESZ
-#undef CLC_LAUNCH_RES_V
-#undef CLC_LAUNCH_RES
+  // W4: the 256-lane form (4 waves); Z: 24-byte slots (p.z != 0 in some record of the batch), on 512 lanes
+  const auto launch = [&](auto Z, auto W4, auto LOSS, auto NT) {
+    constexpr int NW = W4 ? 4 : 8;
+    constexpr int PR = Z ? kResPRz : W4 ? kResPR256 : kResPR512, PL = Z ? kResPLz : W4 ? kResPL256 : kResPL512;
+    hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z>), dim3((unsigned)P), dim3(NW * 64), 0,
+                       h->stream, h->bres.d_xy, d_row, d_desc, h->d_bgroups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results,
+                       nullptr, nullptr, rec_base, rec_host, seg_off, goal, Z ? h->bres.d_z : nullptr);
+  };
+  if (h->bres.with_z) with_flags(launch, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
+  else with_flags(launch, std::false_type{}, h->bres.lanes == 256, opt.use_loss != 0, bl.res_nt);
 }
 
 int batched_check_inputs(const char* who, const clc_options& opt, const double* poses, size_t P) {
@@ -172,6 +126,32 @@ int batched_check_inputs(const char* who, const clc_options& opt, const double* 
 }
 
 }  // namespace clc_abi
+
+namespace {
+
+// The end of every clc_solve_batched path: the stream synchronised (kernel completion makes the outcomes written over PCIe visible),
+// the results valid for clc_gather_results, copied out unless solved in place, the wall time (and with `timed` the kernel time of the
+// event pair around the one launch) in every summary.
+int finish_batched(clc_handle* h, bool in_place, double* poses, clc_summary* summaries, std::chrono::steady_clock::time_point t0,
+                   bool timed) {
+  const size_t P = h->n_problems;
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  float kernel_ms = 0.0f;
+  if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
+  h->results_valid = P;
+  if (!in_place) {
+    std::memcpy(poses, h->h_poses, sizeof(double) * 7 * P);
+    std::memcpy(summaries, h->h_summaries, sizeof(clc_summary) * P);
+  }
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (size_t k = 0; k < P; ++k) {
+    summaries[k].solve_ms = ms;
+    if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
+  }
+  return CLC_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -222,40 +202,17 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
     if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
     // (kernel completion makes the outcomes written over PCIe visible; polling the stream with hipStreamQuery instead of this
     // blocking call was measured: no difference — the 70-80 us between the kernel's end event and the return are not the wake-up)
-    CLC_HIP(hipStreamSynchronize(h->stream));
-    float kernel_ms = 0.0f;
-    if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
-    h->results_valid = P;
-    if (!in_place) {
-      std::memcpy(poses, h->h_poses, sizeof(double) * 7 * P);
-      std::memcpy(summaries, h->h_summaries, sizeof(clc_summary) * P);
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (size_t k = 0; k < P; ++k) {
-      summaries[k].solve_ms = ms;
-      if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
-    }
-    return CLC_OK;
+    return finish_batched(h, in_place, poses, summaries, t0, timed);
   }
   if (bl.whole_solve) {
     // one 256-thread workgroup per problem: the whole solve of every problem in ONE launch (batched_solve_kernel)
     const clc::RowDesc* bdesc = reinterpret_cast<const clc::RowDesc*>(h->d_brdesc);
-#define CLC_LAUNCH_SOLVE(LOSS, NT)                                                                                      \
-  hipLaunchKernelGGL((clc::batched_solve_kernel<LOSS, NT>), dim3((unsigned)P), dim3(clc::BLOCK), 0, h->stream, h->d_brxy, \
-                     bdesc, h->d_prob_row, opt, h->d_poses, h->d_summaries, h->d_results)
-    if (opt.use_loss) { if (bl.rows_nt) CLC_LAUNCH_SOLVE(true, true); else CLC_LAUNCH_SOLVE(true, false); }
-    else { if (bl.rows_nt) CLC_LAUNCH_SOLVE(false, true); else CLC_LAUNCH_SOLVE(false, false); }
-#undef CLC_LAUNCH_SOLVE
+    with_flags([&](auto LOSS, auto NT) {
+      hipLaunchKernelGGL((clc::batched_solve_kernel<LOSS, NT>), dim3((unsigned)P), dim3(clc::BLOCK), 0, h->stream, h->d_brxy, bdesc,
+                         h->d_prob_row, opt, h->d_poses, h->d_summaries, h->d_results);
+    }, opt.use_loss != 0, bl.rows_nt);
     CLC_HIP(hipGetLastError());
-    CLC_HIP(hipStreamSynchronize(h->stream));  // kernel completion makes the outcomes written over PCIe visible
-    h->results_valid = P;
-    if (!in_place) {
-      std::memcpy(poses, h->h_poses, sizeof(double) * 7 * P);
-      std::memcpy(summaries, h->h_summaries, sizeof(clc_summary) * P);
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (size_t k = 0; k < P; ++k) summaries[k].solve_ms = ms;
-    return CLC_OK;
+    return finish_batched(h, in_place, poses, summaries, t0, false);
   }
   const int lm_threads = bl.lm_threads;
   const unsigned lm_blocks = bl.lm_blocks;
@@ -263,52 +220,27 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
                      opt, h->d_poses, (int)P, h->d_queue, h->d_ticket);
   CLC_HIP(hipGetLastError());
   const int lookahead = opt.launch_ahead > 0 ? opt.launch_ahead : default_lookahead();
-  const int max_evals = opt.max_num_iterations + 1;
-  clc::HostMailbox* mb = h->h_mailbox;
-  mb->n_done = 0;
-  mb->status = CLC_RUNNING;
-  std::atomic_thread_fence(std::memory_order_seq_cst);
+  // at the iteration cap the loop ends once every launch is consumed: batched_finish_kernel closes the stragglers
+  const LaunchAhead la = {"clc_solve_batched", opt.max_num_iterations + 1, lookahead, LaunchAhead::kReturn, 60.0};
   int launched = 0;
-  long long spins = 0;
-  int last_done = 0;
-  auto t_last_progress = std::chrono::steady_clock::now();
-  for (;;) {
-    if (__atomic_load_n(&mb->status, __ATOMIC_ACQUIRE) != CLC_RUNNING) break;
-    const int done = __atomic_load_n(&mb->n_done, __ATOMIC_ACQUIRE);
-    if (launched < max_evals && launched - done < lookahead) {
-      launch_batched_eval(h, opt, bl);
-      hipLaunchKernelGGL(clc::batched_lm_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream,
-                         h->d_bpartials, bpp, h->d_states, opt, (int)P, h->d_queue, h->d_ticket, launched,
-                         h->d_mailbox, h->d_poses, h->d_summaries, h->d_results);
-      ++launched;
-      continue;
-    }
-    if (launched >= max_evals && done >= launched) break;  // iteration cap reached for the stragglers
-    if (done != last_done) { last_done = done; t_last_progress = std::chrono::steady_clock::now(); spins = 0; }
-    if ((++spins & 0xFFFF) == 0) {
-      hipError_t e = hipStreamQuery(h->stream);
-      if (e != hipSuccess && e != hipErrorNotReady) return fail(CLC_ERR_HIP, "clc_solve_batched: stream error", e);
-      const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_last_progress).count();
-      if (waited > 60.0) return fail(CLC_ERR_HIP, "clc_solve_batched: no progress from the device for 60 s");
-    }
-  }
+  int rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) {
+    launch_batched_eval(h, opt, bl);
+    hipLaunchKernelGGL(clc::batched_lm_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream,
+                       h->d_bpartials, bpp, h->d_states, opt, (int)P, h->d_queue, h->d_ticket, k,
+                       h->d_mailbox, h->d_poses, h->d_summaries, h->d_results);
+    return CLC_OK;
+  }, &launched);
+  if (rc != CLC_OK) return rc;
   CLC_HIP(hipGetLastError());
-  if (__atomic_load_n(&mb->status, __ATOMIC_ACQUIRE) == CLC_RUNNING) {  // iteration cap of this loop: some problem still runs
+  if (__atomic_load_n(&h->h_mailbox->status, __ATOMIC_ACQUIRE) == CLC_RUNNING) {  // iteration cap of this loop: some problem still runs
     hipLaunchKernelGGL(clc::batched_finish_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream, h->d_states,
                        (int)P, h->d_poses, h->d_summaries, h->d_results);
     CLC_HIP(hipGetLastError());
   }
-  CLC_HIP(hipStreamSynchronize(h->stream));  // kernel completion makes the outcomes written over PCIe visible
-  h->results_valid = P;
-  if (!in_place) {
-    std::memcpy(poses, h->h_poses, sizeof(double) * 7 * P);
-    std::memcpy(summaries, h->h_summaries, sizeof(clc_summary) * P);
-  }
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (size_t k = 0; k < P; ++k) {
-    summaries[k].solve_ms = ms;
+  rc = finish_batched(h, in_place, poses, summaries, t0, false);
+  if (rc != CLC_OK) return rc;
+  for (size_t k = 0; k < P; ++k)
     if (summaries[k].termination == CLC_RUNNING) summaries[k].termination = CLC_FAILURE;
-  }
   return CLC_OK;
 }
 

@@ -1,6 +1,6 @@
 // abi_solve.hip — clc_eval and clc_solve: the launch sequences of one problem (step-kernel chain, single-workgroup resident kernel, cooperative kernel).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "clc_abi_internal.hpp"
+#include "abi_drive.hpp"
 
 using namespace clc_abi;
 
@@ -10,22 +10,23 @@ template <bool WITH_LOSS, bool WITH_JAC>
 void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t* d_status, double lf,
                    const clc::Pose7& pose_arg, int use_pose_arg) {
   const int fl = h->launch_flags;
-#define CLC_LAUNCH(PF, NT, CP, BT)                                                                          \
-  hipLaunchKernelGGL((clc::eval_kernel<WITH_LOSS, WITH_JAC, PF, NT, CP, BT>), dim3(grid), dim3(BT), 0,       \
-                     h->stream, (CP) ? h->d_ctiles : h->d_tiles, h->d_groups, (long long)h->n_obs, d_pose,   \
-                     d_status, lf, fl, h->d_partials, pose_arg, use_pose_arg)
   const bool pf = (fl & clc::FLAG_PREFETCH) != 0, nt = (fl & clc::FLAG_NONTEMPORAL) != 0;
   const bool cp = (fl & clc::FLAG_COMPACT) != 0 && h->compact_ok;
   const bool big = (fl & clc::FLAG_WG512) != 0;
   if (use_rows(h)) {  // row layout: the Jacobian comes with the moments, a cost-only pass would save nothing
     const bool rnt = rows_nontemporal(h, h->n_rows, h->rows_z);
-    if (h->rows_z) {  // rows that carry z: 3:2 wave shares, 8 rows in flight
-#define CLC_LAUNCH_RZ(NT, BT)                                                                                              \
-  hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, NT, BT, true, clc::ROWS_DEPTH, true>), dim3(grid), dim3(BT), 0, h->stream, h->d_rxy, \
-                     reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, d_pose, d_status, lf, fl, h->d_partials, pose_arg, use_pose_arg)
-      if (big) { if (rnt) CLC_LAUNCH_RZ(true, 512); else CLC_LAUNCH_RZ(false, 512); }
-      else { if (rnt) CLC_LAUNCH_RZ(true, 256); else CLC_LAUNCH_RZ(false, 256); }
-#undef CLC_LAUNCH_RZ
+    // rows in flight per wave: 8 while the array is served by the Infinity Cache, 12 (206 VGPRs, still 2 waves/SIMD) when it
+    // streams from HBM with non-temporal loads — throughput there tracks the bytes in flight per CU (profiles/r03_occupancy.md:
+    // 4 rows 0.40 of peak, 8 rows 0.81, 12 rows 0.82-0.83, 16 rows 0.81; 3 waves/SIMD cannot hold more than 6 rows each: 0.80);
+    // rows that carry z keep 8.  BIG: 512-thread workgroups; EQ: equal wave shares (the unweighted form)
+    const auto launch = [&](auto BIG, auto EQ, auto NT, auto Z) {
+      constexpr int BT = BIG ? 512 : 256;
+      hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, NT, BT, !EQ, (NT && !Z) ? 12 : clc::ROWS_DEPTH, Z>), dim3(grid), dim3(BT), 0,
+                         h->stream, h->d_rxy, reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, d_pose, d_status, lf, fl,
+                         h->d_partials, pose_arg, use_pose_arg);
+    };
+    if (h->rows_z) {  // rows that carry z: 3:2 wave shares
+      with_flags(launch, big, std::false_type{}, rnt, std::true_type{});
       return;
     }
     // Equal, scan-aligned shares (flag 512) pay where a wave's share is a scan or two; the evaluation kernel ALONE with
@@ -33,70 +34,35 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
     // 1e6 observations, but 15.4 vs 14.7 at 4e6 and 45.1 vs 42.1 at 1.6e7) — the step kernel is not (its wave 0 starts
     // late anyway): it keeps the equal shares at every size.
     const bool eq = (fl & clc::FLAG_EQUAL_WAVES) != 0 && !(h->launch_auto && h->n_rows > 16LL * 8 * grid);
-    // rows in flight per wave: 8 while the array is served by the Infinity Cache, 12 (206 VGPRs, still 2 waves/SIMD) when it
-    // streams from HBM with non-temporal loads — throughput there tracks the bytes in flight per CU (profiles/r03_occupancy.md:
-    // 4 rows 0.40 of peak, 8 rows 0.81, 12 rows 0.82-0.83, 16 rows 0.81; 3 waves/SIMD cannot hold more than 6 rows each: 0.80)
-#define CLC_LAUNCH_R(NT, BT, WG)                                                                              \
-  hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, NT, BT, WG, (NT) ? 12 : clc::ROWS_DEPTH>), dim3(grid), dim3(BT), 0, h->stream, h->d_rxy, \
-                     reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, d_pose, d_status, lf, fl,       \
-                     h->d_partials, pose_arg, use_pose_arg)
-#ifdef CLC_EVAL_VARIANTS
-    // Occupancy experiment of profiles/r03_occupancy.md (scripts/r03_occupancy.py; -DCLC_EVAL_VARIANTS build only):
-    // CLC_EVAL_VARIANT = <threads>x<rows in flight per wave>: 768x4, 768x6 (3 waves/SIMD), 512x4, 512x12, 512x16 (2 waves/SIMD)
-    static const int variant = [] {
-      const char* e = std::getenv("CLC_EVAL_VARIANT");
-      const char* names[] = {"768x4", "512x4", "512x12", "512x16", "768x6"};
-      for (int i = 0; e && i < 5; ++i)
-        if (std::strcmp(e, names[i]) == 0) return i + 1;
-      return 0;
-    }();
-#define CLC_LAUNCH_VAR(BT, DEPTH)                                                                                                  \
-  do {                                                                                                                             \
-    if (rnt) hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, true, BT, true, DEPTH>), dim3(grid), dim3(BT), 0, h->stream, h->d_rxy,  \
-                                reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, d_pose, d_status, lf, fl, h->d_partials, pose_arg, use_pose_arg); \
-    else hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, false, BT, true, DEPTH>), dim3(grid), dim3(BT), 0, h->stream, h->d_rxy,     \
-                            reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, d_pose, d_status, lf, fl, h->d_partials, pose_arg, use_pose_arg);    \
-    return;                                                                                                                        \
-  } while (0)
-    if (variant == 1) CLC_LAUNCH_VAR(768, 4);
-    if (variant == 2) CLC_LAUNCH_VAR(512, 4);
-    if (variant == 3) CLC_LAUNCH_VAR(512, 12);
-    if (variant == 4) CLC_LAUNCH_VAR(512, 16);
-    if (variant == 5) CLC_LAUNCH_VAR(768, 6);
-#undef CLC_LAUNCH_VAR
-#endif
     if (big) {
       if (eq) ensure_wave_split(h, grid);
-      if (eq) { if (rnt) CLC_LAUNCH_R(true, 512, false); else CLC_LAUNCH_R(false, 512, false); }
-      else { if (rnt) CLC_LAUNCH_R(true, 512, true); else CLC_LAUNCH_R(false, 512, true); }
+      with_flags(launch, std::true_type{}, eq, rnt, std::false_type{});
     } else {
-      if (rnt) CLC_LAUNCH_R(true, 256, true); else CLC_LAUNCH_R(false, 256, true);
+      with_flags(launch, std::false_type{}, std::false_type{}, rnt, std::false_type{});
     }
-#undef CLC_LAUNCH_R
     return;
   }
   // Compact layout: the deep pipeline (two tiles of points in flight per wave) pays only when the array streams
   // from HBM, i.e. no longer fits the 256 MiB Infinity Cache (scripts/size_sweep.py: +10 % at 9e8 B, -8 % at 1e8 B).
   // Well beyond the cache (> 1.5x) the streamed tiles are also loaded non-temporally (+5-8 % at 4.5e8-9e8 B; plain
   // loads win while the array is cache-resident, and at 2.9e8 B — C3 — there is nothing in it).
+  const auto launch = [&](auto CP, auto BIG, auto PF, auto NT) {
+    constexpr int BT = BIG ? 512 : 256;
+    hipLaunchKernelGGL((clc::eval_kernel<WITH_LOSS, WITH_JAC, PF, NT, CP, BT>), dim3(grid), dim3(BT), 0, h->stream,
+                       CP ? h->d_ctiles : h->d_tiles, h->d_groups, (long long)h->n_obs, d_pose, d_status, lf, fl, h->d_partials, pose_arg,
+                       use_pose_arg);
+  };
   const bool beyond_cache = h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes;
   const bool deep = (fl & clc::FLAG_DEEP) != 0 || beyond_cache;
   if (cp) {
-    const bool pf = deep;
-    const bool nt = (fl & clc::FLAG_NONTEMPORAL) != 0 ||
-                    (h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes + kInfinityCacheBytes / 2);
-    if (big && pf) { if (nt) CLC_LAUNCH(true, true, true, 512); else CLC_LAUNCH(true, false, true, 512); }
-    else if (big) { if (nt) CLC_LAUNCH(false, true, true, 512); else CLC_LAUNCH(false, false, true, 512); }
-    else if (pf) { if (nt) CLC_LAUNCH(true, true, true, 256); else CLC_LAUNCH(true, false, true, 256); }
-    else { if (nt) CLC_LAUNCH(false, true, true, 256); else CLC_LAUNCH(false, false, true, 256); }
+    const bool cnt = (fl & clc::FLAG_NONTEMPORAL) != 0 ||
+                     (h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes + kInfinityCacheBytes / 2);
+    with_flags(launch, std::true_type{}, big, deep, cnt);
   } else if (big) {
-    if (nt) CLC_LAUNCH(true, true, false, 512); else CLC_LAUNCH(true, false, false, 512);
+    with_flags(launch, std::false_type{}, std::true_type{}, std::true_type{}, nt);
+  } else {
+    with_flags(launch, std::false_type{}, std::false_type{}, pf, nt);
   }
-  else if (pf && nt) CLC_LAUNCH(true, true, false, 256);
-  else if (pf) CLC_LAUNCH(true, false, false, 256);
-  else if (nt) CLC_LAUNCH(false, true, false, 256);
-  else CLC_LAUNCH(false, false, false, 256);
-#undef CLC_LAUNCH
 }
 
 template <bool WITH_JAC>
@@ -162,6 +128,30 @@ int clc_eval(clc_handle* h, const double pose[7], int with_loss, double loss_sca
 
 namespace {
 
+// Trace rows wanted?  Then the handle's trace buffer holds every row of the solve.
+int prepare_trace(clc_handle* h, const clc_options& opt, const clc_iteration* trace, int trace_cap, bool* want_trace) {
+  *want_trace = trace != nullptr && trace_cap > 0;
+  return *want_trace ? ensure_trace(h, opt.max_num_iterations + 8) : CLC_OK;
+}
+
+// The end of every clc_solve path, once the stream is synchronised where the trace or the events need it: summary and pose out of
+// the pinned buffers the device wrote, the trace rows, the kernel-time fields, the wall time and the finite check.
+int finish_solve(clc_handle* h, const clc_summary& out, const double* out_pose, double pose[7], clc_summary* summary,
+                 clc_iteration* trace, int trace_cap, double kernel_ms, int64_t kernel_launches,
+                 std::chrono::steady_clock::time_point t0) {
+  *summary = out;
+  for (int i = 0; i < 7; ++i) pose[i] = out_pose[i];
+  if (trace != nullptr && trace_cap > 0) {
+    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), h->trace_cap);
+    if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
+  }
+  summary->eval_kernel_ms = kernel_ms;
+  summary->eval_kernel_launches = kernel_launches;
+  summary->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve: non-finite result");
+  return CLC_OK;
+}
+
 }  // namespace
 
 namespace clc_abi {
@@ -173,17 +163,10 @@ namespace clc_abi {
 int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7], clc_summary* summary,
                   clc_iteration* trace, int trace_cap, std::chrono::steady_clock::time_point t0,
                   int win_first, int win_last, float* win_ms) {
-  const bool want_trace = trace != nullptr && trace_cap > 0;
-  if (want_trace) {
-    const int rc = ensure_trace(h, opt.max_num_iterations + 8);
-    if (rc != CLC_OK) return rc;
-  }
+  bool want_trace;
+  int rc = prepare_trace(h, opt, trace, trace_cap, &want_trace);
+  if (rc != CLC_OK) return rc;
   const int lookahead = opt.launch_ahead > 0 ? opt.launch_ahead : default_lookahead();
-  const int max_launches = opt.max_num_iterations + 2;  // (max_iterations + 1) evaluations + the final controller pass
-  clc::HostMailbox* mb = h->h_mailbox;
-  mb->n_done = 0;
-  mb->status = CLC_RUNNING;
-  std::atomic_thread_fence(std::memory_order_seq_cst);
   clc::Pose7 p0;
   for (int i = 0; i < 7; ++i) p0.v[i] = pose[i];
   clc::SolveParams prm;
@@ -201,100 +184,71 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
   const bool rows_eq = (h->launch_flags & clc::FLAG_EQUAL_WAVES) != 0 && !rows_z;
   if (rows && rows_eq) ensure_wave_split(h, grid);
   double* rows_buf[2] = {h->d_partials, h->d_partials_b};
-  int launched = 0, status = CLC_RUNNING, last_done = 0;
-  long long spins = 0;
-  auto t_last_progress = std::chrono::steady_clock::now();
-  for (;;) {
-    status = __atomic_load_n(&mb->status, __ATOMIC_ACQUIRE);
-    if (status != CLC_RUNNING) break;
-    // passes consumed = launches whose rows are used up.  Clamped to what this solve has launched: the early progress
-    // store of the PREVIOUS solve's last launches is relaxed and may land after the reset above.
-    const int done = std::min(__atomic_load_n(&mb->n_done, __ATOMIC_ACQUIRE), launched);
-    if (launched < max_launches && launched - done <= lookahead) {
-      const int k = launched;
-      if (win_ms && k == win_first) CLC_HIP(hipEventRecord(h->ev[0], h->stream));
-      // launch k reads state[(k-1)&1] / rows[(k-1)&1] and writes state[k&1] / rows[k&1]
-      const double* r_in = rows_buf[(k + 1) & 1];
-      double* r_out = rows_buf[k & 1];
-#define CLC_LAUNCH_STEP(LOSS, DEEP, MODE)                                                                     \
-  hipLaunchKernelGGL((clc::step_kernel<LOSS, DEEP, MODE>), dim3(grid), dim3(512), 0, h->stream, r_in,            \
-                     h->d_ctiles, h->d_groups, (int)h->n_obs, grid | ((k & 1) << 30), k, r_out, h->d_block, prm)
-#define CLC_LAUNCH_STEP_R(LOSS, NT, MODE, WG)                                                                 \
-  hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, MODE, 1, WG>), dim3(grid), dim3(512), 0, h->stream, r_in,       \
-                     h->d_rxy, h->d_rdesc, (int)h->n_rows, grid | ((k & 1) << 30), k, r_out, h->d_block, prm)
-#define CLC_LAUNCH_STEP_M(LOSS, DEEP)                                                                         \
-  do { if (k == 0) CLC_LAUNCH_STEP(LOSS, DEEP, 0); else if (k == 1) CLC_LAUNCH_STEP(LOSS, DEEP, 1);             \
-       else CLC_LAUNCH_STEP(LOSS, DEEP, 2); } while (0)
-#define CLC_LAUNCH_STEP_RM(LOSS, NT, WG)                                                                      \
-  do { if (k == 0) CLC_LAUNCH_STEP_R(LOSS, NT, 0, WG); else if (k == 1) CLC_LAUNCH_STEP_R(LOSS, NT, 1, WG);     \
-       else CLC_LAUNCH_STEP_R(LOSS, NT, 2, WG); } while (0)
-      if (rows_z) {  // rows that carry z (LAYOUT 2): 3:2 wave shares
-#define CLC_LAUNCH_STEP_Z(LOSS, NT)                                                                           \
-  do { if (k == 0) hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, 0, 2, true>), dim3(grid), dim3(512), 0, h->stream, r_in, h->d_rxy, h->d_rdesc, (int)h->n_rows, grid | ((k & 1) << 30), k, r_out, h->d_block, prm); \
-       else if (k == 1) hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, 1, 2, true>), dim3(grid), dim3(512), 0, h->stream, r_in, h->d_rxy, h->d_rdesc, (int)h->n_rows, grid | ((k & 1) << 30), k, r_out, h->d_block, prm); \
-       else hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, 2, 2, true>), dim3(grid), dim3(512), 0, h->stream, r_in, h->d_rxy, h->d_rdesc, (int)h->n_rows, grid | ((k & 1) << 30), k, r_out, h->d_block, prm); } while (0)
-        if (opt.use_loss) { if (rows_nt) CLC_LAUNCH_STEP_Z(true, true); else CLC_LAUNCH_STEP_Z(true, false); }
-        else { if (rows_nt) CLC_LAUNCH_STEP_Z(false, true); else CLC_LAUNCH_STEP_Z(false, false); }
-#undef CLC_LAUNCH_STEP_Z
-      }
-      else if (rows) {
-        if (opt.use_loss) {
-          if (rows_eq) { if (rows_nt) CLC_LAUNCH_STEP_RM(true, true, false); else CLC_LAUNCH_STEP_RM(true, false, false); }
-          else { if (rows_nt) CLC_LAUNCH_STEP_RM(true, true, true); else CLC_LAUNCH_STEP_RM(true, false, true); }
-        } else {
-          if (rows_eq) { if (rows_nt) CLC_LAUNCH_STEP_RM(false, true, false); else CLC_LAUNCH_STEP_RM(false, false, false); }
-          else { if (rows_nt) CLC_LAUNCH_STEP_RM(false, true, true); else CLC_LAUNCH_STEP_RM(false, false, true); }
-        }
-      }
-      else if (opt.use_loss) { if (deep) CLC_LAUNCH_STEP_M(true, true); else CLC_LAUNCH_STEP_M(true, false); }
-      else { if (deep) CLC_LAUNCH_STEP_M(false, true); else CLC_LAUNCH_STEP_M(false, false); }
-#undef CLC_LAUNCH_STEP_M
-#undef CLC_LAUNCH_STEP_RM
-#undef CLC_LAUNCH_STEP_R
-#undef CLC_LAUNCH_STEP
-      if (win_ms && k == win_last) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
-      ++launched;
-      continue;
-    }
-    if (done != last_done) { last_done = done; t_last_progress = std::chrono::steady_clock::now(); spins = 0; }
-    if ((++spins & 0xFFFF) == 0) {
-      hipError_t e = hipStreamQuery(h->stream);
-      if (e != hipSuccess && e != hipErrorNotReady) return fail(CLC_ERR_HIP, "clc_solve: stream error", e);
-      if (e == hipSuccess) {
-        status = __atomic_load_n(&mb->status, __ATOMIC_ACQUIRE);
-        if (status != CLC_RUNNING) break;
-        if (launched >= max_launches) return fail(CLC_ERR_HIP, "clc_solve: controller did not terminate");
-      }
-      const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_last_progress).count();
-      if (waited > 30.0) return fail(CLC_ERR_HIP, "clc_solve: no progress from the device for 30 s");
-    }
-  }
+  // (max_iterations + 1) evaluations + the final controller pass; launch k is made while k - (passes consumed) <= lookahead
+  const LaunchAhead la = {"clc_solve", opt.max_num_iterations + 2, lookahead + 1, LaunchAhead::kFail, 30.0};
+  int launched = 0;
+  rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) -> int {
+    if (win_ms && k == win_first) CLC_HIP(hipEventRecord(h->ev[0], h->stream));
+    // launch k reads state[(k-1)&1] / rows[(k-1)&1] and writes state[k&1] / rows[k&1]
+    const double* r_in = rows_buf[(k + 1) & 1];
+    double* r_out = rows_buf[k & 1];
+    // LAYOUT 0: compact tiles (NT is DEEP there), 1: rows, 2: rows that carry z; EQ: equal wave shares, the unweighted form;
+    // MODE 0: launch 0, 1: launch 1, 2: the rest
+    const auto launch = [&](auto LAYOUT, auto LOSS, auto EQ, auto NT, auto MODE) {
+      hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, MODE, LAYOUT, !EQ>), dim3(grid), dim3(512), 0, h->stream, r_in,
+                         LAYOUT ? h->d_rxy : h->d_ctiles, LAYOUT ? h->d_rdesc : h->d_groups, LAYOUT ? (int)h->n_rows : (int)h->n_obs,
+                         grid | ((k & 1) << 30), k, r_out, h->d_block, prm);
+    };
+    const auto at_mode = [&](auto... c) {
+      if (k == 0) launch(c..., cint<0>);
+      else if (k == 1) launch(c..., cint<1>);
+      else launch(c..., cint<2>);
+    };
+    if (rows_z) with_flags(at_mode, cint<2>, opt.use_loss != 0, std::false_type{}, rows_nt);  // 3:2 wave shares
+    else if (rows) with_flags(at_mode, cint<1>, opt.use_loss != 0, rows_eq, rows_nt);
+    else with_flags(at_mode, cint<0>, opt.use_loss != 0, std::false_type{}, deep);
+    if (win_ms && k == win_last) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
+    return CLC_OK;
+  }, &launched);
+  if (rc != CLC_OK) return rc;
   CLC_HIP(hipGetLastError());
   std::atomic_thread_fence(std::memory_order_acquire);
-  *summary = mb->summary;
-  for (int i = 0; i < 7; ++i) pose[i] = mb->pose[i];
-  summary->eval_kernel_ms = 0.0;
-  summary->eval_kernel_launches = 0;
-  if (want_trace) {
+  if (want_trace) CLC_HIP(hipStreamSynchronize(h->stream));
+  rc = finish_solve(h, h->h_mailbox->summary, h->h_mailbox->pose, pose, summary, trace, trace_cap, 0.0, 0, t0);
+  if (rc != CLC_OK || !win_ms) return rc;
+  *win_ms = -1.f;
+  if (launched > win_last && win_first >= 0) {
     CLC_HIP(hipStreamSynchronize(h->stream));
-    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), h->trace_cap);
-    if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
+    CLC_HIP(hipEventElapsedTime(win_ms, h->ev[0], h->ev[1]));
   }
-  summary->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (win_ms) {
-    *win_ms = -1.f;
-    if (launched > win_last && win_first >= 0) {
-      CLC_HIP(hipStreamSynchronize(h->stream));
-      CLC_HIP(hipEventElapsedTime(win_ms, h->ev[0], h->ev[1]));
-    }
-  }
-  if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve: non-finite result");
   return CLC_OK;
 }
 }  // namespace clc_abi
 
 namespace {
 
+// The whole-solve kernels raise a completion flag behind the pose (same pinned allocation) with a system-scope release after the
+// outcome is written.  arm_done_flag clears it and returns its device address.
+int32_t* arm_done_flag(clc_handle* h) {
+  __atomic_store_n(reinterpret_cast<int32_t*>(h->h_spose + 7), 0, __ATOMIC_RELAXED);
+  std::atomic_thread_fence(std::memory_order_seq_cst);
+  return reinterpret_cast<int32_t*>(h->d_spose + 7);
+}
+
+// Polling the flag avoids the wake-up latency of a blocking stream synchronisation (~15 us of a ~120 us solve).  Bounded: a wedged
+// queue falls through to the caller's synchronisation, which reports the error.  Returns the flag (0: not raised).
+int32_t wait_done_flag(clc_handle* h) {
+  const int32_t* h_done = reinterpret_cast<const int32_t*>(h->h_spose + 7);
+  long long spins = 0;
+  const auto t_spin = std::chrono::steady_clock::now();
+  while (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) == 0) {
+    if ((++spins & 0xFFFF) == 0) {
+      if (hipStreamQuery(h->stream) != hipErrorNotReady) break;
+      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spin).count() > 30.0) break;
+    }
+  }
+  return __atomic_load_n(h_done, __ATOMIC_ACQUIRE);
+}
 
 // A problem that fits ONE workgroup (<= 512 lanes x 22 points; the lane layout was built at upload): the whole LM solve in a
 // single launch of resident_solve_kernel<8 waves> — points read from HBM once into registers + LDS, every pass, reduction and
@@ -304,62 +258,33 @@ namespace {
 // exchange and controller.  One CU works, 255 idle — the problem has 5.7e3 points.
 int solve_resident_single(clc_handle* h, const clc_options& opt, double pose[7], clc_summary* summary, clc_iteration* trace,
                           int trace_cap, std::chrono::steady_clock::time_point t0) {
-  const bool want_trace = trace != nullptr && trace_cap > 0;
-  if (want_trace) {
-    const int rc = ensure_trace(h, opt.max_num_iterations + 8);
-    if (rc != CLC_OK) return rc;
-  }
+  bool want_trace;
+  int rc = prepare_trace(h, opt, trace, trace_cap, &want_trace);
+  if (rc != CLC_OK) return rc;
   for (int i = 0; i < 7; ++i) h->h_spose[i] = pose[i];
-  int32_t* h_done = reinterpret_cast<int32_t*>(h->h_spose + 7);  // completion flag behind the pose (same pinned allocation)
-  int32_t* d_done = reinterpret_cast<int32_t*>(h->d_spose + 7);
-  __atomic_store_n(h_done, 0, __ATOMIC_RELAXED);
-  std::atomic_thread_fence(std::memory_order_seq_cst);
+  int32_t* d_done = arm_done_flag(h);
   const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->sres.d_row);
   const clc::ResLane* d_desc = reinterpret_cast<const clc::ResLane*>(h->sres.d_desc);
   clc_iteration* d_trace = want_trace ? h->d_trace : nullptr;
   const int d_cap = want_trace ? h->trace_cap : 0;
-#define CLC_LAUNCH_SINGLE(LOSS, CTRL)                                                                                                   \
-  hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, false, 8, kResPR512, kResPL512, CTRL>), dim3(1), dim3(512), 0, h->stream, h->sres.d_xy, \
-                     d_row, d_desc, h->d_groups, h->sres.uni_ppl, opt, d_trace, d_cap, h->d_spose, h->d_ssummary, h->d_small, d_done, nullptr)
   const bool uni_ctrl = h->single_uni_ctrl;  // the cooperative kernel's controller here: the bit-identity test of the two (hooks build)
   const bool timed = opt.profile_events == 2;  // an event pair around the one launch -> eval_kernel_ms, eval_kernel_launches = 1
   if (timed) {
-    const int rc = ensure_events(h, 2);
+    rc = ensure_events(h, 2);
     if (rc != CLC_OK) return rc;
     CLC_HIP(hipEventRecord(h->ev[0], h->stream));
   }
-  if (opt.use_loss) { if (uni_ctrl) CLC_LAUNCH_SINGLE(true, 1); else CLC_LAUNCH_SINGLE(true, 0); }
-  else { if (uni_ctrl) CLC_LAUNCH_SINGLE(false, 1); else CLC_LAUNCH_SINGLE(false, 0); }
-#undef CLC_LAUNCH_SINGLE
+  with_flags([&](auto LOSS, auto CTRL) {
+    hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, false, 8, kResPR512, kResPL512, CTRL>), dim3(1), dim3(512), 0, h->stream,
+                       h->sres.d_xy, d_row, d_desc, h->d_groups, h->sres.uni_ppl, opt, d_trace, d_cap, h->d_spose, h->d_ssummary,
+                       h->d_small, d_done, nullptr);
+  }, opt.use_loss != 0, uni_ctrl);
   CLC_HIP(hipGetLastError());
   if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
-  // The kernel sets the flag (system-scope release) after the outcome is written: polling it avoids the wake-up latency of a
-  // blocking stream synchronisation (~15 us of a ~120 us solve).  Bounded: a wedged queue falls through to the synchronisation,
-  // which reports the error.
-  {
-    long long spins = 0;
-    const auto t_spin = std::chrono::steady_clock::now();
-    while (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) == 0) {
-      if ((++spins & 0xFFFF) == 0) {
-        if (hipStreamQuery(h->stream) != hipErrorNotReady) break;
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spin).count() > 30.0) break;
-      }
-    }
-    if (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) == 0 || want_trace || timed) CLC_HIP(hipStreamSynchronize(h->stream));
-  }
+  if (wait_done_flag(h) == 0 || want_trace || timed) CLC_HIP(hipStreamSynchronize(h->stream));
   float kernel_ms = 0.0f;
   if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
-  *summary = *h->h_ssummary;
-  for (int i = 0; i < 7; ++i) pose[i] = h->h_spose[i];
-  if (want_trace) {
-    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), h->trace_cap);
-    if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
-  }
-  summary->eval_kernel_ms = timed ? (double)kernel_ms : 0.0;
-  summary->eval_kernel_launches = timed ? 1 : 0;
-  summary->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve: non-finite result");
-  return CLC_OK;
+  return finish_solve(h, *h->h_ssummary, h->h_spose, pose, summary, trace, trace_cap, kernel_ms, timed ? 1 : 0, t0);
 }
 
 // clc_solve as ONE launch of 256 co-resident workgroups that keep the problem on chip (clc_coop.hpp).  Returns kCoopFallback when
@@ -437,20 +362,15 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
     CLC_HIP(hipStreamSynchronize(h->stream));
     h->coop_tag = 1;
   }
-  const bool want_trace = trace != nullptr && trace_cap > 0;
-  if (want_trace) {
-    const int rc = ensure_trace(h, opt.max_num_iterations + 8);
-    if (rc != CLC_OK) return rc;
-  }
+  bool want_trace;
+  int rc = prepare_trace(h, opt, trace, trace_cap, &want_trace);
+  if (rc != CLC_OK) return rc;
   const bool timed = opt.profile_events == 2;  // HIP event pair around the one launch -> clc_summary.eval_kernel_ms
   if (timed) {
-    const int rc = ensure_events(h, 2);
+    rc = ensure_events(h, 2);
     if (rc != CLC_OK) return rc;
   }
-  int32_t* h_done = reinterpret_cast<int32_t*>(h->h_spose + 7);  // completion flag behind the pose (same pinned allocation)
-  int32_t* d_done = reinterpret_cast<int32_t*>(h->d_spose + 7);
-  __atomic_store_n(h_done, 0, __ATOMIC_RELAXED);
-  std::atomic_thread_fence(std::memory_order_seq_cst);
+  int32_t* d_done = arm_done_flag(h);
   clc::Pose7 p0;
   for (int i = 0; i < 7; ++i) p0.v[i] = pose[i];
   const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->cres.d_row);
@@ -463,31 +383,20 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
   const unsigned int wgs = (unsigned int)std::max(1, n_wgs - h->coop_test_drop);
   h->coop_test_drop = 0;
   if (timed) CLC_HIP(hipEventRecord(h->ev[0], h->stream));
-#define CLC_LAUNCH_COOP(LOSS, Z, ONE)                                                                                                         \
-  hipLaunchKernelGGL((clc::coop_solve_kernel<LOSS, false, Z, ONE>), dim3(wgs), dim3(clc::COOP_THREADS), 0, h->stream, h->cres.d_xy, h->cres.d_z, d_row, \
-                     d_desc, h->d_groups, h->cres.uni_ppl, opt, p0, d_trace, d_cap, h->d_board, tag0, h->d_spose, h->d_ssummary, h->d_small, d_done, \
-                     n_wgs)
-  const bool one = n_wgs == clc::COOP_SMALL_WGS;  // the one-hop form on 32 workgroups
-  if (h->cres.with_z) {  // 24-byte slots: p.z != 0
-    if (one) { if (opt.use_loss) CLC_LAUNCH_COOP(true, true, true); else CLC_LAUNCH_COOP(false, true, true); }
-    else { if (opt.use_loss) CLC_LAUNCH_COOP(true, true, false); else CLC_LAUNCH_COOP(false, true, false); }
-  } else if (one) { if (opt.use_loss) CLC_LAUNCH_COOP(true, false, true); else CLC_LAUNCH_COOP(false, false, true); }
-  else { if (opt.use_loss) CLC_LAUNCH_COOP(true, false, false); else CLC_LAUNCH_COOP(false, false, false); }
-#undef CLC_LAUNCH_COOP
+  // Z: 24-byte slots (p.z != 0); ONE: the one-hop form on 32 workgroups
+  with_flags([&](auto Z, auto ONE, auto LOSS) {
+    hipLaunchKernelGGL((clc::coop_solve_kernel<LOSS, false, Z, ONE>), dim3(wgs), dim3(clc::COOP_THREADS), 0, h->stream, h->cres.d_xy,
+                       h->cres.d_z, d_row, d_desc, h->d_groups, h->cres.uni_ppl, opt, p0, d_trace, d_cap, h->d_board, tag0, h->d_spose,
+                       h->d_ssummary, h->d_small, d_done, n_wgs);
+  }, h->cres.with_z, n_wgs == clc::COOP_SMALL_WGS, opt.use_loss != 0);
   CLC_HIP(hipGetLastError());
   if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
-  {  // the kernel raises the flag (system-scope release) after the outcome is written; bounded like solve_resident_single
-    long long spins = 0;
-    const auto t_spin = std::chrono::steady_clock::now();
-    while (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) == 0) {
-      if ((++spins & 0xFFFF) == 0) {
-        if (hipStreamQuery(h->stream) != hipErrorNotReady) break;
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spin).count() > 30.0) break;
-      }
-    }
-    if (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) != clc::COOP_DONE_OK || want_trace || timed) CLC_HIP(hipStreamSynchronize(h->stream));
+  int32_t done = wait_done_flag(h);
+  if (done != clc::COOP_DONE_OK || want_trace || timed) {
+    CLC_HIP(hipStreamSynchronize(h->stream));
+    done = __atomic_load_n(reinterpret_cast<const int32_t*>(h->h_spose + 7), __ATOMIC_ACQUIRE);
   }
-  if (__atomic_load_n(h_done, __ATOMIC_ACQUIRE) != clc::COOP_DONE_OK) {
+  if (done != clc::COOP_DONE_OK) {
     // an exchange timed out (a workgroup was not resident in time): nothing was written; the path rests (see coop_backoff)
     h->coop_retry_at = h->coop_eligible + h->coop_backoff;
     h->coop_backoff = std::min<long long>(h->coop_backoff * 2, 1LL << 20);
@@ -495,23 +404,9 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
     return kCoopFallback;
   }
   ++h->coop_solves;
-  *summary = *h->h_ssummary;
-  for (int i = 0; i < 7; ++i) pose[i] = h->h_spose[i];
-  if (want_trace) {
-    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), h->trace_cap);
-    if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
-  }
-  summary->eval_kernel_ms = 0.0;
-  summary->eval_kernel_launches = 0;
-  if (timed) {
-    float ms = 0.f;
-    CLC_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    summary->eval_kernel_ms = (double)ms;
-    summary->eval_kernel_launches = 1;
-  }
-  summary->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve: non-finite result");
-  return CLC_OK;
+  float kernel_ms = 0.0f;
+  if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
+  return finish_solve(h, *h->h_ssummary, h->h_spose, pose, summary, trace, trace_cap, kernel_ms, timed ? 1 : 0, t0);
 }
 
 }  // namespace
@@ -551,24 +446,15 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
       opt.profile_events != 1)  // 1: HIP events around K1, two-kernel path
     return solve_stepped(h, opt, grid, pose, summary, trace, trace_cap, t0);
   const int max_evals = opt.max_num_iterations + 1;
-  const bool want_trace = trace != nullptr && trace_cap > 0;
-  if (want_trace) {
-    rc = ensure_trace(h, opt.max_num_iterations + 8);
-    if (rc != CLC_OK) return rc;
-  }
+  bool want_trace;
+  rc = prepare_trace(h, opt, trace, trace_cap, &want_trace);
+  if (rc != CLC_OK) return rc;
   if (opt.profile_events) {
     rc = ensure_events(h, 2 * (size_t)max_evals);
     if (rc != CLC_OK) return rc;
   }
-  // Launch-ahead depth: the host keeps this many LM iterations queued beyond the last one the
-  // device has reported done (pinned mailbox), so the stream never drains and the host never
-  // blocks; at most `lookahead` already-queued iterations turn into no-ops after termination.
+  // Launch-ahead depth: the host keeps this many LM iterations queued beyond the last one the device has reported done.
   const int lookahead = opt.launch_ahead > 0 ? opt.launch_ahead : default_lookahead();
-  clc::HostMailbox* mb = h->h_mailbox;
-  mb->n_done = 0;
-  mb->status = CLC_RUNNING;
-  std::atomic_thread_fence(std::memory_order_seq_cst);
-
   clc::Pose7 p0;
   for (int i = 0; i < 7; ++i) p0.v[i] = pose[i];
   const double* d_x_eval = reinterpret_cast<const double*>(
@@ -577,74 +463,34 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
       reinterpret_cast<const char*>(h->d_state) + offsetof(clc::LmState, status));
   clc_iteration* d_trace = want_trace ? h->d_trace : nullptr;
   const int d_trace_cap = want_trace ? h->trace_cap : 0;
-
+  const LaunchAhead la = {"clc_solve", max_evals, lookahead, LaunchAhead::kFailOnceConsumed, 30.0};
   int launched = 0;
-  int status = CLC_RUNNING;
-  long long spins = 0;
-  auto t_last_progress = std::chrono::steady_clock::now();
-  int last_done = 0;
-  for (;;) {
-    status = __atomic_load_n(&mb->status, __ATOMIC_ACQUIRE);
-    if (status != CLC_RUNNING) break;
-    const int done = std::min(__atomic_load_n(&mb->n_done, __ATOMIC_ACQUIRE), launched);  // see solve_stepped
-    if (launched < max_evals && launched - done < lookahead) {
-      if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * launched], h->stream));
-      {
-        // iteration 0 carries the initial pose by value and initialises the LM state in lm_kernel
-        const bool first = launched == 0;
-        launch_eval<true>(h, grid, opt.use_loss != 0, d_x_eval, d_status, opt.loss_scale_factor, first ? &p0 : nullptr);
-        if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * launched + 1], h->stream));
-        if (first)
-          hipLaunchKernelGGL(clc::lm_kernel<true>, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid,
-                             h->d_state, opt, d_trace, d_trace_cap, h->d_mailbox, p0);
-        else
-          hipLaunchKernelGGL(clc::lm_kernel<false>, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid,
-                             h->d_state, opt, d_trace, d_trace_cap, h->d_mailbox, p0);
-      }
-      ++launched;
-      continue;
-    }
-    // nothing to launch: wait for the device (bounded: a wedged queue must not hang the caller)
-    if (done != last_done) { last_done = done; t_last_progress = std::chrono::steady_clock::now(); spins = 0; }
-    if ((++spins & 0xFFFF) == 0) {
-      hipError_t e = hipStreamQuery(h->stream);
-      if (e != hipSuccess && e != hipErrorNotReady) return fail(CLC_ERR_HIP, "clc_solve: stream error", e);
-      if (e == hipSuccess) {  // queue drained: the mailbox must be final now
-        status = __atomic_load_n(&mb->status, __ATOMIC_ACQUIRE);
-        if (status != CLC_RUNNING) break;
-        if (launched >= max_evals && __atomic_load_n(&mb->n_done, __ATOMIC_ACQUIRE) >= launched)
-          return fail(CLC_ERR_HIP, "clc_solve: controller did not terminate");
-      }
-      const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_last_progress).count();
-      if (waited > 30.0) return fail(CLC_ERR_HIP, "clc_solve: no progress from the device for 30 s");
-    }
-  }
+  rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) -> int {
+    if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * k], h->stream));
+    // iteration 0 carries the initial pose by value and initialises the LM state in lm_kernel
+    launch_eval<true>(h, grid, opt.use_loss != 0, d_x_eval, d_status, opt.loss_scale_factor, k == 0 ? &p0 : nullptr);
+    if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * k + 1], h->stream));
+    with_flags([&](auto FIRST) {
+      hipLaunchKernelGGL(clc::lm_kernel<FIRST>, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid, h->d_state, opt,
+                         d_trace, d_trace_cap, h->d_mailbox, p0);
+    }, k == 0);
+    return CLC_OK;
+  }, &launched);
+  if (rc != CLC_OK) return rc;
   CLC_HIP(hipGetLastError());
   std::atomic_thread_fence(std::memory_order_acquire);
-  *summary = mb->summary;
-  for (int i = 0; i < 7; ++i) pose[i] = mb->pose[i];
-  summary->eval_kernel_ms = 0.0;
-  summary->eval_kernel_launches = 0;
   if (want_trace || opt.profile_events) CLC_HIP(hipStreamSynchronize(h->stream));
-  if (want_trace) {
-    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), h->trace_cap);
-    if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
-  }
+  double kernel_ms = 0.0;
+  int64_t kernel_launches = 0;
   if (opt.profile_events) {
-    const int n_real = (int)std::min<int64_t>(summary->num_evaluations, launched);
-    double tot = 0.0;
-    for (int i = 0; i < n_real; ++i) {
+    kernel_launches = std::min<int64_t>(h->h_mailbox->summary.num_evaluations, launched);
+    for (int i = 0; i < kernel_launches; ++i) {
       float ms = 0.f;
       CLC_HIP(hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
-      tot += ms;
+      kernel_ms += ms;
     }
-    summary->eval_kernel_ms = tot;
-    summary->eval_kernel_launches = n_real;
   }
-  summary->solve_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve: non-finite result");
-  return CLC_OK;
+  return finish_solve(h, h->h_mailbox->summary, h->h_mailbox->pose, pose, summary, trace, trace_cap, kernel_ms, kernel_launches, t0);
 }
 
 }  // extern "C"
