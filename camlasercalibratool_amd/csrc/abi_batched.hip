@@ -42,13 +42,13 @@ int batched_launch_setup(clc_handle* h, const clc_options& /*opt*/, BatchedLaunc
   bl->n_blocks = n_blocks;
   bl->lm_threads = 64;
   bl->lm_blocks = (unsigned)((P + bl->lm_threads - 1) / bl->lm_threads);
-  bl->compact = (h->launch_flags & clc::FLAG_COMPACT) != 0 && h->bcompact_ok;
+  bl->compact = (h->launch_flags & clc::FLAG_COMPACT) != 0 && h->batch.compact_ok;
   const bool bbeyond = h->launch_auto && h->batch_total_tiles * clc::CTILE_DOUBLES * sizeof(double) > kInfinityCacheBytes;
   bl->nt = (h->launch_flags & clc::FLAG_NONTEMPORAL) != 0 ||
            (bl->compact && h->launch_auto &&
             h->batch_total_tiles * clc::CTILE_DOUBLES * sizeof(double) > kInfinityCacheBytes + kInfinityCacheBytes / 2);
   bl->deep = (h->launch_flags & clc::FLAG_DEEP) != 0 || bbeyond;
-  bl->rows_nt = bl->rows && rows_nontemporal(h, h->bn_rows, h->brows_z);
+  bl->rows_nt = bl->rows && rows_nontemporal(h, h->batch.n_rows, h->batch.rows_z);
   // One workgroup per problem running the problem's WHOLE solve in one launch (batched_solve_kernel) beats the lockstep
   // launches wherever a pass over the batch is not bandwidth-bound anyway — per evaluation pass, 10^4-observation
   // problems: 17 vs 69 us at 24 problems, 28 vs 52 at 512, 49 vs 65 at 1 024 (C3), 96 vs 115 at 2 048, a tie at 4 096
@@ -56,8 +56,8 @@ int batched_launch_setup(clc_handle* h, const clc_options& /*opt*/, BatchedLaunc
   // 91 vs 70 at 24, a tie at 256 (scripts/probes/c3_exp.py).  So: unless the rows exceed 1 GiB (a C4 shard: lockstep, one
   // wave per problem) or a single problem is so long (> 1 024 rows, ~6.5e4 observations) that four waves are too few.
   {
-    const size_t row_bytes = (size_t)h->bn_rows * ((h->brows_z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES) * sizeof(double) + sizeof(clc::RowDesc));
-    bl->whole_solve = bl->rows && !h->brows_z && (h->launch_flags & clc::FLAG_BATCHED_LOCKSTEP) == 0 && row_bytes <= (1ull << 30) && h->batch_max_rows <= 1024;
+    const size_t row_bytes = (size_t)h->batch.n_rows * ((h->batch.rows_z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES) * sizeof(double) + sizeof(clc::RowDesc));
+    bl->whole_solve = bl->rows && !h->batch.rows_z && (h->launch_flags & clc::FLAG_BATCHED_LOCKSTEP) == 0 && row_bytes <= (1ull << 30) && h->batch_max_rows <= 1024;
   }
   // Problems that fit a workgroup's registers + LDS are read from HBM once and solved on chip (clc_resident.hpp).
   bl->resident = h->bres.ok && (h->launch_flags & (clc::FLAG_NO_RESIDENT | clc::FLAG_BATCHED_LOCKSTEP)) == 0;
@@ -74,15 +74,15 @@ void launch_batched_eval(clc_handle* h, const clc_options& opt, const BatchedLau
   if (bl.rows) {  // WAVE: one wave per workgroup
     with_flags([&](auto Z, auto WAVE, auto LOSS, auto NT) {
       constexpr int BT = WAVE ? 64 : 256;
-      hipLaunchKernelGGL((clc::batched_rows_eval_kernel<LOSS, NT, BT, Z>), dim3(n_blocks), dim3(BT), 0, h->stream, h->d_brxy,
-                         reinterpret_cast<const clc::RowDesc*>(h->d_brdesc), h->d_prob_row, h->d_states, bpp, opt.loss_scale_factor,
+      hipLaunchKernelGGL((clc::batched_rows_eval_kernel<LOSS, NT, BT, Z>), dim3(n_blocks), dim3(BT), 0, h->stream, h->batch.d_rxy,
+                         reinterpret_cast<const clc::RowDesc*>(h->batch.d_rdesc), h->d_prob_row, h->d_states, bpp, opt.loss_scale_factor,
                          h->d_bpartials);
-    }, h->brows_z, bl.rows_wave, opt.use_loss != 0, bl.rows_nt);
+    }, h->batch.rows_z, bl.rows_wave, opt.use_loss != 0, bl.rows_nt);
     return;
   }
   const auto launch = [&](auto CP, auto DEEP, auto LOSS, auto NT) {
     hipLaunchKernelGGL((clc::batched_eval_kernel<LOSS, CP, NT, DEEP>), dim3(n_blocks), dim3(clc::BLOCK), 0, h->stream,
-                       CP ? h->d_bctiles : h->d_btiles, h->d_bgroups, h->d_tile_off, h->d_nobs, h->d_states, bpp, opt.loss_scale_factor,
+                       CP ? h->batch.d_ctiles : h->batch.d_tiles, h->batch.d_groups, h->d_tile_off, h->d_nobs, h->d_states, bpp, opt.loss_scale_factor,
                        h->d_bpartials);
   };
   if (bl.compact) with_flags(launch, std::true_type{}, bl.deep, opt.use_loss != 0, bl.nt);
@@ -103,7 +103,7 @@ void launch_resident_batch(clc_handle* h, const clc_options& opt, const BatchedL
     constexpr int NW = W4 ? 4 : 8;
     constexpr int PR = Z ? kResPRz : W4 ? kResPR256 : kResPR512, PL = Z ? kResPLz : W4 ? kResPL256 : kResPL512;
     hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z>), dim3((unsigned)P), dim3(NW * 64), 0,
-                       h->stream, h->bres.d_xy, d_row, d_desc, h->d_bgroups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results,
+                       h->stream, h->bres.d_xy, d_row, d_desc, h->batch.d_groups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results,
                        nullptr, nullptr, rec_base, rec_host, seg_off, goal, Z ? h->bres.d_z : nullptr);
   };
   if (h->bres.with_z) with_flags(launch, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
@@ -165,7 +165,7 @@ int clc_batched_host_buffers(clc_handle* h, double** poses, clc_summary** summar
 
 int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, clc_summary* summaries) {
   if (!h || !poses || !summaries) return fail(CLC_ERR_INVALID_ARG, "clc_solve_batched: bad argument");
-  if (!h->d_btiles || h->n_problems == 0) return fail(CLC_ERR_NO_DATA, "clc_solve_batched: no problems uploaded");
+  if (!h->batch.d_tiles || h->n_problems == 0) return fail(CLC_ERR_NO_DATA, "clc_solve_batched: no problems uploaded");
   // the handle's own pinned arrays (clc_batched_host_buffers): solved in place, no staging copies
   const bool in_place = poses == h->h_poses && summaries == h->h_summaries;
   if ((poses == h->h_poses) != (summaries == h->h_summaries))
@@ -206,9 +206,9 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
   }
   if (bl.whole_solve) {
     // one 256-thread workgroup per problem: the whole solve of every problem in ONE launch (batched_solve_kernel)
-    const clc::RowDesc* bdesc = reinterpret_cast<const clc::RowDesc*>(h->d_brdesc);
+    const clc::RowDesc* bdesc = reinterpret_cast<const clc::RowDesc*>(h->batch.d_rdesc);
     with_flags([&](auto LOSS, auto NT) {
-      hipLaunchKernelGGL((clc::batched_solve_kernel<LOSS, NT>), dim3((unsigned)P), dim3(clc::BLOCK), 0, h->stream, h->d_brxy, bdesc,
+      hipLaunchKernelGGL((clc::batched_solve_kernel<LOSS, NT>), dim3((unsigned)P), dim3(clc::BLOCK), 0, h->stream, h->batch.d_rxy, bdesc,
                          h->d_prob_row, opt, h->d_poses, h->d_summaries, h->d_results);
     }, opt.use_loss != 0, bl.rows_nt);
     CLC_HIP(hipGetLastError());
@@ -254,7 +254,7 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
 // streaming path.  Same kernel, same arithmetic as clc_solve_batched of n_starts uploaded copies: bit-identical results.
 int clc_solve_multistart(clc_handle* h, const clc_options* opt_in, size_t n_starts, double* poses, clc_summary* summaries) {
   if (!h || !poses || !summaries || n_starts == 0) return fail(CLC_ERR_INVALID_ARG, "clc_solve_multistart: bad argument");
-  if (!h->d_btiles || h->n_problems != 1)
+  if (!h->batch.d_tiles || h->n_problems != 1)
     return fail(CLC_ERR_NO_DATA, "clc_solve_multistart: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
   clc_options opt;
   if (opt_in) opt = *opt_in; else clc_options_default(&opt);

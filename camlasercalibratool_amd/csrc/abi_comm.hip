@@ -357,7 +357,7 @@ int step_enqueue(clc_comm* c, const clc_options& opt, const double* poses0, int6
   const std::string w(who);
   if (P > cap_per_rank) local_fail(CLC_ERR_INVALID_ARG, w + ": cap_per_rank < local problems (this rank contributed padding only)");
   if (P > 0 && !poses0) local_fail(CLC_ERR_INVALID_ARG, w + ": NULL start poses (this rank contributed padding only)");
-  if (P > 0 && fl.local_rc == CLC_OK && (!h->d_btiles || !h->h_poses)) local_fail(CLC_ERR_NO_DATA, w + ": no problems uploaded");
+  if (P > 0 && fl.local_rc == CLC_OK && (!h->batch.d_tiles || !h->h_poses)) local_fail(CLC_ERR_NO_DATA, w + ": no problems uploaded");
   if (P > 0 && fl.local_rc == CLC_OK) {
     // options as clc_solve_batched checks them; the start poses go into the handle's pinned buffer (what the kernel reads) and are
     // checked for non-finite values in the same pass over them.  (The previous step's kernel has finished: nothing still reads that buffer.)

@@ -80,10 +80,10 @@ int ensure_events(clc_handle* h, size_t n) {
 // fixed cost there and the row kernel's 16 prologue loads + per-scan expansion make it 0.4-0.5 us longer per LM iteration
 // (8.5 vs 9.0 us at 5.5x10^3 observations, 8.8 vs 9.2 at 10^5; 13.2 vs 11.1 at 10^6 — scripts/r02_ab.py).
 bool use_rows(const clc_handle* h) {
-  if ((h->launch_flags & clc::FLAG_ROWS) == 0 || !h->rows_ok) return false;
-  return !h->launch_auto || !h->compact_ok || h->n_obs >= 200000;
+  if ((h->launch_flags & clc::FLAG_ROWS) == 0 || !h->obs.rows_ok) return false;
+  return !h->launch_auto || !h->obs.compact_ok || h->n_obs >= 200000;
 }
-bool use_brows(const clc_handle* h) { return (h->launch_flags & clc::FLAG_ROWS) != 0 && h->brows_ok; }
+bool use_brows(const clc_handle* h) { return (h->launch_flags & clc::FLAG_ROWS) != 0 && h->batch.rows_ok; }
 // Rows streamed from HBM rather than the Infinity Cache (> 1.5x its size) are loaded non-temporally.
 bool rows_nontemporal(const clc_handle* h, long long n_rows, bool z) {
   const size_t bytes = (size_t)n_rows * ((z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES) * sizeof(double) + sizeof(clc::RowDesc));
@@ -94,10 +94,10 @@ bool rows_nontemporal(const clc_handle* h, long long n_rows, bool z) {
 // handle's stream in front of the launches that read it, when the grid changed since the last upload.
 void ensure_wave_split(clc_handle* h, int grid) {
   if (h->split_grid == grid) return;
-  const clc::RowDesc* desc = reinterpret_cast<const clc::RowDesc*>(h->d_rdesc);
-  int* table = reinterpret_cast<int*>(reinterpret_cast<char*>(h->d_rdesc) + ((size_t)h->n_rows + 1) * sizeof(clc::RowDesc));
+  const clc::RowDesc* desc = reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc);
+  int* table = reinterpret_cast<int*>(reinterpret_cast<char*>(h->obs.d_rdesc) + ((size_t)h->obs.n_rows + 1) * sizeof(clc::RowDesc));
   const int total = grid * 8 + 1;
-  hipLaunchKernelGGL(clc::wave_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, desc, (int)h->n_rows,
+  hipLaunchKernelGGL(clc::wave_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, desc, (int)h->obs.n_rows,
                      grid, table);
   h->split_grid = grid;
 }
@@ -235,10 +235,11 @@ void clc_destroy(clc_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-  void* ptrs[] = {h->d_tiles, h->d_partials, h->d_block, h->d_trace, h->d_small, h->d_btiles,
-                  h->d_tile_off, h->d_nobs, h->d_queue, h->d_states,
-                  h->d_bpartials, h->d_ticket, h->d_ctiles, h->d_groups, h->d_bctiles, h->d_bgroups, h->d_results,
-                  h->d_rxy, h->d_rdesc, h->d_brxy, h->d_brdesc, h->bres.d_xy, h->bres.d_desc, h->bres.d_row, h->sres.d_xy, h->sres.d_desc, h->sres.d_row, h->cres.d_xy, h->cres.d_desc, h->cres.d_row, h->cres.d_z, h->sres.d_z, h->bres.d_z, h->d_board, h->d_prob_row, h->d_sq, h->d_st, h->d_spts, h->d_sptl, h->d_soff};
+  h->obs.release();
+  h->batch.release();
+  for (clc_abi::ResLayout* L : {&h->sres, &h->bres, &h->cres}) L->release();
+  void* ptrs[] = {h->d_partials, h->d_block, h->d_trace, h->d_small, h->d_tile_off, h->d_nobs, h->d_queue, h->d_states,
+                  h->d_bpartials, h->d_ticket, h->d_results, h->d_board, h->d_prob_row, h->d_sq, h->d_st, h->d_spts, h->d_sptl, h->d_soff};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   h->pool.clear();
@@ -298,12 +299,12 @@ int clc_get_path_info(const clc_handle* h, clc_path_info* out) {
   out->batched_lanes = h->bres.ok ? h->bres.lanes : 0;
   out->batched_points_per_lane = h->bres.ok ? h->bres.max_ppl : 0;
   out->batched_points_carry_z = h->bres.ok && h->bres.with_z ? 1 : 0;
-  out->rows_layout = h->rows_ok ? (h->rows_z ? 2 : 1) : 0;
-  out->batched_rows_layout = h->brows_ok ? (h->brows_z ? 2 : 1) : 0;
+  out->rows_layout = h->obs.rows_ok ? (h->obs.rows_z ? 2 : 1) : 0;
+  out->batched_rows_layout = h->batch.rows_ok ? (h->batch.rows_z ? 2 : 1) : 0;
   out->coop_solves = h->coop_solves;
   out->batched_lane_rows = h->bres.ok ? h->bres.rows : 0;
-  out->n_rows = h->n_rows;
-  out->batched_n_rows = h->bn_rows;
+  out->n_rows = h->obs.n_rows;
+  out->batched_n_rows = h->batch.n_rows;
   out->coop_gate_waits_expired = h->coop_gate_waits_expired;
   return CLC_OK;
 }

@@ -33,7 +33,7 @@ int clc_debug_flatten_device(clc_handle* h, int use_linefitting_data, int use_bo
 // consumes pass k-1; choose 2 <= first <= last <= passes - 1 to cover steady-state launches that all streamed.
 int clc_time_steps(clc_handle* h, const double pose0[7], int first, int last, double* avg_ms, int* passes) {
   if (!h || !pose0 || !avg_ms || first < 0 || last < first) return fail(CLC_ERR_INVALID_ARG, "clc_time_steps: bad argument");
-  if (!h->d_tiles || !(h->compact_ok || h->rows_ok)) return fail(CLC_ERR_NO_DATA, "clc_time_steps: no (compact / row) observations uploaded");
+  if (!h->obs.d_tiles || !(h->obs.compact_ok || h->obs.rows_ok)) return fail(CLC_ERR_NO_DATA, "clc_time_steps: no (compact / row) observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
   int rc = ensure_events(h, 2);
   if (rc != CLC_OK) return rc;
@@ -100,10 +100,10 @@ int clc_debug_build_features(void) {
 // Row-layout report: rows[0/1] + row counts for the single-problem array and the batch.
 int clc_debug_rows(clc_handle* h, int* rows, long long* n_rows, int* brows, long long* bn_rows) {
   if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_debug_rows: NULL handle");
-  if (rows) *rows = h->rows_ok ? (h->rows_z ? 2 : 1) : 0;  // 2: the rows carry z
-  if (n_rows) *n_rows = h->n_rows;
-  if (brows) *brows = h->brows_ok ? (h->brows_z ? 2 : 1) : 0;
-  if (bn_rows) *bn_rows = h->bn_rows;
+  if (rows) *rows = h->obs.rows_ok ? (h->obs.rows_z ? 2 : 1) : 0;  // 2: the rows carry z
+  if (n_rows) *n_rows = h->obs.n_rows;
+  if (brows) *brows = h->batch.rows_ok ? (h->batch.rows_z ? 2 : 1) : 0;
+  if (bn_rows) *bn_rows = h->batch.n_rows;
   return CLC_OK;
 }
 
@@ -111,18 +111,18 @@ int clc_debug_rows(clc_handle* h, int* rows, long long* n_rows, int* brows, long
 // indices — and, per row, whether it starts a scan (first[n_rows], may be NULL).
 int clc_debug_wave_split(clc_handle* h, int grid, int* split, int* first) {
   if (!h || grid < 1 || !split) return fail(CLC_ERR_INVALID_ARG, "clc_debug_wave_split: bad arguments");
-  if (!h->rows_ok) return fail(CLC_ERR_NO_DATA, "clc_debug_wave_split: no row layout");
+  if (!h->obs.rows_ok) return fail(CLC_ERR_NO_DATA, "clc_debug_wave_split: no row layout");
   CLC_HIP(hipSetDevice(h->device));
   h->split_grid = -1;
   ensure_wave_split(h, grid);
   CLC_HIP(hipGetLastError());
   CLC_HIP(hipStreamSynchronize(h->stream));
-  const char* base = reinterpret_cast<const char*>(h->d_rdesc);
-  CLC_HIP(hipMemcpy(split, base + ((size_t)h->n_rows + 1) * sizeof(clc::RowDesc), sizeof(int) * ((size_t)grid * 8 + 1), hipMemcpyDeviceToHost));
+  const char* base = reinterpret_cast<const char*>(h->obs.d_rdesc);
+  CLC_HIP(hipMemcpy(split, base + ((size_t)h->obs.n_rows + 1) * sizeof(clc::RowDesc), sizeof(int) * ((size_t)grid * 8 + 1), hipMemcpyDeviceToHost));
   if (first) {
-    std::vector<clc::RowDesc> d((size_t)h->n_rows);
-    CLC_HIP(hipMemcpy(d.data(), base, sizeof(clc::RowDesc) * (size_t)h->n_rows, hipMemcpyDeviceToHost));
-    for (long long r = 0; r < h->n_rows; ++r) first[r] = d[(size_t)r].first;
+    std::vector<clc::RowDesc> d((size_t)h->obs.n_rows);
+    CLC_HIP(hipMemcpy(d.data(), base, sizeof(clc::RowDesc) * (size_t)h->obs.n_rows, hipMemcpyDeviceToHost));
+    for (long long r = 0; r < h->obs.n_rows; ++r) first[r] = d[(size_t)r].first;
   }
   return CLC_OK;
 }
@@ -198,10 +198,10 @@ extern "C" int clc_debug_coop_set_tag(clc_handle* h, unsigned int tag) {
 
 int clc_debug_layout(clc_handle* h, int* compact, long long* n_groups, int* bcompact, long long* bn_groups) {
   if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_debug_layout: NULL handle");
-  if (compact) *compact = h->compact_ok ? 1 : 0;
-  if (n_groups) *n_groups = h->n_groups;
-  if (bcompact) *bcompact = h->bcompact_ok ? 1 : 0;
-  if (bn_groups) *bn_groups = h->bn_groups;
+  if (compact) *compact = h->obs.compact_ok ? 1 : 0;
+  if (n_groups) *n_groups = h->obs.n_groups;
+  if (bcompact) *bcompact = h->batch.compact_ok ? 1 : 0;
+  if (bn_groups) *bn_groups = h->batch.n_groups;
   return CLC_OK;
 }
 
@@ -219,7 +219,7 @@ int clc_debug_lm_profile(clc_handle* h, long long out[8]) {
 // (poses[P*7]; every problem active, as in the first LM iteration of a batch) with HIP events on the handle's stream.
 int clc_time_batched_eval(clc_handle* h, const double* poses, int reps, double* avg_ms) {
   if (!h || !poses || !avg_ms || reps < 1) return fail(CLC_ERR_INVALID_ARG, "clc_time_batched_eval: bad argument");
-  if (!h->d_btiles || h->n_problems == 0) return fail(CLC_ERR_NO_DATA, "clc_time_batched_eval: no problems uploaded");
+  if (!h->batch.d_tiles || h->n_problems == 0) return fail(CLC_ERR_NO_DATA, "clc_time_batched_eval: no problems uploaded");
   CLC_HIP(hipSetDevice(h->device));
   int rc = ensure_events(h, 2);
   if (rc != CLC_OK) return rc;
@@ -249,7 +249,7 @@ int clc_time_batched_eval(clc_handle* h, const double* poses, int reps, double* 
 int clc_time_eval(clc_handle* h, const double pose[7], int with_loss, double lf, int with_jac, int reps,
                   double* avg_ms) {
   if (!h || !pose || !avg_ms || reps < 1) return fail(CLC_ERR_INVALID_ARG, "clc_time_eval: bad argument");
-  if (!h->d_tiles) return fail(CLC_ERR_NO_DATA, "clc_time_eval: no observations uploaded");
+  if (!h->obs.d_tiles) return fail(CLC_ERR_NO_DATA, "clc_time_eval: no observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
   const int grid = eval_grid(h, h->n_obs);
   int rc = ensure_partials(h, grid);

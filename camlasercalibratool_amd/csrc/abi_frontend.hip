@@ -16,7 +16,7 @@ extern "C" {
 
 int clc_factor_evaluate(clc_handle* h, const double pose[7], double* residuals, double* jacobians) {
   if (!h || !pose || !residuals) return fail(CLC_ERR_INVALID_ARG, "clc_factor_evaluate: bad argument");
-  if (!h->d_tiles) return fail(CLC_ERR_NO_DATA, "clc_factor_evaluate: no observations uploaded");
+  if (!h->obs.d_tiles) return fail(CLC_ERR_NO_DATA, "clc_factor_evaluate: no observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
   const size_t n = h->n_obs;
   if (n == 0) return CLC_OK;
@@ -28,7 +28,7 @@ int clc_factor_evaluate(clc_handle* h, const double pose[7], double* residuals, 
   CLC_HIP(hipMemcpyAsync(h->d_small, h->h_small, 7 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   const int threads = 256;
   hipLaunchKernelGGL(clc::factor_kernel, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0,
-                     h->stream, h->d_tiles, (long long)n, h->d_small, d_r, d_j);
+                     h->stream, h->obs.d_tiles, (long long)n, h->d_small, d_r, d_j);
   CLC_HIP(hipGetLastError());
   CLC_HIP(hipStreamSynchronize(h->stream));
   CLC_HIP(hipMemcpy(residuals, d_r, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -88,27 +88,27 @@ int clc_information(clc_handle* h, const double pose[7], double H[36], double b[
 
 int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9[9]) {
   if (!h || !Tlc || !unobservable) return fail(CLC_ERR_INVALID_ARG, "clc_closed_form: bad argument");
-  if (!h->d_tiles || h->n_obs == 0) return fail(CLC_ERR_NO_DATA, "clc_closed_form: no observations uploaded");
+  if (!h->obs.d_tiles || h->n_obs == 0) return fail(CLC_ERR_NO_DATA, "clc_closed_form: no observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
   const int grid = eval_grid(h, h->n_obs);
   int rc = ensure_partials(h, grid);
   if (rc != CLC_OK) return rc;
   if (use_rows(h)) {
-    const clc::RowDesc* rdesc = reinterpret_cast<const clc::RowDesc*>(h->d_rdesc);
-    if (h->rows_z) {  // bar_p = (x, y, 1): z is not read, only the row stride differs
-      if (rows_nontemporal(h, h->n_rows, true))
-        hipLaunchKernelGGL((clc::normal9_rows_kernel<true, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->d_rxy, rdesc, h->n_rows, h->d_partials);
+    const clc::RowDesc* rdesc = reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc);
+    if (h->obs.rows_z) {  // bar_p = (x, y, 1): z is not read, only the row stride differs
+      if (rows_nontemporal(h, h->obs.n_rows, true))
+        hipLaunchKernelGGL((clc::normal9_rows_kernel<true, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy, rdesc, h->obs.n_rows, h->d_partials);
       else
-        hipLaunchKernelGGL((clc::normal9_rows_kernel<false, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->d_rxy, rdesc, h->n_rows, h->d_partials);
+        hipLaunchKernelGGL((clc::normal9_rows_kernel<false, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy, rdesc, h->obs.n_rows, h->d_partials);
     }
-    else if (rows_nontemporal(h, h->n_rows))
-      hipLaunchKernelGGL(clc::normal9_rows_kernel<true>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->d_rxy,
-                         reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, h->d_partials);
+    else if (rows_nontemporal(h, h->obs.n_rows))
+      hipLaunchKernelGGL(clc::normal9_rows_kernel<true>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy,
+                         reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc), h->obs.n_rows, h->d_partials);
     else
-      hipLaunchKernelGGL(clc::normal9_rows_kernel<false>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->d_rxy,
-                         reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, h->d_partials);
+      hipLaunchKernelGGL(clc::normal9_rows_kernel<false>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy,
+                         reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc), h->obs.n_rows, h->d_partials);
   } else {
-    hipLaunchKernelGGL(clc::normal9_kernel, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->d_tiles,
+    hipLaunchKernelGGL(clc::normal9_kernel, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_tiles,
                        (long long)h->n_obs, h->d_partials);
   }
   CLC_HIP(hipGetLastError());

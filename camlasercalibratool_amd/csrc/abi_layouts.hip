@@ -6,21 +6,15 @@ using namespace clc_abi;
 
 namespace {
 
-int retile_into(clc_handle* h, const double* d_aos, size_t n, double** d_tiles, size_t* cap_bytes) {
+int retile_into(clc_handle* h, const double* d_aos, size_t n, StreamLayout& L) {
   const size_t n_padded = ((n + clc::TILE - 1) / clc::TILE) * clc::TILE;
-  const size_t bytes = std::max<size_t>(n_padded, clc::TILE) * 8 * sizeof(double);
-  if (bytes > *cap_bytes) {
-    if (*d_tiles) CLC_HIP(hipFree(*d_tiles));
-    *d_tiles = nullptr;
-    *cap_bytes = 0;
-    CLC_HIP(hipMalloc(d_tiles, bytes));
-    *cap_bytes = bytes;
-  }
+  const int rc = ensure_bytes(&L.d_tiles, &L.tiles_cap, std::max<size_t>(n_padded, clc::TILE) * 8 * sizeof(double));
+  if (rc != CLC_OK) return rc;
   if (n_padded > 0) {
     const int threads = 256;
     const long long blocks = ((long long)n_padded + threads - 1) / threads;
     hipLaunchKernelGGL(clc::retile_kernel, dim3((unsigned)blocks), dim3(threads), 0, h->stream, d_aos,
-                       *d_tiles, (long long)n, (long long)n_padded);
+                       L.d_tiles, (long long)n, (long long)n_padded);
     CLC_HIP(hipGetLastError());
   }
   return CLC_OK;
@@ -45,7 +39,6 @@ int device_scan(clc_handle* h, const TIn* d_in, long long n, unsigned int minus_
   CLC_HIP(hipGetLastError());
   return CLC_OK;
 }
-
 
 // The lane layout of the batched problems (clc_resident.hpp) from the staged records and their scan structure: plan
 // (points per lane of every problem, on the device), offsets (O(P) on the host), lane descriptors + j-major point rows.
@@ -123,6 +116,132 @@ int build_resident(clc_handle* h, ResLayout& L, int first_try, const double* d_a
   return CLC_OK;
 }
 
+// The scan structure of an observation array: what the layout builds are enqueued from.  Planned on the device (build_layouts:
+// scan flags, prefix sums, read-backs) or, for a single problem one workgroup holds, on the host (plan_small_on_host: no read-back).
+struct LayoutPlan {
+  size_t P = 0, G = 0;    // problems, scans
+  long long n = 0;        // records
+  size_t tiles = 0;       // 64-record tiles of all problems ...
+  long long max_tiles = 0;  // ... and of the longest one
+  bool sparse = false;    // fewer than 4 records per scan on average: the streaming layouts do not pay (the step chain keeps the
+                          // 64-byte tiles) — the on-chip layouts, where a lane carries its own plane anyway, are still built
+  bool any_z = false;     // some record has p.z != 0
+  long long R = 0;        // rows of the row layout
+  bool rows_ok = false;
+  const long long* d_rec_off = nullptr;       // [P + 1]
+  const long long* d_tile_off = nullptr;      // [P + 1]
+  const long long* d_starts = nullptr;        // [G + 1] first record of every scan
+  const unsigned int* d_gid = nullptr;        // [n] scan of every record
+  const unsigned int* d_row_begin = nullptr;  // [G + 1] first row of every scan
+  int ppl = 0;                                // host plan: points per lane of the 512-lane layout (0: build_resident plans it) ...
+  const unsigned int* d_res_row = nullptr;    // ... and its row offsets {0, ppl}
+  void set_scans(size_t g) { G = g; sparse = G * 4 > (size_t)n; }
+  void set_rows(long long r) { R = r; rows_ok = !sparse && R > 0 && (size_t)R * clc::ROW <= 3 * (size_t)n + 64 * P; }  // a third full
+  void publish(StreamLayout& L) const {
+    L.n_groups = (long long)G; L.compact_ok = !sparse; L.n_rows = R; L.rows_ok = rows_ok; L.rows_z = any_z;
+  }
+};
+
+// The builds of a plan, first part: the compact layout — group table (what the on-chip kernels take a lane's plane from) + 28-byte tiles.
+int emit_compact(clc_handle* h, const double* d_aos, const LayoutPlan& p, StreamLayout& L) {
+  const int threads = 256;
+  int rc = ensure_bytes(&L.d_ctiles, &L.ctiles_cap, std::max<size_t>(p.tiles, 1) * clc::CTILE_DOUBLES * sizeof(double));
+  if (rc == CLC_OK) rc = ensure_bytes(&L.d_groups, &L.groups_cap, p.G * clc::GROUP_DOUBLES * sizeof(double));
+  if (rc != CLC_OK) return rc;
+  hipLaunchKernelGGL(clc::build_groups_dev_kernel, dim3((unsigned)((p.G + threads - 1) / threads)), dim3(threads), 0, h->stream, d_aos,
+                     p.d_starts, (long long)p.G, L.d_groups);
+  const long long max_padded = p.max_tiles * clc::TILE;
+  const unsigned ydim = (unsigned)std::min<long long>(4096, std::max<long long>(1, (max_padded + threads - 1) / threads));
+  hipLaunchKernelGGL(clc::build_ctiles_kernel, dim3((unsigned)p.P, ydim), dim3(threads), 0, h->stream, d_aos, p.d_gid, p.d_rec_off,
+                     p.d_tile_off, L.d_ctiles);
+  CLC_HIP(hipGetLastError());
+  return CLC_OK;
+}
+
+// ... second part: the row layout, the batch's first row of every problem (d_prob_row), the lane layouts res / coop.
+int emit_rows_and_lanes(clc_handle* h, const double* d_aos, const LayoutPlan& p, StreamLayout& L, long long* d_prob_row, ResLayout* res,
+                        ResLayout* coop) {
+  const int threads = 256;
+  const long long n = p.n, R = p.R;
+  int rc = CLC_OK;
+  if (p.rows_ok) {
+    // one padding row each: the streaming loop's prologue loads run unconditionally from clamped row indices; + the wave split table
+    const size_t row_doubles = p.any_z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES;
+    rc = ensure_bytes(&L.d_rxy, &L.rxy_cap, ((size_t)R + 1) * row_doubles * sizeof(double));
+    if (rc == CLC_OK) rc = ensure_bytes(&L.d_rdesc, &L.rdesc_cap, ((size_t)R + 1) * sizeof(clc::RowDesc) + clc::wave_split_bytes(R));
+    if (rc != CLC_OK) return rc;
+    CLC_HIP(hipMemsetAsync(L.d_rxy + (size_t)R * row_doubles, 0, row_doubles * sizeof(double), h->stream));
+    CLC_HIP(hipMemsetAsync(reinterpret_cast<char*>(L.d_rdesc) + (size_t)R * sizeof(clc::RowDesc), 0, sizeof(clc::RowDesc), h->stream));
+    const long long slots = R * clc::ROW;
+    hipLaunchKernelGGL(clc::build_rows_kernel, dim3((unsigned)((slots + threads - 1) / threads)), dim3(threads), 0, h->stream, d_aos,
+                       p.d_starts, p.d_row_begin, (long long)p.G, R, (int)row_doubles, L.d_rxy, reinterpret_cast<clc::RowDesc*>(L.d_rdesc));
+    if (d_prob_row)
+      hipLaunchKernelGGL(clc::problem_rows_kernel, dim3((unsigned)((p.P + 1 + threads - 1) / threads)), dim3(threads), 0, h->stream,
+                         p.d_rec_off, p.d_gid, p.d_row_begin, (long long)p.P, n, R, d_prob_row);
+    CLC_HIP(hipGetLastError());
+  }
+  if (res != nullptr && p.ppl > 0) {  // planned on the host: one problem's 512-lane layout (build_resident with first_try = 512)
+    rc = ensure_bytes(&res->d_row, &res->row_cap, 2 * sizeof(unsigned int));
+    if (rc == CLC_OK) rc = ensure_bytes(&res->d_desc, &res->desc_cap, (size_t)512 * sizeof(clc::ResLane));
+    if (rc == CLC_OK) rc = ensure_bytes(&res->d_xy, &res->xy_cap, ((size_t)p.ppl + 1) * 512 * 2 * sizeof(double));
+    if (rc != CLC_OK) return rc;
+    CLC_HIP(hipMemcpyAsync(res->d_row, p.d_res_row, 2 * sizeof(unsigned int), hipMemcpyDeviceToDevice, h->stream));
+    CLC_HIP(hipMemsetAsync(res->d_xy + (size_t)p.ppl * 512 * 2, 0, (size_t)512 * 2 * sizeof(double), h->stream));
+    hipLaunchKernelGGL((clc::res_build_kernel<512>), dim3(1), dim3(512), 0, h->stream, d_aos, p.d_rec_off, p.d_gid, p.d_starts, n,
+                       (long long)p.G, p.d_res_row, reinterpret_cast<clc::ResLane*>(res->d_desc), res->d_xy, (double*)nullptr);
+    CLC_HIP(hipGetLastError());
+    res->lanes = 512; res->max_ppl = p.ppl; res->uni_ppl = p.ppl; res->rows = p.ppl; res->with_z = false; res->ok = true;
+  } else if (res != nullptr) {
+    res->ok = false;
+    if (!p.any_z) {
+      // batches: 256 lanes (two problems per CU) unless flag 8192; a single problem: 512 lanes (it has its CU to itself)
+      const int first_try = (d_prob_row == nullptr || (h->launch_flags & clc::FLAG_RESIDENT_WG512) != 0) ? 512 : 256;
+      rc = build_resident(h, *res, first_try, d_aos, n, p.P, p.G, p.d_rec_off, p.d_gid, p.d_starts);
+      if (rc != CLC_OK) return rc;
+    } else if (d_prob_row != nullptr) {
+      // a BATCH whose points carry z: the 512-lane form with 24-byte slots (one problem per CU; resident_solve_kernel<.., WITH_Z>) — the
+      // batch is still read from HBM once per solve.  (A single problem with z: the cooperative kernel's z form, below.)
+      rc = build_resident(h, *res, 512, d_aos, n, p.P, p.G, p.d_rec_off, p.d_gid, p.d_starts, kResPRz + kResPLz, /*with_z=*/true);
+      if (rc != CLC_OK) return rc;
+    }
+  }
+  if (coop != nullptr) {
+    coop->ok = false;
+    // (records with p.z != 0: the cooperative kernel's WITH_Z form holds 24-byte slots)
+    // (clc_set_small_on_coop: the cooperative layout also for a problem one workgroup holds — clc_solve then prefers it)
+    if (p.P == 1 && n > 0 && h->num_cus >= clc::COOP_WGS && (h->small_on_coop || !(res != nullptr && res->ok))) {
+      // the one problem in chunks of equal record counts, one per workgroup (a chunk may begin and end inside a scan: res_scan_extent):
+      // COOP_WGS of them, or COOP_SMALL_WGS where that leaves a lane at most kCoopSmallMaxPpl points (the one-hop form of the kernel)
+      const int cap_ppl = p.any_z ? clc::COOP_PR_Z + clc::COOP_PL_Z : clc::COOP_PR + clc::COOP_PL;
+      // Up to this many points per lane of 32 workgroups the one-hop form runs (a host-side choice between two launch forms of the same
+      // kernel).  Round 5 sweep (scripts/r05_small_form.py, us per pass, 32 / 256 workgroups): 1e5 observations 5.00 / 5.61, 1.3e5
+      // 5.61 / 5.54, 1.6e5 5.55 / 5.51, 2e5 5.94 / 5.53 — a lane's extra points cost 0.065 us each, the second hop ~1 us: 13 points
+      // per lane (106 496 observations) is where the one-hop form stops paying (round 4: 10).
+      constexpr int kCoopSmallMaxPpl = 13;
+      int small_cap = kCoopSmallMaxPpl;
+#ifdef CLC_TEST_HOOKS
+      if (const char* e = std::getenv("CLC_COOP_SMALL_MAX_PPL")) small_cap = std::max(1, std::atoi(e));  // (tuning hook, hooks build only: scripts/r05_small_form.py)
+#endif
+      const int small_ppl = std::min(small_cap, cap_ppl);
+      const bool small_ok = n <= (long long)clc::COOP_SMALL_WGS * clc::COOP_NL * small_ppl && (h->auto_disable & 8) == 0;
+      for (int attempt = small_ok ? 0 : 1; attempt < 2 && !coop->ok; ++attempt) {
+        const int wgs = attempt == 0 ? clc::COOP_SMALL_WGS : clc::COOP_WGS;
+        std::vector<long long> chunk((size_t)wgs + 1);
+        for (int c = 0; c <= wgs; ++c) chunk[c] = (long long)((__int128)n * c / wgs);
+        DevBuf<long long> bchunk(&h->pool);
+        CLC_HIP(bchunk.alloc(chunk.size()));
+        CLC_HIP(hipMemcpyAsync(bchunk.p, chunk.data(), chunk.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        CLC_HIP(hipStreamSynchronize(h->stream));
+        rc = build_resident(h, *coop, clc::COOP_NL, d_aos, n, (size_t)wgs, p.G, bchunk.p, p.d_gid, p.d_starts,
+                            attempt == 0 ? small_ppl : cap_ppl, p.any_z);
+        if (rc != CLC_OK) return rc;
+        coop->wgs = wgs;
+      }  // (the small form's layout did not fit — scans that leave half-filled lanes: the 256-workgroup form is tried next)
+    }
+  }
+  return CLC_OK;
+}
+
 }  // namespace
 
 namespace clc_abi {
@@ -136,16 +255,19 @@ void warm_layouts() {
   warm_kernel(reinterpret_cast<const void*>(&clc::flatten_kernel));
 }
 
+// The device pipeline: the plan on the device, the builds enqueued from it.  (The row plan is made after the compact layout is enqueued:
+// its read-back then waits for the compact build too.)
 int build_layouts(clc_handle* h, const double* d_aos, size_t n_total, const std::vector<long long>& rec_off,
-                  const std::vector<long long>& tile_off, const LayoutTargets& T) {
-  *T.compact_ok = false;
-  *T.rows_ok = false;
-  *T.n_groups = 0;
-  *T.n_rows = 0;
+                  const std::vector<long long>& tile_off, StreamLayout& L, long long* d_prob_row, ResLayout* res, ResLayout* coop) {
+  L.invalidate();
+  L.n_groups = L.n_rows = 0;
   const size_t P = rec_off.size() - 1;
   if (n_total == 0 || P == 0) return CLC_OK;
   if (n_total >= 0xFFFFFFF0ull) return CLC_OK;  // scan indices are 32-bit; such arrays keep the 64-byte tiles
-  const long long n = (long long)n_total;
+  LayoutPlan p;
+  p.P = P; p.n = (long long)n_total; p.tiles = (size_t)tile_off[P];
+  for (size_t k = 0; k < P; ++k) p.max_tiles = std::max(p.max_tiles, tile_off[k + 1] - tile_off[k]);
+  const long long n = p.n;
   const int threads = 256;
   const long long scan_blocks = (n + clc::SCAN_CHUNK - 1) / clc::SCAN_CHUNK;
   DevBuf<unsigned char> bflag(&h->pool);
@@ -172,138 +294,49 @@ int build_layouts(clc_handle* h, const double* d_aos, size_t n_total, const std:
   CLC_HIP(hipMemcpyAsync(&last_gid, bgid.p + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
   CLC_HIP(hipMemcpyAsync(&any_z, bzflag.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
   CLC_HIP(hipStreamSynchronize(h->stream));
-  const size_t G = (size_t)last_gid + 1;
-  // fewer than 4 points per scan on average: the streaming layouts do not pay (the step chain keeps the 64-byte tiles) — the on-chip
-  // layouts, where a lane carries its own plane anyway, are still built
-  const bool sparse = G * 4 > n_total;
-  if (sparse && T.res == nullptr && T.coop == nullptr) return CLC_OK;
+  p.set_scans((size_t)last_gid + 1);
+  p.any_z = any_z != 0;
+  if (p.sparse && res == nullptr && coop == nullptr) return CLC_OK;
+  const size_t G = p.G;
   DevBuf<long long> bstarts(&h->pool);
   CLC_HIP(bstarts.alloc(G + 1));
   hipLaunchKernelGGL(clc::scan_starts_kernel, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, h->stream,
                      bflag.p, bgid.p, n, (long long)G, bstarts.p);
   CLC_HIP(hipGetLastError());
-  // ---- compact layout ----
-  const size_t total_tiles = (size_t)tile_off[P];
-  rc = ensure_bytes(T.d_ct, T.ct_cap, std::max<size_t>(total_tiles, 1) * clc::CTILE_DOUBLES * sizeof(double));
+  p.d_rec_off = broff.p; p.d_tile_off = btoff.p; p.d_starts = bstarts.p; p.d_gid = bgid.p;
+  rc = emit_compact(h, d_aos, p, L);
   if (rc != CLC_OK) return rc;
-  rc = ensure_bytes(T.d_gr, T.gr_cap, G * clc::GROUP_DOUBLES * sizeof(double));
-  if (rc != CLC_OK) return rc;
-  hipLaunchKernelGGL(clc::build_groups_dev_kernel, dim3((unsigned)((G + threads - 1) / threads)), dim3(threads), 0, h->stream,
-                     d_aos, bstarts.p, (long long)G, *T.d_gr);
-  {
-    long long max_padded = 0;
-    for (size_t k = 0; k < P; ++k) max_padded = std::max(max_padded, (tile_off[k + 1] - tile_off[k]) * clc::TILE);
-    const unsigned ydim = (unsigned)std::min<long long>(4096, std::max<long long>(1, (max_padded + threads - 1) / threads));
-    hipLaunchKernelGGL(clc::build_ctiles_kernel, dim3((unsigned)P, ydim), dim3(threads), 0, h->stream, d_aos, bgid.p, broff.p,
-                       btoff.p, *T.d_ct);
-  }
-  CLC_HIP(hipGetLastError());
-  // ---- row layout ----
-  bool rows_ok = false;
-  long long R = 0;
+  // rows per scan (scan_rows_kernel) -> first row of every scan
   DevBuf<unsigned int> brows(&h->pool), brbeg(&h->pool);
   DevBuf<unsigned long long> btot2(&h->pool);
-  const size_t row_doubles = any_z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES;
-  if (T.rows_z) *T.rows_z = any_z != 0;
-  {
-    const long long gblocks = ((long long)G + clc::SCAN_CHUNK - 1) / clc::SCAN_CHUNK;
-    CLC_HIP(brows.alloc(G));
-    CLC_HIP(brbeg.alloc(G + 1));
-    CLC_HIP(btot2.alloc((size_t)gblocks + 1));
-    hipLaunchKernelGGL(clc::scan_rows_kernel, dim3((unsigned)((G + threads - 1) / threads)), dim3(threads), 0, h->stream,
-                       bstarts.p, (long long)G, brows.p);
-    CLC_HIP(hipMemsetAsync(brbeg.p, 0, sizeof(unsigned int), h->stream));
-    rc = device_scan<unsigned int>(h, brows.p, (long long)G, 0u, brbeg.p + 1, btot2.p);
-    if (rc != CLC_OK) return rc;
-    unsigned int total_rows = 0;
-    CLC_HIP(hipMemcpyAsync(&total_rows, brbeg.p + G, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-    CLC_HIP(hipStreamSynchronize(h->stream));
-    R = (long long)total_rows;
-    rows_ok = !sparse && R > 0 && (size_t)R * clc::ROW <= 3 * n_total + 64 * P;  // rows at least a third full on average
-  }
-  if (rows_ok) {
-    // one padding row each: the streaming loop's prologue loads run unconditionally from clamped row indices
-    rc = ensure_bytes(T.d_rxy, T.rxy_cap, ((size_t)R + 1) * row_doubles * sizeof(double));
-    if (rc != CLC_OK) return rc;
-    rc = ensure_bytes(T.d_rdesc, T.rdesc_cap, ((size_t)R + 1) * sizeof(clc::RowDesc) + clc::wave_split_bytes(R));  // + the wave split table
-    if (rc != CLC_OK) return rc;
-    CLC_HIP(hipMemsetAsync(*T.d_rxy + (size_t)R * row_doubles, 0, row_doubles * sizeof(double), h->stream));
-    CLC_HIP(hipMemsetAsync(reinterpret_cast<char*>(*T.d_rdesc) + (size_t)R * sizeof(clc::RowDesc), 0, sizeof(clc::RowDesc), h->stream));
-    const long long slots = R * clc::ROW;
-    hipLaunchKernelGGL(clc::build_rows_kernel, dim3((unsigned)((slots + threads - 1) / threads)), dim3(threads), 0, h->stream,
-                       d_aos, bstarts.p, brbeg.p, (long long)G, R, (int)row_doubles, *T.d_rxy, reinterpret_cast<clc::RowDesc*>(*T.d_rdesc));
-    if (T.d_prob_row)
-      hipLaunchKernelGGL(clc::problem_rows_kernel, dim3((unsigned)((P + 1 + threads - 1) / threads)), dim3(threads), 0,
-                         h->stream, broff.p, bgid.p, brbeg.p, (long long)P, n, R, *T.d_prob_row);
-    CLC_HIP(hipGetLastError());
-  }
-  if (T.res != nullptr) {
-    T.res->ok = false;
-    if (!any_z) {
-      // batches: 256 lanes (two problems per CU) unless flag 8192; a single problem: 512 lanes (it has its CU to itself)
-      const int first_try = (T.d_prob_row == nullptr || (h->launch_flags & clc::FLAG_RESIDENT_WG512) != 0) ? 512 : 256;
-      rc = build_resident(h, *T.res, first_try, d_aos, n, P, G, broff.p, bgid.p, bstarts.p);
-      if (rc != CLC_OK) return rc;
-    } else if (T.d_prob_row != nullptr) {
-      // a BATCH whose points carry z: the 512-lane form with 24-byte slots (one problem per CU; resident_solve_kernel<.., WITH_Z>) — the
-      // batch is still read from HBM once per solve.  (A single problem with z: the cooperative kernel's z form, below.)
-      rc = build_resident(h, *T.res, 512, d_aos, n, P, G, broff.p, bgid.p, bstarts.p, kResPRz + kResPLz, /*with_z=*/true);
-      if (rc != CLC_OK) return rc;
-    }
-  }
-  if (T.coop != nullptr) {
-    T.coop->ok = false;
-    // (records with p.z != 0: the cooperative kernel's WITH_Z form holds 24-byte slots)
-    // (clc_set_small_on_coop: the cooperative layout also for a problem one workgroup holds — clc_solve then prefers it)
-    const bool small_on_coop = h->small_on_coop;
-    if (P == 1 && n > 0 && h->num_cus >= clc::COOP_WGS && (small_on_coop || !(T.res != nullptr && T.res->ok))) {
-      // the one problem in chunks of equal record counts, one per workgroup (a chunk may begin and end inside a scan: res_scan_extent):
-      // COOP_WGS of them, or COOP_SMALL_WGS where that leaves a lane at most kCoopSmallMaxPpl points (the one-hop form of the kernel)
-      const int cap_ppl = any_z ? clc::COOP_PR_Z + clc::COOP_PL_Z : clc::COOP_PR + clc::COOP_PL;
-      // Up to this many points per lane of 32 workgroups the one-hop form runs (a host-side choice between two launch forms of the same
-      // kernel).  Round 5 sweep (scripts/r05_small_form.py, us per pass, 32 / 256 workgroups): 1e5 observations 5.00 / 5.61, 1.3e5
-      // 5.61 / 5.54, 1.6e5 5.55 / 5.51, 2e5 5.94 / 5.53 — a lane's extra points cost 0.065 us each, the second hop ~1 us: 13 points
-      // per lane (106 496 observations) is where the one-hop form stops paying (round 4: 10).
-      constexpr int kCoopSmallMaxPpl = 13;
-      int small_cap = kCoopSmallMaxPpl;
-#ifdef CLC_TEST_HOOKS
-      if (const char* e = std::getenv("CLC_COOP_SMALL_MAX_PPL")) small_cap = std::max(1, std::atoi(e));  // (tuning hook, hooks build only: scripts/r05_small_form.py)
-#endif
-      const int small_ppl = std::min(small_cap, cap_ppl);
-      const bool small_ok = n <= (long long)clc::COOP_SMALL_WGS * clc::COOP_NL * small_ppl && (h->auto_disable & 8) == 0;
-      for (int attempt = small_ok ? 0 : 1; attempt < 2 && !T.coop->ok; ++attempt) {
-        const int wgs = attempt == 0 ? clc::COOP_SMALL_WGS : clc::COOP_WGS;
-        std::vector<long long> chunk((size_t)wgs + 1);
-        for (int c = 0; c <= wgs; ++c) chunk[c] = (long long)((__int128)n * c / wgs);
-        DevBuf<long long> bchunk(&h->pool);
-        CLC_HIP(bchunk.alloc(chunk.size()));
-        CLC_HIP(hipMemcpyAsync(bchunk.p, chunk.data(), chunk.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        CLC_HIP(hipStreamSynchronize(h->stream));
-        rc = build_resident(h, *T.coop, clc::COOP_NL, d_aos, n, (size_t)wgs, G, bchunk.p, bgid.p, bstarts.p,
-                            attempt == 0 ? small_ppl : cap_ppl, any_z != 0);
-        if (rc != CLC_OK) return rc;
-        T.coop->wgs = wgs;
-      }  // (the small form's layout did not fit — scans that leave half-filled lanes: the 256-workgroup form is tried next)
-    }
-  }
+  const long long gblocks = ((long long)G + clc::SCAN_CHUNK - 1) / clc::SCAN_CHUNK;
+  CLC_HIP(brows.alloc(G));
+  CLC_HIP(brbeg.alloc(G + 1));
+  CLC_HIP(btot2.alloc((size_t)gblocks + 1));
+  hipLaunchKernelGGL(clc::scan_rows_kernel, dim3((unsigned)((G + threads - 1) / threads)), dim3(threads), 0, h->stream,
+                     bstarts.p, (long long)G, brows.p);
+  CLC_HIP(hipMemsetAsync(brbeg.p, 0, sizeof(unsigned int), h->stream));
+  rc = device_scan<unsigned int>(h, brows.p, (long long)G, 0u, brbeg.p + 1, btot2.p);
+  if (rc != CLC_OK) return rc;
+  unsigned int total_rows = 0;
+  CLC_HIP(hipMemcpyAsync(&total_rows, brbeg.p + G, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  p.set_rows((long long)total_rows);
+  p.d_row_begin = brbeg.p;
+  rc = emit_rows_and_lanes(h, d_aos, p, L, d_prob_row, res, coop);
+  if (rc != CLC_OK) return rc;
   CLC_HIP(hipStreamSynchronize(h->stream));  // the temporaries above are freed on return
-  *T.n_groups = (long long)G;
-  *T.compact_ok = !sparse;
-  *T.n_rows = R;
-  *T.rows_ok = rows_ok;
+  p.publish(L);
   return CLC_OK;
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Small single problems — the reference's own sizes (main/calibr_simulation.cpp: 50 poses x ~114 points; main/calibr_offline.cpp:
-// O(10^2) poses): at most 512 x 22 records, p.z == 0, so that ONE workgroup holds the problem.  The generic pipeline above finds the
-// scan structure on the device and reads it back three times (scan count, row count, points per lane) plus two synchronisations for
-// host temporaries: ~0.2 ms of waiting for ~20 us of kernels.  Here the HOST knows the structure — from the stored scans' offsets and tag
-// poses (clc_select_observations) or from the records themselves (clc_upload) —, plans the layouts (scan starts, rows per scan, points
-// per lane: the arithmetic of scan_rows_kernel / res_plan_kernel) and enqueues ONE copy of the tables + the same build kernels, without
-// a single read-back or synchronisation.  Same kernels, same tables: the layouts are bit for bit the generic pipeline's
-// (tests/test_gpu_edge_cases.py::test_small_problems_planned_on_the_host_...).
+// O(10^2) poses): at most 512 x 22 records, p.z == 0, so that ONE workgroup holds the problem.  The device pipeline above reads the
+// scan structure back twice and waits on host temporaries: ~0.2 ms of waiting for ~20 us of kernels.  Here the HOST knows the scans —
+// from the stored scans (clc_select_observations) or from the records themselves (clc_upload) — and plans the layouts, with the
+// arithmetic of scan_rows_kernel / res_plan_kernel; ONE copy of the tables and the same builds follow, without a read-back or a
+// synchronisation (tests/test_gpu_edge_cases.py::test_small_problems_planned_on_the_host_...).
 struct SmallFlatten {  // clc_select_observations: the records are built on the device first (flatten_kernel)
   int n_poses;
   bool linefit, boundary;
@@ -314,129 +347,111 @@ constexpr size_t kSmallMaxRecords = (size_t)512 * (kResPR512 + kResPL512);
 
 static size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
 
-// *used = false: not a case for this path (nothing was enqueued) — the caller runs the generic pipeline.
-int small_fast_upload(clc_handle* h, const std::vector<long long>& starts, long long n, bool any_z, const clc_observation* host_records,
-                      const SmallFlatten* fj, bool* used) {
-  *used = false;
-  const size_t G = starts.size() - 1;
-  if (!h->fast_small || n <= 0 || (size_t)n > kSmallMaxRecords || any_z || h->small_on_coop || G == 0 || G > 512) return CLC_OK;
-  if ((h->launch_flags & clc::FLAG_NO_RESIDENT) != 0) return CLC_OK;
-  // ---- the plan (host): rows per scan (scan_rows_kernel), points per lane of the 512-lane layout (res_plan_kernel) ----
-  const bool sparse = G * 4 > (size_t)n;
-  std::vector<unsigned int> brbeg(G + 1, 0u);
-  for (size_t g = 0; g < G; ++g) brbeg[g + 1] = brbeg[g] + (unsigned int)((starts[g + 1] - starts[g] + clc::ROW - 1) / clc::ROW);
-  const long long R = (long long)brbeg[G];
-  const bool rows_ok = !sparse && R > 0 && (size_t)R * clc::ROW <= 3 * (size_t)n + 64;
-  int ppl = 0;
-  for (long long c = std::max<long long>(1, (n + 511) / 512); c <= kResPR512 + kResPL512 && ppl == 0; ++c) {
-    long long lanes = 0;
-    for (size_t g = 0; g < G && lanes <= 512; ++g) lanes += (starts[g + 1] - starts[g] + c - 1) / c;
-    if (lanes <= 512) ppl = (int)c;
-  }
-  if (ppl == 0) return CLC_OK;  // scans that leave too many half-filled lanes: the generic path (cooperative layout)
-  // ---- staging: [flatten's record offsets][rec_off, tile_off of the one problem][starts][gid][row_begin][res_row][records] ----
-  const size_t P1 = fj ? (size_t)fj->n_poses + 1 : 0;
-  const size_t o_foff = 0, o_off = align8(o_foff + P1 * 8), o_starts = o_off + 4 * 8, o_gid = o_starts + (G + 1) * 8,
-               o_brbeg = align8(o_gid + (size_t)n * 4), o_row = align8(o_brbeg + (G + 1) * 4), o_rec = align8(o_row + 8),
-               total = o_rec + (host_records ? (size_t)n * sizeof(clc_observation) : 0);
-  CLC_HIP(hipSetDevice(h->device));
-  if (total > h->stage_cap) {
+// The single problem's layouts are being replaced: forget the current ones (and the selection they were built from).
+void forget_layouts(clc_handle* h) {
+  h->obs.invalidate(); h->sres.ok = h->cres.ok = false; h->split_grid = -1; h->selection_key = -1;
+}
+
+// The pinned staging block of the small-problem path (+ its device twin), at least `bytes` long and free to be written.
+int ensure_stage(clc_handle* h, size_t bytes) {
+  if (bytes > h->stage_cap) {
     CLC_HIP(hipStreamSynchronize(h->stream));
     if (h->h_stage) CLC_HIP(hipHostFree(h->h_stage));
     if (h->d_stage) CLC_HIP(hipFree(h->d_stage));
     h->h_stage = h->d_stage = nullptr; h->stage_cap = 0; h->stage_busy = false;
-    const size_t cap = std::max<size_t>(total + total / 2, (size_t)256 << 10);
+    const size_t cap = std::max<size_t>(bytes + bytes / 2, (size_t)256 << 10);
     CLC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_stage), cap, hipHostMallocDefault));
     CLC_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stage), cap));
     h->stage_cap = cap;
   }
   if (!h->ev_stage) CLC_HIP(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
   if (h->stage_busy) CLC_HIP(hipEventSynchronize(h->ev_stage));  // the previous copy out of the pinned block (long done in practice)
-  {
-    char* b = h->h_stage;
-    if (fj) std::memcpy(b + o_foff, fj->rec_off->data(), P1 * 8);
-    long long* off = reinterpret_cast<long long*>(b + o_off);
-    off[0] = 0; off[1] = n; off[2] = 0; off[3] = (n + clc::TILE - 1) / clc::TILE;
-    std::memcpy(b + o_starts, starts.data(), (G + 1) * 8);
-    unsigned int* gid = reinterpret_cast<unsigned int*>(b + o_gid);
-    for (size_t g = 0; g < G; ++g)
-      for (long long k = starts[g]; k < starts[g + 1]; ++k) gid[k] = (unsigned int)g;
-    std::memcpy(b + o_brbeg, brbeg.data(), (G + 1) * 4);
-    unsigned int* row = reinterpret_cast<unsigned int*>(b + o_row);
-    row[0] = 0u; row[1] = (unsigned int)ppl;
-    if (host_records) std::memcpy(b + o_rec, host_records, (size_t)n * sizeof(clc_observation));
+  return CLC_OK;
+}
+
+// The host planner: rows per scan, points per lane of the 512-lane layout, and the tables staged and copied to the device —
+// [flatten's record offsets][rec_off, tile_off of the one problem][starts][gid][row_begin][res_row][records].  *used = false: not a
+// case for this path (nothing was enqueued).  Otherwise the handle's layouts are forgotten and the copy is enqueued; *d_records /
+// *d_foff: the staged records / flatten offsets.
+int plan_small_on_host(clc_handle* h, const std::vector<long long>& starts, long long n, bool any_z, const clc_observation* host_records,
+                       const SmallFlatten* fj, LayoutPlan* p, const double** d_records, const long long** d_foff, bool* used) {
+  *used = false;
+  const size_t G = starts.size() - 1;
+  if (!h->fast_small || n <= 0 || (size_t)n > kSmallMaxRecords || any_z || h->small_on_coop || G == 0 || G > 512) return CLC_OK;
+  if ((h->launch_flags & clc::FLAG_NO_RESIDENT) != 0) return CLC_OK;
+  p->P = 1; p->n = n; p->tiles = (size_t)((n + clc::TILE - 1) / clc::TILE); p->max_tiles = (long long)p->tiles;
+  p->set_scans(G);
+  std::vector<unsigned int> brbeg(G + 1, 0u);
+  for (size_t g = 0; g < G; ++g) brbeg[g + 1] = brbeg[g] + (unsigned int)((starts[g + 1] - starts[g] + clc::ROW - 1) / clc::ROW);
+  p->set_rows((long long)brbeg[G]);
+  for (long long c = std::max<long long>(1, (n + 511) / 512); c <= kResPR512 + kResPL512 && p->ppl == 0; ++c) {
+    long long lanes = 0;
+    for (size_t g = 0; g < G && lanes <= 512; ++g) lanes += (starts[g + 1] - starts[g] + c - 1) / c;
+    if (lanes <= 512) p->ppl = (int)c;
   }
+  if (p->ppl == 0) return CLC_OK;  // scans that leave too many half-filled lanes: the generic path (cooperative layout)
+  const size_t P1 = fj ? (size_t)fj->n_poses + 1 : 0;
+  const size_t o_foff = 0, o_off = align8(o_foff + P1 * 8), o_starts = o_off + 4 * 8, o_gid = o_starts + (G + 1) * 8,
+               o_brbeg = align8(o_gid + (size_t)n * 4), o_row = align8(o_brbeg + (G + 1) * 4), o_rec = align8(o_row + 8),
+               total = o_rec + (host_records ? (size_t)n * sizeof(clc_observation) : 0);
+  CLC_HIP(hipSetDevice(h->device));
+  int rc = ensure_stage(h, total);
+  if (rc != CLC_OK) return rc;
+  char* b = h->h_stage;
+  if (fj) std::memcpy(b + o_foff, fj->rec_off->data(), P1 * 8);
+  long long* off = reinterpret_cast<long long*>(b + o_off);
+  off[0] = 0; off[1] = n; off[2] = 0; off[3] = (long long)p->tiles;
+  std::memcpy(b + o_starts, starts.data(), (G + 1) * 8);
+  unsigned int* gid = reinterpret_cast<unsigned int*>(b + o_gid);
+  for (size_t g = 0; g < G; ++g)
+    for (long long k = starts[g]; k < starts[g + 1]; ++k) gid[k] = (unsigned int)g;
+  std::memcpy(b + o_brbeg, brbeg.data(), (G + 1) * 4);
+  unsigned int* row = reinterpret_cast<unsigned int*>(b + o_row);
+  row[0] = 0u; row[1] = (unsigned int)p->ppl;
+  if (host_records) std::memcpy(b + o_rec, host_records, (size_t)n * sizeof(clc_observation));
   // from here on things are enqueued: an error leaves the handle without observations rather than with half of them
-  h->compact_ok = false; h->rows_ok = false; h->sres.ok = false; h->cres.ok = false; h->split_grid = -1; h->selection_key = -1;
+  forget_layouts(h);
   h->n_obs = 0;
   CLC_HIP(hipMemcpyAsync(h->d_stage, h->h_stage, total, hipMemcpyHostToDevice, h->stream));
   CLC_HIP(hipEventRecord(h->ev_stage, h->stream));
   h->stage_busy = true;
-  const long long* d_off = reinterpret_cast<const long long*>(h->d_stage + o_off);
-  const long long* d_starts = reinterpret_cast<const long long*>(h->d_stage + o_starts);
-  const unsigned int* d_gid = reinterpret_cast<const unsigned int*>(h->d_stage + o_gid);
-  const unsigned int* d_brbeg = reinterpret_cast<const unsigned int*>(h->d_stage + o_brbeg);
-  const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->d_stage + o_row);
-  const double* d_aos = reinterpret_cast<const double*>(h->d_stage + o_rec);
-  const int threads = 256;
-  int rc = CLC_OK;
+  const char* d = h->d_stage;
+  p->d_rec_off = reinterpret_cast<const long long*>(d + o_off);
+  p->d_tile_off = p->d_rec_off + 2;
+  p->d_starts = reinterpret_cast<const long long*>(d + o_starts);
+  p->d_gid = reinterpret_cast<const unsigned int*>(d + o_gid);
+  p->d_row_begin = reinterpret_cast<const unsigned int*>(d + o_brbeg);
+  p->d_res_row = reinterpret_cast<const unsigned int*>(d + o_row);
+  *d_records = reinterpret_cast<const double*>(d + o_rec);
+  *d_foff = reinterpret_cast<const long long*>(d + o_foff);
+  *used = true;
+  return CLC_OK;
+}
+
+// *used = false: not a case for this path (nothing was enqueued) — the caller runs the device pipeline.
+int small_fast_upload(clc_handle* h, const std::vector<long long>& starts, long long n, bool any_z, const clc_observation* host_records,
+                      const SmallFlatten* fj, bool* used) {
+  LayoutPlan p;
+  const double* d_aos = nullptr;
+  const long long* d_foff = nullptr;
+  int rc = plan_small_on_host(h, starts, n, any_z, host_records, fj, &p, &d_aos, &d_foff, used);
+  if (rc != CLC_OK || !*used) return rc;
   if (fj) {  // the selection's records, built on the device from the resident scans (bitwise clc_flatten_observations')
     rc = ensure_bytes(&h->d_small_aos, &h->small_aos_cap, (size_t)n * sizeof(clc_observation));
     if (rc != CLC_OK) return rc;
     long long* d_soff = reinterpret_cast<long long*>(h->d_soff);
     hipLaunchKernelGGL(clc::flatten_kernel, dim3((unsigned)fj->n_poses), dim3(clc::BLOCK), 0, h->stream, fj->n_poses, h->d_sq, h->d_st, d_soff,
-                       h->d_spts, d_soff + P1, h->d_sptl, fj->linefit ? 1 : 0, fj->boundary ? 1 : 0,
-                       reinterpret_cast<const long long*>(h->d_stage + o_foff), h->d_small_aos);
+                       h->d_spts, d_soff + (fj->n_poses + 1), h->d_sptl, fj->linefit ? 1 : 0, fj->boundary ? 1 : 0, d_foff, h->d_small_aos);
     CLC_HIP(hipGetLastError());
     d_aos = h->d_small_aos;
   }
-  rc = retile_into(h, d_aos, (size_t)n, &h->d_tiles, &h->tiles_cap_bytes);
+  rc = retile_into(h, d_aos, (size_t)n, h->obs);
+  if (rc == CLC_OK) rc = emit_compact(h, d_aos, p, h->obs);
+  if (rc == CLC_OK) rc = emit_rows_and_lanes(h, d_aos, p, h->obs, nullptr, &h->sres, nullptr);
   if (rc != CLC_OK) return rc;
-  // compact layout: group table (what the on-chip kernels take a lane's plane from) + 28-byte tiles
-  const size_t tiles = (size_t)((n + clc::TILE - 1) / clc::TILE);
-  rc = ensure_bytes(&h->d_ctiles, &h->ctiles_cap_bytes, std::max<size_t>(tiles, 1) * clc::CTILE_DOUBLES * sizeof(double));
-  if (rc == CLC_OK) rc = ensure_bytes(&h->d_groups, &h->groups_cap_bytes, G * clc::GROUP_DOUBLES * sizeof(double));
-  if (rc != CLC_OK) return rc;
-  hipLaunchKernelGGL(clc::build_groups_dev_kernel, dim3((unsigned)((G + threads - 1) / threads)), dim3(threads), 0, h->stream, d_aos, d_starts,
-                     (long long)G, h->d_groups);
-  {
-    const long long max_padded = (long long)tiles * clc::TILE;
-    const unsigned ydim = (unsigned)std::min<long long>(4096, std::max<long long>(1, (max_padded + threads - 1) / threads));
-    hipLaunchKernelGGL(clc::build_ctiles_kernel, dim3(1u, ydim), dim3(threads), 0, h->stream, d_aos, d_gid, d_off, d_off + 2, h->d_ctiles);
-  }
-  CLC_HIP(hipGetLastError());
-  if (rows_ok) {  // row layout (one padding row each: see build_layouts)
-    rc = ensure_bytes(&h->d_rxy, &h->rxy_cap_bytes, ((size_t)R + 1) * clc::ROW_DOUBLES * sizeof(double));
-    if (rc == CLC_OK) rc = ensure_bytes(&h->d_rdesc, &h->rdesc_cap_bytes, ((size_t)R + 1) * sizeof(clc::RowDesc) + clc::wave_split_bytes(R));
-    if (rc != CLC_OK) return rc;
-    CLC_HIP(hipMemsetAsync(h->d_rxy + (size_t)R * clc::ROW_DOUBLES, 0, clc::ROW_DOUBLES * sizeof(double), h->stream));
-    CLC_HIP(hipMemsetAsync(reinterpret_cast<char*>(h->d_rdesc) + (size_t)R * sizeof(clc::RowDesc), 0, sizeof(clc::RowDesc), h->stream));
-    const long long slots = R * clc::ROW;
-    hipLaunchKernelGGL(clc::build_rows_kernel, dim3((unsigned)((slots + threads - 1) / threads)), dim3(threads), 0, h->stream, d_aos, d_starts,
-                       d_brbeg, (long long)G, R, (int)clc::ROW_DOUBLES, h->d_rxy, reinterpret_cast<clc::RowDesc*>(h->d_rdesc));
-    CLC_HIP(hipGetLastError());
-  }
-  {  // the 512-lane layout of the single-workgroup solve (build_resident for one problem, first_try = 512)
-    ResLayout& L = h->sres;
-    rc = ensure_bytes(&L.d_row, &L.row_cap, 2 * sizeof(unsigned int));
-    if (rc == CLC_OK) rc = ensure_bytes(&L.d_desc, &L.desc_cap, (size_t)512 * sizeof(clc::ResLane));
-    if (rc == CLC_OK) rc = ensure_bytes(&L.d_xy, &L.xy_cap, ((size_t)ppl + 1) * 512 * 2 * sizeof(double));
-    if (rc != CLC_OK) return rc;
-    CLC_HIP(hipMemcpyAsync(L.d_row, d_row, 2 * sizeof(unsigned int), hipMemcpyDeviceToDevice, h->stream));
-    CLC_HIP(hipMemsetAsync(L.d_xy + (size_t)ppl * 512 * 2, 0, (size_t)512 * 2 * sizeof(double), h->stream));
-    hipLaunchKernelGGL((clc::res_build_kernel<512>), dim3(1), dim3(512), 0, h->stream, d_aos, d_off, d_gid, d_starts, n, (long long)G, d_row,
-                       reinterpret_cast<clc::ResLane*>(L.d_desc), L.d_xy, (double*)nullptr);
-    CLC_HIP(hipGetLastError());
-    L.lanes = 512; L.max_ppl = ppl; L.uni_ppl = ppl; L.rows = ppl; L.with_z = false; L.ok = true;
-  }
+  p.publish(h->obs);
   h->n_obs = (size_t)n;
-  h->n_groups = (long long)G;
-  h->compact_ok = !sparse;
-  h->n_rows = R;
-  h->rows_ok = rows_ok;
-  h->rows_z = false;
   ++h->fast_small_uploads;
-  *used = true;
   return CLC_OK;
 }
 
@@ -517,28 +532,20 @@ int clc_flatten_observations(int n_poses, const double* tag_q_wxyz, const double
 int clc_upload_device(clc_handle* h, const clc_observation* records_dev, size_t n) {
   if (!h || (n > 0 && !records_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_upload_device: bad argument");
   CLC_HIP(hipSetDevice(h->device));
-  h->compact_ok = false;
-  h->rows_ok = false;
-  h->sres.ok = false;
-  h->cres.ok = false;
-  h->split_grid = -1;
-  h->selection_key = -1;
-  int rc = retile_into(h, reinterpret_cast<const double*>(records_dev), n, &h->d_tiles, &h->tiles_cap_bytes);
+  forget_layouts(h);
+  int rc = retile_into(h, reinterpret_cast<const double*>(records_dev), n, h->obs);
   if (rc != CLC_OK) return rc;
   CLC_HIP(hipStreamSynchronize(h->stream));
   h->n_obs = n;
   const std::vector<long long> rec_off = {0, (long long)n};
   const std::vector<long long> tile_off = {0, (long long)((n + clc::TILE - 1) / clc::TILE)};
-  const LayoutTargets T = {&h->d_ctiles, &h->ctiles_cap_bytes, &h->d_groups, &h->groups_cap_bytes, &h->n_groups, &h->compact_ok,
-                           &h->d_rxy, &h->rxy_cap_bytes, &h->d_rdesc, &h->rdesc_cap_bytes, &h->n_rows, &h->rows_ok, nullptr,
-                           // a problem one workgroup can hold (<= 512 lanes x 22 points) also gets the lane layout: clc_solve then runs
-                           // its whole LM loop in ONE single-workgroup launch from registers + LDS (solve_resident_single)
-                           n <= (size_t)512 * (kResPR512 + kResPL512) ? &h->sres : nullptr, &h->rows_z,
-                           // what one workgroup cannot hold (more points; or more than 512 scans, or scans whose lengths leave
-                           // too many half-filled lanes: a lane holds points of ONE scan), up to 65 536 lanes x 40 points, is
-                           // dealt to 256 workgroups: the cooperative solve (clc_coop.hpp)
-                           n <= (size_t)clc::COOP_WGS * clc::COOP_NL * (clc::COOP_PR + clc::COOP_PL) ? &h->cres : nullptr};
-  return build_layouts(h, reinterpret_cast<const double*>(records_dev), n, rec_off, tile_off, T);
+  // a problem one workgroup can hold (<= 512 lanes x 22 points) also gets the lane layout: clc_solve then runs its whole LM loop in
+  // ONE single-workgroup launch from registers + LDS (solve_resident_single)
+  ResLayout* res = n <= kSmallMaxRecords ? &h->sres : nullptr;
+  // what one workgroup cannot hold (more points; or more than 512 scans, or scans whose lengths leave too many half-filled lanes: a
+  // lane holds points of ONE scan), up to 65 536 lanes x 40 points, is dealt to 256 workgroups: the cooperative solve (clc_coop.hpp)
+  ResLayout* coop = n <= (size_t)clc::COOP_WGS * clc::COOP_NL * (clc::COOP_PR + clc::COOP_PL) ? &h->cres : nullptr;
+  return build_layouts(h, reinterpret_cast<const double*>(records_dev), n, rec_off, tile_off, h->obs, nullptr, res, coop);
 }
 
 int clc_upload(clc_handle* h, const clc_observation* records, size_t n) {
@@ -741,13 +748,8 @@ int upload_batched_impl(clc_handle* h, const clc_observation* records, bool on_d
   h->batch_max_tiles = max_tiles;
   const size_t total_tiles = (size_t)tile_off[P];
   h->batch_total_tiles = total_tiles;
-  const size_t bytes = std::max<size_t>(total_tiles, 1) * clc::TILE_DOUBLES * sizeof(double);
-  if (bytes > h->btiles_cap_bytes) {
-    if (h->d_btiles) CLC_HIP(hipFree(h->d_btiles));
-    h->d_btiles = nullptr; h->btiles_cap_bytes = 0;
-    CLC_HIP(hipMalloc(&h->d_btiles, bytes));
-    h->btiles_cap_bytes = bytes;
-  }
+  const int rc = ensure_bytes(&h->batch.d_tiles, &h->batch.tiles_cap, std::max<size_t>(total_tiles, 1) * clc::TILE_DOUBLES * sizeof(double));
+  if (rc != CLC_OK) return rc;
   if (P > h->problems_cap) {
     void* olds[] = {h->d_tile_off, h->d_nobs, h->d_states, h->d_results, h->d_prob_row};
     for (void* p : olds) if (p) CLC_HIP(hipFree(p));
@@ -789,24 +791,18 @@ int upload_batched_impl(clc_handle* h, const clc_observation* records, bool on_d
   long long* d_off = boff.p;
   CLC_HIP(hipMemcpy(d_off, rel.data(), sizeof(long long) * (P + 1), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(clc::retile_batched_kernel, dim3((unsigned)P), dim3(256), 0, h->stream, d_aos, d_off,
-                     h->d_tile_off, h->d_btiles);
+                     h->d_tile_off, h->batch.d_tiles);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   int crc = CLC_OK;
-  h->bcompact_ok = false;
-  h->brows_ok = false;
+  h->batch.invalidate();
   h->bres.ok = false;
   h->results_valid = 0;
-  if (e == hipSuccess && d_aos) {
-    const LayoutTargets T = {&h->d_bctiles, &h->bctiles_cap_bytes, &h->d_bgroups, &h->bgroups_cap_bytes, &h->bn_groups,
-                             &h->bcompact_ok, &h->d_brxy, &h->brxy_cap_bytes, &h->d_brdesc, &h->brdesc_cap_bytes, &h->bn_rows,
-                             &h->brows_ok, &h->d_prob_row, &h->bres, &h->brows_z};
-    crc = build_layouts(h, d_aos, n_total, rel, tile_off, T);
-  }
+  if (e == hipSuccess && d_aos) crc = build_layouts(h, d_aos, n_total, rel, tile_off, h->batch, h->d_prob_row, &h->bres, nullptr);
   if (e != hipSuccess) return fail(CLC_ERR_HIP, "clc_upload_batched: retile", e);
   if (crc != CLC_OK) return crc;
   h->batch_max_rows = 0;
-  if (h->brows_ok) {  // O(P) words back: the whole-solve kernel is chosen on the real longest problem, not an estimate
+  if (h->batch.rows_ok) {  // O(P) words back: the whole-solve kernel is chosen on the real longest problem, not an estimate
     std::vector<long long> pr(P + 1);
     CLC_HIP(hipMemcpy(pr.data(), h->d_prob_row, sizeof(long long) * (P + 1), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < P; ++k) h->batch_max_rows = std::max(h->batch_max_rows, pr[k + 1] - pr[k]);

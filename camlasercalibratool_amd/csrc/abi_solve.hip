@@ -11,10 +11,10 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
                    const clc::Pose7& pose_arg, int use_pose_arg) {
   const int fl = h->launch_flags;
   const bool pf = (fl & clc::FLAG_PREFETCH) != 0, nt = (fl & clc::FLAG_NONTEMPORAL) != 0;
-  const bool cp = (fl & clc::FLAG_COMPACT) != 0 && h->compact_ok;
+  const bool cp = (fl & clc::FLAG_COMPACT) != 0 && h->obs.compact_ok;
   const bool big = (fl & clc::FLAG_WG512) != 0;
   if (use_rows(h)) {  // row layout: the Jacobian comes with the moments, a cost-only pass would save nothing
-    const bool rnt = rows_nontemporal(h, h->n_rows, h->rows_z);
+    const bool rnt = rows_nontemporal(h, h->obs.n_rows, h->obs.rows_z);
     // rows in flight per wave: 8 while the array is served by the Infinity Cache, 12 (206 VGPRs, still 2 waves/SIMD) when it
     // streams from HBM with non-temporal loads — throughput there tracks the bytes in flight per CU (profiles/r03_occupancy.md:
     // 4 rows 0.40 of peak, 8 rows 0.81, 12 rows 0.82-0.83, 16 rows 0.81; 3 waves/SIMD cannot hold more than 6 rows each: 0.80);
@@ -22,10 +22,10 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
     const auto launch = [&](auto BIG, auto EQ, auto NT, auto Z) {
       constexpr int BT = BIG ? 512 : 256;
       hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, NT, BT, !EQ, (NT && !Z) ? 12 : clc::ROWS_DEPTH, Z>), dim3(grid), dim3(BT), 0,
-                         h->stream, h->d_rxy, reinterpret_cast<const clc::RowDesc*>(h->d_rdesc), h->n_rows, d_pose, d_status, lf, fl,
+                         h->stream, h->obs.d_rxy, reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc), h->obs.n_rows, d_pose, d_status, lf, fl,
                          h->d_partials, pose_arg, use_pose_arg);
     };
-    if (h->rows_z) {  // rows that carry z: 3:2 wave shares
+    if (h->obs.rows_z) {  // rows that carry z: 3:2 wave shares
       with_flags(launch, big, std::false_type{}, rnt, std::true_type{});
       return;
     }
@@ -33,7 +33,7 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
     // tens of rows per wave and more is 3-7 % faster with the 3:2 old/young shares (scripts/r02_ab.py: 6.2 vs 6.8 us at
     // 1e6 observations, but 15.4 vs 14.7 at 4e6 and 45.1 vs 42.1 at 1.6e7) — the step kernel is not (its wave 0 starts
     // late anyway): it keeps the equal shares at every size.
-    const bool eq = (fl & clc::FLAG_EQUAL_WAVES) != 0 && !(h->launch_auto && h->n_rows > 16LL * 8 * grid);
+    const bool eq = (fl & clc::FLAG_EQUAL_WAVES) != 0 && !(h->launch_auto && h->obs.n_rows > 16LL * 8 * grid);
     if (big) {
       if (eq) ensure_wave_split(h, grid);
       with_flags(launch, std::true_type{}, eq, rnt, std::false_type{});
@@ -49,7 +49,7 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
   const auto launch = [&](auto CP, auto BIG, auto PF, auto NT) {
     constexpr int BT = BIG ? 512 : 256;
     hipLaunchKernelGGL((clc::eval_kernel<WITH_LOSS, WITH_JAC, PF, NT, CP, BT>), dim3(grid), dim3(BT), 0, h->stream,
-                       CP ? h->d_ctiles : h->d_tiles, h->d_groups, (long long)h->n_obs, d_pose, d_status, lf, fl, h->d_partials, pose_arg,
+                       CP ? h->obs.d_ctiles : h->obs.d_tiles, h->obs.d_groups, (long long)h->n_obs, d_pose, d_status, lf, fl, h->d_partials, pose_arg,
                        use_pose_arg);
   };
   const bool beyond_cache = h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes;
@@ -96,7 +96,7 @@ size_t clc_num_observations(const clc_handle* h) { return h ? h->n_obs : 0; }
 int clc_eval(clc_handle* h, const double pose[7], int with_loss, double loss_scale_factor,
              double* cost, double g[6], double H[21]) {
   if (!h || !pose || !cost) return fail(CLC_ERR_INVALID_ARG, "clc_eval: bad argument");
-  if (!h->d_tiles) return fail(CLC_ERR_NO_DATA, "clc_eval: no observations uploaded");
+  if (!h->obs.d_tiles) return fail(CLC_ERR_NO_DATA, "clc_eval: no observations uploaded");
   if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_eval: non-finite pose");
   if (with_loss && !(loss_scale_factor > 0.0)) return fail(CLC_ERR_INVALID_ARG, "clc_eval: loss_scale_factor must be > 0");
   CLC_HIP(hipSetDevice(h->device));
@@ -179,8 +179,8 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
   const bool deep = (h->launch_flags & clc::FLAG_DEEP) != 0 ||
                     (h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes);
   const bool rows = use_rows(h);
-  const bool rows_z = rows && h->rows_z;
-  const bool rows_nt = rows && rows_nontemporal(h, h->n_rows, rows_z);
+  const bool rows_z = rows && h->obs.rows_z;
+  const bool rows_nt = rows && rows_nontemporal(h, h->obs.n_rows, rows_z);
   const bool rows_eq = (h->launch_flags & clc::FLAG_EQUAL_WAVES) != 0 && !rows_z;
   if (rows && rows_eq) ensure_wave_split(h, grid);
   double* rows_buf[2] = {h->d_partials, h->d_partials_b};
@@ -196,7 +196,7 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
     // MODE 0: launch 0, 1: launch 1, 2: the rest
     const auto launch = [&](auto LAYOUT, auto LOSS, auto EQ, auto NT, auto MODE) {
       hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, MODE, LAYOUT, !EQ>), dim3(grid), dim3(512), 0, h->stream, r_in,
-                         LAYOUT ? h->d_rxy : h->d_ctiles, LAYOUT ? h->d_rdesc : h->d_groups, LAYOUT ? (int)h->n_rows : (int)h->n_obs,
+                         LAYOUT ? h->obs.d_rxy : h->obs.d_ctiles, LAYOUT ? h->obs.d_rdesc : h->obs.d_groups, LAYOUT ? (int)h->obs.n_rows : (int)h->n_obs,
                          grid | ((k & 1) << 30), k, r_out, h->d_block, prm);
     };
     const auto at_mode = [&](auto... c) {
@@ -276,7 +276,7 @@ int solve_resident_single(clc_handle* h, const clc_options& opt, double pose[7],
   }
   with_flags([&](auto LOSS, auto CTRL) {
     hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, false, 8, kResPR512, kResPL512, CTRL>), dim3(1), dim3(512), 0, h->stream,
-                       h->sres.d_xy, d_row, d_desc, h->d_groups, h->sres.uni_ppl, opt, d_trace, d_cap, h->d_spose, h->d_ssummary,
+                       h->sres.d_xy, d_row, d_desc, h->obs.d_groups, h->sres.uni_ppl, opt, d_trace, d_cap, h->d_spose, h->d_ssummary,
                        h->d_small, d_done, nullptr);
   }, opt.use_loss != 0, uni_ctrl);
   CLC_HIP(hipGetLastError());
@@ -386,7 +386,7 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
   // Z: 24-byte slots (p.z != 0); ONE: the one-hop form on 32 workgroups
   with_flags([&](auto Z, auto ONE, auto LOSS) {
     hipLaunchKernelGGL((clc::coop_solve_kernel<LOSS, false, Z, ONE>), dim3(wgs), dim3(clc::COOP_THREADS), 0, h->stream, h->cres.d_xy,
-                       h->cres.d_z, d_row, d_desc, h->d_groups, h->cres.uni_ppl, opt, p0, d_trace, d_cap, h->d_board, tag0, h->d_spose,
+                       h->cres.d_z, d_row, d_desc, h->obs.d_groups, h->cres.uni_ppl, opt, p0, d_trace, d_cap, h->d_board, tag0, h->d_spose,
                        h->d_ssummary, h->d_small, d_done, n_wgs);
   }, h->cres.with_z, n_wgs == clc::COOP_SMALL_WGS, opt.use_loss != 0);
   CLC_HIP(hipGetLastError());
@@ -416,7 +416,7 @@ extern "C" {
 int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summary* summary,
               clc_iteration* trace, int trace_cap) {
   if (!h || !pose || !summary || trace_cap < 0) return fail(CLC_ERR_INVALID_ARG, "clc_solve: bad argument");
-  if (!h->d_tiles) return fail(CLC_ERR_NO_DATA, "clc_solve: no observations uploaded");
+  if (!h->obs.d_tiles) return fail(CLC_ERR_NO_DATA, "clc_solve: no observations uploaded");
   if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve: non-finite initial pose");
   clc_options opt;
   if (opt_in) opt = *opt_in; else clc_options_default(&opt);
@@ -441,7 +441,7 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
   const int grid = eval_grid(h, h->n_obs);
   int rc = ensure_partials(h, grid);
   if (rc != CLC_OK) return rc;
-  if ((h->launch_flags & clc::FLAG_STEP) != 0 && (((h->launch_flags & clc::FLAG_COMPACT) != 0 && h->compact_ok) || use_rows(h)) &&
+  if ((h->launch_flags & clc::FLAG_STEP) != 0 && (((h->launch_flags & clc::FLAG_COMPACT) != 0 && h->obs.compact_ok) || use_rows(h)) &&
       (h->launch_flags & clc::FLAG_WG512) != 0 && h->n_obs < 0x7FFFFFFFull &&
       opt.profile_events != 1)  // 1: HIP events around K1, two-kernel path
     return solve_stepped(h, opt, grid, pose, summary, trace, trace_cap, t0);

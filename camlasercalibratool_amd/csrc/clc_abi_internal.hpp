@@ -123,6 +123,28 @@ struct ResLayout {
   int uni_ppl = -1;          // >= 0: every problem has this many points per lane
   long long rows = 0;        // j-rows in all
   bool ok = false;
+  void release() {
+    for (double* p : {d_xy, d_desc, d_row, d_z}) if (p) (void)hipFree(p);
+  }
+};
+
+// The streaming layouts of one observation array (the single problem's, the batch's): 64-byte tiles; their compact copy (28 B/obs:
+// tiles + group table), built at upload when the records compress; the row layout (clc_rows.hpp: xy rows + row descriptors).
+struct StreamLayout {
+  double* d_tiles = nullptr;   size_t tiles_cap = 0;
+  double* d_ctiles = nullptr;  size_t ctiles_cap = 0;
+  double* d_groups = nullptr;  size_t groups_cap = 0;
+  double* d_rxy = nullptr;     size_t rxy_cap = 0;
+  double* d_rdesc = nullptr;   size_t rdesc_cap = 0;  // + the wave split table behind the descriptors
+  long long n_groups = 0;
+  long long n_rows = 0;
+  bool compact_ok = false;
+  bool rows_ok = false;
+  bool rows_z = false;  // the rows carry z (some record has p.z != 0): ROW_DOUBLES_Z doubles per row
+  void invalidate() { compact_ok = rows_ok = false; }
+  void release() {
+    for (double* p : {d_tiles, d_ctiles, d_groups, d_rxy, d_rdesc}) if (p) (void)hipFree(p);
+  }
 };
 
 constexpr long long kCoopBackoff0 = 16;  // solves the cooperative path rests after its first abort (doubles with every further one)
@@ -136,25 +158,9 @@ struct clc_handle {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // single problem
-  double* d_tiles = nullptr;
-  size_t tiles_cap_bytes = 0;
+  clc_abi::StreamLayout obs;
   size_t n_obs = 0;
-  // compact copy of the same observations (28 B/obs), built at upload when they compress
-  double* d_ctiles = nullptr;
-  size_t ctiles_cap_bytes = 0;
-  double* d_groups = nullptr;
-  size_t groups_cap_bytes = 0;
-  long long n_groups = 0;
-  bool compact_ok = false;
-  // row layout of the same observations (clc_rows.hpp): xy rows + row descriptors
-  double* d_rxy = nullptr;
-  size_t rxy_cap_bytes = 0;
-  double* d_rdesc = nullptr;
-  size_t rdesc_cap_bytes = 0;
-  long long n_rows = 0;
-  bool rows_ok = false;
-  bool rows_z = false;  // the rows carry z (some record has p.z != 0): ROW_DOUBLES_Z doubles per row
-  int split_grid = -1;  // grid the wave split table behind d_rdesc was built for (-1: none)
+  int split_grid = -1;  // grid the wave split table behind obs.d_rdesc was built for (-1: none)
   // resident pose-major scans (clc_store_observations): device copies + the host-side CSR offsets
   double* d_sq = nullptr; size_t sq_cap = 0;     // tag_q (w,x,y,z) [P*4]
   double* d_st = nullptr; size_t st_cap = 0;     // tag_t [P*3]
@@ -199,21 +205,7 @@ struct clc_handle {
   clc::HostMailbox* d_mailbox = nullptr;  // device address of the same memory
   std::vector<hipEvent_t> ev;
   // batched problems
-  double* d_btiles = nullptr;
-  size_t btiles_cap_bytes = 0;
-  double* d_bctiles = nullptr;
-  size_t bctiles_cap_bytes = 0;
-  double* d_bgroups = nullptr;
-  size_t bgroups_cap_bytes = 0;
-  long long bn_groups = 0;
-  bool bcompact_ok = false;
-  double* d_brxy = nullptr;
-  size_t brxy_cap_bytes = 0;
-  double* d_brdesc = nullptr;
-  size_t brdesc_cap_bytes = 0;
-  long long bn_rows = 0;
-  bool brows_ok = false;
-  bool brows_z = false;
+  clc_abi::StreamLayout batch;
   long long* d_prob_row = nullptr;  // [P+1] first row of every problem
   // resident ("lane") layouts (clc_resident.hpp): of the batched problems, and of a single problem small enough for one workgroup
   clc_abi::ResLayout bres, sres;
@@ -301,16 +293,10 @@ constexpr int kResPRz = 10, kResPLz = 12;
 // controller of the batched launches (clc_resident.hpp CTRL): 4-wave form / 8-wave form
 constexpr int kResCtrl4 = 0, kResCtrl8 = 0;
 
-struct LayoutTargets {
-  double** d_ct; size_t* ct_cap; double** d_gr; size_t* gr_cap; long long* n_groups; bool* compact_ok;
-  double** d_rxy; size_t* rxy_cap; double** d_rdesc; size_t* rdesc_cap; long long* n_rows; bool* rows_ok;
-  long long** d_prob_row;  // nullptr for the single-problem array
-  ResLayout* res = nullptr;  // also build the on-chip resident ("lane") layout (clc_resident.hpp) into this
-  bool* rows_z = nullptr;    // out: the rows carry z
-  ResLayout* coop = nullptr; // single problem only: its lane layout in COOP_WGS chunks (clc_coop.hpp)
-};
+// Re-encodes the staged records into L's compact and row layouts (d_prob_row: the batch's first row of every problem), and the lane
+// layouts res / coop where given (coop: a single problem's lane layout in cooperative chunks, clc_coop.hpp).  L.d_tiles is not touched.
 int build_layouts(clc_handle* h, const double* d_aos, size_t n_total, const std::vector<long long>& rec_off,
-                  const std::vector<long long>& tile_off, const LayoutTargets& T);
+                  const std::vector<long long>& tile_off, StreamLayout& L, long long* d_prob_row, ResLayout* res, ResLayout* coop);
 // builds the records of the stored scans' selection on the device into *aos (allocated here)
 int flatten_on_device(clc_handle* h, bool linefit, bool boundary, DevBuf<double>* aos, long long* n_out);
 
