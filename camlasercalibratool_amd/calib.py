@@ -163,6 +163,21 @@ def LineFittingCeres(Points: np.ndarray, Line: np.ndarray, solver: Optional[Solv
     Line[...] = lines[0]
 
 
+def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:
+    """The calibration board's segment in one scan — mirror of AutoGetLinePts(points, debug), src/selectScanPoints.cpp:17-190:
+    points [n,3] -> the chosen segment's points [k,3] (empty when there is none).  Raises IndexError where the reference's
+    points.at() raises std::out_of_range (an empty scan, or a segment widened past the scan's ends).  `debug` (the
+    reference's drawing) is accepted and ignored.  Many scans at once: Solver.board_segments."""
+    P = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    sv = solver or _shared_solver()
+    seg, status = sv.board_segments(P, np.array([0, P.shape[0]], dtype=np.int64))
+    if status[0] == -1:
+        raise IndexError("AutoGetLinePts: the reference raises std::out_of_range on this scan (selectScanPoints.cpp:47,110,121)")
+    if status[0] == 0:
+        return np.zeros((0, 3))
+    return P[seg[0, 0]:seg[0, 1] + 1].copy()
+
+
 def points_on_fitted_lines(obs_set: ObservationSet, solver: Optional[Solver] = None,
                            line0=(0.0, 0.0)) -> ObservationSet:
     """The scan front-end step of main/calibr_offline.cpp:121-142 for all scans at once: fit a line

@@ -1,6 +1,8 @@
-// abi_frontend.hip — the calls either side of the solve: factor evaluation, manifold plus, information matrix and closed form, line fitting, scan conversion.
+// abi_frontend.hip — the calls either side of the solve: factor evaluation, manifold plus, information matrix and closed form, line fitting, scan conversion,
+// board-segment detection.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "clc_abi_internal.hpp"
+#include "clc_scanseg.hpp"
 
 using namespace clc_abi;
 
@@ -276,5 +278,64 @@ int clc_scan_to_points_device(clc_handle* h, const float* ranges_dev, const int6
   return CLC_OK;
 }
 
+// ---- board-segment detection (K7) -------------------------------------------------------------
+namespace {
+void launch_board_segments(clc_handle* h, const double* points_dev, const int64_t* offsets_dev, size_t n_scans, int64_t* seg_dev,
+                          int32_t* status_dev) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
+  const unsigned blocks = (unsigned)((n_scans + clc::SEG_WAVES_PER_BLOCK - 1) / clc::SEG_WAVES_PER_BLOCK);
+  hipLaunchKernelGGL(clc::board_segment_kernel, dim3(blocks), dim3(64 * clc::SEG_WAVES_PER_BLOCK), 0, h->stream, points_dev,
+                     reinterpret_cast<const long long*>(offsets_dev), (long long)n_scans, reinterpret_cast<long long*>(seg_dev),
+                     reinterpret_cast<int*>(status_dev));
+}
+}  // namespace
+
+int clc_board_segments(clc_handle* h, const double* points, const int64_t* offsets, size_t n_scans, int64_t* seg, int32_t* status) {
+  if (!h || (n_scans > 0 && (!offsets || !seg)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: bad argument");
+  if (n_scans == 0) return CLC_OK;
+  if (n_scans > 0x1FFFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: too many scans");
+  for (size_t k = 0; k < n_scans; ++k) {
+    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: offsets not monotone");
+    if (offsets[k + 1] - offsets[k] > 0x7FFFFFFF) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: a scan has 2^31 points or more");
+  }
+  const size_t n_pts = (size_t)(offsets[n_scans] - offsets[0]);
+  if (n_pts > 0 && !points) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: bad argument");
+  CLC_HIP(hipSetDevice(h->device));
+  std::vector<long long> rel(n_scans + 1);
+  for (size_t k = 0; k <= n_scans; ++k) rel[k] = offsets[k] - offsets[0];
+  DevBuf<double> bp(&h->pool);
+  DevBuf<long long> boff(&h->pool), bseg(&h->pool);
+  DevBuf<int32_t> bst(&h->pool);
+  CLC_HIP(bp.alloc(std::max<size_t>(1, 3 * n_pts)));
+  CLC_HIP(boff.alloc(n_scans + 1));
+  CLC_HIP(bseg.alloc(2 * n_scans));
+  if (status) CLC_HIP(bst.alloc(n_scans));
+  hipError_t e = hipSuccess;
+  if (n_pts > 0) e = hipMemcpyAsync(bp.p, points + 3 * offsets[0], 3 * n_pts * sizeof(double), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(boff.p, rel.data(), (n_scans + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    launch_board_segments(h, bp.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, reinterpret_cast<int64_t*>(bseg.p), status ? bst.p : nullptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(seg, bseg.p, 2 * n_scans * sizeof(long long), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && status) e = hipMemcpyAsync(status, bst.p, n_scans * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(CLC_ERR_HIP, "clc_board_segments", e);
+  return CLC_OK;
+}
+
+int clc_board_segments_device(clc_handle* h, const double* points_dev, const int64_t* offsets_dev, size_t n_scans, int64_t* seg_dev,
+                              int32_t* status_dev) {
+  if (!h || (n_scans > 0 && (!offsets_dev || !points_dev || !seg_dev)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_segments_device: bad argument");
+  if (n_scans == 0) return CLC_OK;
+  if (n_scans > 0x1FFFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments_device: too many scans");
+  CLC_HIP(hipSetDevice(h->device));
+  launch_board_segments(h, points_dev, offsets_dev, n_scans, seg_dev, status_dev);
+  CLC_HIP(hipGetLastError());
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
 
 }  // extern "C"

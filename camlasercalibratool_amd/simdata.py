@@ -10,6 +10,8 @@ produce the configurations named in BASELINE.json / SURVEY.md §8(d):
   C3  sim_batch(...)                 many independent problems, each its own ground-truth Tlc
   C5  sim_board_edges(...)           scan clipped to the 0.5 m board so the board-edge
                                      ("boundary") residuals of LaseCamCalCeres.cpp:258-294 hold
+      sim_laser_scans(...)           raw 1 081-ray scans (board, walls, clutter, dropouts) for the
+                                     board-segment detection (AutoGetLinePts)
 
 All data are pose-major CSR (`ObservationSet`), the flattened form of
 std::vector<Oberserve> (include/LaseCamCalCeres.h:11-24).
@@ -601,3 +603,72 @@ def sim_board_edges(seed: int, n_poses: int, pts_per_pose: int, noise_sigma: flo
     off = np.arange(P + 1, dtype=np.int64) * K
     flat = np.ascontiguousarray(pts.reshape(-1, 3))
     return ObservationSet(tag_q, tag_t, off, flat, off.copy(), flat.copy())
+
+
+# ----------------------------------------------------------------------------------
+# raw laser scans (the input of TranScanToPoints + AutoGetLinePts)
+# ----------------------------------------------------------------------------------
+def _ray_hits(theta: np.ndarray, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Range along the rays `theta` to the 2-D segment a-b (inf where a ray misses it)."""
+    ux, uy = np.cos(theta), np.sin(theta)
+    ex, ey = b[0] - a[0], b[1] - a[1]
+    den = ux * ey - uy * ex
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = (a[0] * ey - a[1] * ex) / den
+        s = (a[0] * uy - a[1] * ux) / den
+    return np.where((np.abs(den) > 1e-12) & (s >= 0) & (s <= 1) & (t > 0), t, np.inf)
+
+
+def sim_laser_scans(seed: int, n_scans: int, n_rays: int = 1081, fov_deg: float = 270.0, board_prob: float = 0.85) -> dict:
+    """Seeded sensor_msgs/LaserScan-like scans for the board-segment detection (AutoGetLinePts): each scan sees background
+    walls at 3-10 m, with probability `board_prob` a 0.6-1.0 m board 0.5-1.9 m ahead (within +-40 deg of the scan's
+    middle ray), longer clutter segments beyond 2 m, short ones near, and dropouts returned as inf, 0 or > 30 m.
+    -> {ranges float32 [S*n_rays], offsets int64 [S+1], angle_min, angle_increment, range_min float32 [S]}."""
+    rng = np.random.default_rng(seed)
+    inc = np.deg2rad(fov_deg) / (n_rays - 1)
+    a0 = -np.deg2rad(fov_deg) / 2
+    th = a0 + np.arange(n_rays) * inc
+    out = np.empty((n_scans, n_rays), dtype=np.float32)
+    for k in range(n_scans):
+        r = np.full(n_rays, np.inf)
+        for _ in range(rng.integers(2, 5)):  # walls: the line at distance rho with normal angle phi
+            rho, phi = rng.uniform(3.0, 10.0), rng.uniform(-np.pi, np.pi)
+            c = np.cos(th - phi)
+            r = np.minimum(r, np.where(c > 0.05, rho / np.maximum(c, 0.05), np.inf))
+
+        def seg(dist, length, ang, tilt):
+            m = np.array([dist * np.cos(ang), dist * np.sin(ang)])
+            d = np.array([-np.sin(ang + tilt), np.cos(ang + tilt)]) * length / 2
+            return m - d, m + d
+
+        if rng.random() < board_prob:
+            r = np.minimum(r, _ray_hits(th, *seg(rng.uniform(0.5, 1.9), rng.uniform(0.6, 1.0), rng.uniform(-0.7, 0.7), rng.uniform(-0.9, 0.9))))
+        for _ in range(rng.integers(0, 3)):  # long clutter beyond 2 m
+            r = np.minimum(r, _ray_hits(th, *seg(rng.uniform(2.2, 4.0), rng.uniform(1.0, 2.0), rng.uniform(-1.2, 1.2), rng.uniform(-1.0, 1.0))))
+        for _ in range(rng.integers(0, 4)):  # short clutter near
+            r = np.minimum(r, _ray_hits(th, *seg(rng.uniform(0.3, 1.5), rng.uniform(0.05, 0.15), rng.uniform(-1.2, 1.2), rng.uniform(-1.0, 1.0))))
+        r = r + rng.normal(0.0, 0.003, n_rays)
+        drop = rng.random(n_rays) < 0.02
+        r[drop] = rng.choice(np.array([np.inf, 0.0, 40.0]), size=int(drop.sum()))
+        out[k] = r.astype(np.float32)
+    S = n_scans
+    return {"ranges": out.ravel(), "offsets": np.arange(S + 1, dtype=np.int64) * n_rays,
+            "angle_min": np.full(S, a0, dtype=np.float32), "angle_increment": np.full(S, inc, dtype=np.float32),
+            "range_min": np.full(S, 0.05, dtype=np.float32)}
+
+
+def scan_points_host(scans: dict) -> np.ndarray:
+    """TranScanToPoints (src/utilities.cpp:181-215) on the host, for building test inputs: (r cos th, r sin th, 0) with
+    th = angle_min + i * angle_increment in double, (1000, 1000, 0) outside [range_min, 30)."""
+    off = scans["offsets"]
+    S = len(off) - 1
+    pts = np.zeros((int(off[-1]), 3))
+    for k in range(S):
+        r = scans["ranges"][off[k]:off[k + 1]]
+        t = np.float64(scans["angle_min"][k]) + np.arange(r.shape[0]) * np.float64(scans["angle_increment"][k])
+        rr = r.astype(np.float64)
+        ok = (r < 30.0) & (r >= scans["range_min"][k])
+        with np.errstate(invalid="ignore"):
+            pts[off[k]:off[k + 1], 0] = np.where(ok, rr * np.cos(t), 1000.0)
+            pts[off[k]:off[k + 1], 1] = np.where(ok, rr * np.sin(t), 1000.0)
+    return pts

@@ -431,6 +431,26 @@ class Solver:
               "clc_scan_to_points")
         return pts
 
+    # ---- board-segment detection ----
+    def board_segments(self, points: np.ndarray, offsets: np.ndarray):
+        """AutoGetLinePts (src/selectScanPoints.cpp:17-190) for many scans: points [M,3], CSR offsets [S+1] ->
+        (seg [S,2] int64: first, last index of the board's segment in its scan, inclusive, or -1, -1;
+        status [S] int32: CLC_SEG_FOUND 1, CLC_SEG_NONE 0, CLC_SEG_REF_THROWS -1 where the reference raises)."""
+        P = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        S = len(offsets) - 1
+        seg = np.empty((max(S, 0), 2), dtype=np.int64)
+        status = np.empty(max(S, 0), dtype=np.int32)
+        check(self._L.clc_board_segments(self._h, dptr(P) if P.size else None, iptr(offsets), C.c_size_t(S),
+                                         seg.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "clc_board_segments")
+        return seg, status
+
+    def board_segments_device(self, points_ptr: int, offsets_ptr: int, n_scans: int, seg_ptr: int, status_ptr: int = 0):
+        """AutoGetLinePts on device-resident arrays (data_ptr()s; ready on the solver's stream): points [M,3] float64,
+        offsets [S+1] int64, seg [S,2] int64 out, status [S] int32 out (0: not written)."""
+        check(self._L.clc_board_segments_device(self._h, C.c_void_p(points_ptr), C.c_void_p(offsets_ptr), C.c_size_t(n_scans),
+                                                C.c_void_p(seg_ptr), C.c_void_p(status_ptr or 0)), "clc_board_segments_device")
+
     # ---- test / profiling hooks ----
     def debug_math(self, op: int, x: np.ndarray) -> np.ndarray:
         """Device branch of a scalar helper, element-wise (hooks build): 0 rsqrt_pos, 1 rcp_pos, 2 rcp_pos_safe, 3 sqrt_pos, 4 rcp_ge1,

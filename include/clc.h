@@ -351,6 +351,28 @@ int clc_scan_to_points_device(clc_handle* h, const float* ranges_dev, const int6
                               size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
                               const float* range_min_dev, double* points_dev);
 
+/* AutoGetLinePts, src/selectScanPoints.cpp:17-190 (the detection; the debug drawing is not reproduced), for n_scans scans at
+ * once: the calibration board's segment in each scan.  Scan k owns points [offsets[k], offsets[k+1]) of points[3 * M]
+ * ((x, y, z) doubles as clc_scan_to_points writes them).  The reference's quirks are kept: the search window is the middle
+ * +-266 points (:36-45), every 3rd point is visited (:53-100), a segment still open when the loop ends is never pushed,
+ * a current point at range == 100 or NaN never moves again (:96-99), each pushed segment is widened by up to 3 points at
+ * either end, always against its original ends (:104-126), and the first of equally long segments wins (:139-148).
+ * Ranges are |(x, y)| with each square and the sum rounded (no FMA), as Eigen's head(2).norm().
+ * seg[2 * n_scans]: first and last index (inclusive, relative to the scan) of the chosen segment, or -1, -1.
+ * status[n_scans] (nullable): CLC_SEG_FOUND, CLC_SEG_NONE, or CLC_SEG_REF_THROWS where the reference's points.at() raises
+ * std::out_of_range — an empty scan (:46), or a pushed segment whose widening to the left would leave the scan (:121; possible
+ * below 538 points, for any pushed segment, not only the chosen one; the widening to the right (:110) cannot leave it: the
+ * point that closed the segment lies beyond it): seg is -1, -1 and the other scans are unaffected. */
+#define CLC_SEG_FOUND 1
+#define CLC_SEG_NONE 0
+#define CLC_SEG_REF_THROWS (-1)
+int clc_board_segments(clc_handle* h, const double* points, const int64_t* offsets, size_t n_scans, int64_t* seg, int32_t* status);
+/* The same with every array in DEVICE memory (ready on the handle's stream; complete on return — it synchronises):
+ * points_dev[3 * M], offsets_dev[n_scans + 1] (absolute, offsets_dev[0] may be > 0; not validated: monotone, and fewer than
+ * 2^31 points per scan), seg_dev[2 * n_scans], status_dev nullable. */
+int clc_board_segments_device(clc_handle* h, const double* points_dev, const int64_t* offsets_dev, size_t n_scans, int64_t* seg_dev,
+                              int32_t* status_dev);
+
 /* Multi-hypothesis calibration on SHARED observations: n_starts independent LM solves (one ceres::Solve each, src/LaseCamCalCeres.cpp
  * :299-309) from n_starts start poses on the ONE problem the handle holds as a batch of one (clc_upload_batched* with n_problems = 1).
  * poses: n_starts x 7, in/out; summaries: n_starts.  Where the problem fits a workgroup (clc_path_info.batched_resident) ONE launch runs
