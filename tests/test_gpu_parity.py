@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import camlasercalibratool_amd as clc
+import lm_near_tie as NT
 from camlasercalibratool_amd import _capi, simdata as sd
 
 pytestmark = pytest.mark.gpu
@@ -563,7 +564,10 @@ def test_wide_ragged_batch_one_wave_per_problem(sv, oracle_mod):
     n_diff = 0
     for k in range(P):
         if sa[k].termination != sb[k].termination or sa[k].num_iterations != sb[k].num_iterations:
-            n_diff += 1  # a tolerance test may flip on a last-bit difference of the sums; rare
+            n_diff += 1  # a tolerance test may flip on a last-bit difference of the sums; rare, and only at a near tie of the oracle's trace
+            NT.require_near_tie(oracle_mod, rec2[off2[k]:off2[k + 1]], x0[k], oracle_mod.default_options(),
+                                (sa[k].termination, sa[k].num_iterations, sa[k].final_cost),
+                                (sb[k].termination, sb[k].num_iterations, sb[k].final_cost), f"one wave vs 256 threads, problem {k}")
             continue
         if keep[k] >= per // 2:
             assert _dT(pa[k], pb[k]) <= T_TOL and abs(sa[k].final_cost - sb[k].final_cost) <= COST_TOL, k

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import camlasercalibratool_amd as clc
+import lm_near_tie as NT
 from camlasercalibratool_amd import _capi, simdata as sd
 
 pytestmark = pytest.mark.gpu
@@ -174,7 +175,10 @@ def test_resident_wide_ragged_batch(sv, oracle_mod):
     n_diff = 0
     for k in range(P):
         if _key(sr[k]) != _key(sl[k]):
-            n_diff += 1  # a tolerance test may flip on a last-bit difference of the sums; rare
+            n_diff += 1  # a tolerance test may flip on a last-bit difference of the sums; rare, and only at a near tie of the oracle's trace
+            NT.require_near_tie(oracle_mod, rec[off[k]:off[k + 1]], x0[k], oracle_mod.default_options(),
+                                (sr[k].termination, sr[k].num_iterations, sr[k].final_cost),
+                                (sl[k].termination, sl[k].num_iterations, sl[k].final_cost), f"resident vs lockstep, problem {k}")
             continue
         if keep[k] >= per // 2:
             assert _dT(pr[k], pl[k]) <= T_TOL and abs(sr[k].final_cost - sl[k].final_cost) <= COST_TOL, k
