@@ -32,12 +32,7 @@ int batched_launch_setup(clc_handle* h, const clc_options& /*opt*/, BatchedLaunc
   bl->one_wave = bl->rows_wave && bpp == 1 && P >= 32 * (size_t)h->num_cus;
   if (bl->rows_wave && !bl->one_wave) bpp *= clc::BLOCK / 64;
   const size_t n_blocks = P * (size_t)bpp;
-  if (n_blocks > h->bpartials_cap_blocks) {
-    if (h->d_bpartials) CLC_HIP(hipFree(h->d_bpartials));
-    h->d_bpartials = nullptr; h->bpartials_cap_blocks = 0;
-    CLC_HIP(hipMalloc(&h->d_bpartials, sizeof(double) * n_blocks * clc::NACC));
-    h->bpartials_cap_blocks = n_blocks;
-  }
+  CLC_HIP(h->d_bpartials.grow(n_blocks * clc::NACC));
   bl->bpp = bpp;
   bl->n_blocks = n_blocks;
   bl->lm_threads = 64;
@@ -75,7 +70,7 @@ void launch_batched_eval(clc_handle* h, const clc_options& opt, const BatchedLau
     with_flags([&](auto Z, auto WAVE, auto LOSS, auto NT) {
       constexpr int BT = WAVE ? 64 : 256;
       hipLaunchKernelGGL((clc::batched_rows_eval_kernel<LOSS, NT, BT, Z>), dim3(n_blocks), dim3(BT), 0, h->stream, h->batch.d_rxy,
-                         reinterpret_cast<const clc::RowDesc*>(h->batch.d_rdesc), h->d_prob_row, h->d_states, bpp, opt.loss_scale_factor,
+                         h->batch.d_rdesc(), h->d_prob_row, h->d_states, bpp, opt.loss_scale_factor,
                          h->d_bpartials);
     }, h->batch.rows_z, bl.rows_wave, opt.use_loss != 0, bl.rows_nt);
     return;
@@ -94,16 +89,14 @@ void launch_resident_batch(clc_handle* h, const clc_options& opt, const BatchedL
   // one workgroup per problem, the problem read from HBM once and kept in registers + LDS for its whole solve
   // (multi-start: one workgroup per START, every one of them on problem 0's points)
   const size_t P = multistart ? multistart->n_starts : h->n_problems;
-  double* const d_poses = multistart ? multistart->d_poses : h->d_poses;
+  double* const d_poses = multistart ? multistart->d_poses : h->h_poses.dev();
   const int uni_ppl = multistart ? -2 - h->bres.max_ppl : h->bres.uni_ppl;
-  const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->bres.d_row);
-  const clc::ResLane* d_desc = reinterpret_cast<const clc::ResLane*>(h->bres.d_desc);
   // W4: the 256-lane form (4 waves); Z: 24-byte slots (p.z != 0 in some record of the batch), on 512 lanes
   const auto launch = [&](auto Z, auto W4, auto LOSS, auto NT) {
     constexpr int NW = W4 ? 4 : 8;
     constexpr int PR = Z ? kResPRz : W4 ? kResPR256 : kResPR512, PL = Z ? kResPLz : W4 ? kResPL256 : kResPL512;
     hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z>), dim3((unsigned)P), dim3(NW * 64), 0,
-                       h->stream, h->bres.d_xy, d_row, d_desc, h->batch.d_groups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results,
+                       h->stream, h->bres.d_xy, h->bres.d_row, h->bres.d_desc, h->batch.d_groups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results,
                        nullptr, nullptr, rec_base, rec_host, seg_off, goal, Z ? h->bres.d_z : nullptr);
   };
   if (h->bres.with_z) with_flags(launch, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
@@ -197,7 +190,7 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
       if (rc != CLC_OK) return rc;
       CLC_HIP(hipEventRecord(h->ev[0], h->stream));
     }
-    launch_resident_batch(h, opt, bl, h->d_summaries, h->d_results, 0.0, nullptr, 0, 0);
+    launch_resident_batch(h, opt, bl, h->h_summaries.dev(), h->d_results, 0.0, nullptr, 0, 0);
     CLC_HIP(hipGetLastError());
     if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
     // (kernel completion makes the outcomes written over PCIe visible; polling the stream with hipStreamQuery instead of this
@@ -206,10 +199,10 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
   }
   if (bl.whole_solve) {
     // one 256-thread workgroup per problem: the whole solve of every problem in ONE launch (batched_solve_kernel)
-    const clc::RowDesc* bdesc = reinterpret_cast<const clc::RowDesc*>(h->batch.d_rdesc);
+    const clc::RowDesc* bdesc = h->batch.d_rdesc();
     with_flags([&](auto LOSS, auto NT) {
       hipLaunchKernelGGL((clc::batched_solve_kernel<LOSS, NT>), dim3((unsigned)P), dim3(clc::BLOCK), 0, h->stream, h->batch.d_rxy, bdesc,
-                         h->d_prob_row, opt, h->d_poses, h->d_summaries, h->d_results);
+                         h->d_prob_row, opt, h->h_poses.dev(), h->h_summaries.dev(), h->d_results);
     }, opt.use_loss != 0, bl.rows_nt);
     CLC_HIP(hipGetLastError());
     return finish_batched(h, in_place, poses, summaries, t0, false);
@@ -217,7 +210,7 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
   const int lm_threads = bl.lm_threads;
   const unsigned lm_blocks = bl.lm_blocks;
   hipLaunchKernelGGL(clc::batched_init_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream, h->d_states,
-                     opt, h->d_poses, (int)P, h->d_queue, h->d_ticket);
+                     opt, h->h_poses.dev(), (int)P, h->d_queue, h->d_ticket);
   CLC_HIP(hipGetLastError());
   const int lookahead = opt.launch_ahead > 0 ? opt.launch_ahead : default_lookahead();
   // at the iteration cap the loop ends once every launch is consumed: batched_finish_kernel closes the stragglers
@@ -227,14 +220,14 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
     launch_batched_eval(h, opt, bl);
     hipLaunchKernelGGL(clc::batched_lm_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream,
                        h->d_bpartials, bpp, h->d_states, opt, (int)P, h->d_queue, h->d_ticket, k,
-                       h->d_mailbox, h->d_poses, h->d_summaries, h->d_results);
+                       h->h_mailbox.dev(), h->h_poses.dev(), h->h_summaries.dev(), h->d_results);
     return CLC_OK;
   }, &launched);
   if (rc != CLC_OK) return rc;
   CLC_HIP(hipGetLastError());
   if (__atomic_load_n(&h->h_mailbox->status, __ATOMIC_ACQUIRE) == CLC_RUNNING) {  // iteration cap of this loop: some problem still runs
     hipLaunchKernelGGL(clc::batched_finish_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream, h->d_states,
-                       (int)P, h->d_poses, h->d_summaries, h->d_results);
+                       (int)P, h->h_poses.dev(), h->h_summaries.dev(), h->d_results);
     CLC_HIP(hipGetLastError());
   }
   rc = finish_batched(h, in_place, poses, summaries, t0, false);
@@ -277,20 +270,9 @@ int clc_solve_multistart(clc_handle* h, const clc_options* opt_in, size_t n_star
     h->results_valid = 0;  // (the handle's result buffer holds the last start only: nothing for clc_gather_results)
     return CLC_OK;
   }
-  if (n_starts > h->ms_cap) {
-    if (h->h_ms_poses) CLC_HIP(hipHostFree(h->h_ms_poses));
-    if (h->h_ms_summaries) CLC_HIP(hipHostFree(h->h_ms_summaries));
-    if (h->d_ms_results) CLC_HIP(hipFree(h->d_ms_results));
-    h->h_ms_poses = h->d_ms_poses = h->d_ms_results = nullptr;
-    h->h_ms_summaries = h->d_ms_summaries = nullptr;
-    h->ms_cap = 0;
-    CLC_HIP(hipHostMalloc(&h->h_ms_poses, sizeof(double) * 7 * n_starts, hipHostMallocMapped));
-    CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_ms_poses), h->h_ms_poses, 0));
-    CLC_HIP(hipHostMalloc(&h->h_ms_summaries, sizeof(clc_summary) * n_starts, hipHostMallocMapped));
-    CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_ms_summaries), h->h_ms_summaries, 0));
-    CLC_HIP(hipMalloc(&h->d_ms_results, sizeof(clc_result_record) * n_starts));
-    h->ms_cap = n_starts;
-  }
+  CLC_HIP(h->h_ms_poses.grow(7 * n_starts));
+  CLC_HIP(h->h_ms_summaries.grow(n_starts));
+  CLC_HIP(h->d_ms_results.grow(sizeof(clc_result_record) / sizeof(double) * n_starts));
   // (the previous call ended with a stream synchronisation: nothing still reads or writes the staging buffers)
   std::memcpy(h->h_ms_poses, poses, sizeof(double) * 7 * n_starts);
   const bool timed = opt.profile_events == 1;
@@ -301,8 +283,8 @@ int clc_solve_multistart(clc_handle* h, const clc_options* opt_in, size_t n_star
   }
   MultiStartLaunch ms;
   ms.n_starts = n_starts;
-  ms.d_poses = h->d_ms_poses;
-  launch_resident_batch(h, opt, bl, h->d_ms_summaries, h->d_ms_results, 0.0, nullptr, 0, 0, &ms);
+  ms.d_poses = h->h_ms_poses.dev();
+  launch_resident_batch(h, opt, bl, h->h_ms_summaries.dev(), h->d_ms_results, 0.0, nullptr, 0, 0, &ms);
   CLC_HIP(hipGetLastError());
   if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
   CLC_HIP(hipStreamSynchronize(h->stream));  // (kernel completion makes the outcomes written over PCIe visible)

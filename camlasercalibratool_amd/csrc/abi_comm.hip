@@ -114,21 +114,19 @@ struct clc_comm {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
   int root = -1;             // clc_comm_set_root: >= 0 = only this rank receives the other ranks' records (and copies them to its host)
-  double* d_base = nullptr;  // device: ONE record of running totals (clc_solve_batched_gather) in front of the gathered array
-  double* d_recv = nullptr;  // = d_base + 12: the gathered records
+  clc_abi::DeviceArray<double> d_base;  // device: ONE record of running totals (clc_solve_batched_gather) in front of the gathered array
   // Host side: TWO pinned, device-mapped twins of d_base.  The kernel of a step writes this rank's records and the totals into the
   // twin of that step itself; the other ranks' segments are copied down into the same twin.  The plain calls stay on twin `cur`; the
   // pipelined form alternates, so that step k's kernel never writes into the records of step k-1 the caller is still reading.
-  double* h_base[2] = {nullptr, nullptr};
-  double* hd_base[2] = {nullptr, nullptr};  // device addresses of h_base[]
+  clc_abi::MappedArray<double> h_base[2];
   int cur = 0;               // twin of the last COMPLETED step (what clc_comm_records returns)
-  size_t cap = 0;            // records per rank the buffers hold
+  size_t cap = 0;            // records per rank all three buffers hold
   // the record in front of d_recv / h_recv: 4 running totals (clc_batch_stats' counters, never reset)
   unsigned long long stats_seen[4] = {0, 0, 0, 0};
   long long pad_from = -1, pad_base = -1;  // own segment's padding records (device + both twins) are in place for this many local problems
   // pipelined steps (clc_solve_batched_gather_pipelined): the copy of step k-1's records overlaps step k's kernel
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_copy = nullptr;
+  clc_abi::Stream copy_stream;
+  clc_abi::Event ev_copy;
   struct Flight {
     bool active = false;
     int twin = 0;
@@ -140,6 +138,7 @@ struct clc_comm {
   } fl;
   // bookkeeping (clc_comm_get_info)
   long long collectives = 0, rooted_collectives = 0, host_copies = 0, host_copy_bytes = 0, pipelined_steps = 0;
+  double* d_recv() const { return d_base ? d_base + 12 : nullptr; }  // the gathered records
   double* h_recv_of(int twin) const { return h_base[twin] + 12; }
 };
 
@@ -154,26 +153,19 @@ static __global__ void pad_records_kernel(double* __restrict__ seg, long long n_
 static int comm_ensure_buffers(clc_comm* c, size_t cap_per_rank) {
   if (cap_per_rank <= c->cap) return CLC_OK;
   clc_handle* h = c->h;
-  if (c->d_base) CLC_HIP(hipFree(c->d_base));
-  for (int t = 0; t < 2; ++t) {
-    if (c->h_base[t]) CLC_HIP(hipHostFree(c->h_base[t]));
-    c->h_base[t] = c->hd_base[t] = nullptr;
-  }
-  c->d_recv = c->d_base = nullptr;
   c->cap = 0;
   c->cur = 0;
   c->pad_from = c->pad_base = -1;
   const size_t n_rec = cap_per_rank * (size_t)c->world + 1;  // the totals' record + the gathered array
-  CLC_HIP(hipMalloc(&c->d_base, sizeof(clc_result_record) * n_rec));
+  const size_t doubles = n_rec * (sizeof(clc_result_record) / sizeof(double));
+  CLC_HIP(c->d_base.grow(doubles));
   // (stream-ordered in front of the pad kernel and the solve launch: the handle's stream is non-blocking, a null-stream memset is not
   // ordered against it by the API)
   CLC_HIP(hipMemsetAsync(c->d_base, 0, sizeof(clc_result_record) * n_rec, h->stream));
   for (int t = 0; t < 2; ++t) {
-    CLC_HIP(hipHostMalloc(&c->h_base[t], sizeof(clc_result_record) * n_rec, hipHostMallocMapped));
-    CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_base[t]), c->h_base[t], 0));
+    CLC_HIP(c->h_base[t].grow(doubles));
     std::memset(c->h_base[t], 0, sizeof(clc_result_record) * n_rec);
   }
-  c->d_recv = c->d_base + 12;
   std::memset(c->stats_seen, 0, sizeof(c->stats_seen));
   c->cap = cap_per_rank;
   return CLC_OK;
@@ -189,11 +181,11 @@ static int comm_copy_others(clc_comm* c, int tw, size_t cap_per_rank, hipStream_
   const long long seg_off = 12ll * (long long)c->rank * (long long)cap_per_rank;
   double* hr = c->h_recv_of(tw);
   if (c->rank > 0) {
-    CLC_HIP(hipMemcpyAsync(hr, c->d_recv, seg_bytes * (size_t)c->rank, hipMemcpyDeviceToHost, stream));
+    CLC_HIP(hipMemcpyAsync(hr, c->d_recv(), seg_bytes * (size_t)c->rank, hipMemcpyDeviceToHost, stream));
     ++c->host_copies; c->host_copy_bytes += (long long)(seg_bytes * (size_t)c->rank);
   }
   if (c->rank + 1 < c->world) {
-    CLC_HIP(hipMemcpyAsync(hr + seg_off + 12 * cap_per_rank, c->d_recv + seg_off + 12 * cap_per_rank,
+    CLC_HIP(hipMemcpyAsync(hr + seg_off + 12 * cap_per_rank, c->d_recv() + seg_off + 12 * cap_per_rank,
                            seg_bytes * (size_t)(c->world - 1 - c->rank), hipMemcpyDeviceToHost, stream));
     ++c->host_copies; c->host_copy_bytes += (long long)(seg_bytes * (size_t)(c->world - 1 - c->rank));
   }
@@ -246,12 +238,8 @@ void clc_comm_destroy(clc_comm* c) {
     (void)hipSetDevice(c->h->device);
     (void)hipStreamSynchronize(c->h->stream);
   }
-  if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-  if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
+  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->comm && rccl().CommDestroy) (void)rccl().CommDestroy(c->comm);
-  if (c->d_base) (void)hipFree(c->d_base);
-  for (int t = 0; t < 2; ++t)
-    if (c->h_base[t]) (void)hipHostFree(c->h_base[t]);
   delete c;
 }
 
@@ -310,18 +298,18 @@ int clc_gather_results(clc_comm* c, int64_t first_global_index, size_t cap_per_r
   // packed straight into this rank's segment of the receive buffer: the collective runs in place
   hipLaunchKernelGGL(clc::pack_results_kernel, dim3((unsigned)((cap_per_rank + threads - 1) / threads)), dim3(threads), 0,
                      h->stream, h->d_results, (long long)n_local, (long long)cap_per_rank, (double)first_global_index,
-                     c->d_recv + seg_off);
+                     c->d_recv() + seg_off);
   if (hipGetLastError() != hipSuccess && local_rc == CLC_OK) { local_rc = CLC_ERR_HIP; local_msg = "clc_gather_results: pack kernel launch failed (this rank's segment is undefined)"; }
   const size_t count = cap_per_rank * (sizeof(clc_result_record) / sizeof(double));
   int rooted = 0;
-  ncclResult_t r = comm_collect(c->comm, c->rank, c->root, c->d_recv + seg_off, c->d_recv, count, h->stream, &rooted);
+  ncclResult_t r = comm_collect(c->comm, c->rank, c->root, c->d_recv() + seg_off, c->d_recv(), count, h->stream, &rooted);
   if (r != ncclSuccess) return rccl_fail(rooted ? "ncclGather" : "ncclAllGather", r);
   ++c->collectives; c->rooted_collectives += rooted;
   const size_t seg_bytes = sizeof(clc_result_record) * cap_per_rank;
   const size_t bytes = seg_bytes * (size_t)c->world;
   double* hr = c->h_recv_of(c->cur);
   // the own segment always (this form's kernel did not write it to the host), the other ranks' at the root / without a root
-  CLC_HIP(hipMemcpyAsync(hr + seg_off, c->d_recv + seg_off, seg_bytes, hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(hr + seg_off, c->d_recv() + seg_off, seg_bytes, hipMemcpyDeviceToHost, h->stream));
   ++c->host_copies; c->host_copy_bytes += (long long)seg_bytes;
   if (comm_copies_others(c)) {
     const int rc = comm_copy_others(c, c->cur, cap_per_rank, h->stream);
@@ -391,7 +379,7 @@ int step_enqueue(clc_comm* c, const clc_options& opt, const double* poses0, int6
   const size_t n_local = fl.local_rc == CLC_OK ? P : 0;
   fl.n_local = n_local;
   const long long seg_off = 12ll * (long long)c->rank * (long long)cap_per_rank;  // this rank's segment of the gathered array (doubles)
-  double* seg = c->d_recv + seg_off;
+  double* seg = c->d_recv() + seg_off;
   if (c->pad_from != (long long)n_local || c->pad_base != (long long)cap_per_rank) {  // (first call, or the shape changed)
     const long long n_pad = (long long)cap_per_rank - (long long)n_local;
     if (n_pad > 0) {  // the padding records of this rank's segment: device (what the collective sends) and both host twins
@@ -412,7 +400,7 @@ int step_enqueue(clc_comm* c, const clc_options& opt, const double* poses0, int6
   if (fl.n_local > 0) {
     if (fl.timed) CLC_HIP(hipEventRecord(h->ev[0], h->stream));
     // the last workgroup to finish (totals' arrival count == goal) copies the totals to the host twin
-    launch_resident_batch(h, opt, bl, nullptr, c->d_base, (double)first_global_index, c->hd_base[tw], seg_off, c->stats_seen[3] + (unsigned long long)P);
+    launch_resident_batch(h, opt, bl, nullptr, c->d_base, (double)first_global_index, c->h_base[tw].dev(), seg_off, c->stats_seen[3] + (unsigned long long)P);
     if (hipGetLastError() != hipSuccess) { local_fail(CLC_ERR_HIP, w + ": kernel launch failed (this rank's records are undefined)"); fl.n_local = 0; }
     else if (fl.timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
   }
@@ -420,7 +408,7 @@ int step_enqueue(clc_comm* c, const clc_options& opt, const double* poses0, int6
   if (wait_copy && c->ev_copy) CLC_HIP(hipStreamWaitEvent(h->stream, c->ev_copy, 0));
   const size_t count = cap_per_rank * (sizeof(clc_result_record) / sizeof(double));
   int rooted = 0;
-  ncclResult_t r = comm_collect(c->comm, c->rank, c->root, seg, c->d_recv, count, h->stream, &rooted);
+  ncclResult_t r = comm_collect(c->comm, c->rank, c->root, seg, c->d_recv(), count, h->stream, &rooted);
   if (r != ncclSuccess) {
     // the kernel may be running: bring the host's view of the running totals back in step with the device before reporting
     (void)hipStreamSynchronize(h->stream);
@@ -473,7 +461,7 @@ int step_two_calls(clc_comm* c, const clc_options& opt, int64_t first_global_ind
   clc_handle* h = c->h;
   const size_t P = h->n_problems;
   const auto t0 = c->fl.t0;
-  std::vector<double> start(h->h_poses, h->h_poses + 7 * P);
+  std::vector<double> start(h->h_poses.get(), h->h_poses + 7 * P);
   int rc = clc_solve_batched(h, &opt, h->h_poses, h->h_summaries);  // (the start poses are in the pinned buffer already)
   std::string msg = rc != CLC_OK ? clc_last_error() : "";
   if (rc != CLC_OK) h->results_valid = 0;
@@ -536,8 +524,8 @@ int clc_solve_batched_gather_pipelined(clc_comm* c, const clc_options* opt_in, c
   if (prev_stats) std::memset(prev_stats, 0, sizeof(*prev_stats));
   CLC_HIP(hipSetDevice(h->device));
   if (!c->copy_stream) {
-    CLC_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    CLC_HIP(hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
+    CLC_HIP(hipStreamCreateWithFlags(c->copy_stream.out(), hipStreamNonBlocking));
+    CLC_HIP(hipEventCreateWithFlags(c->ev_copy.out(), hipEventDisableTiming));
   }
   // 1. the previous step: its kernel and collective have to be over before this step's start poses overwrite the pinned buffer its
   //    kernel reads and before this step's totals are defined; its device -> host copies go to the COPY stream — they run while this

@@ -42,35 +42,26 @@ int eval_grid(const clc_handle* h, size_t n) {
 
 // Partial rows.  The capacity is a whole number of 256-row rounds: the controller reads rows in rounds of 256 from
 // unclamped addresses and masks the ones beyond the grid afterwards (clc::lm_tail), so every round must be mapped.
+// Two buffers: the step kernel alternates between them by launch parity (d_partials_b).
 int ensure_partials(clc_handle* h, int blocks) {
-  if (blocks <= h->partials_cap_blocks) return CLC_OK;
-  const int cap = (blocks + clc::BLOCK - 1) / clc::BLOCK * clc::BLOCK;
-  if (h->d_partials) CLC_HIP(hipFree(h->d_partials));
-  h->d_partials = nullptr;
-  h->partials_cap_blocks = 0;
-  // two buffers: the step kernel alternates between them by launch parity
-  CLC_HIP(hipMalloc(&h->d_partials, 2 * sizeof(double) * (size_t)cap * clc::NACC9));
+  if (2 * (size_t)blocks * clc::NACC9 <= h->d_partials.size()) return CLC_OK;
+  const size_t doubles = 2 * (size_t)((blocks + clc::BLOCK - 1) / clc::BLOCK * clc::BLOCK) * clc::NACC9;
+  CLC_HIP(h->d_partials.grow(doubles));
   // on the handle's stream: a null-stream memset is not ordered against kernels on a non-blocking stream
-  CLC_HIP(hipMemsetAsync(h->d_partials, 0, 2 * sizeof(double) * (size_t)cap * clc::NACC9, h->stream));
-  h->partials_cap_blocks = cap;
-  h->d_partials_b = h->d_partials + (size_t)cap * clc::NACC9;
+  CLC_HIP(hipMemsetAsync(h->d_partials, 0, sizeof(double) * doubles, h->stream));
   return CLC_OK;
 }
 
 int ensure_trace(clc_handle* h, int cap) {
-  if (cap <= h->trace_cap) return CLC_OK;
-  if (h->d_trace) CLC_HIP(hipFree(h->d_trace));
-  h->d_trace = nullptr;
-  CLC_HIP(hipMalloc(&h->d_trace, sizeof(clc_iteration) * (size_t)cap));
-  h->trace_cap = cap;
+  if (cap > 0) CLC_HIP(h->d_trace.grow((size_t)cap));
   return CLC_OK;
 }
 
 int ensure_events(clc_handle* h, size_t n) {
   while (h->ev.size() < n) {
-    hipEvent_t e;
-    CLC_HIP(hipEventCreate(&e));
-    h->ev.push_back(e);
+    Event e;
+    CLC_HIP(hipEventCreate(e.out()));
+    h->ev.push_back(std::move(e));
   }
   return CLC_OK;
 }
@@ -94,21 +85,12 @@ bool rows_nontemporal(const clc_handle* h, long long n_rows, bool z) {
 // handle's stream in front of the launches that read it, when the grid changed since the last upload.
 void ensure_wave_split(clc_handle* h, int grid) {
   if (h->split_grid == grid) return;
-  const clc::RowDesc* desc = reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc);
-  int* table = reinterpret_cast<int*>(reinterpret_cast<char*>(h->obs.d_rdesc) + ((size_t)h->obs.n_rows + 1) * sizeof(clc::RowDesc));
+  const clc::RowDesc* desc = h->obs.d_rdesc();
+  int* table = reinterpret_cast<int*>(h->obs.d_rdesc() + h->obs.n_rows + 1);
   const int total = grid * 8 + 1;
   hipLaunchKernelGGL(clc::wave_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, desc, (int)h->obs.n_rows,
                      grid, table);
   h->split_grid = grid;
-}
-
-int ensure_bytes(double** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap && *p) return CLC_OK;
-  if (*p) CLC_HIP(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  CLC_HIP(hipMalloc(p, bytes));
-  *cap = bytes;
-  return CLC_OK;
 }
 
 }  // namespace clc_abi
@@ -176,26 +158,21 @@ static int create_init(clc_handle* h) {
     if (m >= 0 && m <= 11 && (m & 4) == 0) h->auto_disable = m;
   }
   if (const char* e = std::getenv("CLC_SMALL_ON_COOP")) h->small_on_coop = std::atoi(e) != 0;
-  CLC_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+  CLC_HIP(hipStreamCreateWithFlags(h->own_stream.out(), hipStreamNonBlocking));
   h->stream = h->own_stream;
-  CLC_HIP(hipMalloc(&h->d_block, sizeof(clc::SolveBlock)));
-  h->d_state = &h->d_block->st[0];
-  h->d_state_b = &h->d_block->st[1];
-  CLC_HIP(hipMalloc(&h->d_small, sizeof(double) * kSmallDoubles));
-  CLC_HIP(hipHostMalloc(&h->h_small, sizeof(double) * kSmallDoubles, hipHostMallocDefault));
-  CLC_HIP(hipMalloc(&h->d_queue, sizeof(unsigned int)));
-  CLC_HIP(hipMalloc(&h->d_ticket, sizeof(unsigned int)));
+  CLC_HIP(h->d_block.grow(1));
+  CLC_HIP(h->d_small.grow(kSmallDoubles));
+  CLC_HIP(h->h_small.grow(kSmallDoubles));
+  CLC_HIP(h->d_queue.grow(1));
+  CLC_HIP(h->d_ticket.grow(1));
   CLC_HIP(hipMemsetAsync(h->d_ticket, 0, sizeof(unsigned int), h->own_stream));
   CLC_HIP(hipMemsetAsync(h->d_queue, 0, sizeof(unsigned int), h->own_stream));  // (counters are zero between launches)
   CLC_HIP(hipStreamSynchronize(h->own_stream));  // the caller may switch streams (clc_set_stream) before the first launch
-  CLC_HIP(hipHostMalloc(&h->h_mailbox, sizeof(clc::HostMailbox), hipHostMallocCoherent | hipHostMallocMapped));
-  CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_mailbox), h->h_mailbox, 0));
+  CLC_HIP(h->h_mailbox.grow(1));
   std::memset(h->h_mailbox, 0, sizeof(clc::HostMailbox));
   // start pose / outcome of the single-workgroup resident solve (one allocation: 8 doubles of pose, then the summary)
-  CLC_HIP(hipHostMalloc(&h->h_spose, 8 * sizeof(double) + sizeof(clc_summary), hipHostMallocCoherent | hipHostMallocMapped));
-  CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_spose), h->h_spose, 0));
-  h->h_ssummary = reinterpret_cast<clc_summary*>(h->h_spose + 8);
-  h->d_ssummary = reinterpret_cast<clc_summary*>(h->d_spose + 8);
+  static_assert(sizeof(clc_summary) % sizeof(double) == 0, "the summary follows the pose in whole doubles");
+  CLC_HIP(h->h_spose.grow(8 + sizeof(clc_summary) / sizeof(double)));
   // The code objects of the units that hold kernels are loaded here, not by the first call that launches one of their kernels: the
   // reference's programs call the path once per process, and that one call then took 20 ms instead of 1 (CLC_LAZY_MODULES=1: leave
   // it to the first launches — a process that creates handles it may never use).
@@ -234,28 +211,6 @@ void clc_destroy(clc_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-  h->obs.release();
-  h->batch.release();
-  for (clc_abi::ResLayout* L : {&h->sres, &h->bres, &h->cres}) L->release();
-  void* ptrs[] = {h->d_partials, h->d_block, h->d_trace, h->d_small, h->d_tile_off, h->d_nobs, h->d_queue, h->d_states,
-                  h->d_bpartials, h->d_ticket, h->d_results, h->d_board, h->d_prob_row, h->d_sq, h->d_st, h->d_spts, h->d_sptl, h->d_soff};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  h->pool.clear();
-  if (h->h_small) (void)hipHostFree(h->h_small);
-  if (h->h_mailbox) (void)hipHostFree(h->h_mailbox);
-  if (h->h_spose) (void)hipHostFree(h->h_spose);
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
-  if (h->d_stage) (void)hipFree(h->d_stage);
-  if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
-  if (h->d_small_aos) (void)hipFree(h->d_small_aos);
-  if (h->h_ms_poses) (void)hipHostFree(h->h_ms_poses);
-  if (h->h_ms_summaries) (void)hipHostFree(h->h_ms_summaries);
-  if (h->d_ms_results) (void)hipFree(h->d_ms_results);
-  if (h->h_poses) (void)hipHostFree(h->h_poses);
-  if (h->h_summaries) (void)hipHostFree(h->h_summaries);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }
 

@@ -117,11 +117,11 @@ int clc_debug_wave_split(clc_handle* h, int grid, int* split, int* first) {
   ensure_wave_split(h, grid);
   CLC_HIP(hipGetLastError());
   CLC_HIP(hipStreamSynchronize(h->stream));
-  const char* base = reinterpret_cast<const char*>(h->obs.d_rdesc);
-  CLC_HIP(hipMemcpy(split, base + ((size_t)h->obs.n_rows + 1) * sizeof(clc::RowDesc), sizeof(int) * ((size_t)grid * 8 + 1), hipMemcpyDeviceToHost));
+  const clc::RowDesc* desc = h->obs.d_rdesc();
+  CLC_HIP(hipMemcpy(split, desc + h->obs.n_rows + 1, sizeof(int) * ((size_t)grid * 8 + 1), hipMemcpyDeviceToHost));
   if (first) {
     std::vector<clc::RowDesc> d((size_t)h->obs.n_rows);
-    CLC_HIP(hipMemcpy(d.data(), base, sizeof(clc::RowDesc) * (size_t)h->obs.n_rows, hipMemcpyDeviceToHost));
+    CLC_HIP(hipMemcpy(d.data(), desc, sizeof(clc::RowDesc) * (size_t)h->obs.n_rows, hipMemcpyDeviceToHost));
     for (long long r = 0; r < h->obs.n_rows; ++r) first[r] = d[(size_t)r].first;
   }
   return CLC_OK;
@@ -231,7 +231,7 @@ int clc_time_batched_eval(clc_handle* h, const double* poses, int reps, double* 
   const size_t P = h->n_problems;
   std::memcpy(h->h_poses, poses, sizeof(double) * 7 * P);
   hipLaunchKernelGGL(clc::batched_init_kernel, dim3(bl.lm_blocks), dim3(bl.lm_threads), 0, h->stream, h->d_states, opt,
-                     h->d_poses, (int)P, h->d_queue, h->d_ticket);
+                     h->h_poses.dev(), (int)P, h->d_queue, h->d_ticket);
   for (int w = 0; w < 2; ++w) launch_batched_eval(h, opt, bl);
   CLC_HIP(hipEventRecord(h->ev[0], h->stream));
   for (int r = 0; r < reps; ++r) launch_batched_eval(h, opt, bl);

@@ -96,7 +96,7 @@ int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9
   int rc = ensure_partials(h, grid);
   if (rc != CLC_OK) return rc;
   if (use_rows(h)) {
-    const clc::RowDesc* rdesc = reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc);
+    const clc::RowDesc* rdesc = h->obs.d_rdesc();
     if (h->obs.rows_z) {  // bar_p = (x, y, 1): z is not read, only the row stride differs
       if (rows_nontemporal(h, h->obs.n_rows, true))
         hipLaunchKernelGGL((clc::normal9_rows_kernel<true, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy, rdesc, h->obs.n_rows, h->d_partials);
@@ -105,10 +105,10 @@ int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9
     }
     else if (rows_nontemporal(h, h->obs.n_rows))
       hipLaunchKernelGGL(clc::normal9_rows_kernel<true>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy,
-                         reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc), h->obs.n_rows, h->d_partials);
+                         h->obs.d_rdesc(), h->obs.n_rows, h->d_partials);
     else
       hipLaunchKernelGGL(clc::normal9_rows_kernel<false>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy,
-                         reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc), h->obs.n_rows, h->d_partials);
+                         h->obs.d_rdesc(), h->obs.n_rows, h->d_partials);
   } else {
     hipLaunchKernelGGL(clc::normal9_kernel, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_tiles,
                        (long long)h->n_obs, h->d_partials);

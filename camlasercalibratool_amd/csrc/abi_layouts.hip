@@ -8,8 +8,7 @@ namespace {
 
 int retile_into(clc_handle* h, const double* d_aos, size_t n, StreamLayout& L) {
   const size_t n_padded = ((n + clc::TILE - 1) / clc::TILE) * clc::TILE;
-  const int rc = ensure_bytes(&L.d_tiles, &L.tiles_cap, std::max<size_t>(n_padded, clc::TILE) * 8 * sizeof(double));
-  if (rc != CLC_OK) return rc;
+  CLC_HIP(L.d_tiles.grow(std::max<size_t>(n_padded, clc::TILE) * 8));
   if (n_padded > 0) {
     const int threads = 256;
     const long long blocks = ((long long)n_padded + threads - 1) / threads;
@@ -82,29 +81,23 @@ int build_resident(clc_handle* h, ResLayout& L, int first_try, const double* d_a
   }
   if (total >= 0xFFFFFFF0ull) return CLC_OK;
   row[P] = (unsigned int)total;
-  int rc = ensure_bytes(&L.d_row, &L.row_cap, (P + 1) * sizeof(unsigned int));
-  if (rc != CLC_OK) return rc;
-  rc = ensure_bytes(&L.d_desc, &L.desc_cap, P * (size_t)lanes * sizeof(clc::ResLane));
-  if (rc != CLC_OK) return rc;
+  CLC_HIP(L.d_row.grow(P + 1));
+  CLC_HIP(L.d_desc.grow(P * (size_t)lanes));
   // one padding row: the kernel's loads run unconditionally from clamped row indices (an empty last problem reads it)
-  rc = ensure_bytes(&L.d_xy, &L.xy_cap, ((size_t)total + 1) * (size_t)lanes * 2 * sizeof(double));
-  if (rc != CLC_OK) return rc;
+  CLC_HIP(L.d_xy.grow(((size_t)total + 1) * (size_t)lanes * 2));
   CLC_HIP(hipMemcpyAsync(L.d_row, row.data(), (P + 1) * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
   CLC_HIP(hipMemsetAsync(L.d_xy + (size_t)total * (size_t)lanes * 2, 0, (size_t)lanes * 2 * sizeof(double), h->stream));
   if (with_z) {
-    rc = ensure_bytes(&L.d_z, &L.z_cap, ((size_t)total + 1) * (size_t)lanes * sizeof(double));
-    if (rc != CLC_OK) return rc;
+    CLC_HIP(L.d_z.grow(((size_t)total + 1) * (size_t)lanes));
     CLC_HIP(hipMemsetAsync(L.d_z + (size_t)total * (size_t)lanes, 0, (size_t)lanes * sizeof(double), h->stream));
   }
   double* d_zl = with_z ? L.d_z : nullptr;
-  const unsigned int* d_row = reinterpret_cast<const unsigned int*>(L.d_row);
-  clc::ResLane* d_desc = reinterpret_cast<clc::ResLane*>(L.d_desc);
   if (lanes == 256)
     hipLaunchKernelGGL((clc::res_build_kernel<256>), dim3((unsigned)P), dim3(256), 0, h->stream, d_aos, d_rec_off, d_gid, d_starts, n,
-                       (long long)G, d_row, d_desc, L.d_xy, d_zl);
+                       (long long)G, L.d_row, L.d_desc, L.d_xy, d_zl);
   else
     hipLaunchKernelGGL((clc::res_build_kernel<512>), dim3((unsigned)P), dim3(512), 0, h->stream, d_aos, d_rec_off, d_gid, d_starts, n,
-                       (long long)G, d_row, d_desc, L.d_xy, d_zl);
+                       (long long)G, L.d_row, L.d_desc, L.d_xy, d_zl);
   CLC_HIP(hipGetLastError());
   CLC_HIP(hipStreamSynchronize(h->stream));  // `row` is a host temporary
   L.lanes = lanes;
@@ -145,9 +138,8 @@ struct LayoutPlan {
 // The builds of a plan, first part: the compact layout — group table (what the on-chip kernels take a lane's plane from) + 28-byte tiles.
 int emit_compact(clc_handle* h, const double* d_aos, const LayoutPlan& p, StreamLayout& L) {
   const int threads = 256;
-  int rc = ensure_bytes(&L.d_ctiles, &L.ctiles_cap, std::max<size_t>(p.tiles, 1) * clc::CTILE_DOUBLES * sizeof(double));
-  if (rc == CLC_OK) rc = ensure_bytes(&L.d_groups, &L.groups_cap, p.G * clc::GROUP_DOUBLES * sizeof(double));
-  if (rc != CLC_OK) return rc;
+  CLC_HIP(L.d_ctiles.grow(std::max<size_t>(p.tiles, 1) * clc::CTILE_DOUBLES));
+  CLC_HIP(L.d_groups.grow(p.G * clc::GROUP_DOUBLES));
   hipLaunchKernelGGL(clc::build_groups_dev_kernel, dim3((unsigned)((p.G + threads - 1) / threads)), dim3(threads), 0, h->stream, d_aos,
                      p.d_starts, (long long)p.G, L.d_groups);
   const long long max_padded = p.max_tiles * clc::TILE;
@@ -167,28 +159,26 @@ int emit_rows_and_lanes(clc_handle* h, const double* d_aos, const LayoutPlan& p,
   if (p.rows_ok) {
     // one padding row each: the streaming loop's prologue loads run unconditionally from clamped row indices; + the wave split table
     const size_t row_doubles = p.any_z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES;
-    rc = ensure_bytes(&L.d_rxy, &L.rxy_cap, ((size_t)R + 1) * row_doubles * sizeof(double));
-    if (rc == CLC_OK) rc = ensure_bytes(&L.d_rdesc, &L.rdesc_cap, ((size_t)R + 1) * sizeof(clc::RowDesc) + clc::wave_split_bytes(R));
-    if (rc != CLC_OK) return rc;
+    CLC_HIP(L.d_rxy.grow(((size_t)R + 1) * row_doubles));
+    CLC_HIP(L.rdesc_bytes.grow(((size_t)R + 1) * sizeof(clc::RowDesc) + clc::wave_split_bytes(R)));
     CLC_HIP(hipMemsetAsync(L.d_rxy + (size_t)R * row_doubles, 0, row_doubles * sizeof(double), h->stream));
-    CLC_HIP(hipMemsetAsync(reinterpret_cast<char*>(L.d_rdesc) + (size_t)R * sizeof(clc::RowDesc), 0, sizeof(clc::RowDesc), h->stream));
+    CLC_HIP(hipMemsetAsync(L.d_rdesc() + R, 0, sizeof(clc::RowDesc), h->stream));
     const long long slots = R * clc::ROW;
     hipLaunchKernelGGL(clc::build_rows_kernel, dim3((unsigned)((slots + threads - 1) / threads)), dim3(threads), 0, h->stream, d_aos,
-                       p.d_starts, p.d_row_begin, (long long)p.G, R, (int)row_doubles, L.d_rxy, reinterpret_cast<clc::RowDesc*>(L.d_rdesc));
+                       p.d_starts, p.d_row_begin, (long long)p.G, R, (int)row_doubles, L.d_rxy, L.d_rdesc());
     if (d_prob_row)
       hipLaunchKernelGGL(clc::problem_rows_kernel, dim3((unsigned)((p.P + 1 + threads - 1) / threads)), dim3(threads), 0, h->stream,
                          p.d_rec_off, p.d_gid, p.d_row_begin, (long long)p.P, n, R, d_prob_row);
     CLC_HIP(hipGetLastError());
   }
   if (res != nullptr && p.ppl > 0) {  // planned on the host: one problem's 512-lane layout (build_resident with first_try = 512)
-    rc = ensure_bytes(&res->d_row, &res->row_cap, 2 * sizeof(unsigned int));
-    if (rc == CLC_OK) rc = ensure_bytes(&res->d_desc, &res->desc_cap, (size_t)512 * sizeof(clc::ResLane));
-    if (rc == CLC_OK) rc = ensure_bytes(&res->d_xy, &res->xy_cap, ((size_t)p.ppl + 1) * 512 * 2 * sizeof(double));
-    if (rc != CLC_OK) return rc;
+    CLC_HIP(res->d_row.grow(2));
+    CLC_HIP(res->d_desc.grow(512));
+    CLC_HIP(res->d_xy.grow(((size_t)p.ppl + 1) * 512 * 2));
     CLC_HIP(hipMemcpyAsync(res->d_row, p.d_res_row, 2 * sizeof(unsigned int), hipMemcpyDeviceToDevice, h->stream));
     CLC_HIP(hipMemsetAsync(res->d_xy + (size_t)p.ppl * 512 * 2, 0, (size_t)512 * 2 * sizeof(double), h->stream));
     hipLaunchKernelGGL((clc::res_build_kernel<512>), dim3(1), dim3(512), 0, h->stream, d_aos, p.d_rec_off, p.d_gid, p.d_starts, n,
-                       (long long)p.G, p.d_res_row, reinterpret_cast<clc::ResLane*>(res->d_desc), res->d_xy, (double*)nullptr);
+                       (long long)p.G, p.d_res_row, res->d_desc, res->d_xy, (double*)nullptr);
     CLC_HIP(hipGetLastError());
     res->lanes = 512; res->max_ppl = p.ppl; res->uni_ppl = p.ppl; res->rows = p.ppl; res->with_z = false; res->ok = true;
   } else if (res != nullptr) {
@@ -354,17 +344,14 @@ void forget_layouts(clc_handle* h) {
 
 // The pinned staging block of the small-problem path (+ its device twin), at least `bytes` long and free to be written.
 int ensure_stage(clc_handle* h, size_t bytes) {
-  if (bytes > h->stage_cap) {
+  if (bytes > std::min(h->h_stage.size(), h->d_stage.size())) {
     CLC_HIP(hipStreamSynchronize(h->stream));
-    if (h->h_stage) CLC_HIP(hipHostFree(h->h_stage));
-    if (h->d_stage) CLC_HIP(hipFree(h->d_stage));
-    h->h_stage = h->d_stage = nullptr; h->stage_cap = 0; h->stage_busy = false;
+    h->stage_busy = false;
     const size_t cap = std::max<size_t>(bytes + bytes / 2, (size_t)256 << 10);
-    CLC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_stage), cap, hipHostMallocDefault));
-    CLC_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stage), cap));
-    h->stage_cap = cap;
+    CLC_HIP(h->h_stage.grow(cap));
+    CLC_HIP(h->d_stage.grow(cap));
   }
-  if (!h->ev_stage) CLC_HIP(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+  if (!h->ev_stage) CLC_HIP(hipEventCreateWithFlags(h->ev_stage.out(), hipEventDisableTiming));
   if (h->stage_busy) CLC_HIP(hipEventSynchronize(h->ev_stage));  // the previous copy out of the pinned block (long done in practice)
   return CLC_OK;
 }
@@ -437,11 +424,9 @@ int small_fast_upload(clc_handle* h, const std::vector<long long>& starts, long 
   int rc = plan_small_on_host(h, starts, n, any_z, host_records, fj, &p, &d_aos, &d_foff, used);
   if (rc != CLC_OK || !*used) return rc;
   if (fj) {  // the selection's records, built on the device from the resident scans (bitwise clc_flatten_observations')
-    rc = ensure_bytes(&h->d_small_aos, &h->small_aos_cap, (size_t)n * sizeof(clc_observation));
-    if (rc != CLC_OK) return rc;
-    long long* d_soff = reinterpret_cast<long long*>(h->d_soff);
-    hipLaunchKernelGGL(clc::flatten_kernel, dim3((unsigned)fj->n_poses), dim3(clc::BLOCK), 0, h->stream, fj->n_poses, h->d_sq, h->d_st, d_soff,
-                       h->d_spts, d_soff + (fj->n_poses + 1), h->d_sptl, fj->linefit ? 1 : 0, fj->boundary ? 1 : 0, d_foff, h->d_small_aos);
+    CLC_HIP(h->d_small_aos.grow((size_t)n * (sizeof(clc_observation) / sizeof(double))));
+    hipLaunchKernelGGL(clc::flatten_kernel, dim3((unsigned)fj->n_poses), dim3(clc::BLOCK), 0, h->stream, fj->n_poses, h->d_sq, h->d_st, h->d_soff,
+                       h->d_spts, h->d_soff + (fj->n_poses + 1), h->d_sptl, fj->linefit ? 1 : 0, fj->boundary ? 1 : 0, d_foff, h->d_small_aos);
     CLC_HIP(hipGetLastError());
     d_aos = h->d_small_aos;
   }
@@ -571,8 +556,6 @@ int clc_upload(clc_handle* h, const clc_observation* records, size_t n) {
 // ---- resident scans + device-side problem assembly ---------------------------------------------------------------
 namespace {
 
-int grow(double** p, size_t* cap, size_t bytes) { return ensure_bytes(p, cap, std::max<size_t>(bytes, 8)); }
-
 // per-pose record offsets of a selection (host, O(poses)); CLC_ERR_EMPTY_SCAN mirrors the reference's .at(0) throw
 
 int selection_offsets(const clc_handle* h, bool linefit, bool boundary, std::vector<long long>* rec_off) {
@@ -606,7 +589,7 @@ int flatten_on_device(clc_handle* h, bool linefit, bool boundary, DevBuf<double>
   *n_out = N;
   CLC_HIP(aos->alloc((size_t)std::max<long long>(N, 1) * 8));
   if (N == 0 || P == 0) return CLC_OK;
-  long long* d_off = reinterpret_cast<long long*>(h->d_soff);
+  long long* d_off = h->d_soff;
   CLC_HIP(hipMemcpyAsync(d_off + 2 * ((size_t)P + 1), rec_off.data(), sizeof(long long) * ((size_t)P + 1), hipMemcpyHostToDevice,
                          h->stream));
   hipLaunchKernelGGL(clc::flatten_kernel, dim3((unsigned)P), dim3(clc::BLOCK), 0, h->stream, P, h->d_sq, h->d_st, d_off,
@@ -639,16 +622,16 @@ int clc_store_observations(clc_handle* h, int n_poses, const double* tag_q_wxyz,
   const size_t M = (size_t)h->s_pts_off[P], ML = (size_t)h->s_ptl_off[P];
   if ((M > 0 && !pts) || (ML > 0 && !ptl)) return fail(CLC_ERR_INVALID_ARG, "clc_store_observations: NULL points");
   CLC_HIP(hipSetDevice(h->device));
-  int rc = grow(&h->d_sq, &h->sq_cap, P * 4 * sizeof(double));
-  if (rc == CLC_OK) rc = grow(&h->d_st, &h->st_cap, P * 3 * sizeof(double));
-  if (rc == CLC_OK) rc = grow(&h->d_spts, &h->spts_cap, M * 3 * sizeof(double));
-  if (rc == CLC_OK) rc = grow(&h->d_sptl, &h->sptl_cap, ML * 3 * sizeof(double));
-  if (rc == CLC_OK) rc = grow(&h->d_soff, &h->soff_cap, 3 * (P + 1) * sizeof(long long));
-  if (rc != CLC_OK) return rc;
+  // (never empty: at least one element each)
+  CLC_HIP(h->d_sq.grow(std::max<size_t>(P * 4, 1)));
+  CLC_HIP(h->d_st.grow(std::max<size_t>(P * 3, 1)));
+  CLC_HIP(h->d_spts.grow(std::max<size_t>(M * 3, 1)));
+  CLC_HIP(h->d_sptl.grow(std::max<size_t>(ML * 3, 1)));
+  CLC_HIP(h->d_soff.grow(3 * (P + 1)));
   if (P > 0) {
     CLC_HIP(hipMemcpyAsync(h->d_sq, tag_q_wxyz, P * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     CLC_HIP(hipMemcpyAsync(h->d_st, tag_t, P * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    long long* d_off = reinterpret_cast<long long*>(h->d_soff);
+    long long* d_off = h->d_soff;
     CLC_HIP(hipMemcpyAsync(d_off, h->s_pts_off.data(), (P + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     CLC_HIP(hipMemcpyAsync(d_off + (P + 1), h->s_ptl_off.data(), (P + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
   }
@@ -748,29 +731,17 @@ int upload_batched_impl(clc_handle* h, const clc_observation* records, bool on_d
   h->batch_max_tiles = max_tiles;
   const size_t total_tiles = (size_t)tile_off[P];
   h->batch_total_tiles = total_tiles;
-  const int rc = ensure_bytes(&h->batch.d_tiles, &h->batch.tiles_cap, std::max<size_t>(total_tiles, 1) * clc::TILE_DOUBLES * sizeof(double));
-  if (rc != CLC_OK) return rc;
-  if (P > h->problems_cap) {
-    void* olds[] = {h->d_tile_off, h->d_nobs, h->d_states, h->d_results, h->d_prob_row};
-    for (void* p : olds) if (p) CLC_HIP(hipFree(p));
-    if (h->h_poses) CLC_HIP(hipHostFree(h->h_poses));
-    if (h->h_summaries) CLC_HIP(hipHostFree(h->h_summaries));
-    h->h_poses = nullptr; h->h_summaries = nullptr;
-    h->d_tile_off = nullptr; h->d_nobs = nullptr; h->d_poses = nullptr; h->d_summaries = nullptr;
-    h->d_states = nullptr; h->d_results = nullptr; h->results_valid = 0; h->d_prob_row = nullptr;
-    h->problems_cap = 0;
-    CLC_HIP(hipMalloc(&h->d_tile_off, sizeof(long long) * (P + 1)));
-    CLC_HIP(hipMalloc(&h->d_nobs, sizeof(long long) * P));
-    CLC_HIP(hipHostMalloc(&h->h_poses, sizeof(double) * 7 * P, hipHostMallocMapped));
-    CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_poses), h->h_poses, 0));
-    CLC_HIP(hipHostMalloc(&h->h_summaries, sizeof(clc_summary) * P, hipHostMallocMapped));
-    CLC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_summaries), h->h_summaries, 0));
-    CLC_HIP(hipMalloc(&h->d_states, sizeof(clc::LmState) * P));
-    CLC_HIP(hipMalloc(&h->d_results, sizeof(clc_result_record) * P));
-    CLC_HIP(hipMalloc(&h->d_prob_row, sizeof(long long) * (P + 1)));
-    h->problems_cap = P;
-  }
+  CLC_HIP(h->batch.d_tiles.grow(std::max<size_t>(total_tiles, 1) * clc::TILE_DOUBLES));
   if (P == 0) { h->n_problems = 0; return CLC_OK; }
+  const size_t rec_doubles = sizeof(clc_result_record) / sizeof(double);
+  if (P * rec_doubles > h->d_results.size()) h->results_valid = 0;  // (the records are about to be freed)
+  CLC_HIP(h->d_tile_off.grow(P + 1));
+  CLC_HIP(h->d_nobs.grow(P));
+  CLC_HIP(h->h_poses.grow(7 * P));
+  CLC_HIP(h->h_summaries.grow(P));
+  CLC_HIP(h->d_states.grow(P));
+  CLC_HIP(h->d_results.grow(P * rec_doubles));
+  CLC_HIP(h->d_prob_row.grow(P + 1));
   CLC_HIP(hipMemcpy(h->d_tile_off, tile_off.data(), sizeof(long long) * (P + 1), hipMemcpyHostToDevice));
   CLC_HIP(hipMemcpy(h->d_nobs, nobs.data(), sizeof(long long) * P, hipMemcpyHostToDevice));
   // stage the AoS records, then re-tile every problem into its own whole tiles

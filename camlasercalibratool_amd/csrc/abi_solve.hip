@@ -22,7 +22,7 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
     const auto launch = [&](auto BIG, auto EQ, auto NT, auto Z) {
       constexpr int BT = BIG ? 512 : 256;
       hipLaunchKernelGGL((clc::eval_rows_kernel<WITH_LOSS, NT, BT, !EQ, (NT && !Z) ? 12 : clc::ROWS_DEPTH, Z>), dim3(grid), dim3(BT), 0,
-                         h->stream, h->obs.d_rxy, reinterpret_cast<const clc::RowDesc*>(h->obs.d_rdesc), h->obs.n_rows, d_pose, d_status, lf, fl,
+                         h->stream, h->obs.d_rxy, h->obs.d_rdesc(), h->obs.n_rows, d_pose, d_status, lf, fl,
                          h->d_partials, pose_arg, use_pose_arg);
     };
     if (h->obs.rows_z) {  // rows that carry z: 3:2 wave shares
@@ -142,7 +142,7 @@ int finish_solve(clc_handle* h, const clc_summary& out, const double* out_pose, 
   *summary = out;
   for (int i = 0; i < 7; ++i) pose[i] = out_pose[i];
   if (trace != nullptr && trace_cap > 0) {
-    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), h->trace_cap);
+    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), (int)h->d_trace.size());
     if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
   }
   summary->eval_kernel_ms = kernel_ms;
@@ -174,8 +174,8 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
   prm.opt = opt;
   prm.pose0 = p0;
   prm.trace = want_trace ? h->d_trace : nullptr;
-  prm.mailbox = h->d_mailbox;
-  prm.trace_cap = want_trace ? h->trace_cap : 0;
+  prm.mailbox = h->h_mailbox.dev();
+  prm.trace_cap = want_trace ? (int)h->d_trace.size() : 0;
   const bool deep = (h->launch_flags & clc::FLAG_DEEP) != 0 ||
                     (h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes);
   const bool rows = use_rows(h);
@@ -183,7 +183,7 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
   const bool rows_nt = rows && rows_nontemporal(h, h->obs.n_rows, rows_z);
   const bool rows_eq = (h->launch_flags & clc::FLAG_EQUAL_WAVES) != 0 && !rows_z;
   if (rows && rows_eq) ensure_wave_split(h, grid);
-  double* rows_buf[2] = {h->d_partials, h->d_partials_b};
+  double* rows_buf[2] = {h->d_partials, h->d_partials_b()};
   // (max_iterations + 1) evaluations + the final controller pass; launch k is made while k - (passes consumed) <= lookahead
   const LaunchAhead la = {"clc_solve", opt.max_num_iterations + 2, lookahead + 1, LaunchAhead::kFail, 30.0};
   int launched = 0;
@@ -196,7 +196,7 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
     // MODE 0: launch 0, 1: launch 1, 2: the rest
     const auto launch = [&](auto LAYOUT, auto LOSS, auto EQ, auto NT, auto MODE) {
       hipLaunchKernelGGL((clc::step_kernel<LOSS, NT, MODE, LAYOUT, !EQ>), dim3(grid), dim3(512), 0, h->stream, r_in,
-                         LAYOUT ? h->obs.d_rxy : h->obs.d_ctiles, LAYOUT ? h->obs.d_rdesc : h->obs.d_groups, LAYOUT ? (int)h->obs.n_rows : (int)h->n_obs,
+                         LAYOUT ? h->obs.d_rxy : h->obs.d_ctiles, LAYOUT ? reinterpret_cast<const double*>(h->obs.d_rdesc()) : h->obs.d_groups.get(), LAYOUT ? (int)h->obs.n_rows : (int)h->n_obs,
                          grid | ((k & 1) << 30), k, r_out, h->d_block, prm);
     };
     const auto at_mode = [&](auto... c) {
@@ -232,7 +232,7 @@ namespace {
 int32_t* arm_done_flag(clc_handle* h) {
   __atomic_store_n(reinterpret_cast<int32_t*>(h->h_spose + 7), 0, __ATOMIC_RELAXED);
   std::atomic_thread_fence(std::memory_order_seq_cst);
-  return reinterpret_cast<int32_t*>(h->d_spose + 7);
+  return reinterpret_cast<int32_t*>(h->h_spose.dev() + 7);
 }
 
 // Polling the flag avoids the wake-up latency of a blocking stream synchronisation (~15 us of a ~120 us solve).  Bounded: a wedged
@@ -263,10 +263,8 @@ int solve_resident_single(clc_handle* h, const clc_options& opt, double pose[7],
   if (rc != CLC_OK) return rc;
   for (int i = 0; i < 7; ++i) h->h_spose[i] = pose[i];
   int32_t* d_done = arm_done_flag(h);
-  const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->sres.d_row);
-  const clc::ResLane* d_desc = reinterpret_cast<const clc::ResLane*>(h->sres.d_desc);
   clc_iteration* d_trace = want_trace ? h->d_trace : nullptr;
-  const int d_cap = want_trace ? h->trace_cap : 0;
+  const int d_cap = want_trace ? (int)h->d_trace.size() : 0;
   const bool uni_ctrl = h->single_uni_ctrl;  // the cooperative kernel's controller here: the bit-identity test of the two (hooks build)
   const bool timed = opt.profile_events == 2;  // an event pair around the one launch -> eval_kernel_ms, eval_kernel_launches = 1
   if (timed) {
@@ -276,7 +274,7 @@ int solve_resident_single(clc_handle* h, const clc_options& opt, double pose[7],
   }
   with_flags([&](auto LOSS, auto CTRL) {
     hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, false, 8, kResPR512, kResPL512, CTRL>), dim3(1), dim3(512), 0, h->stream,
-                       h->sres.d_xy, d_row, d_desc, h->obs.d_groups, h->sres.uni_ppl, opt, d_trace, d_cap, h->d_spose, h->d_ssummary,
+                       h->sres.d_xy, h->sres.d_row, h->sres.d_desc, h->obs.d_groups, h->sres.uni_ppl, opt, d_trace, d_cap, h->h_spose.dev(), h->d_ssummary(),
                        h->d_small, d_done, nullptr);
   }, opt.use_loss != 0, uni_ctrl);
   CLC_HIP(hipGetLastError());
@@ -284,7 +282,7 @@ int solve_resident_single(clc_handle* h, const clc_options& opt, double pose[7],
   if (wait_done_flag(h) == 0 || want_trace || timed) CLC_HIP(hipStreamSynchronize(h->stream));
   float kernel_ms = 0.0f;
   if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
-  return finish_solve(h, *h->h_ssummary, h->h_spose, pose, summary, trace, trace_cap, kernel_ms, timed ? 1 : 0, t0);
+  return finish_solve(h, *h->h_ssummary(), h->h_spose, pose, summary, trace, trace_cap, kernel_ms, timed ? 1 : 0, t0);
 }
 
 // clc_solve as ONE launch of 256 co-resident workgroups that keep the problem on chip (clc_coop.hpp).  Returns kCoopFallback when
@@ -342,7 +340,7 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
   CoopGate gate;  // (released when this function returns: the kernel has finished, or was never launched)
   if (!gate.acquire(h->device)) { ++h->coop_gate_waits_expired; return kCoopFallback; }
   if (!h->d_board) {
-    CLC_HIP(hipMalloc(&h->d_board, sizeof(clc::CoopBoard)));
+    CLC_HIP(h->d_board.grow(1));
     // (ordered on the handle's stream AND waited for: the caller may switch streams, clc_set_stream, before the next solve)
     CLC_HIP(hipMemsetAsync(h->d_board, 0, sizeof(clc::CoopBoard), h->stream));
     CLC_HIP(hipStreamSynchronize(h->stream));
@@ -373,10 +371,8 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
   int32_t* d_done = arm_done_flag(h);
   clc::Pose7 p0;
   for (int i = 0; i < 7; ++i) p0.v[i] = pose[i];
-  const unsigned int* d_row = reinterpret_cast<const unsigned int*>(h->cres.d_row);
-  const clc::ResLane* d_desc = reinterpret_cast<const clc::ResLane*>(h->cres.d_desc);
   clc_iteration* d_trace = want_trace ? h->d_trace : nullptr;
-  const int d_cap = want_trace ? h->trace_cap : 0;
+  const int d_cap = want_trace ? (int)h->d_trace.size() : 0;
   const unsigned int tag0 = h->coop_tag;
   h->coop_tag += passes;
   const int n_wgs = h->cres.wgs > 0 ? h->cres.wgs : clc::COOP_WGS;  // COOP_WGS, or COOP_SMALL_WGS: the one-hop form
@@ -386,8 +382,8 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
   // Z: 24-byte slots (p.z != 0); ONE: the one-hop form on 32 workgroups
   with_flags([&](auto Z, auto ONE, auto LOSS) {
     hipLaunchKernelGGL((clc::coop_solve_kernel<LOSS, false, Z, ONE>), dim3(wgs), dim3(clc::COOP_THREADS), 0, h->stream, h->cres.d_xy,
-                       h->cres.d_z, d_row, d_desc, h->obs.d_groups, h->cres.uni_ppl, opt, p0, d_trace, d_cap, h->d_board, tag0, h->d_spose,
-                       h->d_ssummary, h->d_small, d_done, n_wgs);
+                       h->cres.d_z, h->cres.d_row, h->cres.d_desc, h->obs.d_groups, h->cres.uni_ppl, opt, p0, d_trace, d_cap, h->d_board, tag0, h->h_spose.dev(),
+                       h->d_ssummary(), h->d_small, d_done, n_wgs);
   }, h->cres.with_z, n_wgs == clc::COOP_SMALL_WGS, opt.use_loss != 0);
   CLC_HIP(hipGetLastError());
   if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
@@ -406,7 +402,7 @@ int solve_coop(clc_handle* h, const clc_options& opt, double pose[7], clc_summar
   ++h->coop_solves;
   float kernel_ms = 0.0f;
   if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
-  return finish_solve(h, *h->h_ssummary, h->h_spose, pose, summary, trace, trace_cap, kernel_ms, timed ? 1 : 0, t0);
+  return finish_solve(h, *h->h_ssummary(), h->h_spose, pose, summary, trace, trace_cap, kernel_ms, timed ? 1 : 0, t0);
 }
 
 }  // namespace
@@ -458,11 +454,11 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
   clc::Pose7 p0;
   for (int i = 0; i < 7; ++i) p0.v[i] = pose[i];
   const double* d_x_eval = reinterpret_cast<const double*>(
-      reinterpret_cast<const char*>(h->d_state) + offsetof(clc::LmState, x_eval));
+      reinterpret_cast<const char*>(h->d_state()) + offsetof(clc::LmState, x_eval));
   const int32_t* d_status = reinterpret_cast<const int32_t*>(
-      reinterpret_cast<const char*>(h->d_state) + offsetof(clc::LmState, status));
+      reinterpret_cast<const char*>(h->d_state()) + offsetof(clc::LmState, status));
   clc_iteration* d_trace = want_trace ? h->d_trace : nullptr;
-  const int d_trace_cap = want_trace ? h->trace_cap : 0;
+  const int d_trace_cap = want_trace ? (int)h->d_trace.size() : 0;
   const LaunchAhead la = {"clc_solve", max_evals, lookahead, LaunchAhead::kFailOnceConsumed, 30.0};
   int launched = 0;
   rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) -> int {
@@ -471,8 +467,8 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
     launch_eval<true>(h, grid, opt.use_loss != 0, d_x_eval, d_status, opt.loss_scale_factor, k == 0 ? &p0 : nullptr);
     if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * k + 1], h->stream));
     with_flags([&](auto FIRST) {
-      hipLaunchKernelGGL(clc::lm_kernel<FIRST>, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid, h->d_state, opt,
-                         d_trace, d_trace_cap, h->d_mailbox, p0);
+      hipLaunchKernelGGL(clc::lm_kernel<FIRST>, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid, h->d_state(), opt,
+                         d_trace, d_trace_cap, h->h_mailbox.dev(), p0);
     }, k == 0);
     return CLC_OK;
   }, &launched);

@@ -31,6 +31,7 @@
 #include "clc_kernels.hpp"
 #include "clc_resident.hpp"
 #include "clc_coop.hpp"
+#include "abi_memory.hpp"
 
 namespace clc_abi {
 
@@ -42,55 +43,6 @@ int fail(int code, const char* what, hipError_t e = hipSuccess);  // abi_core.hi
     hipError_t e_ = (expr);                                           \
     if (e_ != hipSuccess) return fail(CLC_ERR_HIP, #expr, e_);        \
   } while (0)
-
-// Temporaries of one call come from a per-handle pool of device blocks: hipMalloc / hipFree of tens of megabytes cost
-// milliseconds each with the system runtime (and hipFree synchronises the device), which made a 0.7 ms
-// clc_select_observations take 20 ms when called from a plain C++ program.  A block goes back to the pool on scope
-// exit and is handed out again (best fit) to later calls; blocks beyond 1 GiB are really freed.  Every entry point
-// synchronises its stream before it returns, so a recycled block is never still in use.
-struct DevPool {
-  struct Block { void* p; size_t cap; };
-  std::vector<Block> free_blocks;
-  static constexpr size_t kKeepLimit = (size_t)1 << 30;
-  hipError_t acquire(size_t bytes, void** out, size_t* cap) {
-    bytes = std::max<size_t>(bytes, 256);
-    int best = -1;
-    for (int i = 0; i < (int)free_blocks.size(); ++i)
-      if (free_blocks[(size_t)i].cap >= bytes && (best < 0 || free_blocks[(size_t)i].cap < free_blocks[(size_t)best].cap)) best = i;
-    if (best >= 0 && free_blocks[(size_t)best].cap <= 4 * bytes + ((size_t)1 << 20)) {
-      *out = free_blocks[(size_t)best].p;
-      *cap = free_blocks[(size_t)best].cap;
-      free_blocks.erase(free_blocks.begin() + best);
-      return hipSuccess;
-    }
-    *cap = bytes;
-    return hipMalloc(out, bytes);
-  }
-  void release(void* p, size_t cap) {
-    if (!p) return;
-    if (cap > kKeepLimit || free_blocks.size() >= 64) { (void)hipFree(p); return; }
-    free_blocks.push_back({p, cap});
-  }
-  void clear() {
-    for (const Block& b : free_blocks) (void)hipFree(b.p);
-    free_blocks.clear();
-  }
-};
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap_bytes = 0;
-  DevPool* pool;
-  explicit DevBuf(DevPool* pl) : pool(pl) {}
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) pool->release(p, cap_bytes); }
-  hipError_t alloc(size_t count) {
-    if (p) { pool->release(p, cap_bytes); p = nullptr; }
-    return pool->acquire(std::max<size_t>(count, 1) * sizeof(T), reinterpret_cast<void**>(&p), &cap_bytes);
-  }
-};
 
 inline bool all_finite(const double* p, int n) {
   for (int i = 0; i < n; ++i)
@@ -108,14 +60,10 @@ constexpr int kSmallDoubles = 512;  // device + pinned scratch for small transfe
 
 // Lane layout of clc_resident.hpp: j-major point rows, lane descriptors, row offsets per problem.
 struct ResLayout {
-  double* d_xy = nullptr;
-  size_t xy_cap = 0;
-  double* d_desc = nullptr;  // clc::ResLane [P * lanes]
-  size_t desc_cap = 0;
-  double* d_row = nullptr;   // unsigned int [P + 1]
-  size_t row_cap = 0;
-  double* d_z = nullptr;     // with_z: the slots' z, j-major like d_xy, 8 bytes per slot
-  size_t z_cap = 0;
+  DeviceArray<double> d_xy;
+  DeviceArray<clc::ResLane> d_desc;  // [P * lanes]
+  DeviceArray<unsigned int> d_row;   // [P + 1]
+  DeviceArray<double> d_z;   // with_z: the slots' z, j-major like d_xy, 8 bytes per slot
   bool with_z = false;       // some record has p.z != 0: 24-byte slots (cooperative layout; batched layout: the 512-lane z form)
   int wgs = 0;               // cooperative layout only: the workgroups the problem is dealt to (COOP_WGS, or COOP_SMALL_WGS: one-hop form)
   int lanes = 0;             // lanes per problem of the built layout (256 / 512)
@@ -123,50 +71,46 @@ struct ResLayout {
   int uni_ppl = -1;          // >= 0: every problem has this many points per lane
   long long rows = 0;        // j-rows in all
   bool ok = false;
-  void release() {
-    for (double* p : {d_xy, d_desc, d_row, d_z}) if (p) (void)hipFree(p);
-  }
 };
 
 // The streaming layouts of one observation array (the single problem's, the batch's): 64-byte tiles; their compact copy (28 B/obs:
 // tiles + group table), built at upload when the records compress; the row layout (clc_rows.hpp: xy rows + row descriptors).
 struct StreamLayout {
-  double* d_tiles = nullptr;   size_t tiles_cap = 0;
-  double* d_ctiles = nullptr;  size_t ctiles_cap = 0;
-  double* d_groups = nullptr;  size_t groups_cap = 0;
-  double* d_rxy = nullptr;     size_t rxy_cap = 0;
-  double* d_rdesc = nullptr;   size_t rdesc_cap = 0;  // + the wave split table behind the descriptors
+  DeviceArray<double> d_tiles;
+  DeviceArray<double> d_ctiles;
+  DeviceArray<double> d_groups;
+  DeviceArray<double> d_rxy;
+  DeviceArray<char> rdesc_bytes;  // the row descriptors [n_rows + 1], then the wave split table behind them (clc::wave_split)
   long long n_groups = 0;
   long long n_rows = 0;
   bool compact_ok = false;
   bool rows_ok = false;
   bool rows_z = false;  // the rows carry z (some record has p.z != 0): ROW_DOUBLES_Z doubles per row
   void invalidate() { compact_ok = rows_ok = false; }
-  void release() {
-    for (double* p : {d_tiles, d_ctiles, d_groups, d_rxy, d_rdesc}) if (p) (void)hipFree(p);
-  }
+  clc::RowDesc* d_rdesc() const { return reinterpret_cast<clc::RowDesc*>(static_cast<char*>(rdesc_bytes)); }
 };
 
 constexpr long long kCoopBackoff0 = 16;  // solves the cooperative path rests after its first abort (doubles with every further one)
 
 }  // namespace clc_abi
 
+// Every owning member releases itself; the own stream is declared first, so it is destroyed after everything allocated on the device.
 struct clc_handle {
+  clc_abi::Stream own_stream;
   clc_abi::DevPool pool;  // temporaries of the entry points (DevBuf)
   int device = 0;
   int num_cus = 0;
-  hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   // single problem
   clc_abi::StreamLayout obs;
   size_t n_obs = 0;
   int split_grid = -1;  // grid the wave split table behind obs.d_rdesc was built for (-1: none)
   // resident pose-major scans (clc_store_observations): device copies + the host-side CSR offsets
-  double* d_sq = nullptr; size_t sq_cap = 0;     // tag_q (w,x,y,z) [P*4]
-  double* d_st = nullptr; size_t st_cap = 0;     // tag_t [P*3]
-  double* d_spts = nullptr; size_t spts_cap = 0; // points [M*3]
-  double* d_sptl = nullptr; size_t sptl_cap = 0; // points_on_line [ML*3]
-  double* d_soff = nullptr; size_t soff_cap = 0; // pts_off [P+1], ptl_off [P+1], rec_off [P+1] as long long
+  clc_abi::DeviceArray<double> d_sq;             // tag_q (w,x,y,z) [P*4]
+  clc_abi::DeviceArray<double> d_st;             // tag_t [P*3]
+  clc_abi::DeviceArray<double> d_spts;           // points [M*3]
+  clc_abi::DeviceArray<double> d_sptl;           // points_on_line [ML*3]
+  clc_abi::DeviceArray<long long> d_soff;        // pts_off [P+1], ptl_off [P+1], rec_off [P+1]
   std::vector<long long> s_pts_off, s_ptl_off;
   int store_poses = -1;                          // -1: nothing stored
   int64_t store_generation = 0;                  // bumped by every successful clc_store_observations (clc_store_generation)
@@ -176,9 +120,10 @@ struct clc_handle {
   std::vector<double> s_tag_q, s_tag_t;          // tag poses (w, x, y, z) / t of the stored scans
   bool s_any_z_pts = false, s_any_z_ptl = false, s_any_z_ends = false;  // some p.z != 0 in points / points_on_line / the first + last point of a scan
   // staging of the small-problem upload path: ONE pinned block + its device twin per handle; `ev_stage` marks the last copy out of it
-  char* h_stage = nullptr; char* d_stage = nullptr; size_t stage_cap = 0;
-  hipEvent_t ev_stage = nullptr; bool stage_busy = false;
-  double* d_small_aos = nullptr; size_t small_aos_cap = 0;  // the records of a small problem (never a pool block: kernels may still read it after the call returned)
+  clc_abi::PinnedArray<char> h_stage;
+  clc_abi::DeviceArray<char> d_stage;
+  clc_abi::Event ev_stage; bool stage_busy = false;
+  clc_abi::DeviceArray<double> d_small_aos;      // the records of a small problem (never a pool block: kernels may still read it after the call returned)
   bool fast_small = true;                        // (hooks build: clc_debug_fast_small switches the path off for the A/B tests)
   long long fast_small_uploads = 0;
   bool store_lines_equal_points = false;         // points_on_line is bit for bit points (reference-size inputs only: see clc_store_observations)
@@ -191,28 +136,24 @@ struct clc_handle {
   bool small_on_coop = false;    // clc_set_small_on_coop (at upload): problems one workgroup holds also get the cooperative layout
   bool single_uni_ctrl = false;  // hooks build (clc_debug_single_controller): the single-workgroup kernel runs the cooperative kernel's controller
   bool launch_auto = true;  // default flags: size-dependent choices (deep pipeline) are made per launch
-  double* d_partials = nullptr;
-  int partials_cap_blocks = 0;
+  clc_abi::DeviceArray<double> d_partials;  // two buffers of partial rows (ensure_partials): the step kernel alternates between them
   // LM state
-  clc::SolveBlock* d_block = nullptr;  // {per-solve constants of the step-kernel chain, LM state x 2}: one allocation
-  clc::LmState* d_state = nullptr;     // = &d_block->st[0]
-  clc_iteration* d_trace = nullptr;
-  int trace_cap = 0;
+  clc_abi::DeviceArray<clc::SolveBlock> d_block;  // {per-solve constants of the step-kernel chain, LM state x 2}: one allocation
+  clc_abi::DeviceArray<clc_iteration> d_trace;
   // scratch
-  double* d_small = nullptr;
-  double* h_small = nullptr;  // pinned
-  clc::HostMailbox* h_mailbox = nullptr;  // pinned, device-visible
-  clc::HostMailbox* d_mailbox = nullptr;  // device address of the same memory
-  std::vector<hipEvent_t> ev;
+  clc_abi::DeviceArray<double> d_small;
+  clc_abi::PinnedArray<double> h_small;
+  clc_abi::PinnedArray<clc::HostMailbox, hipHostMallocCoherent | hipHostMallocMapped> h_mailbox;  // device address: h_mailbox.dev()
+  std::vector<clc_abi::Event> ev;
   // batched problems
   clc_abi::StreamLayout batch;
-  long long* d_prob_row = nullptr;  // [P+1] first row of every problem
+  clc_abi::DeviceArray<long long> d_prob_row;  // [P+1] first row of every problem
   // resident ("lane") layouts (clc_resident.hpp): of the batched problems, and of a single problem small enough for one workgroup
   clc_abi::ResLayout bres, sres;
   // cooperative whole-GPU solve of one problem (clc_coop.hpp): the problem's lane layout in 256 chunks, the exchange boards, the
   // next free pass tag; disabled on the handle after a launch that timed out (the step chain takes over)
   clc_abi::ResLayout cres;
-  clc::CoopBoard* d_board = nullptr;
+  clc_abi::DeviceArray<clc::CoopBoard> d_board;
   unsigned int coop_tag = 1;
   int coop_checked = 0;  // 0: co-residency not checked yet, 1: 256 workgroups fit the device, -1: they do not
   // after a launch that aborted the path rests for `coop_backoff` eligible solves (16, doubling with every further abort up to 2^20:
@@ -224,38 +165,34 @@ struct clc_handle {
   long long coop_solves = 0;
   int coop_test_drop = 0;  // test hook: launch the next cooperative solve this many workgroups short (its exchange must time out)
   // single-problem resident solve: start pose in / result out through page-locked, device-mapped host memory
-  double* h_spose = nullptr;          // [7] host view
-  double* d_spose = nullptr;          // device view of the same allocation
-  clc_summary* h_ssummary = nullptr;
-  clc_summary* d_ssummary = nullptr;
-  long long* d_tile_off = nullptr;
-  long long* d_nobs = nullptr;
+  // (one allocation: 8 doubles of pose, then the summary)
+  clc_abi::PinnedArray<double, hipHostMallocCoherent | hipHostMallocMapped> h_spose;
+  clc_abi::DeviceArray<long long> d_tile_off;  // [P+1]
+  clc_abi::DeviceArray<long long> d_nobs;      // [P]
   // batched poses / summaries live in pinned, device-mapped host memory: the init kernel reads the start poses and the
   // finish kernel writes the results straight over PCIe (57 + 64 KB at C3) — three staged hipMemcpy calls through
   // pageable memory cost ~35 us each, a fifth of a C3 batch
-  double* h_poses = nullptr;            // host view
-  double* d_poses = nullptr;            // device view of the same allocation
-  clc_summary* h_summaries = nullptr;
-  clc_summary* d_summaries = nullptr;
-  double* d_results = nullptr;      // clc_result_record per problem of the last clc_solve_batched (device; clc_gather_results)
-  size_t results_valid = 0;         // number of valid records in d_results
-  unsigned int* d_queue = nullptr;  // small device counter (active problems)
-  unsigned int* d_ticket = nullptr; // arrival counter of the fused evaluation+controller launch
-  double* d_partials_b = nullptr;   // second row buffer (inside the d_partials allocation) for the step kernel
-  clc::LmState* d_state_b = nullptr;  // second LM state buffer for the step kernel
-  clc::LmState* d_states = nullptr;
-  double* d_bpartials = nullptr;
-  size_t bpartials_cap_blocks = 0;
+  clc_abi::MappedArray<double> h_poses;           // [P*7]
+  clc_abi::MappedArray<clc_summary> h_summaries;  // [P]
+  clc_abi::DeviceArray<double> d_results;   // clc_result_record per problem of the last clc_solve_batched (clc_gather_results)
+  size_t results_valid = 0;                 // number of valid records in d_results
+  clc_abi::DeviceArray<unsigned int> d_queue;   // small device counter (active problems)
+  clc_abi::DeviceArray<unsigned int> d_ticket;  // arrival counter of the fused evaluation+controller launch
+  clc_abi::DeviceArray<clc::LmState> d_states;
+  clc_abi::DeviceArray<double> d_bpartials;
   long long batch_max_tiles = 0;
   long long batch_max_rows = 0;  // most rows of the row layout any one problem owns (exact, from prob_row)
   size_t batch_total_tiles = 0;
   size_t n_problems = 0;
-  size_t problems_cap = 0;
   // clc_solve_multistart: start poses / summaries (pinned, device-mapped) and result records of the starts
-  double* h_ms_poses = nullptr; double* d_ms_poses = nullptr;
-  clc_summary* h_ms_summaries = nullptr; clc_summary* d_ms_summaries = nullptr;
-  double* d_ms_results = nullptr;
-  size_t ms_cap = 0;
+  clc_abi::MappedArray<double> h_ms_poses;
+  clc_abi::MappedArray<clc_summary> h_ms_summaries;
+  clc_abi::DeviceArray<double> d_ms_results;
+
+  clc::LmState* d_state() const { return &d_block->st[0]; }
+  double* d_partials_b() const { return d_partials + d_partials.size() / 2; }  // the step kernel's second row buffer
+  clc_summary* h_ssummary() const { return reinterpret_cast<clc_summary*>(h_spose + 8); }
+  clc_summary* d_ssummary() const { return reinterpret_cast<clc_summary*>(h_spose.dev() + 8); }
 };
 
 namespace clc_abi {
@@ -265,7 +202,6 @@ int eval_grid(const clc_handle* h, size_t n);
 int ensure_partials(clc_handle* h, int blocks);
 int ensure_trace(clc_handle* h, int cap);
 int ensure_events(clc_handle* h, size_t n);
-int ensure_bytes(double** p, size_t* cap, size_t bytes);
 bool use_rows(const clc_handle* h);
 bool use_brows(const clc_handle* h);
 bool rows_nontemporal(const clc_handle* h, long long n_rows, bool z = false);
