@@ -12,54 +12,11 @@ void warm_batched() {
 }
 
 int batched_launch_setup(clc_handle* h, const clc_options& /*opt*/, BatchedLaunch* bl) {
-  const size_t P = h->n_problems;
-  bl->rows = use_brows(h);
-  // one wave per workgroup once the batch is many times wider than the chip (C4 shard: 8 192 problems, -5...7 % per
-  // batch); for batches of about a thousand problems the 256-thread form is 3-4 % ahead (scripts/r02_shard_step_timing.py)
-  bl->rows_wave = bl->rows && (h->launch_flags & clc::FLAG_BATCHED_WG256) == 0 && (!h->launch_auto || P >= 8 * (size_t)h->num_cus);
-  // enough workgroups to fill the chip: >= 2 per CU in total, never more than one per 4 tiles
-  const size_t target_blocks = h->grid_override > 0 ? (size_t)h->grid_override : 4 * (size_t)h->num_cus;
-  int bpp = (int)((target_blocks + P - 1) / P);
-  const long long max_tiles = h->batch_max_tiles;
-  const int bpp_cap = (int)std::max<long long>(1, max_tiles / 4);
-  bpp = std::max(1, std::min(bpp, bpp_cap));
-  // batched_lm_kernel sums a problem's partial rows in ONE thread: with hundreds of rows per problem (a handful of long
-  // problems) that sum took longer than the evaluation (393 us per pass at 4 problems x 9.6e4 observations, 256 rows each)
-  bpp = std::min(bpp, 16);
-  // single-wave workgroups: as many waves as the 256-thread form would have — except for batches at least four times
-  // wider than the chip's resident waves (C4 shard), where ONE wave per problem is faster still (224-235 vs 239-245 us
-  // per launch, 1.52 vs 1.60 ms per batch): no partial rows to combine, scans never cut
-  bl->one_wave = bl->rows_wave && bpp == 1 && P >= 32 * (size_t)h->num_cus;
-  if (bl->rows_wave && !bl->one_wave) bpp *= clc::BLOCK / 64;
-  const size_t n_blocks = P * (size_t)bpp;
-  CLC_HIP(h->d_bpartials.grow(n_blocks * clc::NACC));
-  bl->bpp = bpp;
-  bl->n_blocks = n_blocks;
-  bl->lm_threads = 64;
-  bl->lm_blocks = (unsigned)((P + bl->lm_threads - 1) / bl->lm_threads);
-  bl->compact = (h->launch_flags & clc::FLAG_COMPACT) != 0 && h->batch.compact_ok;
-  const bool bbeyond = h->launch_auto && h->batch_total_tiles * clc::CTILE_DOUBLES * sizeof(double) > kInfinityCacheBytes;
-  bl->nt = (h->launch_flags & clc::FLAG_NONTEMPORAL) != 0 ||
-           (bl->compact && h->launch_auto &&
-            h->batch_total_tiles * clc::CTILE_DOUBLES * sizeof(double) > kInfinityCacheBytes + kInfinityCacheBytes / 2);
-  bl->deep = (h->launch_flags & clc::FLAG_DEEP) != 0 || bbeyond;
-  bl->rows_nt = bl->rows && rows_nontemporal(h, h->batch.n_rows, h->batch.rows_z);
-  // One workgroup per problem running the problem's WHOLE solve in one launch (batched_solve_kernel) beats the lockstep
-  // launches wherever a pass over the batch is not bandwidth-bound anyway — per evaluation pass, 10^4-observation
-  // problems: 17 vs 69 us at 24 problems, 28 vs 52 at 512, 49 vs 65 at 1 024 (C3), 96 vs 115 at 2 048, a tie at 4 096
-  // (0.7 GB), 390 vs 370 at 8 192 (1.4 GB); 10^5-observation problems (1 500 rows each): 78 vs 54 us at 4 problems,
-  // 91 vs 70 at 24, a tie at 256 (scripts/probes/c3_exp.py).  So: unless the rows exceed 1 GiB (a C4 shard: lockstep, one
-  // wave per problem) or a single problem is so long (> 1 024 rows, ~6.5e4 observations) that four waves are too few.
-  {
-    const size_t row_bytes = (size_t)h->batch.n_rows * ((h->batch.rows_z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES) * sizeof(double) + sizeof(clc::RowDesc));
-    bl->whole_solve = bl->rows && !h->batch.rows_z && (h->launch_flags & clc::FLAG_BATCHED_LOCKSTEP) == 0 && row_bytes <= (1ull << 30) && h->batch_max_rows <= 1024;
-  }
-  // Problems that fit a workgroup's registers + LDS are read from HBM once and solved on chip (clc_resident.hpp).
-  bl->resident = h->bres.ok && (h->launch_flags & (clc::FLAG_NO_RESIDENT | clc::FLAG_BATCHED_LOCKSTEP)) == 0;
-  {
-    const size_t res_bytes = (size_t)h->bres.rows * (size_t)h->bres.lanes * (h->bres.with_z ? 3 : 2) * sizeof(double);
-    bl->res_nt = (h->launch_flags & clc::FLAG_NONTEMPORAL) != 0 || (h->launch_auto && res_bytes > kInfinityCacheBytes + kInfinityCacheBytes / 2);
-  }
+  const StreamLayout& L = h->batch;
+  const BatchShape b = {h->n_problems, h->batch_total_tiles, h->batch_max_tiles, L.n_rows, h->batch_max_rows, L.compact_ok, L.rows_ok, L.rows_z,
+                        h->bres.ok, h->bres.with_z, h->bres.rows, h->bres.lanes};
+  *bl = plan_batched(h->steer, b, h->num_cus);
+  CLC_HIP(h->d_bpartials.grow(bl->n_blocks * clc::NACC));
   return CLC_OK;
 }
 

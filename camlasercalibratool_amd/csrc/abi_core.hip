@@ -28,18 +28,6 @@ int default_lookahead() {
   return v;
 }
 
-int eval_grid(const clc_handle* h, size_t n) {
-  const long long tiles = (long long)((n + clc::TILE - 1) / clc::TILE);
-  const bool big = (h->launch_flags & clc::FLAG_WG512) != 0;
-  // Every CU takes a share (the tile map is proportional, a wave may own zero tiles): up to one
-  // workgroup per CU keeps the partial-row reduction of lm_kernel short; with 256-thread workgroups,
-  // arrays long enough to give every wave >= 16 tiles are streamed with 2 workgroups per CU.
-  const int per_cu = (!big && tiles >= 16LL * (clc::BLOCK / 64) * 2 * h->num_cus) ? 2 * kDefaultBlocksPerCU : kDefaultBlocksPerCU;
-  const long long cap = h->grid_override > 0 ? h->grid_override : (long long)per_cu * h->num_cus;
-  const long long want = tiles < 1 ? 1 : tiles;  // never more workgroups than tiles
-  return (int)(want < cap ? want : cap);
-}
-
 // Partial rows.  The capacity is a whole number of 256-row rounds: the controller reads rows in rounds of 256 from
 // unclamped addresses and masks the ones beyond the grid afterwards (clc::lm_tail), so every round must be mapped.
 // Two buffers: the step kernel alternates between them by launch parity (d_partials_b).
@@ -64,21 +52,6 @@ int ensure_events(clc_handle* h, size_t n) {
     h->ev.push_back(std::move(e));
   }
   return CLC_OK;
-}
-
-// Row layout in use for the single-problem array?
-// With the library's default flags, arrays below ~2x10^5 observations keep the per-point compact layout: a launch is pure
-// fixed cost there and the row kernel's 16 prologue loads + per-scan expansion make it 0.4-0.5 us longer per LM iteration
-// (8.5 vs 9.0 us at 5.5x10^3 observations, 8.8 vs 9.2 at 10^5; 13.2 vs 11.1 at 10^6 — scripts/r02_ab.py).
-bool use_rows(const clc_handle* h) {
-  if ((h->launch_flags & clc::FLAG_ROWS) == 0 || !h->obs.rows_ok) return false;
-  return !h->launch_auto || !h->obs.compact_ok || h->n_obs >= 200000;
-}
-bool use_brows(const clc_handle* h) { return (h->launch_flags & clc::FLAG_ROWS) != 0 && h->batch.rows_ok; }
-// Rows streamed from HBM rather than the Infinity Cache (> 1.5x its size) are loaded non-temporally.
-bool rows_nontemporal(const clc_handle* h, long long n_rows, bool z) {
-  const size_t bytes = (size_t)n_rows * ((z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES) * sizeof(double) + sizeof(clc::RowDesc));
-  return (h->launch_flags & clc::FLAG_NONTEMPORAL) != 0 || (h->launch_auto && bytes > kInfinityCacheBytes + kInfinityCacheBytes / 2);
 }
 
 // The wave split table of the row layout's equal-shares mode (clc_kernels.hpp wave_split_kernel): rebuilt, on the
@@ -267,9 +240,8 @@ int clc_get_path_info(const clc_handle* h, clc_path_info* out) {
 int clc_set_launch(clc_handle* h, int grid_blocks, int flags) {
   if (!h || grid_blocks < 0 || flags < -1 || flags > 16383)
     return fail(CLC_ERR_INVALID_ARG, "clc_set_launch: bad argument");
-  h->grid_override = grid_blocks;
   h->launch_flags = flags < 0 ? kDefaultLaunchFlags : flags;
-  h->launch_auto = flags < 0;
+  h->steer = decode_launch(grid_blocks, flags);
   return CLC_OK;
 }
 

@@ -33,12 +33,12 @@ int clc_debug_flatten_device(clc_handle* h, int use_linefitting_data, int use_bo
 // consumes pass k-1; choose 2 <= first <= last <= passes - 1 to cover steady-state launches that all streamed.
 int clc_time_steps(clc_handle* h, const double pose0[7], int first, int last, double* avg_ms, int* passes) {
   if (!h || !pose0 || !avg_ms || first < 0 || last < first) return fail(CLC_ERR_INVALID_ARG, "clc_time_steps: bad argument");
-  if (!h->obs.d_tiles || !(h->obs.compact_ok || h->obs.rows_ok)) return fail(CLC_ERR_NO_DATA, "clc_time_steps: no (compact / row) observations uploaded");
+  const StreamPlan sp = stream_plan(h);  // (the step chain streams the row layout the plan picks, else the compact tiles)
+  if (!h->obs.d_tiles || !(sp.rows() || h->obs.compact_ok)) return fail(CLC_ERR_NO_DATA, "clc_time_steps: no (compact / row) observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
   int rc = ensure_events(h, 2);
   if (rc != CLC_OK) return rc;
-  const int grid = eval_grid(h, h->n_obs);
-  rc = ensure_partials(h, grid);
+  rc = ensure_partials(h, sp.grid);
   if (rc != CLC_OK) return rc;
   clc_options opt;
   clc_options_default(&opt);
@@ -46,7 +46,7 @@ int clc_time_steps(clc_handle* h, const double pose0[7], int first, int last, do
   for (int i = 0; i < 7; ++i) pose[i] = pose0[i];
   clc_summary sm;
   float ms = -1.f;
-  rc = solve_stepped(h, opt, grid, pose, &sm, nullptr, 0, std::chrono::steady_clock::now(), first, last, &ms);
+  rc = solve_stepped(h, opt, sp, pose, &sm, nullptr, 0, std::chrono::steady_clock::now(), first, last, &ms);
   if (rc != CLC_OK) return rc;
   if (passes) *passes = (int)sm.num_evaluations;
   if (ms < 0.f) return fail(CLC_ERR_INVALID_ARG, "clc_time_steps: the solve ended before launch `last`");
@@ -251,19 +251,19 @@ int clc_time_eval(clc_handle* h, const double pose[7], int with_loss, double lf,
   if (!h || !pose || !avg_ms || reps < 1) return fail(CLC_ERR_INVALID_ARG, "clc_time_eval: bad argument");
   if (!h->obs.d_tiles) return fail(CLC_ERR_NO_DATA, "clc_time_eval: no observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
-  const int grid = eval_grid(h, h->n_obs);
-  int rc = ensure_partials(h, grid);
+  const StreamPlan sp = stream_plan(h);
+  int rc = ensure_partials(h, sp.grid);
   if (rc != CLC_OK) return rc;
   rc = ensure_events(h, 2);
   if (rc != CLC_OK) return rc;
   std::memcpy(h->h_small, pose, 7 * sizeof(double));
   CLC_HIP(hipMemcpyAsync(h->d_small, h->h_small, 7 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   for (int w = 0; w < 3; ++w) {
-    launch_eval(h, grid, with_jac != 0, with_loss != 0, h->d_small, nullptr, lf);
+    launch_eval(h, sp, with_jac != 0, with_loss != 0, h->d_small, nullptr, lf);
   }
   CLC_HIP(hipEventRecord(h->ev[0], h->stream));
   for (int r = 0; r < reps; ++r) {
-    launch_eval(h, grid, with_jac != 0, with_loss != 0, h->d_small, nullptr, lf);
+    launch_eval(h, sp, with_jac != 0, with_loss != 0, h->d_small, nullptr, lf);
   }
   CLC_HIP(hipEventRecord(h->ev[1], h->stream));
   CLC_HIP(hipGetLastError());

@@ -1,7 +1,7 @@
 // abi_frontend.hip — the calls either side of the solve: factor evaluation, manifold plus, information matrix and closed form, line fitting, scan conversion,
 // board-segment detection.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "clc_abi_internal.hpp"
+#include "abi_drive.hpp"
 #include "clc_scanseg.hpp"
 
 using namespace clc_abi;
@@ -92,23 +92,15 @@ int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9
   if (!h || !Tlc || !unobservable) return fail(CLC_ERR_INVALID_ARG, "clc_closed_form: bad argument");
   if (!h->obs.d_tiles || h->n_obs == 0) return fail(CLC_ERR_NO_DATA, "clc_closed_form: no observations uploaded");
   CLC_HIP(hipSetDevice(h->device));
-  const int grid = eval_grid(h, h->n_obs);
+  const StreamPlan sp = stream_plan(h);
+  const int grid = sp.grid;
   int rc = ensure_partials(h, grid);
   if (rc != CLC_OK) return rc;
-  if (use_rows(h)) {
-    const clc::RowDesc* rdesc = h->obs.d_rdesc();
-    if (h->obs.rows_z) {  // bar_p = (x, y, 1): z is not read, only the row stride differs
-      if (rows_nontemporal(h, h->obs.n_rows, true))
-        hipLaunchKernelGGL((clc::normal9_rows_kernel<true, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy, rdesc, h->obs.n_rows, h->d_partials);
-      else
-        hipLaunchKernelGGL((clc::normal9_rows_kernel<false, clc::ROW_DOUBLES_Z>), dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy, rdesc, h->obs.n_rows, h->d_partials);
-    }
-    else if (rows_nontemporal(h, h->obs.n_rows))
-      hipLaunchKernelGGL(clc::normal9_rows_kernel<true>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy,
-                         h->obs.d_rdesc(), h->obs.n_rows, h->d_partials);
-    else
-      hipLaunchKernelGGL(clc::normal9_rows_kernel<false>, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_rxy,
-                         h->obs.d_rdesc(), h->obs.n_rows, h->d_partials);
+  if (sp.rows()) {  // rows that carry z: bar_p = (x, y, 1) — z is not read, only the row stride differs
+    with_flags([&](auto Z, auto NT) {
+      hipLaunchKernelGGL((clc::normal9_rows_kernel<NT, Z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES>), dim3(grid), dim3(clc::BLOCK), 0, h->stream,
+                         h->obs.d_rxy, h->obs.d_rdesc(), h->obs.n_rows, h->d_partials);
+    }, sp.layout == Layout::rows_z, sp.nt);
   } else {
     hipLaunchKernelGGL(clc::normal9_kernel, dim3(grid), dim3(clc::BLOCK), 0, h->stream, h->obs.d_tiles,
                        (long long)h->n_obs, h->d_partials);

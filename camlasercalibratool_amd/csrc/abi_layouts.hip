@@ -50,7 +50,7 @@ int build_resident(clc_handle* h, ResLayout& L, int first_try, const double* d_a
   L.lanes = 0;
   L.max_ppl = 0;
   L.rows = 0;
-  if ((h->launch_flags & clc::FLAG_NO_RESIDENT) != 0) return CLC_OK;
+  if (!plan_upload(h->steer, h->auto_disable, false).resident) return CLC_OK;
   const int threads = 256;
   DevBuf<unsigned int> bppl(&h->pool), bfail(&h->pool);
   CLC_HIP(bppl.alloc(P));
@@ -184,9 +184,7 @@ int emit_rows_and_lanes(clc_handle* h, const double* d_aos, const LayoutPlan& p,
   } else if (res != nullptr) {
     res->ok = false;
     if (!p.any_z) {
-      // batches: 256 lanes (two problems per CU) unless flag 8192; a single problem: 512 lanes (it has its CU to itself)
-      const int first_try = (d_prob_row == nullptr || (h->launch_flags & clc::FLAG_RESIDENT_WG512) != 0) ? 512 : 256;
-      rc = build_resident(h, *res, first_try, d_aos, n, p.P, p.G, p.d_rec_off, p.d_gid, p.d_starts);
+      rc = build_resident(h, *res, plan_upload(h->steer, h->auto_disable, d_prob_row != nullptr).first_lanes, d_aos, n, p.P, p.G, p.d_rec_off, p.d_gid, p.d_starts);
       if (rc != CLC_OK) return rc;
     } else if (d_prob_row != nullptr) {
       // a BATCH whose points carry z: the 512-lane form with 24-byte slots (one problem per CU; resident_solve_kernel<.., WITH_Z>) — the
@@ -213,7 +211,7 @@ int emit_rows_and_lanes(clc_handle* h, const double* d_aos, const LayoutPlan& p,
       if (const char* e = std::getenv("CLC_COOP_SMALL_MAX_PPL")) small_cap = std::max(1, std::atoi(e));  // (tuning hook, hooks build only: scripts/r05_small_form.py)
 #endif
       const int small_ppl = std::min(small_cap, cap_ppl);
-      const bool small_ok = n <= (long long)clc::COOP_SMALL_WGS * clc::COOP_NL * small_ppl && (h->auto_disable & 8) == 0;
+      const bool small_ok = n <= (long long)clc::COOP_SMALL_WGS * clc::COOP_NL * small_ppl && plan_upload(h->steer, h->auto_disable, false).one_hop;
       for (int attempt = small_ok ? 0 : 1; attempt < 2 && !coop->ok; ++attempt) {
         const int wgs = attempt == 0 ? clc::COOP_SMALL_WGS : clc::COOP_WGS;
         std::vector<long long> chunk((size_t)wgs + 1);
@@ -365,7 +363,7 @@ int plan_small_on_host(clc_handle* h, const std::vector<long long>& starts, long
   *used = false;
   const size_t G = starts.size() - 1;
   if (!h->fast_small || n <= 0 || (size_t)n > kSmallMaxRecords || any_z || h->small_on_coop || G == 0 || G > 512) return CLC_OK;
-  if ((h->launch_flags & clc::FLAG_NO_RESIDENT) != 0) return CLC_OK;
+  if (!plan_upload(h->steer, h->auto_disable, false).resident) return CLC_OK;
   p->P = 1; p->n = n; p->tiles = (size_t)((n + clc::TILE - 1) / clc::TILE); p->max_tiles = (long long)p->tiles;
   p->set_scans(G);
   std::vector<unsigned int> brbeg(G + 1, 0u);

@@ -7,14 +7,11 @@ using namespace clc_abi;
 namespace {
 
 template <bool WITH_LOSS, bool WITH_JAC>
-void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t* d_status, double lf,
+void launch_eval_v(clc_handle* h, const StreamPlan& sp, const double* d_pose, const int32_t* d_status, double lf,
                    const clc::Pose7& pose_arg, int use_pose_arg) {
-  const int fl = h->launch_flags;
-  const bool pf = (fl & clc::FLAG_PREFETCH) != 0, nt = (fl & clc::FLAG_NONTEMPORAL) != 0;
-  const bool cp = (fl & clc::FLAG_COMPACT) != 0 && h->obs.compact_ok;
-  const bool big = (fl & clc::FLAG_WG512) != 0;
-  if (use_rows(h)) {  // row layout: the Jacobian comes with the moments, a cost-only pass would save nothing
-    const bool rnt = rows_nontemporal(h, h->obs.n_rows, h->obs.rows_z);
+  const int grid = sp.grid, fl = h->launch_flags;
+  const bool big = sp.threads == 512;
+  if (sp.rows()) {  // row layout: the Jacobian comes with the moments, a cost-only pass would save nothing
     // rows in flight per wave: 8 while the array is served by the Infinity Cache, 12 (206 VGPRs, still 2 waves/SIMD) when it
     // streams from HBM with non-temporal loads — throughput there tracks the bytes in flight per CU (profiles/r03_occupancy.md:
     // 4 rows 0.40 of peak, 8 rows 0.81, 12 rows 0.82-0.83, 16 rows 0.81; 3 waves/SIMD cannot hold more than 6 rows each: 0.80);
@@ -25,53 +22,30 @@ void launch_eval_v(clc_handle* h, int grid, const double* d_pose, const int32_t*
                          h->stream, h->obs.d_rxy, h->obs.d_rdesc(), h->obs.n_rows, d_pose, d_status, lf, fl,
                          h->d_partials, pose_arg, use_pose_arg);
     };
-    if (h->obs.rows_z) {  // rows that carry z: 3:2 wave shares
-      with_flags(launch, big, std::false_type{}, rnt, std::true_type{});
-      return;
-    }
-    // Equal, scan-aligned shares (flag 512) pay where a wave's share is a scan or two; the evaluation kernel ALONE with
-    // tens of rows per wave and more is 3-7 % faster with the 3:2 old/young shares (scripts/r02_ab.py: 6.2 vs 6.8 us at
-    // 1e6 observations, but 15.4 vs 14.7 at 4e6 and 45.1 vs 42.1 at 1.6e7) — the step kernel is not (its wave 0 starts
-    // late anyway): it keeps the equal shares at every size.
-    const bool eq = (fl & clc::FLAG_EQUAL_WAVES) != 0 && !(h->launch_auto && h->obs.n_rows > 16LL * 8 * grid);
-    if (big) {
-      if (eq) ensure_wave_split(h, grid);
-      with_flags(launch, std::true_type{}, eq, rnt, std::false_type{});
-    } else {
-      with_flags(launch, std::false_type{}, std::false_type{}, rnt, std::false_type{});
-    }
+    if (sp.eval_equal) ensure_wave_split(h, grid);
+    if (sp.layout == Layout::rows_z) with_flags(launch, big, std::false_type{}, sp.nt, std::true_type{});
+    else if (big) with_flags(launch, std::true_type{}, sp.eval_equal, sp.nt, std::false_type{});
+    else with_flags(launch, std::false_type{}, std::false_type{}, sp.nt, std::false_type{});
     return;
   }
-  // Compact layout: the deep pipeline (two tiles of points in flight per wave) pays only when the array streams
-  // from HBM, i.e. no longer fits the 256 MiB Infinity Cache (scripts/size_sweep.py: +10 % at 9e8 B, -8 % at 1e8 B).
-  // Well beyond the cache (> 1.5x) the streamed tiles are also loaded non-temporally (+5-8 % at 4.5e8-9e8 B; plain
-  // loads win while the array is cache-resident, and at 2.9e8 B — C3 — there is nothing in it).
   const auto launch = [&](auto CP, auto BIG, auto PF, auto NT) {
     constexpr int BT = BIG ? 512 : 256;
     hipLaunchKernelGGL((clc::eval_kernel<WITH_LOSS, WITH_JAC, PF, NT, CP, BT>), dim3(grid), dim3(BT), 0, h->stream,
                        CP ? h->obs.d_ctiles : h->obs.d_tiles, h->obs.d_groups, (long long)h->n_obs, d_pose, d_status, lf, fl, h->d_partials, pose_arg,
                        use_pose_arg);
   };
-  const bool beyond_cache = h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes;
-  const bool deep = (fl & clc::FLAG_DEEP) != 0 || beyond_cache;
-  if (cp) {
-    const bool cnt = (fl & clc::FLAG_NONTEMPORAL) != 0 ||
-                     (h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes + kInfinityCacheBytes / 2);
-    with_flags(launch, std::true_type{}, big, deep, cnt);
-  } else if (big) {
-    with_flags(launch, std::false_type{}, std::true_type{}, std::true_type{}, nt);
-  } else {
-    with_flags(launch, std::false_type{}, std::false_type{}, pf, nt);
-  }
+  if (sp.layout == Layout::compact) with_flags(launch, std::true_type{}, big, sp.prefetch, sp.nt);
+  else if (big) with_flags(launch, std::false_type{}, std::true_type{}, std::true_type{}, sp.nt);
+  else with_flags(launch, std::false_type{}, std::false_type{}, sp.prefetch, sp.nt);
 }
 
 template <bool WITH_JAC>
-void launch_eval(clc_handle* h, int grid, bool with_loss, const double* d_pose,
+void launch_eval(clc_handle* h, const StreamPlan& sp, bool with_loss, const double* d_pose,
                  const int32_t* d_status, double lf, const clc::Pose7* pose_arg = nullptr) {
   const clc::Pose7 zero = {};
   const clc::Pose7& pa = pose_arg ? *pose_arg : zero;
-  if (with_loss) launch_eval_v<true, WITH_JAC>(h, grid, d_pose, d_status, lf, pa, pose_arg ? 1 : 0);
-  else launch_eval_v<false, WITH_JAC>(h, grid, d_pose, d_status, lf, pa, pose_arg ? 1 : 0);
+  if (with_loss) launch_eval_v<true, WITH_JAC>(h, sp, d_pose, d_status, lf, pa, pose_arg ? 1 : 0);
+  else launch_eval_v<false, WITH_JAC>(h, sp, d_pose, d_status, lf, pa, pose_arg ? 1 : 0);
 }
 
 }  // namespace
@@ -82,10 +56,10 @@ void warm_solve() {
   warm_kernel(reinterpret_cast<const void*>(&clc::coop_solve_kernel<true, false>));
 }
 
-void launch_eval(clc_handle* h, int grid, bool with_jac, bool with_loss, const double* d_pose, const int32_t* d_status, double lf,
+void launch_eval(clc_handle* h, const StreamPlan& sp, bool with_jac, bool with_loss, const double* d_pose, const int32_t* d_status, double lf,
                  const clc::Pose7* pose_arg) {
-  if (with_jac) ::launch_eval<true>(h, grid, with_loss, d_pose, d_status, lf, pose_arg);
-  else ::launch_eval<false>(h, grid, with_loss, d_pose, d_status, lf, pose_arg);
+  if (with_jac) ::launch_eval<true>(h, sp, with_loss, d_pose, d_status, lf, pose_arg);
+  else ::launch_eval<false>(h, sp, with_loss, d_pose, d_status, lf, pose_arg);
 }
 }  // namespace clc_abi
 
@@ -100,18 +74,18 @@ int clc_eval(clc_handle* h, const double pose[7], int with_loss, double loss_sca
   if (!all_finite(pose, 7)) return fail(CLC_ERR_NONFINITE, "clc_eval: non-finite pose");
   if (with_loss && !(loss_scale_factor > 0.0)) return fail(CLC_ERR_INVALID_ARG, "clc_eval: loss_scale_factor must be > 0");
   CLC_HIP(hipSetDevice(h->device));
-  const int grid = eval_grid(h, h->n_obs);
-  int rc = ensure_partials(h, grid);
+  const StreamPlan sp = stream_plan(h);
+  int rc = ensure_partials(h, sp.grid);
   if (rc != CLC_OK) return rc;
   std::memcpy(h->h_small, pose, 7 * sizeof(double));
   CLC_HIP(hipMemcpyAsync(h->d_small, h->h_small, 7 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   const bool want_jac = (g != nullptr) || (H != nullptr);
   if (want_jac)
-    launch_eval<true>(h, grid, with_loss != 0, h->d_small, nullptr, loss_scale_factor);
+    launch_eval<true>(h, sp, with_loss != 0, h->d_small, nullptr, loss_scale_factor);
   else
-    launch_eval<false>(h, grid, with_loss != 0, h->d_small, nullptr, loss_scale_factor);
+    launch_eval<false>(h, sp, with_loss != 0, h->d_small, nullptr, loss_scale_factor);
   CLC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(clc::reduce_kernel, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid,
+  hipLaunchKernelGGL(clc::reduce_kernel, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, sp.grid,
                      with_loss, loss_scale_factor, h->d_small + 16);
   CLC_HIP(hipGetLastError());
   CLC_HIP(hipMemcpyAsync(h->h_small + 16, h->d_small + 16, clc::NACC * sizeof(double), hipMemcpyDeviceToHost,
@@ -160,7 +134,7 @@ namespace clc_abi {
 // host only keeps `lookahead` launches queued beyond the last pass the device reported consumed.
 // win_first/win_last/win_ms (profiling hook clc_time_steps): HIP events are recorded on the stream right before launch
 // `win_first` and right after launch `win_last`; *win_ms receives the elapsed time between them.
-int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7], clc_summary* summary,
+int solve_stepped(clc_handle* h, const clc_options& opt, const StreamPlan& sp, double pose[7], clc_summary* summary,
                   clc_iteration* trace, int trace_cap, std::chrono::steady_clock::time_point t0,
                   int win_first, int win_last, float* win_ms) {
   bool want_trace;
@@ -176,13 +150,8 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
   prm.trace = want_trace ? h->d_trace : nullptr;
   prm.mailbox = h->h_mailbox.dev();
   prm.trace_cap = want_trace ? (int)h->d_trace.size() : 0;
-  const bool deep = (h->launch_flags & clc::FLAG_DEEP) != 0 ||
-                    (h->launch_auto && (size_t)h->n_obs * 28 > kInfinityCacheBytes);
-  const bool rows = use_rows(h);
-  const bool rows_z = rows && h->obs.rows_z;
-  const bool rows_nt = rows && rows_nontemporal(h, h->obs.n_rows, rows_z);
-  const bool rows_eq = (h->launch_flags & clc::FLAG_EQUAL_WAVES) != 0 && !rows_z;
-  if (rows && rows_eq) ensure_wave_split(h, grid);
+  const int grid = sp.grid;
+  if (sp.step_equal) ensure_wave_split(h, grid);
   double* rows_buf[2] = {h->d_partials, h->d_partials_b()};
   // (max_iterations + 1) evaluations + the final controller pass; launch k is made while k - (passes consumed) <= lookahead
   const LaunchAhead la = {"clc_solve", opt.max_num_iterations + 2, lookahead + 1, LaunchAhead::kFail, 30.0};
@@ -204,9 +173,9 @@ int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7
       else if (k == 1) launch(c..., cint<1>);
       else launch(c..., cint<2>);
     };
-    if (rows_z) with_flags(at_mode, cint<2>, opt.use_loss != 0, std::false_type{}, rows_nt);  // 3:2 wave shares
-    else if (rows) with_flags(at_mode, cint<1>, opt.use_loss != 0, rows_eq, rows_nt);
-    else with_flags(at_mode, cint<0>, opt.use_loss != 0, std::false_type{}, deep);
+    if (sp.layout == Layout::rows_z) with_flags(at_mode, cint<2>, opt.use_loss != 0, std::false_type{}, sp.nt);  // 3:2 wave shares
+    else if (sp.rows()) with_flags(at_mode, cint<1>, opt.use_loss != 0, sp.step_equal, sp.nt);
+    else with_flags(at_mode, cint<0>, opt.use_loss != 0, std::false_type{}, sp.deep);
     if (win_ms && k == win_last) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
     return CLC_OK;
   }, &launched);
@@ -422,25 +391,21 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
   CLC_HIP(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
 
-  // a problem one workgroup holds: the whole solve in one single-workgroup launch (default flags only: the explicit flag
-  // sets select the step chain / launch pair the bit-identity tests compare; profile_events = 1 asks for per-pass events)
-  // (clc_set_small_on_coop at upload: such a problem ALSO has the cooperative layout and runs on 32 workgroups first — 4.6 instead
-  // of 5.3-5.9 us per pass —, with this kernel as the fall-back when the cooperative launch times out or rests)
-  const bool single_ok = h->sres.ok && h->launch_auto && (h->auto_disable & 2) == 0 && h->grid_override == 0 && opt.profile_events != 1;
-  if (single_ok && !(h->cres.ok && h->small_on_coop)) return solve_resident_single(h, opt, pose, summary, trace, trace_cap, t0);
-  // a problem the 256 CUs hold together: the whole solve in one launch of 256 (or 32) co-resident workgroups (same conditions)
-  if (h->cres.ok && h->launch_auto && (h->auto_disable & 1) == 0 && h->grid_override == 0 && opt.profile_events != 1 && ++h->coop_eligible > h->coop_retry_at) {
+  // a problem one workgroup holds: the whole solve in one single-workgroup launch; a problem the 256 CUs hold together: in one
+  // launch of 256 (or 32) co-resident workgroups (clc_set_small_on_coop: a problem one workgroup holds tries that first — 4.6 instead
+  // of 5.3-5.9 us per pass —, with the single-workgroup kernel as the fall-back when the cooperative launch times out or rests)
+  const StreamPlan sp = stream_plan(h);
+  const SolvePlan route = plan_solve(h->steer, sp, h->n_obs, h->sres.ok, h->cres.ok, h->small_on_coop, h->auto_disable, opt.profile_events);
+  if (route.single && !route.coop) return solve_resident_single(h, opt, pose, summary, trace, trace_cap, t0);
+  if (route.coop && ++h->coop_eligible > h->coop_retry_at) {
     const int rc = solve_coop(h, opt, pose, summary, trace, trace_cap, t0);
     if (rc != kCoopFallback) return rc;
   }
-  if (single_ok) return solve_resident_single(h, opt, pose, summary, trace, trace_cap, t0);
-  const int grid = eval_grid(h, h->n_obs);
+  if (route.single) return solve_resident_single(h, opt, pose, summary, trace, trace_cap, t0);
+  const int grid = sp.grid;
   int rc = ensure_partials(h, grid);
   if (rc != CLC_OK) return rc;
-  if ((h->launch_flags & clc::FLAG_STEP) != 0 && (((h->launch_flags & clc::FLAG_COMPACT) != 0 && h->obs.compact_ok) || use_rows(h)) &&
-      (h->launch_flags & clc::FLAG_WG512) != 0 && h->n_obs < 0x7FFFFFFFull &&
-      opt.profile_events != 1)  // 1: HIP events around K1, two-kernel path
-    return solve_stepped(h, opt, grid, pose, summary, trace, trace_cap, t0);
+  if (route.step_chain) return solve_stepped(h, opt, sp, pose, summary, trace, trace_cap, t0);  // (profile_events 1: the launch pair)
   const int max_evals = opt.max_num_iterations + 1;
   bool want_trace;
   rc = prepare_trace(h, opt, trace, trace_cap, &want_trace);
@@ -464,7 +429,7 @@ int clc_solve(clc_handle* h, const clc_options* opt_in, double pose[7], clc_summ
   rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) -> int {
     if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * k], h->stream));
     // iteration 0 carries the initial pose by value and initialises the LM state in lm_kernel
-    launch_eval<true>(h, grid, opt.use_loss != 0, d_x_eval, d_status, opt.loss_scale_factor, k == 0 ? &p0 : nullptr);
+    launch_eval<true>(h, sp, opt.use_loss != 0, d_x_eval, d_status, opt.loss_scale_factor, k == 0 ? &p0 : nullptr);
     if (opt.profile_events) CLC_HIP(hipEventRecord(h->ev[2 * k + 1], h->stream));
     with_flags([&](auto FIRST) {
       hipLaunchKernelGGL(clc::lm_kernel<FIRST>, dim3(1), dim3(clc::BLOCK), 0, h->stream, h->d_partials, grid, h->d_state(), opt,

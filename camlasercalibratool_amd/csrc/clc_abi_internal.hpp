@@ -32,6 +32,7 @@
 #include "clc_resident.hpp"
 #include "clc_coop.hpp"
 #include "abi_memory.hpp"
+#include "abi_paths.hpp"
 
 namespace clc_abi {
 
@@ -52,9 +53,6 @@ inline bool all_finite(const double* p, int n) {
 
 constexpr int kDefaultLookahead = 2;
 int default_lookahead();  // abi_core.hip
-constexpr size_t kInfinityCacheBytes = 256u << 20;  // MI355X memory-side cache (MI355X_MICROARCH.md)
-constexpr int kDefaultLaunchFlags = 2 | 16 | 32 | 128 | 256 | 512;  // prefetch + compact layout + 512-thread weighted workgroups + step kernel (clc::FLAG_*), tuned on MI355X (scripts/tune_eval.py, scripts/step_check.py)
-constexpr int kDefaultBlocksPerCU = 1;   // 4 waves per CU with 2 tiles in flight each     // single-problem solver: launch-ahead depth
 constexpr int kSmallDoubles = 512;  // device + pinned scratch for small transfers
 
 
@@ -129,13 +127,12 @@ struct clc_handle {
   bool store_lines_equal_points = false;         // points_on_line is bit for bit points (reference-size inputs only: see clc_store_observations)
   long long selection_key = -1;                  // the (stored scans, selection) the observation array was built from by clc_select_observations; -1: none
   long long selection_cfg = -1;                  // ... under these upload-time settings (launch flags, auto paths)
-  // launch geometry
-  int grid_override = 0;
+  // launch geometry (clc_set_launch): decoded into `steer`; the raw flags are the kernels' reduce_mode and part of selection_cfg
+  clc_abi::Steering steer = clc_abi::decode_launch(0, -1);
   int launch_flags = clc_abi::kDefaultLaunchFlags;
   int auto_disable = 0;     // clc_set_auto_paths: 1 no cooperative solve, 2 no single-workgroup resident solve, 8 (at upload) no one-hop form
   bool small_on_coop = false;    // clc_set_small_on_coop (at upload): problems one workgroup holds also get the cooperative layout
   bool single_uni_ctrl = false;  // hooks build (clc_debug_single_controller): the single-workgroup kernel runs the cooperative kernel's controller
-  bool launch_auto = true;  // default flags: size-dependent choices (deep pipeline) are made per launch
   clc_abi::DeviceArray<double> d_partials;  // two buffers of partial rows (ensure_partials): the step kernel alternates between them
   // LM state
   clc_abi::DeviceArray<clc::SolveBlock> d_block;  // {per-solve constants of the step-kernel chain, LM state x 2}: one allocation
@@ -198,13 +195,9 @@ struct clc_handle {
 namespace clc_abi {
 
 // ---- abi_core.hip ----
-int eval_grid(const clc_handle* h, size_t n);
 int ensure_partials(clc_handle* h, int blocks);
 int ensure_trace(clc_handle* h, int cap);
 int ensure_events(clc_handle* h, size_t n);
-bool use_rows(const clc_handle* h);
-bool use_brows(const clc_handle* h);
-bool rows_nontemporal(const clc_handle* h, long long n_rows, bool z = false);
 void ensure_wave_split(clc_handle* h, int grid);
 
 // Every unit with kernels: load its code object on the current device now (hipFuncGetAttributes on a kernel of the unit), so that
@@ -237,26 +230,17 @@ int build_layouts(clc_handle* h, const double* d_aos, size_t n_total, const std:
 int flatten_on_device(clc_handle* h, bool linefit, bool boundary, DevBuf<double>* aos, long long* n_out);
 
 // ---- abi_solve.hip ----
-// one launch of the evaluation kernel the handle's flags and layouts select (K1), partial rows into h->d_partials
-void launch_eval(clc_handle* h, int grid, bool with_jac, bool with_loss, const double* d_pose, const int32_t* d_status, double lf,
+// the single problem's streaming launches under the handle's flags and layouts
+inline StreamPlan stream_plan(const clc_handle* h) {
+  return plan_stream(h->steer, h->n_obs, h->obs.n_rows, h->obs.rows_ok, h->obs.rows_z, h->obs.compact_ok, h->num_cus);
+}
+// one launch of the evaluation kernel the plan selects (K1), partial rows into h->d_partials
+void launch_eval(clc_handle* h, const StreamPlan& sp, bool with_jac, bool with_loss, const double* d_pose, const int32_t* d_status, double lf,
                  const clc::Pose7* pose_arg = nullptr);
-int solve_stepped(clc_handle* h, const clc_options& opt, int grid, double pose[7], clc_summary* summary, clc_iteration* trace,
+int solve_stepped(clc_handle* h, const clc_options& opt, const StreamPlan& sp, double pose[7], clc_summary* summary, clc_iteration* trace,
                   int trace_cap, std::chrono::steady_clock::time_point t0, int ev_first = -1, int ev_last = -1, float* ev_ms = nullptr);
 
 // ---- abi_batched.hip ----
-// Launch geometry of the batched solver (shared by clc_solve_batched and the timing hook).
-struct BatchedLaunch {
-  int bpp = 1;            // workgroups per problem
-  size_t n_blocks = 0;
-  int lm_threads = 64;
-  unsigned lm_blocks = 0;
-  bool compact = false, deep = false, nt = false;
-  bool rows = false, rows_nt = false, rows_wave = false;
-  bool one_wave = false;  // rows_wave with exactly one wave per problem
-  bool whole_solve = false;  // batched_solve_kernel: one workgroup per problem, the whole solve in one launch
-  bool resident = false;     // resident_solve_kernel: the same with the problem read from HBM once and kept on chip
-  bool res_nt = false;
-};
 int batched_launch_setup(clc_handle* h, const clc_options& opt, BatchedLaunch* bl);
 void launch_batched_eval(clc_handle* h, const clc_options& opt, const BatchedLaunch& bl);
 // ONE launch of resident_solve_kernel over the handle's batch (bl.resident) on the handle's stream; start poses from the handle's pinned

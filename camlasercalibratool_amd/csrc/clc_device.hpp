@@ -1,7 +1,7 @@
 // clc_device.hpp — device-side building blocks shared by every kernel of the point-to-plane path (gfx950 / CDNA4, wave64):
 // wave-uniform pose, the per-observation rank-1 accumulation (PointInPlaneFactor::Evaluate + Cauchy corrector,
-// src/LaseCamCalCeres.cpp:43-66,249), the wavefront / workgroup reductions of the 28 accumulators, the launch flags of
-// clc_set_launch, and the static tile -> wave maps.  Included by the kernel headers, never by host-only code.
+// src/LaseCamCalCeres.cpp:43-66,249), the wavefront / workgroup reductions of the 28 accumulators and the static tile -> wave
+// maps.  Included by the kernel headers, never by host-only code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,10 +11,8 @@
 
 namespace clc {
 
-constexpr int TILE = 128;               // records per tile
 constexpr int TILE_DOUBLES = TILE * 8;  // 1024 doubles = 8 KiB
 constexpr int NACC = 28;                // 21 (H upper triangle) + 6 (g) + 1 (cost)
-constexpr int BLOCK = 256;              // threads per workgroup (4 waves)
 
 // ---------------------------------------------------------------------------------------
 // small device helpers
@@ -247,22 +245,6 @@ __device__ __forceinline__ double readlane_d(double v, int src) {
 }
 
 
-// ---------------------------------------------------------------------------------------
-// launch flags (clc_set_launch)
-constexpr int FLAG_REDUCE_SHUFFLE = 1;  // reference wave reduction instead of the butterfly
-constexpr int FLAG_PREFETCH = 2;        // software-pipelined tile loads (next tile in flight while computing)
-constexpr int FLAG_NONTEMPORAL = 4;     // nt loads for the streamed tiles
-constexpr int FLAG_COMPACT = 16;      // stream the compact layout (clc_stream.hpp) when it is available
-constexpr int FLAG_DEEP = 64;            // compact layout: two tiles of points in flight per wave (HBM-resident arrays)
-constexpr int FLAG_WG512 = 32;          // 512-thread workgroups with the 3:2 old/young wave tile weighting
-constexpr int FLAG_STEP = 128;          // clc_solve: one step_kernel launch per LM iteration (compact or row layout)
-constexpr int FLAG_ROWS = 256;          // row layout (clc_rows.hpp): 16 B/observation + 64 B/row, per-scan moments
-constexpr int FLAG_EQUAL_WAVES = 512;        // row layout, 512-thread workgroups: equal shares per wave, cut at scan starts, instead of the 3:2 old/young weighting
-constexpr int FLAG_BATCHED_WG256 = 1024;     // batched row kernel: 256-thread workgroups + block reduction instead of one wave per workgroup
-constexpr int FLAG_BATCHED_LOCKSTEP = 2048;  // one-workgroup-per-problem batches: lockstep launches instead of batched_solve_kernel
-constexpr int FLAG_NO_RESIDENT = 4096;       // batched solver: not the on-chip resident kernel (clc_resident.hpp) even where the problems fit
-constexpr int FLAG_RESIDENT_WG512 = 8192;    // resident layout over 512 lanes per problem (one workgroup per CU) even where 256 lanes hold it
-
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 
@@ -286,7 +268,6 @@ __device__ __forceinline__ glb_cdouble* global_opaque(const double* device_ptr) 
 }
 
 // compact layout (clc_stream.hpp): tiles of 128 points x[128], y[128], z[128] (FP64) + gid[128] (u32); one 48-byte group entry per scan
-constexpr int CTILE_DOUBLES = 3 * TILE + TILE / 2;  // 448 doubles = 3 584 B
 constexpr int GROUP_DOUBLES = 6;                    // {n.x, n.y, n.z, d, scale, 0}: 48 B, 16-B aligned
 
 // Static tile -> wave map, two levels, no division by a run-time weight total.  The T tiles of the array are dealt to the

@@ -24,6 +24,10 @@
 
 namespace clc {
 
+// layout sizes (host code plans launches with them: abi_paths.hpp)
+constexpr int TILE = 128;               // records per tile
+constexpr int BLOCK = 256;              // threads per workgroup (4 waves)
+constexpr int CTILE_DOUBLES = 3 * TILE + TILE / 2;  // compact tiles (clc_stream.hpp): 448 doubles = 3 584 B
 constexpr int ROW = 64;          // points per row = lanes per wavefront: one point per lane per row
 constexpr int ROW_DOUBLES = 128; // (x, y) interleaved: lane l reads doubles 2l, 2l+1 with one 16-byte load
 constexpr int ROW_DOUBLES_Z = 192;  // rows that carry z: the 64 z of the row follow its 64 (x, y) pairs

@@ -259,7 +259,7 @@ def test_wave_split_table_moves_boundaries_to_scan_starts_only(sv, n_poses, pts)
     ok, n_rows = sv.debug_rows()[:2]
     assert ok
     for grid in (1, 3, 64, 256, 1000):
-        g = min(grid, (rec.shape[0] + 127) // 128)  # never more workgroups than 128-record tiles (eval_grid)
+        g = min(grid, (rec.shape[0] + 127) // 128)  # never more workgroups than 128-record tiles (plan_stream, csrc/abi_paths.hpp)
         split, first = sv.debug_wave_split(g)
         assert split[0] == 0 and split[-1] == n_rows and np.all(np.diff(split) >= 0), g
         q, r = divmod(n_rows, g)
