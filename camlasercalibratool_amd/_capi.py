@@ -34,6 +34,7 @@ EXPORTED = [
     "clc_store_observations", "clc_select_observations", "clc_upload_batched_device", "clc_line_fit_batched_device",
     "clc_scan_to_points_device", "clc_pinned_alloc", "clc_pinned_free", "clc_store_generation", "clc_batched_host_buffers",
     "clc_get_path_info", "clc_device_info", "clc_comm_library", "clc_board_segments", "clc_board_segments_device",
+    "clc_closed_form_batched", "clc_information_batched",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -192,6 +193,12 @@ def load(path: str):
         L.clc_comm_records.argtypes = [C.c_void_p]
         L.clc_comm_records.restype = C.POINTER(C.c_double)
         L.clc_get_path_info.argtypes = [C.c_void_p, C.c_void_p]
+        P = C.POINTER
+        L.clc_closed_form_batched.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_int32)]
+        L.clc_closed_form_batched.restype = C.c_int
+        L.clc_information_batched.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double),
+                                              P(C.c_double), P(C.c_int32)]
+        L.clc_information_batched.restype = C.c_int
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L

@@ -11,7 +11,7 @@ values of H, null space, "recover chi2") are printed too and also returned."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
@@ -137,6 +137,56 @@ def CamLaserCalibrationFromStarts(obs: ObsLike, Tcls: np.ndarray, use_linefittin
     np.asarray(Tcls)[...] = T.reshape(np.asarray(Tcls).shape)
     costs = np.array([s.final_cost for s in sms])
     return int(np.argmin(costs)), costs, sms
+
+
+def _upload_problems(sv: Solver, sets: Sequence[ObservationSet], use_linefitting_data: bool, use_boundary_constraint: bool):
+    recs = [flatten_observations(S, use_linefitting_data, use_boundary_constraint) for S in sets]
+    off = np.zeros(len(recs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([r.shape[0] for r in recs])
+    sv.upload_batched(np.concatenate(recs) if recs else np.zeros((0, 8)), off)
+
+
+def CamLaserCalibrationBatch(problems: Sequence[ObsLike], use_linefitting_data: bool = True, use_boundary_constraint: bool = False,
+                             options: Optional[Options] = None, solver: Optional[Solver] = None) -> Dict[str, np.ndarray]:
+    """The reference's three steps (main/calibr_offline.cpp:166-170) for a list of independent problems, every step batched on the
+    device: the closed form on the points_on_line records (clc_closed_form_batched), the solve from those starts in place on the
+    handle's buffers (clc_solve_batched), the analysis pass on the solve's point set without board-edge terms
+    (clc_information_batched).  With the default flags the three record sets are the same and one upload serves every step;
+    otherwise the batch is uploaded again between the steps.  A problem whose closed form fails (status != 0: no records, a
+    non-finite solution) starts from the identity pose.
+    -> dict of per-problem arrays: Tlc_initial [P,4,4], unobservable [P], sv9 [P,9], closed_form_status [P], poses [P,7],
+    Tcl [P,4,4], termination / num_iterations [P], initial_cost / final_cost [P], summaries (ctypes array), Tlc [P,4,4]
+    (the inverse of Tcl), H [P,6,6], b [P,6], chi2 [P], sv [P,6], V [P,6,6], n_null [P]."""
+    sets = [_as_set(p) for p in problems]
+    sv = solver or _shared_solver()
+    P = len(sets)
+    if P == 0:
+        raise ValueError("CamLaserCalibrationBatch: no problems")
+    cf_same = use_linefitting_data and not use_boundary_constraint  # solve records == points_on_line records
+    _upload_problems(sv, sets, True, False)  # :143, points_on_line only
+    poses, _ = sv.batched_buffers()
+    poses[...] = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0])
+    Tlc0, unobs, sv9, st, _ = sv.closed_form_batched(poses)
+    start = poses.copy()
+    if not cf_same:
+        _upload_problems(sv, sets, use_linefitting_data, use_boundary_constraint)
+        poses, _ = sv.batched_buffers()
+        poses[...] = start
+    poses, sms = sv.solve_batched_inplace(options)
+    res = poses.copy()
+    summaries = (type(sms[0]) * P)(*sms)
+    if use_boundary_constraint:  # the analysis pass: no board-edge terms (:316-362)
+        _upload_problems(sv, sets, use_linefitting_data, False)
+    H, b, chi2, s6, V, nn = sv.information_batched(res)
+    Tcl = np.stack([simdata.T_from_pose7(p) for p in res])
+    return {
+        "Tlc_initial": Tlc0, "unobservable": unobs, "sv9": sv9, "closed_form_status": st, "start_poses": start,
+        "poses": res, "Tcl": Tcl, "Tlc": np.linalg.inv(Tcl), "summaries": summaries,
+        "termination": np.array([s.termination for s in summaries], dtype=np.int32),
+        "num_iterations": np.array([s.num_iterations for s in summaries], dtype=np.int32),
+        "initial_cost": np.array([s.initial_cost for s in summaries]), "final_cost": np.array([s.final_cost for s in summaries]),
+        "H": H, "b": b, "chi2": chi2, "sv": s6, "V": V, "n_null": nn,
+    }
 
 
 def CamLaserCalClosedSolution(obs: ObsLike, Tlc: np.ndarray, solver: Optional[Solver] = None, verbose: bool = True):

@@ -185,6 +185,9 @@ struct clc_handle {
   clc_abi::MappedArray<double> h_ms_poses;
   clc_abi::MappedArray<clc_summary> h_ms_summaries;
   clc_abi::DeviceArray<double> d_ms_results;
+  // clc_closed_form_batched / clc_information_batched: the per-problem outputs of the finishing kernels, written straight over PCIe
+  // (pinned, device-mapped), then the staged poses of clc_information_batched
+  clc_abi::MappedArray<double> h_flow;
 
   clc::LmState* d_state() const { return &d_block->st[0]; }
   double* d_partials_b() const { return d_partials + d_partials.size() / 2; }  // the step kernel's second row buffer

@@ -379,6 +379,37 @@ class Solver:
         check(self._L.clc_solve_batched(self._h, C.byref(o), dptr(poses), sm), "clc_solve_batched")
         return poses, sm
 
+    def closed_form_batched(self, poses_out: Optional[np.ndarray] = None):
+        """clc_closed_form_batched: CamLaserCalClosedSolution of every uploaded problem (its records taken as points_on_line records)
+        -> (Tlc [P,4,4], unobservable [P] bool, sv9 [P,9], status [P] int32, poses [P,7]).  poses: the start pose Tcl = Tlc^-1 of
+        every problem with status CLC_OK, written into poses_out when given (e.g. the pose view of batched_buffers(), ready for
+        solve_batched_inplace); other rows are left as they were (NaN in a new array)."""
+        P = self.num_problems
+        T = np.full((P, 16), np.nan); sv9 = np.full((P, 9), np.nan)
+        un = np.zeros(P, dtype=np.int32); st = np.zeros(P, dtype=np.int32)
+        if poses_out is None:
+            poses = np.full((P, 7), np.nan)
+        else:
+            poses = poses_out
+            assert poses.shape == (P, 7) and poses.dtype == np.float64 and poses.flags["C_CONTIGUOUS"], "poses_out: C-contiguous [P,7] float64"
+        i32 = C.POINTER(C.c_int32)
+        check(self._L.clc_closed_form_batched(self._h, poses.ctypes.data_as(C.POINTER(C.c_double)), dptr(T), un.ctypes.data_as(i32),
+                                              dptr(sv9), st.ctypes.data_as(i32)), "clc_closed_form_batched")
+        return T.reshape(P, 4, 4), un.astype(bool), sv9, st, poses
+
+    def information_batched(self, poses: np.ndarray):
+        """clc_information_batched: the analysis pass of every uploaded problem at poses [P,7] (may be the pose view of
+        batched_buffers()) -> (H [P,6,6], b [P,6], chi2 [P], sv [P,6], V [P,6,6], n_null [P])."""
+        P = self.num_problems
+        if not (isinstance(poses, np.ndarray) and poses.dtype == np.float64 and poses.flags["C_CONTIGUOUS"]):
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+        assert poses.size == 7 * P, "poses: [P,7]"
+        H = np.empty((P, 36)); b = np.empty((P, 6)); chi = np.empty(P); sv = np.empty((P, 6)); V = np.empty((P, 36))
+        nn = np.empty(P, dtype=np.int32)
+        check(self._L.clc_information_batched(self._h, poses.ctypes.data_as(C.POINTER(C.c_double)), dptr(H), dptr(b), dptr(chi), dptr(sv),
+                                              dptr(V), nn.ctypes.data_as(C.POINTER(C.c_int32))), "clc_information_batched")
+        return H.reshape(P, 6, 6), b, chi, sv, V.reshape(P, 6, 6), nn
+
     def solve_multistart(self, poses0: np.ndarray, options: Optional[Options] = None):
         """clc_solve_multistart: S independent LM solves from S start poses [S, 7] on the ONE problem uploaded as a batch of one
         (upload_batched(records, [0, n])) — one copy of the observations on the device -> (poses [S, 7], summaries [S])."""

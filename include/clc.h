@@ -304,6 +304,28 @@ int clc_information(clc_handle* h, const double pose[7], double H[36], double b[
  * finite; *unobservable is set either way); sv9 nullable. */
 int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9[9]);
 
+/* ---- closed form and analysis pass of every problem of the uploaded batch --------------------
+ * The first and the last of the reference's three steps (main/calibr_offline.cpp:166-170) for all P problems of
+ * clc_upload_batched* at once, on the device: per problem a device reduction (split over several workgroups when the
+ * batch is small), then one wave per problem runs the dense back end (same sweep order, stopping rule and pivot rule as
+ * the single-problem calls).  Record-set rule, as for clc_closed_form / clc_information: the closed form takes the
+ * points_on_line records, the analysis pass the point records without board-edge terms — a caller who solved with
+ * board-edge terms uploads the point records again for these two calls.
+ *
+ * clc_closed_form_batched: CamLaserCalClosedSolution for every problem; each problem's records are taken as points_on_line
+ * records (n, d, p.x, p.y; z ignored) exactly as clc_closed_form does.  status[P] (required): CLC_OK, CLC_ERR_NO_DATA
+ * (empty problem), CLC_ERR_NONFINITE (non-finite solution).  One problem's failure does not fail the call.
+ * poses[P*7] (nullable): the start pose Tcl = Tlc^-1 of every CLC_OK problem; other problems' poses are left as they were.
+ * Passing the handle's own buffer (clc_batched_host_buffers) writes it in place, ready for clc_solve_batched in place.
+ * Tlc[P*16], unobservable[P], sv9[P*9]: nullable (left as they were for an empty problem). */
+int clc_closed_form_batched(clc_handle* h, double* poses, double* Tlc, int32_t* unobservable, double* sv9, int32_t* status);
+
+/* clc_information_batched: the analysis pass of clc_information for every problem at poses[P*7] (may be the handle's own
+ * buffer).  Poses are validated as in clc_solve_batched.  chi2[P], sv[P*6], n_null[P] required; H[P*36], b[P*6], V[P*36]
+ * nullable.  An empty problem reports H = 0, chi2 = 0 and n_null = 6. */
+int clc_information_batched(clc_handle* h, const double* poses, double* H, double* b, double* chi2, double* sv,
+                            double* V, int32_t* n_null);
+
 /* ---- batched independent problems ---------------------------------------------------------
  * P independent T_cl problems (own observations, own pose, own LM state), problem k owning
  * records [offsets[k], offsets[k+1]).  One workgroup per problem runs the whole LM loop on
