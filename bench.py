@@ -6,9 +6,12 @@ Contract:  python bench.py --gpus N --steps K --warmup W
   --gpus N ...` — or WITHOUT a launcher: `python bench.py --gpus N` then starts the N ranks itself (it never measures fewer GPUs than
   it reports: --gpus != WORLD_SIZE is an error).
 
-Output: ONE JSON line of at most 4 KB on stdout (compact_line: the contract's fields + config + roofline + cpu_baseline + parity +
-scale_base + one-number summaries of the side measurements under `side`); the full result — every sub-object of the side measurements —
-goes to bench_detail.json beside this file (`detail_file` on the line; --detail-file moves it) and to stderr.
+Output: ONE JSON line of at most 4 KB on stdout (compact_line); the full result goes to bench_detail.json beside this file
+(`detail_file` on the line; --detail-file moves it) and to stderr.  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line: the contract's fields, config and what the timed steps themselves returned.  --full then runs the
+side measurements, each with runs of its own — roofline and per-kernel figures, the larger and batched configurations, CPU baseline,
+parity with the oracle, cold start — and the line also carries roofline + cpu_baseline + parity + scale_base + one-number summaries
+of them under `side` (every sub-object in the detail file).
 
 Workload (BASELINE.json configs[1], "C2"): a single T_cl problem with 10^6 synthetic
 point-to-plane observations (2000 board poses x 500 scan points, range noise sigma = 0.01 m,
@@ -24,7 +27,7 @@ ONLY ITS OWN contiguous shard (problem k is a pure function of (seed, k)), keeps
 (clc_upload_batched), and a step is ONE call, clc_solve_batched_gather (include/clc.h): the on-chip batched solve of the shard, whose
 epilogue writes every problem's 12-double result record into the gather buffer, + ONE RCCL all-gather (in place) over xGMI of the
 records of all 8 192 x N problems + the copy of the other ranks' records to the host, inside the timed region.
-No collective on the data path.  At N=1 the same shard workload (with a world-size-1 RCCL communicator) is reported
+No collective on the data path.  At N=1 --full reports the same shard workload (with a world-size-1 RCCL communicator)
 as the `batched_c4_shard` sub-object (detail file; `side.c4_*` on the line), the like-for-like base of the 1 -> 8 curve: the N=1 line
 carries it at top level as `scale_base` {workload, value, ms_per_step}, the N>1 lines carry `per_gpu_value` (= value / N).
 
@@ -33,7 +36,7 @@ sides; every block's time is the MAX over ranks; ms_per_step is the MEDIAN block
 --dump-outputs DIR writes what the last timed step returned (N=1: the pose and summary of clc_solve; N>1: the gathered result records)
 as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
-`roofline` is the dominant kernel of the timed region.  Both whole-solve kernels (coop_solve_kernel at C2, resident_solve_kernel
+`roofline` (--full) is the dominant kernel of the timed region.  Both whole-solve kernels (coop_solve_kernel at C2, resident_solve_kernel
 at C4) read the data from HBM once per SOLVE and are bound by FP64 VALU issue / latency: their object has "bound": "valu_f64"
 and `frac` = VALU lane-instructions (measured counts of profiles/valu_counts.json — used only when they belong to the kernel sources
 in the tree — x this run's passes) / this run's kernel time / issue peak; `frac_moved` (bytes moved / time / 8 TB/s, bounded by 1) and
@@ -120,6 +123,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement (roofline and per-kernel figures, the larger and batched "
+                         "configurations, CPU baseline, parity with the oracle, cold start; the --no-* options below switch single ones "
+                         "off); default: the headline figure alone")
     ap.add_argument("--poses", type=int, default=2000)
     ap.add_argument("--pts", type=int, default=500)
     ap.add_argument("--noise", type=float, default=0.01)
@@ -323,10 +330,11 @@ def coop_kernel_report(clc, solver, x0, n_obs, n_scans):
     return rep
 
 
-def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_rccl=True, outputs=None):
+def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_rccl=True, outputs=None, side=False):
     """BASELINE.json configs[3] on this rank: generate problems [lo, hi) of the 8 192 x world batch, keep them resident,
     then time `steps` x (clc_solve_batched + RCCL all-gather of every rank's result records).
-    Returns the dict rank 0 reports (None on other ranks); on rank 0, `outputs` (a dict) receives the last step's records."""
+    Returns the dict rank 0 reports (None on other ranks); on rank 0, `outputs` (a dict) receives the last step's records.
+    `side`: rank 0 also checks the results (ground truth, oracle sample) and measures the kernels (`roofline`) after the timed steps."""
     import camlasercalibratool_amd as clc
     from camlasercalibratool_amd import dist as cdist, simdata as sd
 
@@ -346,8 +354,8 @@ def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_
     ss.upload(rec, off)
     t_up = time.perf_counter() - t_up0
     n_obs_local = int(off[-1])
-    keep = {k: rec[off[k]:off[k + 1]].copy() for k in (0, len(off) - 2)} if rank == 0 else {}
-    hs = hooks_solver(clc, local_rank) if rank == 0 else None  # (rank 0, outside the timed region: the streaming kernel's own timing)
+    keep = {k: rec[off[k]:off[k + 1]].copy() for k in (0, len(off) - 2)} if rank == 0 and side else {}
+    hs = hooks_solver(clc, local_rank) if rank == 0 and side else None  # (rank 0, outside the timed region: the streaming kernel's own timing)
     if hs is not None:
         hs.upload_batched(rec, off)
     del rec
@@ -445,36 +453,37 @@ def run_c4_shard(args, torch, dist, rank, world, local_rank, steps, warmup, use_
             "device": dev_name, "compute_units": n_cus,
             "first_and_last_record": [full[0].tolist(), full[-1].tolist()],
         }
-        # ground truth recovery of this rank's problems (sanity, outside the timed region)
-        mine = full[ss.lo:ss.hi]
-        err = max(float(np.abs(sd.T_from_pose7(mine[k, :7]) - gt[k]).max()) for k in range(0, ss.hi - ss.lo, max(1, (ss.hi - ss.lo) // 256)))
-        res["max_abs_T_err_vs_ground_truth_sampled"] = err
-        # dominant kernel of the step: ONE launch of the resident kernel; its report leads, the streaming evaluation launch of the
-        # lockstep path (still what runs when a problem does not fit a workgroup) follows as `streaming_eval_kernel`
-        res["resident"] = dict(zip(("built", "lanes_per_problem", "max_points_per_lane", "rows"), ss.solver.debug_resident()))
-        rk = resident_kernel_report(clc, ss.solver, x0, ss.hi - ss.lo, n_obs_local, (ss.hi - ss.lo) * args.shard_poses)
-        # batched_eval_kernel over the whole shard (all problems active)
-        _, _, brows_ok, bn_rows = ss.solver.debug_rows()
-        streamed = bn_rows * ROW_BYTES if brows_ok else COMPACT_BYTES_PER_EVAL * n_obs_local
-        kms = min(hs.time_batched_eval(x0, reps=10) for _ in range(3)) if hs is not None else float("nan")
-        res["roofline"] = dict(hbm_figures(streamed, BYTES_PER_EVAL * n_obs_local, kms * 1e-3), traffic=None,
-                               kernel=("clc::batched_rows_eval_kernel<loss=1,nt=1>" if brows_ok else "clc::batched_eval_kernel<compact,deep>")
-                                      + " (all problems of the shard active)",
-                               avg_kernel_ms=kms, served_from="infinity_cache" if streamed <= INFINITY_CACHE_BYTES else "hbm",
-                               traffic_measured_in_run=False, timing="hipEvent pair around 10 back-to-back launches on the solver's stream (best of 3)")
-        if hs is None:
-            res["roofline"] = None
-        if rk is not None:
-            rk["streaming_eval_kernel"] = res["roofline"]
-            res["roofline"] = rk
-        if not args.no_cpu_baseline:
-            import oracle as _o
-            w = 0.0
-            for k, r_k in keep.items():
-                rk = _o.solve(r_k, x0[k], linear_solver="qr")
-                w = max(w, float(np.abs(sd.T_from_pose7(mine[k, :7]) - sd.T_from_pose7(rk.pose)).max()))
-            res["T_cl_max_abs_err_vs_oracle_sample"] = w
-            res["oracle_sample"] = f"{len(keep)} of {ss.hi - ss.lo} problems of rank 0 (tests/test_gpu_parity.py::test_c4_full_size_shard checks 512 of 8192)"
+        if side:
+            # ground truth recovery of this rank's problems (sanity, outside the timed region)
+            mine = full[ss.lo:ss.hi]
+            err = max(float(np.abs(sd.T_from_pose7(mine[k, :7]) - gt[k]).max()) for k in range(0, ss.hi - ss.lo, max(1, (ss.hi - ss.lo) // 256)))
+            res["max_abs_T_err_vs_ground_truth_sampled"] = err
+            # dominant kernel of the step: ONE launch of the resident kernel; its report leads, the streaming evaluation launch of the
+            # lockstep path (still what runs when a problem does not fit a workgroup) follows as `streaming_eval_kernel`
+            res["resident"] = dict(zip(("built", "lanes_per_problem", "max_points_per_lane", "rows"), ss.solver.debug_resident()))
+            rk = resident_kernel_report(clc, ss.solver, x0, ss.hi - ss.lo, n_obs_local, (ss.hi - ss.lo) * args.shard_poses)
+            # batched_eval_kernel over the whole shard (all problems active)
+            _, _, brows_ok, bn_rows = ss.solver.debug_rows()
+            streamed = bn_rows * ROW_BYTES if brows_ok else COMPACT_BYTES_PER_EVAL * n_obs_local
+            kms = min(hs.time_batched_eval(x0, reps=10) for _ in range(3)) if hs is not None else float("nan")
+            res["roofline"] = dict(hbm_figures(streamed, BYTES_PER_EVAL * n_obs_local, kms * 1e-3), traffic=None,
+                                   kernel=("clc::batched_rows_eval_kernel<loss=1,nt=1>" if brows_ok else "clc::batched_eval_kernel<compact,deep>")
+                                          + " (all problems of the shard active)",
+                                   avg_kernel_ms=kms, served_from="infinity_cache" if streamed <= INFINITY_CACHE_BYTES else "hbm",
+                                   traffic_measured_in_run=False, timing="hipEvent pair around 10 back-to-back launches on the solver's stream (best of 3)")
+            if hs is None:
+                res["roofline"] = None
+            if rk is not None:
+                rk["streaming_eval_kernel"] = res["roofline"]
+                res["roofline"] = rk
+            if not args.no_cpu_baseline:
+                import oracle as _o
+                w = 0.0
+                for k, r_k in keep.items():
+                    rk = _o.solve(r_k, x0[k], linear_solver="qr")
+                    w = max(w, float(np.abs(sd.T_from_pose7(mine[k, :7]) - sd.T_from_pose7(rk.pose)).max()))
+                res["T_cl_max_abs_err_vs_oracle_sample"] = w
+                res["oracle_sample"] = f"{len(keep)} of {ss.hi - ss.lo} problems of rank 0 (tests/test_gpu_parity.py::test_c4_full_size_shard checks 512 of 8192)"
     if hs is not None:
         hs.close()
     ss.close()
@@ -698,7 +707,8 @@ def main():
     if world > 1:
         # ---- N>1: the C4 workload (sharded batch + RCCL gather); see run_c4_shard ----
         dumped = {}
-        c4 = run_c4_shard(args, torch, dist, rank, world, local_rank, args.steps, args.warmup, use_rccl=(args.backend == "nccl"), outputs=dumped)
+        c4 = run_c4_shard(args, torch, dist, rank, world, local_rank, args.steps, args.warmup, use_rccl=(args.backend == "nccl"), outputs=dumped,
+                          side=args.full)
         if rank == 0:
             if args.dump_outputs:
                 dump_outputs(args.dump_outputs, dumped)
@@ -714,13 +724,13 @@ def main():
                 "timed_blocks": len(c4["ms_per_step_blocks"]), "ms_per_step_min": min(c4["ms_per_step_blocks"]),
                 "ms_per_step_max": max(c4["ms_per_step_blocks"]), "ms_per_step_first_block": c4["ms_per_step_blocks"][0],
                 "problems_per_s": c4["problems_per_s"], "lm_iters_per_s": c4["lm_iters_per_s"],
-                "roofline": c4["roofline"],
+                "roofline": c4.get("roofline"),
                 "batched_c4_shard": c4,
                 # the N=1 line's `value` is C2 (the configuration the metric is quoted on, a single problem that does not shard); the base
                 # of THIS curve is the same line's top-level `scale_base.value` (= its batched_c4_shard.evals_per_s)
                 "per_gpu_value": c4["evals_per_s"] / world,
-                "scale_base_field": "scale_base.value of the `bench.py --gpus 1` line (this workload, one GPU's shard)",
-                "single_gpu_base": "run `bench.py --gpus 1`: its `batched_c4_shard` sub-object is this workload on one GPU",
+                "scale_base_field": "scale_base.value of the `bench.py --gpus 1 --full` line (this workload, one GPU's shard)",
+                "single_gpu_base": "run `bench.py --gpus 1 --full`: its `batched_c4_shard` sub-object is this workload on one GPU",
             }
             _emit(out, args.detail_file)
         dist.destroy_process_group()
@@ -798,6 +808,13 @@ def main():
             "termination": clc.TERMINATION.get(res.summary.termination),
         }
 
+    if not args.full:  # the headline figure is complete: every measurement below takes runs of its own
+        if rank == 0:
+            _emit(out, args.detail_file)
+        solver.close()
+        return
+
+    if rank == 0:
         # ---- roofline of the dominant kernel ----
         # The timed region consists of step_kernel launches only: one per evaluation pass (every workgroup first runs
         # the LM controller on the previous launch's partial rows, then streams its share of the observations) plus
@@ -1142,7 +1159,7 @@ def main():
         dog = threading.Timer(300.0, _give_up)
         dog.daemon = True
         dog.start()
-        out["batched_c4_shard"] = run_c4_shard(args, torch, None, 0, 1, local_rank, args.shard_steps, 2)
+        out["batched_c4_shard"] = run_c4_shard(args, torch, None, 0, 1, local_rank, args.shard_steps, 2, side=True)
         dog.cancel()
         # what the --gpus N>1 lines scale from: their `value` / N (`per_gpu_value`) against this figure, not against `value` above
         out["scale_base"] = {"workload": "C4 shard", "value": out["batched_c4_shard"]["evals_per_s"], "unit": "evals/s",

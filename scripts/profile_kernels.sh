@@ -27,7 +27,7 @@ run res_fetch 180 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/res_
 run res_write 180 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/res_write -o w -- $P resident 8192
 run res_valu 180 --pmc $VALU --kernel-trace --output-format csv -d $O/res_valu -o w -- $P resident 8192
 fi
-[ "$1" = "--counters-only" ] || run bench_trace 500 --kernel-trace --stats --output-format csv -d $O/bench_trace -o b -- python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-cold-start
+[ "$1" = "--counters-only" ] || run bench_trace 500 --kernel-trace --stats --output-format csv -d $O/bench_trace -o b -- python $R/bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-cold-start
 cd $R
 find $O -name "*.db" -delete 2>/dev/null
 du -sh $O

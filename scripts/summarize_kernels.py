@@ -5,7 +5,7 @@
                               appended from gpurun_out/r05_stamps.txt when present
   r05_coop_traffic.json       what bench.py reads: HBM bytes per launch, VALU wave-instructions per workgroup and pass
   r05_resident.md / r05_resident_traffic.json   the resident batched kernel at the C4 shard (8 192 problems x 1e4 observations)
-  r05_bench_kernel_stats.csv  rocprofv3 --stats table of `bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-cold-start`
+  r05_bench_kernel_stats.csv  rocprofv3 --stats table of `bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-cold-start`
 PMC units (MI355X_MICROARCH.md, HBM / rocprofv3 section): read bytes = 2 x FETCH_SIZE x 1024 (gfx950 half-counts 16-byte-per-lane reads;
 calibrated against the 64-byte-tile kernel in profiles/r03_kernels.md: 1.00008), write = WRITE_SIZE x 1024; separate --pmc passes."""
 import collections, csv, json, os, shutil, statistics

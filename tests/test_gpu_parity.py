@@ -779,7 +779,7 @@ def test_bench_two_rank_path_dry_run(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     detail = str(tmp_path / "detail.json")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--blocks", "2",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--blocks", "2", "--full",
            "--backend", "gloo", "--oversubscribe", "--problems-per-gpu", "96", "--shard-poses", "6", "--shard-pts", "100", "--detail-file", detail]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -832,6 +832,36 @@ def test_bench_one_gpu_dump_outputs(tmp_path, oracle_mod):
     assert outs[0]["summary"][1] == ref.summary.num_iterations
 
 
+BENCH_SIDE = ("roofline", "roofline_step_chain", "roofline_large", "roofline_large_solve", "batched_c3", "multistart", "cpu_baseline",
+              "parity", "cold_start", "batched_c4_shard", "scale_base")
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_side_measurements(tmp_path):
+    """bench.py --gpus 1 without --full sets up, warms up, times the steps and prints the line: no side measurement runs.  With --full
+    (small sizes, cold start and C3 off) the roofline, large-working-set, CPU baseline, parity and C4-shard legs run after the same
+    timed steps."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--poses", "40", "--pts", "100"]
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--large-obs", "100000", "--cpu-seconds", "0.5", "--no-cold-start", "--no-batched",
+                                                 "--problems-per-gpu", "64", "--shard-poses", "6", "--shard-pts", "100", "--shard-steps", "2"])):
+        detail = tmp_path / f"{mode}.json"
+        p = subprocess.run(base + extra + ["--detail-file", str(detail)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and len(lines[0]) < 4096
+        runs[mode] = json.loads(lines[0]), json.load(open(detail))
+    line, full = runs["plain"]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    assert not [k for k in BENCH_SIDE if k in full] and "side" not in line
+    line, full = runs["full"]
+    assert line["steps"] == 2 and line["value"] > 0 and all(k in full for k in ("roofline", "roofline_large", "cpu_baseline", "parity", "scale_base"))
+    assert full["parity"]["T_cl_max_abs_err_vs_oracle"] <= T_TOL and full["parity"]["final_cost_abs_err_vs_oracle"] <= COST_TOL
+    assert full["batched_c4_shard"]["T_cl_max_abs_err_vs_oracle_sample"] <= T_TOL and "side" in line
+    assert runs["plain"][0]["evaluation_passes_per_solve"] == line["evaluation_passes_per_solve"]  # the same timed steps in both modes
+
+
 def test_bench_four_rank_path_uneven_shards_dry_run(tmp_path):
     """What C4 looks like on several ranks, through bench.py's own N>1 path: 4 processes (oversubscribing the one visible GPU, gloo
     process group; with this test's own process that is 5 processes holding the GPU, fewer than a shared machine allows), a problem
@@ -846,7 +876,7 @@ def test_bench_four_rank_path_uneven_shards_dry_run(tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--blocks", "1",
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--blocks", "1", "--full",
            "--backend", "gloo", "--oversubscribe", "--problems-total", "50", "--problems-per-gpu", "13", "--shard-poses", "6",
            "--shard-pts", "100", "--detail-file", detail, "--dump-outputs", str(dump)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
