@@ -14,10 +14,10 @@ CSRC = os.path.join(_HERE, "csrc")
 PRODUCT_LIB_PATH = os.path.join(CSRC, "libclc_hip.so")
 HOOKS_LIB_PATH = os.path.join(CSRC, "libclc_hip_hooks.so")
 LIB_PATH = os.environ.get("CLC_LIBRARY") or PRODUCT_LIB_PATH  # CLC_LIBRARY: run the package on a different build
-UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_batchflow.hip", "abi_comm.hip", "abi_debug.hip"]
+UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_batchflow.hip", "abi_campose.hip", "abi_comm.hip", "abi_debug.hip"]
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
-           "clc_batchflow.hpp"]
+           "clc_batchflow.hpp", "clc_campose.hpp"]
 HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
 SOURCES = UNITS + HEADERS + HOST_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default

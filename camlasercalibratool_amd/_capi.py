@@ -35,6 +35,7 @@ EXPORTED = [
     "clc_scan_to_points_device", "clc_pinned_alloc", "clc_pinned_free", "clc_store_generation", "clc_batched_host_buffers",
     "clc_get_path_info", "clc_device_info", "clc_comm_library", "clc_board_segments", "clc_board_segments_device",
     "clc_closed_form_batched", "clc_information_batched",
+    "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -243,6 +244,13 @@ def iptr(a):
 def default_options() -> Options:
     o = Options()
     lib().clc_options_default(C.byref(o))
+    return o
+
+
+def default_pose_options() -> Options:
+    """clc_pose_options_default: no loss, tolerances tight enough for the float32-rounding floor of the lifted corners."""
+    o = Options()
+    lib().clc_pose_options_default(C.byref(o))
     return o
 
 

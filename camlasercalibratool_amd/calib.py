@@ -213,6 +213,23 @@ def LineFittingCeres(Points: np.ndarray, Line: np.ndarray, solver: Optional[Solv
     Line[...] = lines[0]
 
 
+def CalcCamPoses(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], solver: Optional[Solver] = None,
+                 options: Optional[Options] = None):
+    """CamPoseEst::calcCamPose (src/calcCamPose.cpp:270-303) for many images at once, from detected corners: corners_px[k] [m_k, 2]
+    pixels and board_xy[k] [m_k, 2] board-plane points of image k (camera: camera.Camera).  Returns (tag_q [n, 4] (w, x, y, z),
+    tag_t [n, 3], status [n], rms [n]): T_ca = (R_cw, t_cw), the tagPose_Qca / tagPose_tca of Oberserve
+    (main/calibr_offline.cpp:145-146); an image with status != CLC_POSE_OK (1) has no pose."""
+    counts = [len(np.asarray(c).reshape(-1, 2)) for c in corners_px]
+    if counts != [len(np.asarray(b).reshape(-1, 2)) for b in board_xy]:
+        raise ValueError("CalcCamPoses: corners_px and board_xy differ in length")
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cat = lambda seq: (np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a in seq]) if len(seq)
+                       else np.zeros((0, 2), np.float32))
+    sv = solver or _shared_solver()
+    q, t, rms, st, _ = sv.board_poses(camera, cat(corners_px), cat(board_xy), off, options)
+    return q, t, st, rms
+
+
 def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:
     """The calibration board's segment in one scan — mirror of AutoGetLinePts(points, debug), src/selectScanPoints.cpp:17-190:
     points [n,3] -> the chosen segment's points [k,3] (empty when there is none).  Raises IndexError where the reference's

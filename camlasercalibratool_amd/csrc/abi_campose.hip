@@ -1,0 +1,190 @@
+// abi_campose.hip — clc_camera_lift, clc_camera_project, clc_board_poses(_device): the camera models and the batched planar PnP
+// (K10 in clc_campose.hpp).
+// (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
+#include "abi_drive.hpp"
+#include "clc_campose.hpp"
+
+using namespace clc_abi;
+
+namespace {
+
+int camera_check(const clc_camera* c, const char* who) {
+  if (!c || (c->model != CLC_CAMERA_PINHOLE && c->model != CLC_CAMERA_KANNALA_BRANDT))
+    return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": unknown camera model").c_str());
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(c->proj[i]) || !std::isfinite(c->dist[i]))
+      return fail(CLC_ERR_NONFINITE, (std::string(who) + ": non-finite camera parameter").c_str());
+  if (c->proj[0] == 0.0 || c->proj[1] == 0.0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": zero focal length").c_str());
+  return CLC_OK;
+}
+
+int pose_options(const clc_options* in, clc_options* o, const char* who) {
+  if (in) *o = *in; else clc_pose_options_default(o);
+  if (o->max_num_iterations < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": max_num_iterations < 0").c_str());
+  if (o->use_loss) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": the pose refinement has no loss (use_loss must be 0)").c_str());
+  return CLC_OK;
+}
+
+unsigned lift_blocks(size_t n) { return (unsigned)((n + clc::cp::LIFT_THREADS - 1) / clc::cp::LIFT_THREADS); }
+
+// lift (rounded) into lifted_dev[2 * n_corners] (corner `first` first), then one wave per image; every array on the device, offsets
+// absolute
+hipError_t launch_board_poses(clc_handle* h, const clc_camera& cam, const clc_options& opt, const float* corners_dev, const float* board_dev,
+                              const long long* off_dev, long long first, size_t n_corners, size_t n_images, float* lifted_dev,
+                              double* q_dev, double* t_dev, double* rms_dev, int32_t* status_dev, clc_summary* sum_dev) {
+  if (n_corners > 0) {
+    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<true>), dim3(lift_blocks(n_corners)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, cam,
+                       corners_dev + 2 * first, (long long)n_corners, nullptr, lifted_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(clc::cp::board_pose_kernel, dim3((unsigned)n_images), dim3(64), 0, h->stream, opt, lifted_dev, board_dev, off_dev,
+                     first, q_dev, t_dev, rms_dev, status_dev, sum_dev);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+void clc_pose_options_default(clc_options* o) {
+  clc_options_default(o);
+  if (!o) return;
+  o->use_loss = 0;
+  o->max_num_iterations = 50;
+  o->function_tolerance = 1e-15;
+  o->parameter_tolerance = 1e-14;
+  o->gradient_tolerance = 1e-16;
+}
+
+int clc_camera_lift(clc_handle* h, const clc_camera* cam, const float* px, size_t n, double* xy_norm) {
+  if (!h || (n > 0 && (!px || !xy_norm))) return fail(CLC_ERR_INVALID_ARG, "clc_camera_lift: bad argument");
+  {
+    const int rc = camera_check(cam, "clc_camera_lift");
+    if (rc != CLC_OK) return rc;
+  }
+  if (n == 0) return CLC_OK;
+  if (n > 0x3FFFFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_camera_lift: too many points");
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<float> bp(&h->pool);
+  DevBuf<double> bo(&h->pool);
+  CLC_HIP(bp.alloc(2 * n));
+  CLC_HIP(bo.alloc(2 * n));
+  CLC_HIP(hipMemcpyAsync(bp.p, px, 2 * n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL((clc::cp::campose_lift_kernel<false>), dim3(lift_blocks(n)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, *cam, bp.p,
+                     (long long)n, bo.p, nullptr);
+  CLC_HIP(hipGetLastError());
+  CLC_HIP(hipMemcpyAsync(xy_norm, bo.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+int clc_camera_project(clc_handle* h, const clc_camera* cam, const double pose7[7], const double* pts, size_t n, double* px) {
+  if (!h || (n > 0 && (!pts || !px))) return fail(CLC_ERR_INVALID_ARG, "clc_camera_project: bad argument");
+  {
+    const int rc = camera_check(cam, "clc_camera_project");
+    if (rc != CLC_OK) return rc;
+  }
+  clc::cp::Pose7Arg pose{};
+  if (pose7) {
+    for (int i = 0; i < 7; ++i) {
+      if (!std::isfinite(pose7[i])) return fail(CLC_ERR_NONFINITE, "clc_camera_project: non-finite pose");
+      pose.v[i] = pose7[i];
+    }
+  }
+  if (n == 0) return CLC_OK;
+  if (n > 0x3FFFFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_camera_project: too many points");
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bp(&h->pool), bo(&h->pool);
+  CLC_HIP(bp.alloc(3 * n));
+  CLC_HIP(bo.alloc(2 * n));
+  CLC_HIP(hipMemcpyAsync(bp.p, pts, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(clc::cp::campose_project_kernel, dim3(lift_blocks(n)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, *cam, pose,
+                     pose7 ? 1 : 0, bp.p, (long long)n, bo.p);
+  CLC_HIP(hipGetLastError());
+  CLC_HIP(hipMemcpyAsync(px, bo.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+int clc_board_poses(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const float* corners_px, const float* board_xy,
+                    const int64_t* offsets, size_t n_images, double* q_ca_wxyz, double* t_ca, double* rms, int32_t* status,
+                    clc_summary* summaries) {
+  if (!h || (n_images > 0 && (!offsets || !q_ca_wxyz || !t_ca || !status)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: bad argument");
+  int rc = camera_check(cam, "clc_board_poses");
+  if (rc != CLC_OK) return rc;
+  clc_options opt;
+  rc = pose_options(opt_in, &opt, "clc_board_poses");
+  if (rc != CLC_OK) return rc;
+  if (n_images == 0) return CLC_OK;
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: too many images");
+  if (offsets[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: negative offset");
+  for (size_t k = 0; k < n_images; ++k)
+    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: offsets not monotone");
+  const size_t M = (size_t)(offsets[n_images] - offsets[0]);
+  if (M > 0 && (!corners_px || !board_xy)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: bad argument");
+  CLC_HIP(hipSetDevice(h->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<long long> rel(n_images + 1);
+  for (size_t k = 0; k <= n_images; ++k) rel[k] = offsets[k] - offsets[0];
+  DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  DevBuf<double> bq(&h->pool), bt(&h->pool), br(&h->pool);
+  DevBuf<int32_t> bs(&h->pool);
+  DevBuf<clc_summary> bsum(&h->pool);
+  CLC_HIP(bc.alloc(2 * M)); CLC_HIP(bb.alloc(2 * M)); CLC_HIP(bl.alloc(2 * M)); CLC_HIP(boff.alloc(n_images + 1));
+  CLC_HIP(bq.alloc(4 * n_images)); CLC_HIP(bt.alloc(3 * n_images)); CLC_HIP(bs.alloc(n_images));
+  if (rms) CLC_HIP(br.alloc(n_images));
+  if (summaries) CLC_HIP(bsum.alloc(n_images));
+  if (M > 0) {
+    CLC_HIP(hipMemcpyAsync(bc.p, corners_px + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    CLC_HIP(hipMemcpyAsync(bb.p, board_xy + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  }
+  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n_images + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(launch_board_poses(h, *cam, opt, bc.p, bb.p, boff.p, 0, M, n_images, bl.p, bq.p, bt.p, rms ? br.p : nullptr, bs.p,
+                             summaries ? bsum.p : nullptr));
+  CLC_HIP(hipMemcpyAsync(q_ca_wxyz, bq.p, 4 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(t_ca, bt.p, 3 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(status, bs.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (rms) CLC_HIP(hipMemcpyAsync(rms, br.p, n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (summaries) CLC_HIP(hipMemcpyAsync(summaries, bsum.p, n_images * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (summaries) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (size_t k = 0; k < n_images; ++k) summaries[k].solve_ms = ms;
+  }
+  return CLC_OK;
+}
+
+int clc_board_poses_device(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const float* corners_px_dev,
+                           const float* board_xy_dev, const int64_t* offsets_dev, size_t n_images, double* q_ca_wxyz_dev,
+                           double* t_ca_dev, double* rms_dev, int32_t* status_dev, clc_summary* summaries_dev) {
+  if (!h || (n_images > 0 && (!offsets_dev || !q_ca_wxyz_dev || !t_ca_dev || !status_dev)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: bad argument");
+  int rc = camera_check(cam, "clc_board_poses_device");
+  if (rc != CLC_OK) return rc;
+  clc_options opt;
+  rc = pose_options(opt_in, &opt, "clc_board_poses_device");
+  if (rc != CLC_OK) return rc;
+  if (n_images == 0) return CLC_OK;
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: too many images");
+  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
+  CLC_HIP(hipSetDevice(h->device));
+  // the corner range: the two ends of the offsets (a small read; the lifted corners go to a scratch array of the same indexing)
+  long long ends[2];
+  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n_images, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: offsets not monotone");
+  const size_t M = (size_t)(ends[1] - ends[0]);
+  if (M > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: bad argument");
+  DevBuf<float> bl(&h->pool);
+  CLC_HIP(bl.alloc(2 * M));
+  CLC_HIP(launch_board_poses(h, *cam, opt, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev), ends[0], M,
+                             n_images, bl.p, q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+}  // extern "C"

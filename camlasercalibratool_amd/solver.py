@@ -462,6 +462,49 @@ class Solver:
               "clc_scan_to_points")
         return pts
 
+    # ---- camera models and board poses (K10) ----
+    def camera_lift(self, camera, px: np.ndarray) -> np.ndarray:
+        """liftProjective of pixels px [n, 2] (float32) -> x/z, y/z [n, 2] (unrounded)."""
+        p = np.ascontiguousarray(px, dtype=np.float32).reshape(-1, 2)
+        out = np.empty((p.shape[0], 2))
+        c = camera.to_c()
+        check(self._L.clc_camera_lift(self._h, C.byref(c), p.ctypes.data_as(C.c_void_p), C.c_size_t(p.shape[0]), dptr(out)), "clc_camera_lift")
+        return out
+
+    def camera_project(self, camera, pts: np.ndarray, pose7: Optional[np.ndarray] = None) -> np.ndarray:
+        """spaceToPlane of pts [n, 3] after p_c = R p + t of pose7 = T_cl [t, qx, qy, qz, qw] (None: identity) -> pixels [n, 2]."""
+        P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        out = np.empty((P.shape[0], 2))
+        c = camera.to_c()
+        pp = None if pose7 is None else dptr(np.ascontiguousarray(pose7, dtype=np.float64).reshape(7))
+        check(self._L.clc_camera_project(self._h, C.byref(c), pp, dptr(P), C.c_size_t(P.shape[0]), dptr(out)), "clc_camera_project")
+        return out
+
+    def board_poses(self, camera, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray,
+                    options: Optional[Options] = None, want_summaries: bool = False):
+        """One board pose per image (CamPoseEst::calcCamPose): corners_px [M, 2] float32 pixels, board_xy [M, 2] float32 board-plane
+        points, CSR offsets [n+1] -> (q_ca_wxyz [n, 4], t_ca [n, 3], rms [n], status [n] int32, summaries or None)."""
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        q = np.empty((n, 4)); t = np.empty((n, 3)); rms = np.empty(n); st = np.empty(n, dtype=np.int32)
+        sm = (Summary * n)() if want_summaries and n > 0 else None
+        c = camera.to_c()
+        o = C.byref(options) if options is not None else None
+        check(self._L.clc_board_poses(self._h, C.byref(c), o, cp.ctypes.data_as(C.c_void_p), bx.ctypes.data_as(C.c_void_p), iptr(offsets),
+                                      C.c_size_t(n), dptr(q), dptr(t), dptr(rms), st.ctypes.data_as(C.c_void_p), sm), "clc_board_poses")
+        return q, t, rms, st, sm
+
+    def board_poses_device(self, camera, corners_ptr: int, board_ptr: int, offsets_ptr: int, n_images: int, q_ptr: int, t_ptr: int,
+                           rms_ptr: int = 0, status_ptr: int = 0, summaries_ptr: int = 0, options: Optional[Options] = None):
+        """clc_board_poses_device on device-resident arrays (data_ptr()s; ready on the solver's stream)."""
+        c = camera.to_c()
+        o = C.byref(options) if options is not None else None
+        check(self._L.clc_board_poses_device(self._h, C.byref(c), o, C.c_void_p(corners_ptr), C.c_void_p(board_ptr), C.c_void_p(offsets_ptr),
+                                             C.c_size_t(n_images), C.c_void_p(q_ptr), C.c_void_p(t_ptr), C.c_void_p(rms_ptr or 0),
+                                             C.c_void_p(status_ptr), C.c_void_p(summaries_ptr or 0)), "clc_board_poses_device")
+
     # ---- board-segment detection ----
     def board_segments(self, points: np.ndarray, offsets: np.ndarray):
         """AutoGetLinePts (src/selectScanPoints.cpp:17-190) for many scans: points [M,3], CSR offsets [S+1] ->

@@ -395,6 +395,59 @@ int clc_board_segments(clc_handle* h, const double* points, const int64_t* offse
 int clc_board_segments_device(clc_handle* h, const double* points_dev, const int64_t* offsets_dev, size_t n_scans, int64_t* seg_dev,
                               int32_t* status_dev);
 
+/* ---- board poses from tag corners (the numeric half of CamPoseEst::calcCamPose, src/calcCamPose.cpp:270-303) -------------
+ * The two camera models the reference's nodes select (main/kalibratag_detector_node.cpp:90-105), restated from camodocal:
+ *   CLC_CAMERA_PINHOLE         PinholeCamera:     proj = fx fy cx cy, dist = k1 k2 p1 p2
+ *   CLC_CAMERA_KANNALA_BRANDT  EquidistantCamera: proj = mu mv u0 v0, dist = k2 k3 k4 k5
+ * Pinhole lift (liftProjective, camera_models/src/PinholeCamera.cc): mx_d = (1/fx) u + (-cx/fx) (inverse-K constants as at
+ * :208-211), identity when k1 = k2 = p1 = p2 = 0 (:196-205), otherwise the recursive model, 8 evaluations of distortion()
+ * (:401-415, :554-571).  Kannala-Brandt lift (EquidistantCamera.cc:342-356, backprojectSymmetric :632-733): theta = the
+ * smallest real root >= -1e-10 (clamped to 0) of theta + k2 theta^3 + k3 theta^5 + k4 theta^7 + k5 theta^9 = |p_u|, the degree
+ * dropping by 2 for every zero coefficient (:647-663); theta = |p_u| when no root qualifies; phi = 0 when |p_u| < 1e-10.  The
+ * reference takes the eigenvalues of the companion matrix; here the first sign change on [0, inf) is bracketed and polished
+ * (safeguarded Newton / bisection), the same root.  Project: spaceToPlane (PinholeCamera.cc:428-453, EquidistantCamera.cc:364-377). */
+#define CLC_CAMERA_PINHOLE 1
+#define CLC_CAMERA_KANNALA_BRANDT 2
+typedef struct clc_camera {
+  int32_t model;    /* CLC_CAMERA_* */
+  int32_t reserved; /* 0 */
+  double proj[4];   /* fx fy cx cy | mu mv u0 v0 */
+  double dist[4];   /* k1 k2 p1 p2 | k2 k3 k4 k5 */
+} clc_camera;       /* 72 bytes */
+
+/* Pose status of clc_board_poses. */
+#define CLC_POSE_OK 1
+#define CLC_POSE_TOO_FEW 0        /* fewer than 4 corners (EstimatePose, src/calcCamPose.cpp:217) */
+#define CLC_POSE_DEGENERATE (-1)  /* rank-deficient homography (e.g. collinear corners) */
+#define CLC_POSE_NONFINITE (-2)   /* a non-finite corner, board point or result, or no start with every corner in front */
+
+/* clc_options for clc_board_poses: Ceres defaults with no loss, function tolerance 1e-15, parameter tolerance 1e-14, gradient
+ * tolerance 1e-16 and 50 iterations — the iterate reaches the least-squares minimiser of the float32-rounded lifted points. */
+void clc_pose_options_default(clc_options* opt);
+/* liftProjective of n pixels px[2n] (float32, as cornerSubPix writes them), on the device: xy_norm[2n] = x/z, y/z (unrounded). */
+int clc_camera_lift(clc_handle* h, const clc_camera* cam, const float* px, size_t n, double* xy_norm);
+/* spaceToPlane of n points pts[3n] after the transform pose7 = T_cl = [t, qx, qy, qz, qw] (p_c = R p + t, as the verification
+ * overlay debug_code/showscan_node.cpp:96-130 maps laser points; NULL = identity), on the device: px[2n]. */
+int clc_camera_project(clc_handle* h, const clc_camera* cam, const double pose7[7], const double* pts, size_t n, double* px);
+/* One board pose per image (EstimatePose, src/calcCamPose.cpp:211-232, with calcCamPose's lift :277-287): image k owns corners
+ * [offsets[k], offsets[k+1]) of corners_px[2M] (float32 pixels) and board_xy[2M] (float32 board-plane x, y; z = 0, the
+ * cv::Point3f of every board type).  Per image: every corner lifted in fp64 and x/z, y/z rounded to float32 (:284-286);
+ * a normalized-DLT homography, decomposed with the board in front; then Levenberg-Marquardt (no loss) on the K = I reprojection error
+ * (R X + t)_xy / (R X + t)_z - x_lifted over the PoseLocalParameterization tangent — the least-squares minimiser that
+ * cv::solvePnP (K = I, no distortion, :222-226) iterates towards.  Outputs: q_ca_wxyz[4n] (w >= 0) and t_ca[3n] of
+ * T_ca = (R_cw, t_cw): p_c = R X + t, the tagPose_Qca / tagPose_tca of Oberserve (main/calibr_offline.cpp:145-146);
+ * rms[n] (nullable): sqrt(sum |r|^2 / corners), normalized units; status[n] (required): CLC_POSE_*; summaries[n] (nullable).
+ * An image that is not CLC_POSE_OK gets q = (1, 0, 0, 0), t = 0, rms = NaN; it never fails the call or affects other images.
+ * opt NULL = clc_pose_options_default(). */
+int clc_board_poses(clc_handle* h, const clc_camera* cam, const clc_options* opt, const float* corners_px, const float* board_xy,
+                    const int64_t* offsets, size_t n_images, double* q_ca_wxyz, double* t_ca, double* rms, int32_t* status,
+                    clc_summary* summaries);
+/* The same with every array in DEVICE memory (ready on the handle's stream; complete on return — it synchronises):
+ * offsets_dev[n_images + 1] absolute (offsets_dev[0] may be > 0; not validated: monotone). */
+int clc_board_poses_device(clc_handle* h, const clc_camera* cam, const clc_options* opt, const float* corners_px_dev,
+                           const float* board_xy_dev, const int64_t* offsets_dev, size_t n_images, double* q_ca_wxyz_dev,
+                           double* t_ca_dev, double* rms_dev, int32_t* status_dev, clc_summary* summaries_dev);
+
 /* Multi-hypothesis calibration on SHARED observations: n_starts independent LM solves (one ceres::Solve each, src/LaseCamCalCeres.cpp
  * :299-309) from n_starts start poses on the ONE problem the handle holds as a batch of one (clc_upload_batched* with n_problems = 1).
  * poses: n_starts x 7, in/out; summaries: n_starts.  Where the problem fits a workgroup (clc_path_info.batched_resident) ONE launch runs
