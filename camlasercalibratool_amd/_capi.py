@@ -36,6 +36,7 @@ EXPORTED = [
     "clc_get_path_info", "clc_device_info", "clc_comm_library", "clc_board_segments", "clc_board_segments_device",
     "clc_closed_form_batched", "clc_information_batched",
     "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
+    "clc_solve_subsets",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -189,6 +190,9 @@ def load(path: str):
         L.clc_solve_batched_gather_pipelined.restype = C.c_int
         L.clc_gather_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.clc_gather_flush.restype = C.c_int
+        L.clc_solve_subsets.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_uint8),
+                                        C.POINTER(C.c_double), C.c_void_p]
+        L.clc_solve_subsets.restype = C.c_int
         L.clc_comm_set_root.argtypes = [C.c_void_p, C.c_int]
         L.clc_comm_get_info.argtypes = [C.c_void_p, C.c_void_p]
         L.clc_comm_records.argtypes = [C.c_void_p]

@@ -139,6 +139,55 @@ def CamLaserCalibrationFromStarts(obs: ObsLike, Tcls: np.ndarray, use_linefittin
     return int(np.argmin(costs)), costs, sms
 
 
+def pose_block_offsets(obs: ObsLike, use_linefitting_data: bool = True, use_boundary_constraint: bool = False) -> np.ndarray:
+    """Record offsets [P + 1] of flatten_observations' output, one block per Oberserve: its point rows, then (board-edge terms on) its
+    two edge rows."""
+    S = _as_set(obs)
+    off = np.asarray(S.ptl_off if use_linefitting_data else S.pts_off, dtype=np.int64)
+    extra = 2 if (use_boundary_constraint and use_linefitting_data) else 0
+    out = np.zeros(S.n_poses + 1, dtype=np.int64)
+    out[1:] = np.cumsum(np.diff(off) + extra)
+    return out
+
+
+def CamLaserCalibrationResample(obs: ObsLike, Tcl: np.ndarray, use_linefitting_data: bool = True, use_boundary_constraint: bool = False,
+                                mode: str = "jackknife", n: int = 0, seed: int = 0, m: int = 0,
+                                options: Optional[Options] = None, solver: Optional[Solver] = None) -> Dict[str, object]:
+    """How much does Tcl depend on the poses that were recorded?  The full problem is solved from Tcl (refined in place), then — on the
+    same upload, one launch (clc_solve_subsets) — its resampled versions from the full solution: mode "jackknife" (every pose left out
+    once), "bootstrap" (n rows of P draws with replacement) or "subsets" (n random m-of-P subsets).
+    -> {"pose": full solution [7], "summary", "weights" [S, P], "poses" [S, 7], "summaries", "deltas" [S, 6] (local coordinates of
+    every resampled solution about the full one), "covariance" [6, 6] (jackknife / bootstrap estimate; None for "subsets"),
+    "influence" [P] (jackknife only: |delta_k|, how far leaving pose k out moves the solution)}."""
+    from . import resample
+    S = _as_set(obs)
+    sv = solver or _shared_solver()
+    rec = flatten_observations(S, use_linefitting_data, use_boundary_constraint)
+    off = pose_block_offsets(S, use_linefitting_data, use_boundary_constraint)
+    sv.upload_batched(rec, np.array([0, rec.shape[0]], dtype=np.int64))
+    P = S.n_poses
+    full, fsm = sv.solve_multistart(simdata.pose7_from_T(np.asarray(Tcl, dtype=np.float64).reshape(4, 4))[None], options)
+    x_full = full[0]
+    if mode == "jackknife":
+        W = resample.jackknife_weights(P)
+    elif mode == "bootstrap":
+        W = resample.bootstrap_weights(P, n, seed)
+    elif mode == "subsets":
+        W = resample.random_subset_weights(P, n, m, seed)
+    else:
+        raise ValueError("mode: 'jackknife', 'bootstrap' or 'subsets'")
+    poses, sms = sv.solve_subsets(off, W, x_full, options)
+    np.asarray(Tcl)[...] = simdata.T_from_pose7(x_full).reshape(np.asarray(Tcl).shape)
+    D = resample.local_deltas(x_full, poses)
+    cov = None
+    if mode == "jackknife":
+        cov = resample.jackknife_covariance(x_full, poses)
+    elif mode == "bootstrap":
+        cov = resample.bootstrap_covariance(x_full, poses)
+    return {"pose": x_full, "summary": fsm[0], "weights": W, "poses": poses, "summaries": sms, "deltas": D, "covariance": cov,
+            "influence": np.linalg.norm(D, axis=1) if mode == "jackknife" else None}
+
+
 def _upload_problems(sv: Solver, sets: Sequence[ObservationSet], use_linefitting_data: bool, use_boundary_constraint: bool):
     recs = [flatten_observations(S, use_linefitting_data, use_boundary_constraint) for S in sets]
     off = np.zeros(len(recs) + 1, dtype=np.int64)

@@ -1,4 +1,5 @@
-// abi_batched.hip — clc_solve_batched: many independent problems per launch (resident kernel, whole-solve kernel, lockstep launches).
+// abi_batched.hip — clc_solve_batched: many independent problems per launch (resident kernel, whole-solve kernel, lockstep launches);
+// clc_solve_multistart / clc_solve_subsets: many starts / weighted pose subsets on ONE uploaded problem.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 
@@ -256,6 +257,117 @@ int clc_solve_multistart(clc_handle* h, const clc_options* opt_in, size_t n_star
   }
   for (size_t k = 0; k < n_starts; ++k)
     if (!all_finite(poses + 7 * k, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve_multistart: non-finite result");
+  return CLC_OK;
+}
+
+
+// Resampled calibrations on SHARED observations: n_subsets independent LM solves of the ONE problem the handle holds as a batch of one,
+// subset k being the problem in which every record of block b (records [block_offsets[b], block_offsets[b + 1]) — a pose's rows)
+// appears weights[k * n_blocks + b] times (0: left out).  One launch of the weighted resident kernel: a workgroup per subset on problem 0's lane
+// layout, which is neither re-planned nor touched (clc_solve_multistart before and after returns the same bits).
+int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks, const int64_t* block_offsets, size_t n_subsets,
+                      const uint8_t* weights, double* poses, clc_summary* summaries) {
+  if (!h || !block_offsets || !weights || !poses || !summaries || n_blocks == 0 || n_subsets == 0)
+    return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: bad argument");
+  if (!h->batch.d_tiles || h->n_problems != 1)
+    return fail(CLC_ERR_NO_DATA, "clc_solve_subsets: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
+  if (n_blocks > 0x7FFFFFFFull || n_subsets > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: too many blocks or subsets");
+  if (block_offsets[0] != 0 || block_offsets[n_blocks] != (int64_t)h->batch_records)
+    return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: block_offsets must start at 0 and end at the problem's record count");
+  for (size_t b = 0; b < n_blocks; ++b)
+    if (block_offsets[b + 1] < block_offsets[b]) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: block_offsets not monotone");
+  clc_options opt;
+  if (opt_in) opt = *opt_in; else clc_options_default(&opt);
+  {
+    const int rc = batched_check_inputs("clc_solve_subsets", opt, poses, n_subsets);
+    if (rc != CLC_OK) return rc;
+  }
+  CLC_HIP(hipSetDevice(h->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  BatchedLaunch bl;
+  {
+    const int rc = batched_launch_setup(h, opt, &bl);
+    if (rc != CLC_OK) return rc;
+  }
+  if (!bl.resident)
+    return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: the problem is not held by one workgroup (clc_path_info.batched_resident == 0, or the "
+                                     "launch flags rule the resident kernel out): materialise the subsets and use clc_solve_batched");
+  const int lanes = h->bres.lanes;
+  // the lane -> block map: built once per (n_blocks, offsets) and upload
+  if (h->sub_offsets.size() != n_blocks + 1 || std::memcmp(h->sub_offsets.data(), block_offsets, sizeof(int64_t) * (n_blocks + 1)) != 0) {
+    h->sub_offsets.clear();
+    CLC_HIP(h->d_sub_lane_block.grow((size_t)lanes));
+    DevBuf<long long> d_off(&h->pool);
+    DevBuf<unsigned int> d_flag(&h->pool);
+    CLC_HIP(d_off.alloc(n_blocks + 1));
+    CLC_HIP(d_flag.alloc(1));
+    static_assert(sizeof(long long) == sizeof(int64_t), "block offsets are copied as they are");
+    CLC_HIP(hipMemcpyAsync(d_off.p, block_offsets, sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, h->stream));
+    CLC_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(unsigned int), h->stream));
+    if (lanes == 256)
+      hipLaunchKernelGGL(clc::subset_lane_map_kernel<256>, dim3(1), dim3(256), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
+                         (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
+    else
+      hipLaunchKernelGGL(clc::subset_lane_map_kernel<512>, dim3(1), dim3(512), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
+                         (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
+    CLC_HIP(hipGetLastError());
+    unsigned int flag = 0;
+    CLC_HIP(hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
+    CLC_HIP(hipStreamSynchronize(h->stream));
+    if (flag & 2u) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: the lane layout does not match the record count");
+    if (flag & 1u)
+      return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: a block boundary falls inside a scan (consecutive records of one plane): "
+                                       "a block must hold whole scans");
+    h->sub_offsets.assign(block_offsets, block_offsets + n_blocks + 1);
+  }
+  CLC_HIP(h->h_ms_poses.grow(7 * n_subsets));
+  CLC_HIP(h->h_ms_summaries.grow(n_subsets));
+  CLC_HIP(h->d_ms_results.grow(sizeof(clc_result_record) / sizeof(double) * n_subsets));
+  CLC_HIP(h->h_sub_weights.grow(n_subsets * n_blocks));
+  // (the previous call ended with a stream synchronisation: nothing still reads or writes the staging buffers)
+  std::memcpy(h->h_ms_poses, poses, sizeof(double) * 7 * n_subsets);
+  std::memcpy(h->h_sub_weights, weights, n_subsets * n_blocks);
+  // a workgroup whose subset is empty writes nothing: its summary stays what it is set to here
+  clc_summary none;
+  std::memset(&none, 0, sizeof(none));
+  none.termination = CLC_FAILURE;
+  none.num_evaluations = -1;  // (no written summary has it)
+  for (size_t k = 0; k < n_subsets; ++k) h->h_ms_summaries[k] = none;
+  const bool timed = opt.profile_events == 1;
+  if (timed) {
+    const int rc = ensure_events(h, 2);
+    if (rc != CLC_OK) return rc;
+    CLC_HIP(hipEventRecord(h->ev[0], h->stream));
+  }
+  // the forms of launch_resident_batch: 256 lanes, 512 lanes, 512 lanes with z
+  const auto launch = [&](auto Z, auto W4, auto LOSS, auto NT) {
+    constexpr int NW = W4 ? 4 : 8;
+    constexpr int PR = Z ? kResPRz : W4 ? kResPR256 : kResPR512, PL = Z ? kResPLz : W4 ? kResPL256 : kResPL512;
+    // (the weighted form's three inputs ride in res_row, trace and trace_cap: clc_resident.hpp, WEIGHTED)
+    hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z, true>), dim3((unsigned)n_subsets),
+                       dim3(NW * 64), 0, h->stream, h->bres.d_xy, h->d_sub_lane_block, h->bres.d_desc, h->batch.d_groups, -2 - h->bres.max_ppl, opt,
+                       reinterpret_cast<clc_iteration*>(h->h_sub_weights.dev()), (int)n_blocks, h->h_ms_poses.dev(), h->h_ms_summaries.dev(),
+                       h->d_ms_results, nullptr, nullptr, 0.0, nullptr, 0, 0, Z ? h->bres.d_z : nullptr);
+  };
+  if (h->bres.with_z) with_flags(launch, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
+  else with_flags(launch, std::false_type{}, lanes == 256, opt.use_loss != 0, bl.res_nt);
+  CLC_HIP(hipGetLastError());
+  if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));  // (kernel completion makes the outcomes written over PCIe visible)
+  float kernel_ms = 0.0f;
+  if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
+  std::memcpy(summaries, h->h_ms_summaries, sizeof(clc_summary) * n_subsets);
+  const double ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (size_t k = 0; k < n_subsets; ++k) {
+    // an empty subset or a non-finite end: CLC_FAILURE in its summary, its pose left as the caller passed it — never the call's failure
+    const double* out = h->h_ms_poses + 7 * k;
+    const bool written = summaries[k].num_evaluations >= 0;
+    if (written && all_finite(out, 7)) std::memcpy(poses + 7 * k, out, sizeof(double) * 7);
+    else summaries[k].termination = CLC_FAILURE;
+    if (!written) summaries[k].num_evaluations = 0;
+    summaries[k].solve_ms = ms_wall;
+    if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
+  }
   return CLC_OK;
 }
 

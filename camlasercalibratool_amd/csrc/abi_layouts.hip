@@ -766,6 +766,7 @@ int upload_batched_impl(clc_handle* h, const clc_observation* records, bool on_d
   int crc = CLC_OK;
   h->batch.invalidate();
   h->bres.ok = false;
+  h->sub_offsets.clear();  // (the lane -> block map of clc_solve_subsets belongs to the layout about to be rebuilt)
   h->results_valid = 0;
   if (e == hipSuccess && d_aos) crc = build_layouts(h, d_aos, n_total, rel, tile_off, h->batch, h->d_prob_row, &h->bres, nullptr);
   if (e != hipSuccess) return fail(CLC_ERR_HIP, "clc_upload_batched: retile", e);
@@ -777,6 +778,7 @@ int upload_batched_impl(clc_handle* h, const clc_observation* records, bool on_d
     for (size_t k = 0; k < P; ++k) h->batch_max_rows = std::max(h->batch_max_rows, pr[k + 1] - pr[k]);
   }
   h->n_problems = P;
+  h->batch_records = n_total;
   return CLC_OK;
 }
 }  // namespace

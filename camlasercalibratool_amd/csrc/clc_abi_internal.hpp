@@ -4,7 +4,7 @@
 //   abi_layouts.hip   upload paths: re-encoding of the records into the compact / row / lane layouts, stored scans
 //   abi_solve.hip     clc_eval, clc_solve and its launch sequences (step chain, single-workgroup resident, cooperative)
 //   abi_frontend.hip  factor evaluation, manifold plus, information matrix, closed form, line fitting, scan conversion
-//   abi_batched.hip   clc_solve_batched
+//   abi_batched.hip   clc_solve_batched, clc_solve_multistart, clc_solve_subsets
 //   abi_comm.hip      RCCL gather of the sharded batch's result records
 //   abi_debug.hip     clc_debug_* / clc_time_* (test and profiling hooks; only with -DCLC_TEST_HOOKS)
 // Built for gfx950 only (camlasercalibratool_amd/_build.py): every unit with
@@ -185,6 +185,12 @@ struct clc_handle {
   clc_abi::MappedArray<double> h_ms_poses;
   clc_abi::MappedArray<clc_summary> h_ms_summaries;
   clc_abi::DeviceArray<double> d_ms_results;
+  // clc_solve_subsets (staged like multi-start, in the three arrays above): the weight rows (pinned, device-mapped), and the lane -> block
+  // map of problem 0's lane layout with the block offsets it was built for (empty: no map; dropped by every batched upload)
+  clc_abi::MappedArray<uint8_t> h_sub_weights;
+  clc_abi::DeviceArray<unsigned int> d_sub_lane_block;
+  std::vector<int64_t> sub_offsets;
+  size_t batch_records = 0;  // records of the uploaded batch
   // clc_closed_form_batched / clc_information_batched: the per-problem outputs of the finishing kernels, written straight over PCIe
   // (pinned, device-mapped), then the staged poses of clc_information_batched
   clc_abi::MappedArray<double> h_flow;

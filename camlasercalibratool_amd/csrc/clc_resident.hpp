@@ -159,6 +159,42 @@ __global__ __launch_bounds__(NL) void res_build_kernel(const double* __restrict_
   }
 }
 
+// clc_solve_subsets: the lane -> block map of problem 0's lane layout, one workgroup of NL threads.  res_build_kernel deals a problem's
+// records to its lanes in order (scan after scan, a scan's lanes one after the other), so lane t holds the records
+// [k0, k0 + cnt), k0 = the counts of the lanes before it.  lane_block[t] = the block b with block_off[b] <= k0 < block_off[b + 1]
+// (binary search; idle lanes: block 0).  *flag |= 1 when a lane's records reach beyond its block (a block boundary inside a scan's
+// lane: the lane would need two multiplicities), |= 2 when the counts do not add up to n_records (never, for a layout of these records).
+template <int NL>
+__global__ __launch_bounds__(NL) void subset_lane_map_kernel(const ResLane* __restrict__ desc, const long long* __restrict__ block_off,
+                                                             const int n_blocks, const long long n_records,
+                                                             unsigned int* __restrict__ lane_block, unsigned int* __restrict__ flag) {
+  __shared__ long long first[NL + 1];
+  const int t = threadIdx.x;
+  const long long cnt = desc[t].cnt;
+  first[t + 1] = cnt;
+  if (t == 0) first[0] = 0;
+  __syncthreads();
+  for (int off = 1; off < NL; off <<= 1) {  // inclusive scan of first[1..NL]
+    const long long a = t >= off ? first[t + 1 - off] : 0;
+    __syncthreads();
+    first[t + 1] += a;
+    __syncthreads();
+  }
+  if (t == 0 && first[NL] != n_records) atomicOr(flag, 2u);
+  int b = 0;
+  if (cnt > 0) {
+    const long long k0 = first[t];
+    int lo = 0, hi = n_blocks;  // block_off[lo] <= k0 < block_off[hi] (block_off[0] = 0, block_off[n_blocks] = n_records: checked by the host)
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (block_off[mid] <= k0) lo = mid; else hi = mid;
+    }
+    b = lo;
+    if (k0 + cnt > block_off[lo + 1]) atomicOr(flag, 1u);
+  }
+  lane_block[t] = (unsigned int)b;
+}
+
 #ifdef CLC_STAMPS
 // Debug build only (scripts/stamps_resident.py): stamps of the first RES_STAMP_WGS problems' waves 0 and 1 —
 // slot 0: wall clock (100 MHz) at kernel entry, 1: wall clock at exit, 2: shader clock at entry, 3: after the loads landed;
@@ -198,7 +234,17 @@ __device__ __forceinline__ v2d res_load(const v2d* p) {
 // state (the round-2/3 controller: what tests/test_gpu_lmuni.py compares the other against, bit for bit — same pass, same totals).
 // WITH_Z (8-wave form only): the points carry z (p.z != 0 somewhere in the batch) — 24-byte slots, a third register / LDS array per lane
 // (`zl`: the z rows, j-major like the (x, y) rows), 14 moments per lane (rows3_*, clc_rows.hpp), padded slots masked (as clc_coop.hpp).
-template <bool WITH_LOSS, bool NT, int NW, int PR, int PL, int CTRL, bool WITH_Z = false>
+//
+// WEIGHTED (clc_solve_subsets; with the multi-start layout, uni_ppl <= -2, only): workgroup k solves problem 0 with every record of block b
+// taken weights[k * n_blocks + b] times.  The argument list is the unweighted kernel's, so that the unweighted instantiations stay what they
+// were to the byte; three arguments that a multi-start launch never reads carry the subsets: res_row = the lane -> block map
+// (subset_lane_map_kernel), trace_cap = n_blocks, trace = the weight rows (uint8_t [n_subsets * n_blocks]).
+// A lane holds points of one scan and hence of one block, so its multiplicity is one scalar, and it enters in ONE place: every term of a lane's expanded contribution —
+// Hessian and gradient moments, the analytic padding correction, the cost s^2 log(prod) — carries the factor q.s2 = scale^2 exactly once,
+// and the robust loss never sees it (its argument r0^2 / lf^2 is free of the scale: a = lf scale), so w rho(r^2) is q.s2 <- w q.s2 after
+// the plane set-up: one multiply per lane and pass, exact for w = 1 (the all-ones row is bit-identical to multi-start).  w = 0 takes
+// the idle-lane route (plane zeroed).  A workgroup none of whose lanes has points left returns before its first pass and writes nothing.
+template <bool WITH_LOSS, bool NT, int NW, int PR, int PL, int CTRL, bool WITH_Z = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(NW * 64, 2) void resident_solve_kernel(
     const double* __restrict__ xyl, const unsigned int* __restrict__ res_row, const ResLane* __restrict__ lane_desc,
     const double* __restrict__ groups, const int uni_ppl, const clc_options opt, clc_iteration* __restrict__ trace,
@@ -235,8 +281,8 @@ __global__ __launch_bounds__(NW * 64, 2) void resident_solve_kernel(
   const int prob = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the iteration trace exists for the single-problem (8-wave) launches only: in the 4-wave form the controller shares the
   // register file with 92 VGPRs of points, and the trace record's code must not be there at all
-  clc_iteration* const tr = (NW == 8 && !WITH_Z) ? trace : nullptr;
-  const int tr_cap = (NW == 8 && !WITH_Z) ? trace_cap : 0;
+  clc_iteration* const tr = (NW == 8 && !WITH_Z && !WEIGHTED) ? trace : nullptr;
+  const int tr_cap = (NW == 8 && !WITH_Z && !WEIGHTED) ? trace_cap : 0;
   // The controller runs on wave 0.  (Picking wave 0 / wave 2 by the workgroup's LDS allocation base — s_getreg HW_REG_LDS_ALLOC — so
   // that the two workgroups of a CU never run their controllers on the same SIMD was measured: no gain, and the run-time wave
   // index cost a live SGPR in a kernel that already spills scalars — a -DCLC_STAMPS build of that form computed wrong steps.)
@@ -298,7 +344,15 @@ __global__ __launch_bounds__(NW * 64, 2) void resident_solve_kernel(
   // The lane's plane is fetched again in every pass (48 bytes per lane out of L1/L2: a problem's group entries are ~1 KB)
   // rather than held in 10 VGPRs across the controller, which needs every register it can get.
   const double* __restrict__ gp = groups + (size_t)dl.gid * GROUP_DOUBLES;
-  const int cnt = dl.cnt;
+  // WEIGHTED: the lane's multiplicity, one VGPR held across the controller; a lane whose block is left out of this subset becomes an
+  // idle lane (cnt = 0: plane and scale zeroed in the pass — its moments are finite and expand to nothing)
+  int wgt = 1;
+  if constexpr (WEIGHTED) {
+    const uint8_t* __restrict__ sub_weights = reinterpret_cast<const uint8_t*>(trace);  // (see WEIGHTED above)
+    wgt = dl.cnt > 0 ? (int)sub_weights[(size_t)prob * (size_t)trace_cap + (size_t)res_row[tid]] : 0;
+    if (!__syncthreads_or(wgt)) return;  // nothing left of the problem (an all-zero row): no outcome written, the host reports CLC_FAILURE
+  }
+  const int cnt = WEIGHTED && wgt == 0 ? 0 : dl.cnt;
   if (tid < 7) sh_park[tid] = pose_w;
   const double inv_lf2 = make_uniform(1.0 / (opt.loss_scale_factor * opt.loss_scale_factor));
   // points processed per lane and pass: ppl rounded up to whole groups (GRP points per basic block: independent
@@ -385,6 +439,7 @@ __global__ __launch_bounds__(NW * 64, 2) void resident_solve_kernel(
       load_pose(x, P);
       rows_plane_setup(P.R, P.t, nx, ny, nz, pd, ps, q);
     }
+    if constexpr (WEIGHTED) q.s2 *= (double)wgt;  // the point loop does not read s2; the expansion and the padding correction carry it once per term
 #ifdef CLC_STAMPS
     if (wave != cw) { asm volatile("" :: "v"(q.mx), "v"(q.c0)); RES_STAMP(8 + 6 * pass_no, clock64()); }  // plane + pose have arrived
 #endif

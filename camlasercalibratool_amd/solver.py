@@ -420,6 +420,24 @@ class Solver:
         check(self._L.clc_solve_multistart(self._h, C.byref(o), C.c_size_t(S), dptr(poses), sm), "clc_solve_multistart")
         return poses, sm
 
+    def solve_subsets(self, block_offsets: np.ndarray, weights: np.ndarray, poses0: np.ndarray, options: Optional[Options] = None):
+        """clc_solve_subsets: S resampled solves on the ONE problem uploaded as a batch of one (upload_batched(records, [0, n])).
+        block_offsets [B + 1] cuts the records into consecutive blocks (one per pose), weights [S, B] uint8 says how many times subset k
+        takes block b (0: left out; resample.jackknife_weights / bootstrap_weights / random_subset_weights), poses0 [S, 7] or [7] (every
+        subset from the same start) -> (poses [S, 7], summaries [S]).  An empty or non-finite subset: termination FAILURE, pose kept."""
+        off = np.ascontiguousarray(block_offsets, dtype=np.int64).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.uint8)
+        B = off.size - 1
+        assert B >= 1 and w.size % B == 0 and w.size > 0, "weights: [S, len(block_offsets) - 1]"
+        S = w.size // B
+        p0 = np.asarray(poses0, dtype=np.float64)
+        poses = np.ascontiguousarray(np.broadcast_to(p0.reshape(-1, 7), (S, 7))).copy()
+        sm = (Summary * S)()
+        o = options or default_options()
+        check(self._L.clc_solve_subsets(self._h, C.byref(o), B, off.ctypes.data_as(C.POINTER(C.c_int64)), S,
+                                        w.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(poses), sm), "clc_solve_subsets")
+        return poses, sm
+
     # ---- scan line fitting ----
     def line_fit_batched(self, xy: np.ndarray, offsets: np.ndarray, lines0: np.ndarray,
                          options: Optional[Options] = None, want_summaries: bool = True):

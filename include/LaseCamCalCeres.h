@@ -401,6 +401,70 @@ class Session {
         return best;
     }
 
+    // Resampled calibrations (no counterpart in the reference): how much does Tcl depend on the poses that were recorded?  weights is
+    // n_subsets rows of obs.size() multiplicities — row k is the calibration in which observation i counts weights[k * obs.size() + i]
+    // times (0: left out; leave-one-out rows for a jackknife, draws with replacement for a bootstrap) — and every row is solved from
+    // Tcls[k] on the SAME uploaded observations by ONE launch (clc_solve_subsets: a workgroup per row; the problem must fit a workgroup,
+    // as the reference's sizes do).  Tcls[] are overwritten with the refined Tcl; final_costs / terminations (optional, n_subsets each)
+    // receive each solve's final cost and CLC_* termination — a row with nothing in it keeps its Tcl and reports CLC_FAILURE.
+    // Returns false when the call could not run.
+    bool CalibrationSubsets(const uint8_t* weights, size_t n_subsets, Eigen::Matrix4d* Tcls, bool use_linefitting_data = true,
+                            bool use_boundary_constraint = false, double* final_costs = NULL, int* terminations = NULL)
+    {
+        Handle H;
+        ok_ = false;
+        if (!H.h || !weights || !Tcls || n_subsets == 0) return false;
+        const Flat f = flatten(*obs_);
+        const int P = (int)(f.pts_off.size() - 1);
+        if (P <= 0) return false;
+        int64_t n_rec = 0;
+        if (clc_flatten_observations(P, f.tag_q.data(), f.tag_t.data(), f.pts_off.data(), f.pts, f.ptl_off.data(), f.ptl,
+                                     use_linefitting_data, use_boundary_constraint, NULL, &n_rec) != CLC_OK) {
+            std::cerr << "[clc] " << clc_last_error() << std::endl;
+            return false;
+        }
+        std::vector<clc_observation> rec((size_t)n_rec);
+        clc_flatten_observations(P, f.tag_q.data(), f.tag_t.data(), f.pts_off.data(), f.pts, f.ptl_off.data(), f.ptl,
+                                 use_linefitting_data, use_boundary_constraint, rec.data(), &n_rec);
+        // one block per observation: its point rows, then (board-edge terms on) its two edge rows
+        const std::vector<int64_t>& src = use_linefitting_data ? f.ptl_off : f.pts_off;
+        const int64_t extra = (use_boundary_constraint && use_linefitting_data) ? 2 : 0;
+        std::vector<int64_t> blocks((size_t)P + 1, 0);
+        for (int i = 0; i < P; ++i) blocks[(size_t)i + 1] = blocks[(size_t)i] + (src[(size_t)i + 1] - src[(size_t)i]) + extra;
+        const int64_t off[2] = {0, n_rec};
+        std::vector<double> poses(7 * n_subsets);
+        for (size_t k = 0; k < n_subsets; ++k) {
+            double R[9];
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[3 * i + j] = Tcls[k](i, j);
+            rot_to_quat_xyzw(R, &poses[7 * k + 3]);
+            for (int i = 0; i < 3; ++i) poses[7 * k + i] = Tcls[k](i, 3);
+        }
+        std::vector<clc_summary> sums(n_subsets);
+        clc_options opt; clc_options_default(&opt);
+        if (clc_upload_batched(H.h, rec.data(), off, 1) != CLC_OK ||
+            clc_solve_subsets(H.h, &opt, (size_t)P, blocks.data(), n_subsets, weights, poses.data(), sums.data()) != CLC_OK) {
+            std::cerr << "[clc] " << clc_last_error() << std::endl;
+            return false;
+        }
+        for (size_t k = 0; k < n_subsets; ++k) {
+            if (final_costs) final_costs[k] = sums[k].final_cost;
+            if (terminations) terminations[k] = sums[k].termination;
+            if (sums[k].termination == CLC_FAILURE) continue;  // (Tcls[k] stays what the caller passed)
+            const double* q = &poses[7 * k];
+            const double x = q[3], y = q[4], z = q[5], w = q[6];
+            const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
+            const double txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+            Eigen::Matrix4d& T = Tcls[k];
+            T(0, 0) = 1 - (tyy + tzz); T(0, 1) = txy - twz;       T(0, 2) = txz + twy;
+            T(1, 0) = txy + twz;       T(1, 1) = 1 - (txx + tzz); T(1, 2) = tyz - twx;
+            T(2, 0) = txz - twy;       T(2, 1) = tyz + twx;       T(2, 2) = 1 - (txx + tyy);
+            T(0, 3) = q[0]; T(1, 3) = q[1]; T(2, 3) = q[2];
+            T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+        }
+        ok_ = true;
+        return true;
+    }
+
  private:
     bool store(clc_handle* h)
     {

@@ -457,6 +457,23 @@ int clc_board_poses_device(clc_handle* h, const clc_camera* cam, const clc_optio
  * one clc_solve per start: the cooperative solve uses the whole GPU for each). */
 int clc_solve_multistart(clc_handle* h, const clc_options* opt, size_t n_starts, double* poses_inout, clc_summary* summaries);
 
+/* Resampled calibrations on SHARED observations (jackknife, bootstrap, random subsets of the poses): n_subsets independent LM solves on
+ * the ONE problem the handle holds as a batch of one (clc_upload_batched* with n_problems = 1), each with some poses left out or
+ * repeated.  The records are cut into n_blocks consecutive blocks — block_offsets[n_blocks + 1], block_offsets[0] = 0, last = the
+ * record count, non-decreasing; one block per pose keeps a pose's point rows and edge rows together — and subset k is BY DEFINITION the
+ * problem in which every record of block b appears weights[k * n_blocks + b] times (0: left out), each record with its own scale and
+ * loss: exactly what clc_solve_batched computes for the sub-problem with those records repeated, to rounding (sums in another order).
+ * poses: n_subsets x 7, in/out; summaries: n_subsets.  ONE launch, a workgroup per subset on the one on-chip layout; the layout is not
+ * changed (clc_solve_multistart on the same upload is unaffected), the lane -> block map is kept on the handle until the offsets change
+ * or the next upload.  A weight row of 1s returns the bits clc_solve_multistart returns.
+ * CLC_ERR_NO_DATA unless a batch of one is uploaded.  CLC_ERR_INVALID_ARG: bad offsets; a block boundary inside a scan (the library
+ * treats consecutive records with bitwise-equal planes as one scan; a block must hold whole scans); a problem that one workgroup does
+ * not hold (clc_path_info.batched_resident == 0: materialise the subsets and use clc_solve_batched).
+ * A subset with nothing in it (all weights 0) or with a non-finite end gets termination = CLC_FAILURE and keeps its pose; it does not
+ * fail the call. */
+int clc_solve_subsets(clc_handle* h, const clc_options* opt, size_t n_blocks, const int64_t* block_offsets, size_t n_subsets,
+                      const uint8_t* weights, double* poses_inout, clc_summary* summaries);
+
 /* ---- multi-GPU: sharded batches + RCCL gather ------------------------------------------------
  * BASELINE.json configs[3]: independent T_cl problems shard across the GPUs of a node, one process
  * per GPU, no collective on the data path; the fixed-size result records of all ranks are gathered
