@@ -19,7 +19,11 @@ HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_lay
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
            "clc_batchflow.hpp", "clc_campose.hpp"]
 HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
-SOURCES = UNITS + HEADERS + HOST_HEADERS
+# kernels of their own that include HEADERS and are included by none of them: the kernels whose measured constants csrc_sha16 guards
+# (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
+# abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md).  They rebuild the libraries and are not part of csrc_sha16.
+SIDE_HEADERS = ["clc_consensus.hpp"]
+SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the
 # same device functions — the step kernel and the [eval, lm] launch pair then differed in the last bits on 1 of 60
@@ -39,7 +43,8 @@ def csrc_sha16() -> str:
     the .hpp files; the abi_*.hip units are the host side — launchers, checks, RCCL calls) and the compiler flags.  Constants that were
     measured on a build (the VALU instruction counts bench.py prices the whole-solve kernels with, profiles/valu_counts.json) carry
     it, and bench.py refuses them when it differs from the sources in the tree.  HOST_HEADERS are left out: they hold host code only
-    (launch drivers), which no kernel is built from, so editing them leaves the measured constants valid."""
+    (launch drivers), which no kernel is built from, so editing them leaves the measured constants valid; SIDE_HEADERS hold kernels
+    that none of the measured kernels' sources includes."""
     import hashlib
     h = hashlib.sha256()
     for s in HEADERS:

@@ -36,7 +36,7 @@ EXPORTED = [
     "clc_get_path_info", "clc_device_info", "clc_comm_library", "clc_board_segments", "clc_board_segments_device",
     "clc_closed_form_batched", "clc_information_batched",
     "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
-    "clc_solve_subsets",
+    "clc_solve_subsets", "clc_score_blocks",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -45,6 +45,7 @@ HOOKS = [
     "clc_debug_wave_split", "clc_debug_resident", "clc_debug_resident_single", "clc_debug_coop", "clc_debug_coop_control",
     "clc_debug_coop_set_tag", "clc_debug_layout", "clc_debug_lm_profile", "clc_time_steps", "clc_time_batched_eval", "clc_time_eval",
     "clc_debug_comm_create_layout", "clc_debug_single_controller", "clc_debug_fast_small",
+    "clc_debug_lane_map_builds",
 ]
 
 
@@ -193,6 +194,9 @@ def load(path: str):
         L.clc_solve_subsets.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_uint8),
                                         C.POINTER(C.c_double), C.c_void_p]
         L.clc_solve_subsets.restype = C.c_int
+        L.clc_score_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_double), C.c_double,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.clc_score_blocks.restype = C.c_int
         L.clc_comm_set_root.argtypes = [C.c_void_p, C.c_int]
         L.clc_comm_get_info.argtypes = [C.c_void_p, C.c_void_p]
         L.clc_comm_records.argtypes = [C.c_void_p]

@@ -188,6 +188,49 @@ def CamLaserCalibrationResample(obs: ObsLike, Tcl: np.ndarray, use_linefitting_d
             "influence": np.linalg.norm(D, axis=1) if mode == "jackknife" else None}
 
 
+def CamLaserCalibrationConsensus(obs: ObsLike, Tcl: np.ndarray, use_linefitting_data: bool = True, use_boundary_constraint: bool = False,
+                                 n: int = 256, m: int = 5, rms_max: Optional[float] = None, seed: int = 0,
+                                 options: Optional[Options] = None, solver: Optional[Solver] = None) -> Dict[str, object]:
+    """Calibration by consensus over the recorded poses: which recordings are bad, and the answer without them.  A whole scan can be
+    consistently off by centimetres (its tag pose taken from the wrong camera frame, its board segment cut wrongly); the per-point
+    Cauchy loss has its largest influence exactly there and all of that scan's points pull the same way.  Steps, on ONE upload:
+      1. n random m-of-P subsets (resample.random_subset_weights(P, n, m, seed)) solved from Tcl          — solve_subsets, one launch
+      2. every candidate scored against every pose: ssq [n, P]                                          — score_blocks, one launch
+      3. resample.consensus_select(ssq, rms_max): the candidate most poses agree with, and those poses   — numpy
+      4. one refit on the supporting poses only (the mask as weights), started at the winner            — solve_subsets, one launch
+      5. the refit scored against every pose                                                            — score_blocks
+    m defaults to 5: the reference refuses fewer than 5 observations (main/calibr_offline.cpp:158).
+    rms_max (required) is the largest RMS point-to-plane distance, in metres, that a pose consistent with a candidate may show (with
+    point rows only sqrt(ssq) is exactly that RMS).  Base it on the scanner's range noise: a few sigma — the tests use 3 sigma of the
+    simulated noise.  A wrong recording must stand clear of it: at sigma = 0.01 m and rms_max = 0.03 m, poses 0.08 m off are
+    separated exactly, poses 0.05 m off slip into the support and the refit is no better than the plain solve.
+    Tcl is refined in place (left alone when no candidate finds support).
+    -> {"pose" [7], "summary", "inliers" [P] bool, "rms" [P] (per-pose RMS at the result), "sizes" [n] (support of every candidate),
+        "best" (the winning row; -1: none), "weights" [n, P], "candidates" [n, 7], "ssq" [n, P]}."""
+    from . import resample
+    if rms_max is None:
+        raise TypeError("rms_max is required: a few sigma of the scanner's range noise, in metres (see the docstring)")
+    S = _as_set(obs)
+    sv = solver or _shared_solver()
+    rec = flatten_observations(S, use_linefitting_data, use_boundary_constraint)
+    off = pose_block_offsets(S, use_linefitting_data, use_boundary_constraint)
+    sv.upload_batched(rec, np.array([0, rec.shape[0]], dtype=np.int64))
+    P = S.n_poses
+    x0 = simdata.pose7_from_T(np.asarray(Tcl, dtype=np.float64).reshape(4, 4))
+    W = resample.random_subset_weights(P, n, m, seed)
+    cands, _ = sv.solve_subsets(off, W, x0, options)
+    ssq, _, _ = sv.score_blocks(off, cands, rms_max, options)
+    best, mask, sizes = resample.consensus_select(ssq, rms_max)
+    if best < 0:
+        return {"pose": x0, "summary": None, "inliers": mask, "rms": np.full(P, np.nan), "sizes": sizes, "best": -1, "weights": W,
+                "candidates": cands, "ssq": ssq}
+    refit, sms = sv.solve_subsets(off, mask.astype(np.uint8)[None], cands[best], options)
+    q, _, _ = sv.score_blocks(off, refit, rms_max, options)
+    np.asarray(Tcl)[...] = simdata.T_from_pose7(refit[0]).reshape(np.asarray(Tcl).shape)
+    return {"pose": refit[0], "summary": sms[0], "inliers": mask, "rms": np.sqrt(q[0]), "sizes": sizes, "best": best, "weights": W,
+            "candidates": cands, "ssq": ssq}
+
+
 def _upload_problems(sv: Solver, sets: Sequence[ObservationSet], use_linefitting_data: bool, use_boundary_constraint: bool):
     recs = [flatten_observations(S, use_linefitting_data, use_boundary_constraint) for S in sets]
     off = np.zeros(len(recs) + 1, dtype=np.int64)

@@ -1,7 +1,9 @@
 // abi_batched.hip — clc_solve_batched: many independent problems per launch (resident kernel, whole-solve kernel, lockstep launches);
-// clc_solve_multistart / clc_solve_subsets: many starts / weighted pose subsets on ONE uploaded problem.
+// clc_solve_multistart / clc_solve_subsets / clc_score_blocks: many starts / weighted pose subsets / block scores of many poses on ONE
+// uploaded problem.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
+#include "clc_consensus.hpp"
 
 using namespace clc_abi;
 
@@ -99,6 +101,54 @@ int finish_batched(clc_handle* h, bool in_place, double* poses, clc_summary* sum
     summaries[k].solve_ms = ms;
     if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
   }
+  return CLC_OK;
+}
+
+std::atomic<long long> g_lane_map_builds{0};  // lane -> block maps built in this process (hooks build: clc_debug_lane_map_builds)
+
+// clc_solve_subsets / clc_score_blocks: the cut of the one uploaded problem's records into consecutive blocks
+int check_block_offsets(const char* who, const clc_handle* h, size_t n_blocks, const int64_t* block_offsets) {
+  const std::string w(who);
+  if (n_blocks > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, (w + ": too many blocks").c_str());
+  if (block_offsets[0] != 0 || block_offsets[n_blocks] != (int64_t)h->batch_records)
+    return fail(CLC_ERR_INVALID_ARG, (w + ": block_offsets must start at 0 and end at the problem's record count").c_str());
+  for (size_t b = 0; b < n_blocks; ++b)
+    if (block_offsets[b + 1] < block_offsets[b]) return fail(CLC_ERR_INVALID_ARG, (w + ": block_offsets not monotone").c_str());
+  return CLC_OK;
+}
+
+// The lane -> block map of problem 0's lane layout (h->d_sub_lane_block): built once per (n_blocks, offsets) and upload, shared by
+// clc_solve_subsets and clc_score_blocks.  Ends with the stream synchronised when it builds.
+int ensure_lane_block_map(const char* who, clc_handle* h, size_t n_blocks, const int64_t* block_offsets) {
+  if (h->sub_offsets.size() == n_blocks + 1 && std::memcmp(h->sub_offsets.data(), block_offsets, sizeof(int64_t) * (n_blocks + 1)) == 0)
+    return CLC_OK;
+  const std::string w(who);
+  const int lanes = h->bres.lanes;
+  h->sub_offsets.clear();
+  CLC_HIP(h->d_sub_lane_block.grow((size_t)lanes));
+  DevBuf<long long> d_off(&h->pool);
+  DevBuf<unsigned int> d_flag(&h->pool);
+  CLC_HIP(d_off.alloc(n_blocks + 1));
+  CLC_HIP(d_flag.alloc(1));
+  static_assert(sizeof(long long) == sizeof(int64_t), "block offsets are copied as they are");
+  CLC_HIP(hipMemcpyAsync(d_off.p, block_offsets, sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(unsigned int), h->stream));
+  if (lanes == 256)
+    hipLaunchKernelGGL(clc::subset_lane_map_kernel<256>, dim3(1), dim3(256), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
+                       (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
+  else
+    hipLaunchKernelGGL(clc::subset_lane_map_kernel<512>, dim3(1), dim3(512), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
+                       (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
+  CLC_HIP(hipGetLastError());
+  unsigned int flag = 0;
+  CLC_HIP(hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  g_lane_map_builds.fetch_add(1, std::memory_order_relaxed);
+  if (flag & 2u) return fail(CLC_ERR_INVALID_ARG, (w + ": the lane layout does not match the record count").c_str());
+  if (flag & 1u)
+    return fail(CLC_ERR_INVALID_ARG, (w + ": a block boundary falls inside a scan (consecutive records of one plane): "
+                                          "a block must hold whole scans").c_str());
+  h->sub_offsets.assign(block_offsets, block_offsets + n_blocks + 1);
   return CLC_OK;
 }
 
@@ -271,11 +321,11 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks,
     return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: bad argument");
   if (!h->batch.d_tiles || h->n_problems != 1)
     return fail(CLC_ERR_NO_DATA, "clc_solve_subsets: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
-  if (n_blocks > 0x7FFFFFFFull || n_subsets > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: too many blocks or subsets");
-  if (block_offsets[0] != 0 || block_offsets[n_blocks] != (int64_t)h->batch_records)
-    return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: block_offsets must start at 0 and end at the problem's record count");
-  for (size_t b = 0; b < n_blocks; ++b)
-    if (block_offsets[b + 1] < block_offsets[b]) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: block_offsets not monotone");
+  if (n_subsets > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: too many subsets");
+  {
+    const int rc = check_block_offsets("clc_solve_subsets", h, n_blocks, block_offsets);
+    if (rc != CLC_OK) return rc;
+  }
   clc_options opt;
   if (opt_in) opt = *opt_in; else clc_options_default(&opt);
   {
@@ -293,32 +343,9 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks,
     return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: the problem is not held by one workgroup (clc_path_info.batched_resident == 0, or the "
                                      "launch flags rule the resident kernel out): materialise the subsets and use clc_solve_batched");
   const int lanes = h->bres.lanes;
-  // the lane -> block map: built once per (n_blocks, offsets) and upload
-  if (h->sub_offsets.size() != n_blocks + 1 || std::memcmp(h->sub_offsets.data(), block_offsets, sizeof(int64_t) * (n_blocks + 1)) != 0) {
-    h->sub_offsets.clear();
-    CLC_HIP(h->d_sub_lane_block.grow((size_t)lanes));
-    DevBuf<long long> d_off(&h->pool);
-    DevBuf<unsigned int> d_flag(&h->pool);
-    CLC_HIP(d_off.alloc(n_blocks + 1));
-    CLC_HIP(d_flag.alloc(1));
-    static_assert(sizeof(long long) == sizeof(int64_t), "block offsets are copied as they are");
-    CLC_HIP(hipMemcpyAsync(d_off.p, block_offsets, sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, h->stream));
-    CLC_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(unsigned int), h->stream));
-    if (lanes == 256)
-      hipLaunchKernelGGL(clc::subset_lane_map_kernel<256>, dim3(1), dim3(256), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
-                         (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
-    else
-      hipLaunchKernelGGL(clc::subset_lane_map_kernel<512>, dim3(1), dim3(512), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
-                         (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
-    CLC_HIP(hipGetLastError());
-    unsigned int flag = 0;
-    CLC_HIP(hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
-    CLC_HIP(hipStreamSynchronize(h->stream));
-    if (flag & 2u) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: the lane layout does not match the record count");
-    if (flag & 1u)
-      return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: a block boundary falls inside a scan (consecutive records of one plane): "
-                                       "a block must hold whole scans");
-    h->sub_offsets.assign(block_offsets, block_offsets + n_blocks + 1);
+  {
+    const int rc = ensure_lane_block_map("clc_solve_subsets", h, n_blocks, block_offsets);
+    if (rc != CLC_OK) return rc;
   }
   CLC_HIP(h->h_ms_poses.grow(7 * n_subsets));
   CLC_HIP(h->h_ms_summaries.grow(n_subsets));
@@ -371,7 +398,79 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks,
   return CLC_OK;
 }
 
+// Consensus scores on SHARED observations: every one of n_poses candidate poses judged against every block of the ONE problem the
+// handle holds as a batch of one — per (pose k, block b) the sum of squared residuals, the robust cost and the number of records within
+// tau of their plane.  One launch of block_scores_kernel (clc_consensus.hpp): a workgroup per pose on problem 0's lane layout and the
+// lane -> block map clc_solve_subsets uses (built here when the offsets are new, kept for both).  Nothing of the layout or the stored
+// observations is written.  The tables are staged in h_flow (pinned, device-mapped: the per-call output area of the batched analysis
+// calls), the poses in the multi-start staging array.
+int clc_score_blocks(clc_handle* h, const clc_options* opt_in, size_t n_blocks, const int64_t* block_offsets, size_t n_poses,
+                     const double* poses, double tau, double* ssq, double* cost, int32_t* inliers) {
+  if (!h || !block_offsets || !poses || n_blocks == 0 || n_poses == 0 || tau != tau)
+    return fail(CLC_ERR_INVALID_ARG, "clc_score_blocks: bad argument");
+  if (!h->batch.d_tiles || h->n_problems != 1)
+    return fail(CLC_ERR_NO_DATA, "clc_score_blocks: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
+  if (n_poses > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_score_blocks: too many poses");
+  {
+    const int rc = check_block_offsets("clc_score_blocks", h, n_blocks, block_offsets);
+    if (rc != CLC_OK) return rc;
+  }
+  clc_options opt;
+  if (opt_in) opt = *opt_in; else clc_options_default(&opt);
+  {
+    // the options as clc_solve_batched checks them; a non-finite pose is not an error here: its row reports NaN / NaN / 0
+    const int rc = batched_check_inputs("clc_score_blocks", opt, poses, 0);
+    if (rc != CLC_OK) return rc;
+  }
+  CLC_HIP(hipSetDevice(h->device));
+  BatchedLaunch bl;
+  {
+    const int rc = batched_launch_setup(h, opt, &bl);
+    if (rc != CLC_OK) return rc;
+  }
+  if (!bl.resident)
+    return fail(CLC_ERR_INVALID_ARG, "clc_score_blocks: the problem is not held by one workgroup (clc_path_info.batched_resident == 0, or the "
+                                     "launch flags rule the resident kernel out): score the poses one by one with clc_factor_evaluate");
+  {
+    const int rc = ensure_lane_block_map("clc_score_blocks", h, n_blocks, block_offsets);
+    if (rc != CLC_OK) return rc;
+  }
+  const size_t cells = n_poses * n_blocks;
+  CLC_HIP(h->h_ms_poses.grow(7 * n_poses));
+  CLC_HIP(h->h_flow.grow(2 * cells + (cells + 1) / 2));  // [ssq | cost | inliers (int32)]
+  // (the previous call ended with a stream synchronisation: nothing still reads or writes the staging buffers)
+  std::memcpy(h->h_ms_poses, poses, sizeof(double) * 7 * n_poses);
+  double* const d_ssq = h->h_flow.dev();
+  double* const d_cost = d_ssq + cells;
+  int32_t* const d_inl = reinterpret_cast<int32_t*>(d_cost + cells);
+  const auto launch = [&](auto NL) {
+    hipLaunchKernelGGL(clc::block_scores_kernel<NL>, dim3((unsigned)n_poses), dim3(NL), 0, h->stream, h->bres.d_xy,
+                       h->bres.with_z ? h->bres.d_z.get() : nullptr, h->bres.d_desc, h->batch.d_groups, h->d_sub_lane_block, h->bres.max_ppl,
+                       (int)n_blocks, h->h_ms_poses.dev(), opt.loss_scale_factor, opt.use_loss != 0 ? 1 : 0, tau, ssq ? d_ssq : nullptr,
+                       cost ? d_cost : nullptr, inliers ? d_inl : nullptr);
+  };
+  if (h->bres.lanes == 256) launch(cint<256>); else launch(cint<512>);
+  CLC_HIP(hipGetLastError());
+  CLC_HIP(hipStreamSynchronize(h->stream));  // (kernel completion makes the tables written over PCIe visible)
+  const double* const o_ssq = h->h_flow;
+  if (ssq) std::memcpy(ssq, o_ssq, sizeof(double) * cells);
+  if (cost) std::memcpy(cost, o_ssq + cells, sizeof(double) * cells);
+  if (inliers) std::memcpy(inliers, o_ssq + 2 * cells, sizeof(int32_t) * cells);
+  return CLC_OK;
+}
+
 }  // extern "C"
+
+#ifdef CLC_TEST_HOOKS
+// Test hook: how many lane -> block maps this process has built (clc_solve_subsets and clc_score_blocks share one per offsets and upload).
+#pragma GCC visibility push(default)
+extern "C" int clc_debug_lane_map_builds(long long* count) {
+  if (!count) return fail(CLC_ERR_INVALID_ARG, "clc_debug_lane_map_builds: NULL count");
+  *count = g_lane_map_builds.load(std::memory_order_relaxed);
+  return CLC_OK;
+}
+#pragma GCC visibility pop
+#endif
 
 #if defined(CLC_STAMPS) && defined(CLC_TEST_HOOKS)
 // Debug build only (scripts/*_stamps.py): copy the stamp buffers of THIS unit's kernels out (and clear them).

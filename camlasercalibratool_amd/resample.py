@@ -1,5 +1,6 @@
 """Resampling over poses (pure numpy; needs no GPU): weight rows for Solver.solve_subsets / clc_solve_subsets, the definition of a
-weighted subset as a materialised problem, and the covariance estimates that the resampled solutions give.
+weighted subset as a materialised problem, the covariance estimates that the resampled solutions give, and the selection rule of the
+consensus calibration (consensus_select, on the block scores of Solver.score_blocks / clc_score_blocks).
 
 A weight row holds one unsigned 8-bit multiplicity per block of records (one block per pose): subset k is the problem in which every
 record of block b appears w[k, b] times.  Poses are [p(3), q(x, y, z, w)], as everywhere in this package; their differences are taken
@@ -85,3 +86,29 @@ def bootstrap_covariance(x_full, X) -> np.ndarray:
     S = D.shape[0]
     E = D - D.mean(axis=0)
     return (E.T @ E) / max(S - 1, 1)
+
+
+def consensus_select(ssq, rms_max: float):
+    """The consensus rule on a table of block scores ssq [S, B] (Solver.score_blocks: per candidate k and block b the sum of squared
+    residuals; with one block per pose and point rows, sqrt(ssq) is that pose's RMS point-to-plane distance).  Block b SUPPORTS
+    candidate k when sqrt(ssq[k, b]) <= rms_max (NaN supports nothing).  The candidate with the largest support wins; ties go to the
+    smaller sum of ssq over the supporting blocks, then to the lower index.
+    -> (best_index, inlier_mask [B] bool: the winner's supporting blocks, sizes [S]: every candidate's support).  No candidate has any
+    support (or S = 0): best_index = -1 and an all-False mask."""
+    q = np.asarray(ssq, dtype=np.float64)
+    if q.ndim != 2:
+        raise ValueError("ssq: [S, B]")
+    S, B = q.shape
+    with np.errstate(invalid="ignore"):
+        sup = np.sqrt(q) <= float(rms_max)   # (NaN, and the square root of a negative number, compare False)
+    sizes = sup.sum(axis=1).astype(np.int64)
+    if S == 0 or sizes.max() == 0:
+        return -1, np.zeros(B, dtype=bool), sizes
+    total = np.where(sup, q, 0.0).sum(axis=1)
+    best = -1
+    for k in range(S):   # (the documented order, written out: support, then sum, then index)
+        if sizes[k] == 0:
+            continue
+        if best < 0 or sizes[k] > sizes[best] or (sizes[k] == sizes[best] and total[k] < total[best]):
+            best = k
+    return int(best), sup[best].copy(), sizes

@@ -438,6 +438,24 @@ class Solver:
                                         w.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(poses), sm), "clc_solve_subsets")
         return poses, sm
 
+    def score_blocks(self, block_offsets: np.ndarray, poses: np.ndarray, tau: float, options: Optional[Options] = None):
+        """clc_score_blocks: S candidate poses [S, 7] judged against every block (block_offsets [B + 1], one block per recorded pose) of
+        the ONE problem uploaded as a batch of one -> (ssq [S, B] sum of squared residuals without the loss, cost [S, B] robust cost under
+        `options`, inliers [S, B] int32: records within tau of their plane).  One launch, a workgroup per pose, on the upload that
+        solve_multistart / solve_subsets use; a non-finite pose: NaN / NaN / 0 in its row."""
+        off = np.ascontiguousarray(block_offsets, dtype=np.int64).reshape(-1)
+        B = off.size - 1
+        x = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 7))
+        S = x.shape[0]
+        assert B >= 1 and S >= 1, "block_offsets: [B + 1], poses: [S, 7]"
+        ssq = np.empty((S, B))
+        cost = np.empty((S, B))
+        inl = np.empty((S, B), dtype=np.int32)
+        o = options or default_options()
+        check(self._L.clc_score_blocks(self._h, C.byref(o), B, off.ctypes.data_as(C.POINTER(C.c_int64)), S, dptr(x), C.c_double(tau),
+                                       dptr(ssq), dptr(cost), inl.ctypes.data_as(C.POINTER(C.c_int32))), "clc_score_blocks")
+        return ssq, cost, inl
+
     # ---- scan line fitting ----
     def line_fit_batched(self, xy: np.ndarray, offsets: np.ndarray, lines0: np.ndarray,
                          options: Optional[Options] = None, want_summaries: bool = True):

@@ -33,6 +33,7 @@
 #include <iostream>
 #include <string>
 #include <mutex>
+#include <random>
 #include <thread>
 #include <vector>
 
@@ -460,6 +461,125 @@ class Session {
             T(2, 0) = txz - twy;       T(2, 1) = tyz + twx;       T(2, 2) = 1 - (txx + tyy);
             T(0, 3) = q[0]; T(1, 3) = q[1]; T(2, 3) = q[2];
             T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+        }
+        ok_ = true;
+        return true;
+    }
+
+    // Calibration by consensus over the recorded observations (no counterpart in the reference): which recordings are bad, and the Tcl
+    // without them.  A whole scan can be consistently off by centimetres — its tag pose taken from the wrong camera frame
+    // (main/calibr_offline.cpp:102-116), its board segment cut wrongly — and the per-point Cauchy loss does not reject it.  On ONE
+    // upload: n_rows candidate calibrations, each from m of the observations (rows: n_rows x obs.size() weights of 0 / 1, or NULL:
+    // random m-of-P rows drawn here from std::mt19937(seed)), all started at Tcl (clc_solve_subsets, one launch); every candidate scored
+    // against every observation (clc_score_blocks, one launch); observation i SUPPORTS candidate k when the root of its sum of squared
+    // residuals — with point rows only its RMS point-to-plane distance — is at most rms_max; the candidate with the largest support wins
+    // (ties: the smaller sum over its supporting observations, then the lower index); one refit on the supporting observations only,
+    // started at the winner; the refit scored again.
+    // rms_max (metres) has no default: base it on the scanner's range noise (a few sigma).  A wrong recording must stand clear of it.
+    // m defaults to 5: the reference refuses fewer than 5 observations (main/calibr_offline.cpp:158).
+    // Tcl is in/out; a call that could not run, or in which no candidate found any support, returns false and leaves Tcl alone.
+    // inliers (obs.size()): 1 where the observation supports the result; rms (optional): per-observation RMS at the result;
+    // sizes (optional): the support of every candidate; best_row (optional): the winning row.
+    bool CalibrationConsensus(Eigen::Matrix4d& Tcl, double rms_max, std::vector<uint8_t>& inliers, size_t n_rows = 256, size_t m = 5,
+                              unsigned seed = 0, bool use_linefitting_data = true, bool use_boundary_constraint = false,
+                              const uint8_t* rows = NULL, std::vector<double>* rms = NULL, std::vector<int>* sizes = NULL,
+                              int* best_row = NULL, double* final_cost = NULL)
+    {
+        Handle H;
+        ok_ = false;
+        if (!H.h || n_rows == 0 || !(rms_max >= 0.0)) return false;
+        const Flat f = flatten(*obs_);
+        const int P = (int)(f.pts_off.size() - 1);
+        if (P <= 0 || (!rows && m > (size_t)P)) return false;
+        int64_t n_rec = 0;
+        if (clc_flatten_observations(P, f.tag_q.data(), f.tag_t.data(), f.pts_off.data(), f.pts, f.ptl_off.data(), f.ptl,
+                                     use_linefitting_data, use_boundary_constraint, NULL, &n_rec) != CLC_OK) {
+            std::cerr << "[clc] " << clc_last_error() << std::endl;
+            return false;
+        }
+        std::vector<clc_observation> rec((size_t)n_rec);
+        clc_flatten_observations(P, f.tag_q.data(), f.tag_t.data(), f.pts_off.data(), f.pts, f.ptl_off.data(), f.ptl,
+                                 use_linefitting_data, use_boundary_constraint, rec.data(), &n_rec);
+        // one block per observation: its point rows, then (board-edge terms on) its two edge rows
+        const std::vector<int64_t>& src = use_linefitting_data ? f.ptl_off : f.pts_off;
+        const int64_t extra = (use_boundary_constraint && use_linefitting_data) ? 2 : 0;
+        std::vector<int64_t> blocks((size_t)P + 1, 0);
+        for (int i = 0; i < P; ++i) blocks[(size_t)i + 1] = blocks[(size_t)i] + (src[(size_t)i + 1] - src[(size_t)i]) + extra;
+        std::vector<uint8_t> drawn;
+        if (!rows) {  // m of P without replacement per row: a partial Fisher-Yates shuffle
+            drawn.assign(n_rows * (size_t)P, 0);
+            std::mt19937 gen(seed);
+            std::vector<int> idx((size_t)P);
+            for (size_t k = 0; k < n_rows; ++k) {
+                for (int i = 0; i < P; ++i) idx[(size_t)i] = i;
+                for (size_t j = 0; j < m; ++j) {
+                    const size_t pick = j + (size_t)(gen() % (unsigned long)((size_t)P - j));
+                    std::swap(idx[j], idx[pick]);
+                    drawn[k * (size_t)P + (size_t)idx[j]] = 1;
+                }
+            }
+            rows = drawn.data();
+        }
+        double x0[7];
+        {
+            double R[9];
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[3 * i + j] = Tcl(i, j);
+            rot_to_quat_xyzw(R, x0 + 3);
+            for (int i = 0; i < 3; ++i) x0[i] = Tcl(i, 3);
+        }
+        std::vector<double> cands(7 * n_rows);
+        for (size_t k = 0; k < n_rows; ++k) for (int i = 0; i < 7; ++i) cands[7 * k + (size_t)i] = x0[i];
+        std::vector<clc_summary> sums(n_rows);
+        std::vector<double> ssq(n_rows * (size_t)P);
+        const int64_t off[2] = {0, n_rec};
+        clc_options opt; clc_options_default(&opt);
+        if (clc_upload_batched(H.h, rec.data(), off, 1) != CLC_OK ||
+            clc_solve_subsets(H.h, &opt, (size_t)P, blocks.data(), n_rows, rows, cands.data(), sums.data()) != CLC_OK ||
+            clc_score_blocks(H.h, &opt, (size_t)P, blocks.data(), n_rows, cands.data(), rms_max, ssq.data(), NULL, NULL) != CLC_OK) {
+            std::cerr << "[clc] " << clc_last_error() << std::endl;
+            return false;
+        }
+        // the selection rule (camlasercalibratool_amd/resample.py, consensus_select): support, then the sum over the support, then the index
+        int best = -1, best_size = 0;
+        double best_total = 0.0;
+        if (sizes) sizes->assign(n_rows, 0);
+        for (size_t k = 0; k < n_rows; ++k) {
+            int size = 0;
+            double total = 0.0;
+            for (int b = 0; b < P; ++b) {
+                const double q = ssq[k * (size_t)P + (size_t)b];
+                if (std::sqrt(q) <= rms_max) { ++size; total += q; }  // (NaN compares false)
+            }
+            if (sizes) (*sizes)[k] = size;
+            if (size > 0 && (best < 0 || size > best_size || (size == best_size && total < best_total))) {
+                best = (int)k; best_size = size; best_total = total;
+            }
+        }
+        if (best_row) *best_row = best;
+        inliers.assign((size_t)P, 0);
+        if (best < 0) return false;  // no candidate has any support: Tcl untouched
+        for (int b = 0; b < P; ++b) inliers[(size_t)b] = std::sqrt(ssq[(size_t)best * (size_t)P + (size_t)b]) <= rms_max ? 1 : 0;
+        double x[7];
+        for (int i = 0; i < 7; ++i) x[i] = cands[7 * (size_t)best + (size_t)i];
+        clc_summary sum;
+        std::vector<double> q1((size_t)P);
+        if (clc_solve_subsets(H.h, &opt, (size_t)P, blocks.data(), 1, inliers.data(), x, &sum) != CLC_OK ||
+            clc_score_blocks(H.h, &opt, (size_t)P, blocks.data(), 1, x, rms_max, q1.data(), NULL, NULL) != CLC_OK) {
+            std::cerr << "[clc] " << clc_last_error() << std::endl;
+            return false;
+        }
+        if (sum.termination == CLC_FAILURE) return false;
+        if (final_cost) *final_cost = sum.final_cost;
+        if (rms) { rms->resize((size_t)P); for (int b = 0; b < P; ++b) (*rms)[(size_t)b] = std::sqrt(q1[(size_t)b]); }
+        {
+            const double qx = x[3], qy = x[4], qz = x[5], qw = x[6];
+            const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz, twx = tx * qw, twy = ty * qw, twz = tz * qw;
+            const double txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+            Tcl(0, 0) = 1 - (tyy + tzz); Tcl(0, 1) = txy - twz;       Tcl(0, 2) = txz + twy;
+            Tcl(1, 0) = txy + twz;       Tcl(1, 1) = 1 - (txx + tzz); Tcl(1, 2) = tyz - twx;
+            Tcl(2, 0) = txz - twy;       Tcl(2, 1) = tyz + twx;       Tcl(2, 2) = 1 - (txx + tyy);
+            Tcl(0, 3) = x[0]; Tcl(1, 3) = x[1]; Tcl(2, 3) = x[2];
+            Tcl(3, 0) = 0; Tcl(3, 1) = 0; Tcl(3, 2) = 0; Tcl(3, 3) = 1;
         }
         ok_ = true;
         return true;

@@ -474,6 +474,25 @@ int clc_solve_multistart(clc_handle* h, const clc_options* opt, size_t n_starts,
 int clc_solve_subsets(clc_handle* h, const clc_options* opt, size_t n_blocks, const int64_t* block_offsets, size_t n_subsets,
                       const uint8_t* weights, double* poses_inout, clc_summary* summaries);
 
+/* Consensus scores on SHARED observations: n_poses candidate poses, each judged against EVERY block of the ONE problem the handle holds
+ * as a batch of one (blocks as in clc_solve_subsets: one per recorded pose) — what a RANSAC / least-median step over recordings needs,
+ * where clc_solve_subsets reports a subset's own total only.  Per pose k and block b, at index k * n_blocks + b (each table nullable):
+ *   ssq      sum of r^2 over the block's records, r = scale * (n.(R p + t) + d) the factor's residual, no loss (one block per pose,
+ *            point rows only: that pose's mean squared point-to-plane distance, scale^2 being 1 / count)
+ *   cost     1/2 sum rho(r^2) under opt's loss (Cauchy, loss_scale_factor * scale per record, as the solves; use_loss = 0: ssq / 2)
+ *   inliers  records with |n.(R p + t) + d| <= tau (the plane expression before the scale: metres for unit normals)
+ * ONE launch, a workgroup per pose on the one on-chip layout, one evaluation pass; sums in a fixed order (two calls return the same
+ * bits, and the sum over b agrees with clc_eval / clc_information to rounding).  The layout, the observations and what clc_solve_multistart /
+ * clc_solve_subsets return afterwards are unchanged; the lane -> block map is the one clc_solve_subsets keeps (built once per offsets
+ * and upload, by whichever call comes first).
+ * Errors as clc_solve_subsets: CLC_ERR_NO_DATA unless a batch of one is uploaded; CLC_ERR_INVALID_ARG for bad offsets, a block boundary
+ * inside a scan, tau = NaN, loss_scale_factor <= 0 with use_loss, or a problem that one workgroup does not hold
+ * (clc_path_info.batched_resident == 0).  A pose with a non-finite entry does not fail the call: its row is NaN / NaN / 0.  A block
+ * without records scores 0 / 0 / 0. */
+int clc_score_blocks(clc_handle* h, const clc_options* opt, size_t n_blocks, const int64_t* block_offsets, size_t n_poses,
+                     const double* poses /* n_poses x 7 */, double tau,
+                     double* ssq, double* cost, int32_t* inliers /* each n_poses x n_blocks, each nullable */);
+
 /* ---- multi-GPU: sharded batches + RCCL gather ------------------------------------------------
  * BASELINE.json configs[3]: independent T_cl problems shard across the GPUs of a node, one process
  * per GPU, no collective on the data path; the fixed-size result records of all ranks are gathered
