@@ -350,7 +350,13 @@ size_t clc_num_problems(const clc_handle* h);
  * lines[2*n_scans] is in/out = (m0, m1) of the line m0 x + m1 y + 1 = 0: initial guess in (:403),
  * result out (:430-431).  Residual m0 x + m1 y + 1 (:391), CauchyLoss(opt->loss_scale_factor) per
  * point (:416), the same Ceres LM semantics as clc_solve.  clc_line_options_default() = Ceres
- * defaults with max_num_iterations = 10 and loss 0.05 (:416,:424-425).  summaries nullable. */
+ * defaults with max_num_iterations = 10 and loss 0.05 (:416,:424-425).  summaries nullable.
+ * A scan with a non-finite point has a non-finite cost at iteration 0: as in Ceres that scan ends
+ * with termination = CLC_FAILURE and its line left as it was.  The call still returns CLC_OK, and
+ * every other scan, the three that share its wavefront included, gets the bits it gets without
+ * that scan.  Refused with CLC_ERR_INVALID_ARG: opt->use_loss with loss_scale_factor <= 0 or NaN,
+ * max_num_iterations < 0, offsets that decrease.  Refused with CLC_ERR_NONFINITE: a non-finite
+ * start line. */
 void clc_line_options_default(clc_options* opt);
 int clc_line_fit_batched(clc_handle* h, const clc_options* opt, const double* xy, const int64_t* offsets,
                          size_t n_scans, double* lines, clc_summary* summaries);

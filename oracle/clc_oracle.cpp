@@ -560,6 +560,14 @@ static int lm_minimize(const LmProblem& pb, const oracle_options* opt, double* x
   it.iteration = 0;
   evaluate_gradient_and_jacobian(true);
   summary->initial_cost = x_cost;
+  if (!std::isfinite(x_cost)) {
+    // Ceres: a non-finite residual makes the evaluation fail, IterationZero returns false and the solve ends with FAILURE
+    // ("initial residual and Jacobian evaluation failed") before any step: the parameters stay as they were.
+    summary->termination = ORACLE_FAILURE;
+    summary->num_iterations = 0;
+    summary->final_cost = x_cost;
+    return ORACLE_FAILURE;
+  }
   it.step_is_valid = 1;
   it.step_is_successful = 1;
   min_iter_cost = x_cost;
