@@ -37,6 +37,8 @@ EXPORTED = [
     "clc_closed_form_batched", "clc_information_batched",
     "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
     "clc_solve_subsets", "clc_score_blocks",
+    "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
+    "clc_stored_observations",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -45,7 +47,7 @@ HOOKS = [
     "clc_debug_wave_split", "clc_debug_resident", "clc_debug_resident_single", "clc_debug_coop", "clc_debug_coop_control",
     "clc_debug_coop_set_tag", "clc_debug_layout", "clc_debug_lm_profile", "clc_time_steps", "clc_time_batched_eval", "clc_time_eval",
     "clc_debug_comm_create_layout", "clc_debug_single_controller", "clc_debug_fast_small",
-    "clc_debug_lane_map_builds",
+    "clc_debug_lane_map_builds", "clc_debug_assemble_lines",
 ]
 
 
@@ -119,6 +121,21 @@ class PathInfo(C.Structure):
                                          "coop_points_carry_z", "coop_resting", "coop_timeouts", "batched_resident", "batched_lanes", "batched_points_per_lane",
                                          "rows_layout", "batched_rows_layout", "coop_workgroups", "batched_points_carry_z", "reserved_")] + \
                [(n, C.c_int64) for n in ("coop_solves", "batched_lane_rows", "n_rows", "batched_n_rows", "coop_gate_waits_expired")]
+
+
+class AssembleOptions(C.Structure):
+    """clc_assemble_options (include/clc.h)."""
+    _fields_ = [("keyframe_dist_min", C.c_double), ("keyframe_theta_min", C.c_double), ("max_dt", C.c_double), ("line0", C.c_double * 2),
+                ("line", Options)]
+
+
+class AssembleInfo(C.Structure):
+    """clc_assemble_info (include/clc.h)."""
+    _fields_ = [(n, C.c_int64) for n in ("n_keyframes", "n_segments", "n_ref_throws", "n_unmatched", "n_observations", "n_points",
+                                         "n_line_points")]
+
+
+SCAN_NO_SEGMENT, SCAN_REF_THROWS, SCAN_NO_POSE = -1, -2, -3  # CLC_SCAN_*
 
 
 class ClcError(RuntimeError):
@@ -208,6 +225,13 @@ def load(path: str):
         L.clc_information_batched.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double),
                                               P(C.c_double), P(C.c_int32)]
         L.clc_information_batched.restype = C.c_int
+        V = C.c_void_p
+        L.clc_assemble_options_default.argtypes = [V]
+        L.clc_assemble_options_default.restype = None
+        L.clc_keyframes.argtypes = [V, V, C.c_size_t, V, V, V, V]
+        L.clc_assemble_observations.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V]
+        L.clc_assemble_observations_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V]
+        L.clc_stored_observations.argtypes = [V, V, V, V, V, V, V, V]
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -259,6 +283,13 @@ def default_pose_options() -> Options:
     """clc_pose_options_default: no loss, tolerances tight enough for the float32-rounding floor of the lifted corners."""
     o = Options()
     lib().clc_pose_options_default(C.byref(o))
+    return o
+
+
+def default_assemble_options() -> AssembleOptions:
+    """The reference's settings, main/calibr_offline.cpp:66-67,:116: 0.20 m, 10 degrees (with pi = 3.1415926), 20 ms; line fits from (0, 0)."""
+    o = AssembleOptions()
+    lib().clc_assemble_options_default(C.byref(o))
     return o
 
 

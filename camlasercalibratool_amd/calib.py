@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import simdata
-from ._capi import Options, TERMINATION, default_line_options, default_options
+from ._capi import AssembleOptions, ClcError, Options, TERMINATION, default_line_options, default_options
 from .simdata import Oberserve, ObservationSet
 from .solver import SolveResult, Solver, flatten_observations
 
@@ -55,10 +55,24 @@ class Session:
     main/calibr_offline.cpp:166-170 — then select their residual blocks on the device (clc_select_observations) instead
     of re-flattening and re-uploading 64-byte records per call.  The module-level functions below are one-call sessions."""
 
-    def __init__(self, obs: ObsLike, solver: Optional[Solver] = None):
-        self.S = _as_set(obs)
+    def __init__(self, obs: Optional[ObsLike], solver: Optional[Solver] = None):
+        """obs None: adopt the scans the solver's handle already holds (Solver.assemble_observations built them on the device) — no
+        host copy is kept and nothing is uploaded; see Session.adopt."""
         self.sv = solver or _shared_solver()
-        self._store()
+        if obs is None:
+            self.S = None
+            self._generation = self.sv.store_generation
+            if self._generation <= 0:
+                raise ClcError(-5, "Session", "no scans stored on the solver's handle to adopt")
+        else:
+            self.S = _as_set(obs)
+            self._store()
+
+    @classmethod
+    def adopt(cls, solver: Solver) -> "Session":
+        """A session on the scans `solver` holds right now.  It keeps no host copy, so it cannot put them back: once another caller
+        has replaced the stored scans every call of the session raises ClcError instead of solving somebody else's data."""
+        return cls(None, solver)
 
     def _store(self):
         self.sv.store_observations(self.S)
@@ -68,6 +82,9 @@ class Session:
         """The stored scans belong to the (possibly shared) solver handle: if somebody else — another Session, one of the
         module-level calls below — stored theirs since, put ours back before selecting from them."""
         if self.sv.store_generation != self._generation:
+            if self.S is None:
+                raise ClcError(-5, "Session", "the scans this session adopted were replaced on the solver's handle (store generation "
+                               f"{self._generation} -> {self.sv.store_generation}); it keeps no host copy to put back")
             self._store()
 
     def CamLaserCalClosedSolution(self, Tlc: np.ndarray, verbose: bool = True):
@@ -291,6 +308,39 @@ def CamLaserCalibration(obs: ObsLike, Tcl: np.ndarray, use_linefitting_data: boo
                         solver: Optional[Solver] = None, verbose: bool = True) -> CalibrationReport:
     """Nonlinear refinement; Tcl (laser->camera) is in/out like LaseCamCalCeres.cpp:215,:311-314."""
     return Session(obs, solver).CamLaserCalibration(Tcl, use_linefitting_data, use_boundary_constraint, options, verbose)
+
+
+def CalibrateOffline(pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, assemble_options: Optional[AssembleOptions] = None,
+                     options: Optional[Options] = None, solver: Optional[Solver] = None, verbose: bool = True):
+    """The offline node, main/calibr_offline.cpp:51-175, from its two inputs: the stamped tag poses of apriltag_pose.txt (pose_stamp
+    [n], q_wc [n, 4] (w, x, y, z), t_wc [n, 3]) and the laser scans (`scans` as simdata.sim_laser_scans returns them, scan_stamp [S]).
+    Key frames, board segments, scan -> pose matching, line fits and the Oberserve records are built on the device
+    (Solver.assemble_observations) and stay there; then the closed form on points_on_line (:167), Tcl = inv(Tlc) (:169) and
+    CamLaserCalibration(obs, Tcl, false) with its analysis pass (:170).
+    Returns None under the reference's gates — fewer than 10 poses (:56), fewer than 5 observations (:158) — otherwise
+    {"Tlc_initial", "Tcl", "Tlc" [4, 4], "report" (CalibrationReport), "info" (AssembleInfo), "scan_pose" [S], "session"}."""
+    if len(np.asarray(pose_stamp).reshape(-1)) < 10:
+        if verbose:
+            print("apriltag pose less than 10.")
+        return None
+    sv = solver or _shared_solver()
+    info, scan_pose = sv.assemble_observations(pose_stamp, q_wc, t_wc, scans, scan_stamp, assemble_options)
+    if info.n_observations < 5:
+        if verbose:
+            print("Valid Calibra Data Less")
+        return None
+    if verbose:
+        print("obs size: ", info.n_observations)
+    ses = Session.adopt(sv)
+    Tlc0 = np.eye(4)
+    ses.CamLaserCalClosedSolution(Tlc0, verbose)
+    Tcl = np.linalg.inv(Tlc0)
+    report = ses.CamLaserCalibration(Tcl, False, False, options, verbose)
+    Tlc = np.linalg.inv(Tcl)
+    if verbose:
+        print("\n----- Transform from Camera to Laser Tlc is: -----\n")
+        print(Tlc)
+    return {"Tlc_initial": Tlc0, "Tcl": Tcl, "Tlc": Tlc, "report": report, "info": info, "scan_pose": scan_pose, "session": ses}
 
 
 def LineFittingCeres(Points: np.ndarray, Line: np.ndarray, solver: Optional[Solver] = None,

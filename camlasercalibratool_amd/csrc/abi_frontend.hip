@@ -1,8 +1,10 @@
 // abi_frontend.hip — the calls either side of the solve: factor evaluation, manifold plus, information matrix and closed form, line fitting, scan conversion,
-// board-segment detection.
+// board-segment detection, assembly of the offline flow's observations (K13).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 #include "clc_scanseg.hpp"
+#include "clc_assemble.hpp"
+#include "abi_assemble.hpp"
 
 using namespace clc_abi;
 
@@ -227,6 +229,25 @@ int clc_scan_to_points(clc_handle* h, const float* ranges, const int64_t* offset
   return CLC_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// K6 on device arrays, enqueued on the handle's stream (no wait)
+void launch_line_fit(clc_handle* h, const clc_options& opt, const double* xy_dev, const long long* d_off, size_t n_scans, double* lines_dev,
+                     clc_summary* summaries_dev) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
+  const unsigned blocks = (unsigned)((n_scans + clc::LINE_SCANS_PER_BLOCK - 1) / clc::LINE_SCANS_PER_BLOCK);
+  if (opt.use_loss)
+    hipLaunchKernelGGL((clc::line_fit_kernel<true>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
+                       (int)n_scans, opt, lines_dev, summaries_dev);
+  else
+    hipLaunchKernelGGL((clc::line_fit_kernel<false>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
+                       (int)n_scans, opt, lines_dev, summaries_dev);
+}
+}  // namespace
+
+extern "C" {
+
 int clc_line_fit_batched_device(clc_handle* h, const clc_options* opt_in, const double* xy_dev, const int64_t* offsets_dev,
                                 size_t n_scans, double* lines_dev, clc_summary* summaries_dev) {
   if (!h || (n_scans > 0 && (!offsets_dev || !lines_dev || !xy_dev)))
@@ -239,15 +260,7 @@ int clc_line_fit_batched_device(clc_handle* h, const clc_options* opt_in, const 
   if (n_scans == 0) return CLC_OK;
   if (n_scans > 0x7FFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched_device: too many scans");
   CLC_HIP(hipSetDevice(h->device));
-  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
-  const unsigned blocks = (unsigned)((n_scans + clc::LINE_SCANS_PER_BLOCK - 1) / clc::LINE_SCANS_PER_BLOCK);
-  const long long* d_off = reinterpret_cast<const long long*>(offsets_dev);
-  if (opt.use_loss)
-    hipLaunchKernelGGL((clc::line_fit_kernel<true>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
-                       (int)n_scans, opt, lines_dev, summaries_dev);
-  else
-    hipLaunchKernelGGL((clc::line_fit_kernel<false>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
-                       (int)n_scans, opt, lines_dev, summaries_dev);
+  launch_line_fit(h, opt, xy_dev, reinterpret_cast<const long long*>(offsets_dev), n_scans, lines_dev, summaries_dev);
   CLC_HIP(hipGetLastError());
   CLC_HIP(hipStreamSynchronize(h->stream));
   return CLC_OK;
@@ -331,3 +344,249 @@ int clc_board_segments_device(clc_handle* h, const double* points_dev, const int
 }
 
 }  // extern "C"
+
+// ---- the offline flow's observations (K13, clc_assemble.hpp) ----------------------------------------------------------------------
+namespace {
+
+#ifdef CLC_TEST_HOOKS
+std::vector<double> g_last_lines;  // (m0, m1) per observation of the last assembly in this process (hooks build only)
+#endif
+
+int check_assemble_options(const char* who, const clc_assemble_options* in, clc_assemble_options* opt) {
+  if (in) *opt = *in; else clc_assemble_options_default(opt);
+  if (opt->line.max_num_iterations < 0 || (opt->line.use_loss && !(opt->line.loss_scale_factor > 0.0))) return fail(CLC_ERR_INVALID_ARG, who);
+  if (!std::isfinite(opt->line0[0]) || !std::isfinite(opt->line0[1])) return fail(CLC_ERR_NONFINITE, who);
+  return CLC_OK;
+}
+
+// Every array in device memory; host_scan_pose (nullable): where scan_pose is copied to on the host.  The kernels run at sizes
+// the host knows — n_scans, n_rays — and learn the number of observations from the counters on the device: workgroups and rows
+// behind it leave at once, so nothing is read back before the ONE wait at the end.
+int assemble_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_poses, const double* d_stamp, const double* d_q,
+                       const double* d_t, const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am,
+                       const float* d_ai, const float* d_rm, const double* d_sstamp, int32_t* d_scan_pose, int32_t* host_scan_pose,
+                       clc_assemble_info* info) {
+  const size_t cap_points = std::min(n_rays, S * (size_t)clc::ASM_SEG_MAX_POINTS);
+  h->store_poses = -1;
+  // the handle's pose-major arrays at what S scans can need at most (the number of observations is not known on the host yet)
+  CLC_HIP(h->d_sq.grow(std::max<size_t>(S * 4, 1)));
+  CLC_HIP(h->d_st.grow(std::max<size_t>(S * 3, 1)));
+  CLC_HIP(h->d_spts.grow(std::max<size_t>(cap_points * 3, 1)));
+  CLC_HIP(h->d_sptl.grow(std::max<size_t>(S * 6, 1)));
+  CLC_HIP(h->d_soff.grow(3 * (S + 1)));
+  DevBuf<long long> cnt(&h->pool), seg(&h->pool), obs_scan(&h->pool), fit_off(&h->pool);
+  DevBuf<unsigned char> keep(&h->pool);
+  DevBuf<int> kf(&h->pool), status(&h->pool), spose(&h->pool);
+  DevBuf<double> points(&h->pool), xy(&h->pool), lines(&h->pool);
+  CLC_HIP(cnt.alloc(clc::ASM_COUNTERS)); CLC_HIP(seg.alloc(2 * S)); CLC_HIP(obs_scan.alloc(S)); CLC_HIP(fit_off.alloc(S + 1));
+  CLC_HIP(keep.alloc(n_poses)); CLC_HIP(kf.alloc(n_poses)); CLC_HIP(status.alloc(S));
+  if (!d_scan_pose) { CLC_HIP(spose.alloc(S)); d_scan_pose = spose.p; }
+  CLC_HIP(points.alloc(3 * n_rays)); CLC_HIP(xy.alloc(2 * cap_points)); CLC_HIP(lines.alloc(2 * S));
+  const long long* off = reinterpret_cast<const long long*>(d_off);
+  long long* soff = h->d_soff;
+  CLC_HIP(hipMemsetAsync(cnt.p, 0, clc::ASM_COUNTERS * sizeof(long long), h->stream));
+  hipLaunchKernelGGL(clc::keyframe_kernel, dim3(1), dim3(64), 0, h->stream, d_q, d_t, d_stamp, (long long)n_poses, opt.keyframe_dist_min,
+                     opt.keyframe_theta_min, keep.p, kf.p, cnt.p);
+  CLC_HIP(hipGetLastError());
+  const int threads = 256;
+  if (S > 0) {
+    if (n_rays > 0) {
+      hipLaunchKernelGGL(clc::scan_to_points_flat_kernel, dim3((unsigned)((n_rays + threads - 1) / threads)), dim3(threads), 0, h->stream,
+                         d_ranges, off, (long long)S, (long long)n_rays, d_am, d_ai, d_rm, points.p);
+      CLC_HIP(hipGetLastError());
+    }
+    launch_board_segments(h, points.p, d_off, S, reinterpret_cast<int64_t*>(seg.p), status.p);
+    CLC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(clc::associate_kernel, dim3((unsigned)((S + threads - 1) / threads)), dim3(threads), 0, h->stream, status.p, d_sstamp,
+                       (long long)S, d_stamp, kf.p, cnt.p, opt.max_dt, d_scan_pose);
+    CLC_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(clc::compact_kernel, dim3(1), dim3(clc::ASM_SCAN_BLOCK), 0, h->stream, d_scan_pose, seg.p, (long long)S,
+                     (long long)cap_points, obs_scan.p, fit_off.p, soff, cnt.p);
+  CLC_HIP(hipGetLastError());
+  if (S > 0) {
+    hipLaunchKernelGGL(clc::gather_kernel, dim3((unsigned)S), dim3(256), 0, h->stream, points.p, off, seg.p, d_scan_pose, obs_scan.p, fit_off.p,
+                       cnt.p, d_q, d_t, opt.line0[0], opt.line0[1], h->d_spts.get(), xy.p, lines.p, h->d_sq.get(), h->d_st.get());
+    CLC_HIP(hipGetLastError());
+    launch_line_fit(h, opt.line, xy.p, fit_off.p, S, lines.p, nullptr);  // rows behind the observations are empty scans
+    CLC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(clc::endpoints_kernel, dim3((unsigned)((S + threads - 1) / threads)), dim3(threads), 0, h->stream, h->d_spts.get(), soff,
+                       cnt.p, lines.p, h->d_sptl.get());
+    CLC_HIP(hipGetLastError());
+  }
+  // what comes back: the counters, the packed offsets, the tag poses a reference-size store keeps on the host
+  long long c[clc::ASM_COUNTERS];
+  std::vector<long long> hoff(2 * (S + 1));
+  const size_t n_small = std::min<size_t>(S, 4096);
+  std::vector<double> tq(4 * n_small + 1), tt(3 * n_small + 1);
+  CLC_HIP(hipMemcpyAsync(c, cnt.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(hoff.data(), soff, hoff.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  if (n_small > 0) {
+    CLC_HIP(hipMemcpyAsync(tq.data(), h->d_sq.get(), 4 * n_small * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CLC_HIP(hipMemcpyAsync(tt.data(), h->d_st.get(), 3 * n_small * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (host_scan_pose && S > 0) CLC_HIP(hipMemcpyAsync(host_scan_pose, d_scan_pose, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (c[clc::ASM_OVERFLOW] != 0) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: the segments hold more points than the scans");
+  const size_t P = (size_t)c[clc::ASM_N_OBS];
+#ifdef CLC_TEST_HOOKS
+  g_last_lines.assign(2 * P, 0.0);  // test hook: the lines the end points were computed from (clc_debug_assemble_lines)
+  if (P > 0) CLC_HIP(hipMemcpy(g_last_lines.data(), lines.p, 2 * P * sizeof(double), hipMemcpyDeviceToHost));
+#endif
+  h->s_pts_off.assign(hoff.begin(), hoff.begin() + (P + 1));
+  h->s_ptl_off.assign(hoff.begin() + (P + 1), hoff.begin() + 2 * (P + 1));
+  StoreFacts f;  // scan points have z = 0 (TranScanToPoints), the points on the line too; points_on_line is never the points
+  f.tag_q = tq.data();
+  f.tag_t = tt.data();
+  const int rc = adopt_store(h, (int)P, f);
+  if (rc != CLC_OK) return rc;
+  if (info) {
+    info->n_keyframes = c[clc::ASM_N_KEYFRAMES];
+    info->n_segments = c[clc::ASM_N_SEGMENTS];
+    info->n_ref_throws = c[clc::ASM_N_REF_THROWS];
+    info->n_unmatched = c[clc::ASM_N_UNMATCHED];
+    info->n_observations = c[clc::ASM_N_OBS];
+    info->n_points = c[clc::ASM_N_POINTS];
+    info->n_line_points = c[clc::ASM_N_LINE_POINTS];
+  }
+  return CLC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void clc_assemble_options_default(clc_assemble_options* o) {
+  if (!o) return;
+  o->keyframe_dist_min = 0.20;                     // main/calibr_offline.cpp:66
+  o->keyframe_theta_min = 3.1415926 * 10 / 180.;   // :67
+  o->max_dt = 0.02;                                // :116
+  o->line0[0] = o->line0[1] = 0.0;
+  clc_line_options_default(&o->line);
+}
+
+int clc_keyframes(clc_handle* h, const clc_assemble_options* opt_in, size_t n_poses, const double* q_wc_wxyz, const double* t_wc,
+                  uint8_t* keep, int64_t* n_kept) {
+  if (!h || (n_poses > 0 && (!q_wc_wxyz || !t_wc)) || n_poses > 0x7FFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_keyframes: bad argument");
+  clc_assemble_options opt;
+  int rc = check_assemble_options("clc_keyframes: bad options", opt_in, &opt);
+  if (rc != CLC_OK) return rc;
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bq(&h->pool), bt(&h->pool);
+  DevBuf<unsigned char> bkeep(&h->pool);
+  DevBuf<int> bkf(&h->pool);
+  DevBuf<long long> bcnt(&h->pool);
+  CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bkeep.alloc(n_poses)); CLC_HIP(bkf.alloc(n_poses));
+  CLC_HIP(bcnt.alloc(clc::ASM_COUNTERS));
+  if (n_poses > 0) {
+    CLC_HIP(hipMemcpyAsync(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CLC_HIP(hipMemcpyAsync(bt.p, t_wc, 3 * n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  hipLaunchKernelGGL(clc::keyframe_kernel, dim3(1), dim3(64), 0, h->stream, bq.p, bt.p, (const double*)nullptr, (long long)n_poses,
+                     opt.keyframe_dist_min, opt.keyframe_theta_min, bkeep.p, bkf.p, bcnt.p);
+  CLC_HIP(hipGetLastError());
+  long long c[2] = {0, 0};
+  CLC_HIP(hipMemcpyAsync(c, bcnt.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  if (keep && n_poses > 0) CLC_HIP(hipMemcpyAsync(keep, bkeep.p, n_poses, hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (n_kept) *n_kept = c[clc::ASM_N_KEYFRAMES];
+  return CLC_OK;
+}
+
+int clc_assemble_observations_device(clc_handle* h, const clc_assemble_options* opt_in, size_t n_poses, const double* pose_stamp_dev,
+                                     const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev,
+                                     const int64_t* offsets_dev, size_t n_scans, size_t n_rays, const float* angle_min_dev,
+                                     const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
+                                     int32_t* scan_pose_dev, clc_assemble_info* info) {
+  if (!h || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
+      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
+      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations_device: bad argument");
+  clc_assemble_options opt;
+  const int rc = check_assemble_options("clc_assemble_observations_device: bad options", opt_in, &opt);
+  if (rc != CLC_OK) return rc;
+  CLC_HIP(hipSetDevice(h->device));
+  return assemble_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays, angle_min_dev,
+                            angle_increment_dev, range_min_dev, scan_stamp_dev, scan_pose_dev, nullptr, info);
+}
+
+int clc_assemble_observations(clc_handle* h, const clc_assemble_options* opt_in, size_t n_poses, const double* pose_stamp,
+                              const double* q_wc_wxyz, const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans,
+                              const float* angle_min, const float* angle_increment, const float* range_min, const double* scan_stamp,
+                              int32_t* scan_pose, clc_assemble_info* info) {
+  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
+      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
+      n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: bad argument");
+  clc_assemble_options opt;
+  const int rc = check_assemble_options("clc_assemble_observations: bad options", opt_in, &opt);
+  if (rc != CLC_OK) return rc;
+  if (n_scans > 0 && offsets[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: negative offset");
+  std::vector<long long> rel(n_scans + 1, 0);
+  for (size_t k = 0; k < n_scans; ++k) {
+    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: offsets not monotone");
+    if (offsets[k + 1] - offsets[k] > 0x7FFFFFFF) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: a scan has 2^31 rays or more");
+    rel[k + 1] = offsets[k + 1] - offsets[0];
+  }
+  const size_t n_rays = (size_t)rel[n_scans];
+  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: NULL ranges");
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
+  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
+  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
+  CLC_HIP(boff.alloc(n_scans + 1));
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
+  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
+  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
+  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
+  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
+  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
+  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
+  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
+  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
+  return assemble_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p, bai.p,
+                            brm.p, bss.p, nullptr, scan_pose, info);
+}
+
+int clc_stored_observations(clc_handle* h, int* n_poses, double* tag_q_wxyz, double* tag_t, int64_t* pts_off, double* pts,
+                            int64_t* ptl_off, double* ptl) {
+  if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_stored_observations: NULL handle");
+  if (h->store_poses < 0) return fail(CLC_ERR_NO_DATA, "clc_stored_observations: no scans stored");
+  const size_t P = (size_t)h->store_poses;
+  if (n_poses) *n_poses = h->store_poses;
+  const size_t M = (size_t)h->s_pts_off[P], ML = (size_t)h->s_ptl_off[P];
+  if (pts_off) for (size_t i = 0; i <= P; ++i) pts_off[i] = h->s_pts_off[i];
+  if (ptl_off) for (size_t i = 0; i <= P; ++i) ptl_off[i] = h->s_ptl_off[i];
+  CLC_HIP(hipSetDevice(h->device));
+  auto down = [&](void* dst, const double* src, size_t count) {
+    return (!dst || count == 0) ? hipSuccess : hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  };
+  CLC_HIP(down(tag_q_wxyz, h->d_sq.get(), 4 * P));
+  CLC_HIP(down(tag_t, h->d_st.get(), 3 * P));
+  CLC_HIP(down(pts, h->d_spts.get(), 3 * M));
+  CLC_HIP(down(ptl, h->d_sptl.get(), 3 * ML));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+}  // extern "C"
+
+#ifdef CLC_TEST_HOOKS
+#pragma GCC visibility push(default)
+// test hook: the fitted lines (m0, m1 per observation) of the last clc_assemble_observations[_device] of this process
+extern "C" int clc_debug_assemble_lines(double* lines_out, int64_t cap_lines, int64_t* n_lines) {
+  if (!n_lines) return fail(CLC_ERR_INVALID_ARG, "clc_debug_assemble_lines: bad argument");
+  *n_lines = (int64_t)(g_last_lines.size() / 2);
+  if (lines_out) {
+    if (cap_lines < *n_lines) return fail(CLC_ERR_INVALID_ARG, "clc_debug_assemble_lines: buffer too small");
+    std::memcpy(lines_out, g_last_lines.data(), g_last_lines.size() * sizeof(double));
+  }
+  return CLC_OK;
+}
+#pragma GCC visibility pop
+#endif  // CLC_TEST_HOOKS

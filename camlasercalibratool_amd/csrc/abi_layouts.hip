@@ -1,6 +1,7 @@
 // abi_layouts.hip — the upload paths: staged records -> 64-byte tiles, scan structure, compact / row / lane layouts; stored scans.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "clc_abi_internal.hpp"
+#include "abi_assemble.hpp"
 
 using namespace clc_abi;
 
@@ -575,6 +576,24 @@ int selection_offsets(const clc_handle* h, bool linefit, bool boundary, std::vec
 }  // namespace
 
 namespace clc_abi {
+int adopt_store(clc_handle* h, int n_poses, const StoreFacts& f) {
+  const size_t P = (size_t)n_poses;
+  const size_t M = (size_t)h->s_pts_off[P], ML = (size_t)h->s_ptl_off[P];
+  h->store_small = store_is_reference_size(P, M, ML);
+  if (h->store_small) {
+    h->s_tag_q.assign(f.tag_q, f.tag_q + 4 * P);
+    h->s_tag_t.assign(f.tag_t, f.tag_t + 3 * P);
+    h->s_any_z_pts = f.any_z_pts;
+    h->s_any_z_ptl = f.any_z_ptl;
+    h->s_any_z_ends = f.any_z_ends;
+  }
+  h->store_lines_equal_points = f.lines_equal_points;
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  h->store_poses = n_poses;
+  h->store_generation++;
+  return CLC_OK;
+}
+
 // builds the records of the selection on the device into *aos (allocated here)
 int flatten_on_device(clc_handle* h, bool linefit, bool boundary, DevBuf<double>* aos, long long* n_out) {
   if (h->store_poses < 0) return fail(CLC_ERR_NO_DATA, "clc_select_observations: no scans stored (clc_store_observations)");
@@ -636,25 +655,21 @@ int clc_store_observations(clc_handle* h, int n_poses, const double* tag_q_wxyz,
   if (M > 0) CLC_HIP(hipMemcpyAsync(h->d_spts, pts + 3 * pts_off[0], M * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (ML > 0) CLC_HIP(hipMemcpyAsync(h->d_sptl, ptl + 3 * ptl_off[0], ML * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   // reference-size scans: the host keeps what it needs to plan a selection's layouts itself (tag poses, whether any z is non-zero)
-  h->store_small = P > 0 && P <= 4096 && M <= 16384 && ML <= 16384;
-  if (h->store_small) {
-    h->s_tag_q.assign(tag_q_wxyz, tag_q_wxyz + 4 * P);
-    h->s_tag_t.assign(tag_t, tag_t + 3 * P);
+  StoreFacts f;
+  if (store_is_reference_size(P, M, ML)) {
+    f.tag_q = tag_q_wxyz;
+    f.tag_t = tag_t;
     auto any_z = [](const double* p, size_t count) { for (size_t k = 0; k < count; ++k) if (p[3 * k + 2] != 0.0) return true; return false; };
-    h->s_any_z_pts = M > 0 && any_z(pts + 3 * pts_off[0], M);
-    h->s_any_z_ptl = ML > 0 && any_z(ptl + 3 * ptl_off[0], ML);
-    h->s_any_z_ends = false;
+    f.any_z_pts = M > 0 && any_z(pts + 3 * pts_off[0], M);
+    f.any_z_ptl = ML > 0 && any_z(ptl + 3 * ptl_off[0], ML);
     for (size_t i = 0; i < P; ++i)
-      if (pts_off[i + 1] > pts_off[i] && (pts[3 * pts_off[i] + 2] != 0.0 || pts[3 * (pts_off[i + 1] - 1) + 2] != 0.0)) h->s_any_z_ends = true;
+      if (pts_off[i + 1] > pts_off[i] && (pts[3 * pts_off[i] + 2] != 0.0 || pts[3 * (pts_off[i + 1] - 1) + 2] != 0.0)) f.any_z_ends = true;
   }
   // points_on_line bit-identical to points (the simulation node's input): the selections (linefit, no boundary) and (no linefit) are
   // then the same records and clc_select_observations builds them once.  Checked for reference-size inputs only (a memcmp of <= 384 KB).
-  h->store_lines_equal_points = M == ML && M <= 16384 && h->s_pts_off == h->s_ptl_off &&
-                                (M == 0 || std::memcmp(pts + 3 * pts_off[0], ptl + 3 * ptl_off[0], M * 3 * sizeof(double)) == 0);
-  CLC_HIP(hipStreamSynchronize(h->stream));  // the caller's arrays may go away
-  h->store_poses = n_poses;
-  h->store_generation++;
-  return CLC_OK;
+  f.lines_equal_points = M == ML && M <= 16384 && h->s_pts_off == h->s_ptl_off &&
+                         (M == 0 || std::memcmp(pts + 3 * pts_off[0], ptl + 3 * ptl_off[0], M * 3 * sizeof(double)) == 0);
+  return adopt_store(h, n_poses, f);  // (waits for the stream: the caller's arrays may go away)
 }
 
 int64_t clc_store_generation(const clc_handle* h) { return h ? h->store_generation : -1; }

@@ -561,6 +561,78 @@ class Solver:
         check(self._L.clc_board_segments_device(self._h, C.c_void_p(points_ptr), C.c_void_p(offsets_ptr), C.c_size_t(n_scans),
                                                 C.c_void_p(seg_ptr), C.c_void_p(status_ptr or 0)), "clc_board_segments_device")
 
+    # ---- the offline flow: stamped tag poses + raw scans -> stored observations (K13) ----
+    def keyframes(self, q_wc: np.ndarray, t_wc: np.ndarray, options: Optional["_capi.AssembleOptions"] = None) -> np.ndarray:
+        """The key-frame filter of main/calibr_offline.cpp:62-78 on tag poses q_wc [n, 4] (w, x, y, z), t_wc [n, 3] -> keep [n] bool."""
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        assert q.shape[0] == t.shape[0], "one translation per quaternion"
+        keep = np.zeros(q.shape[0], dtype=np.uint8)
+        n = C.c_int64()
+        o = options or _capi.default_assemble_options()
+        check(self._L.clc_keyframes(self._h, C.byref(o), q.shape[0], q.ctypes.data, t.ctypes.data, keep.ctypes.data, C.byref(n)), "clc_keyframes")
+        assert n.value == int(keep.sum())
+        return keep.astype(bool)
+
+    def assemble_observations(self, pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, options: Optional["_capi.AssembleOptions"] = None):
+        """main/calibr_offline.cpp:62-155 in one call: stamped tag poses (pose_stamp [n], q_wc [n, 4] (w, x, y, z), t_wc [n, 3]) and
+        raw scans (`scans` as simdata.sim_laser_scans returns them: ranges, offsets, angle_min, angle_increment, range_min;
+        scan_stamp [S]) -> (AssembleInfo, scan_pose [S] int32).  The observations are left stored on the handle
+        (select_observations, closed_form, solve, information follow; stored_observations() copies them back)."""
+        ps = np.ascontiguousarray(pose_stamp, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        assert q.shape[0] == t.shape[0] == ps.shape[0], "one stamp, quaternion and translation per pose"
+        r = np.ascontiguousarray(scans["ranges"], dtype=np.float32)
+        off = np.ascontiguousarray(scans["offsets"], dtype=np.int64)
+        S = len(off) - 1
+        f = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (S,)))
+        am, ai, rm = f(scans["angle_min"]), f(scans["angle_increment"]), f(scans["range_min"])
+        ss = np.ascontiguousarray(scan_stamp, dtype=np.float64).reshape(-1)
+        assert ss.shape[0] == S, "one stamp per scan"
+        scan_pose = np.zeros(S, dtype=np.int32)
+        info = _capi.AssembleInfo()
+        o = options or _capi.default_assemble_options()
+        check(self._L.clc_assemble_observations(self._h, C.byref(o), ps.shape[0], ps.ctypes.data, q.ctypes.data, t.ctypes.data, r.ctypes.data,
+                                                off.ctypes.data, S, am.ctypes.data, ai.ctypes.data, rm.ctypes.data, ss.ctypes.data,
+                                                scan_pose.ctypes.data, C.byref(info)), "clc_assemble_observations")
+        return info, scan_pose
+
+    def assemble_observations_device(self, n_poses: int, pose_stamp_ptr: int, q_wc_ptr: int, t_wc_ptr: int, ranges_ptr: int, offsets_ptr: int,
+                                     n_scans: int, n_rays: int, angle_min_ptr: int, angle_increment_ptr: int, range_min_ptr: int,
+                                     scan_stamp_ptr: int, scan_pose_ptr: int = 0, options: Optional["_capi.AssembleOptions"] = None):
+        """clc_assemble_observations_device on device-resident arrays (data_ptr()s; ready on the solver's stream) -> AssembleInfo."""
+        info = _capi.AssembleInfo()
+        o = options or _capi.default_assemble_options()
+        check(self._L.clc_assemble_observations_device(self._h, C.byref(o), n_poses, pose_stamp_ptr or None, q_wc_ptr or None, t_wc_ptr or None,
+                                                       ranges_ptr or None, offsets_ptr or None, n_scans, n_rays, angle_min_ptr or None,
+                                                       angle_increment_ptr or None, range_min_ptr or None, scan_stamp_ptr or None,
+                                                       scan_pose_ptr or None, C.byref(info)), "clc_assemble_observations_device")
+        return info
+
+    def stored_observations(self):
+        """The scans stored on the handle (store_observations / assemble_observations), copied back -> simdata.ObservationSet."""
+        from .simdata import ObservationSet
+        n = C.c_int()
+        check(self._L.clc_stored_observations(self._h, C.byref(n), None, None, None, None, None, None, None), "clc_stored_observations")
+        P = n.value
+        pts_off = np.zeros(P + 1, dtype=np.int64); ptl_off = np.zeros(P + 1, dtype=np.int64)
+        check(self._L.clc_stored_observations(self._h, None, None, None, pts_off.ctypes.data, None, ptl_off.ctypes.data, None),
+              "clc_stored_observations")
+        tq = np.zeros((P, 4)); tt = np.zeros((P, 3)); pts = np.zeros((int(pts_off[P]), 3)); ptl = np.zeros((int(ptl_off[P]), 3))
+        check(self._L.clc_stored_observations(self._h, None, tq.ctypes.data, tt.ctypes.data, None, pts.ctypes.data, None, ptl.ctypes.data),
+              "clc_stored_observations")
+        return ObservationSet(tq, tt, pts_off, pts, ptl_off, ptl)
+
+    def debug_assemble_lines(self) -> np.ndarray:
+        """Test hook: the fitted lines [P, 2] the last assemble_observations[_device] of this process computed its end points from."""
+        n = C.c_int64()
+        f = self._hook("clc_debug_assemble_lines")
+        check(f(None, C.c_int64(0), C.byref(n)), "clc_debug_assemble_lines")
+        out = np.zeros((n.value, 2))
+        check(f(out.ctypes.data_as(C.c_void_p), C.c_int64(n.value), C.byref(n)), "clc_debug_assemble_lines")
+        return out
+
     # ---- test / profiling hooks ----
     def debug_math(self, op: int, x: np.ndarray) -> np.ndarray:
         """Device branch of a scalar helper, element-wise (hooks build): 0 rsqrt_pos, 1 rcp_pos, 2 rcp_pos_safe, 3 sqrt_pos, 4 rcp_ge1,

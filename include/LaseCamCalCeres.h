@@ -225,6 +225,21 @@ class Session {
     // reference-size inputs are small, a C2-size one is 53 MB).
     // A temporary cannot be kept alive: `Session s(load_obs());` does not compile (the re-store would read freed memory).
     explicit Session(std::vector<Oberserve>&&) = delete;
+    // Adopts the scans the shared context ALREADY holds (AssembleObservations below built them on the device): nothing is uploaded
+    // and no host copy is kept, so this Session cannot put them back — once another caller has replaced the stored scans its calls
+    // fail (ok() == false, message on std::cerr) instead of solving somebody else's data.  ClosedSolution and Calibration work on
+    // it; CalibrationFromStarts / CalibrationSubsets / CalibrationConsensus need the observations on the host and refuse (-1 / false):
+    // use Session(obs) with the vector AssembleObservations returned for those.
+    struct AdoptStored {};
+    explicit Session(AdoptStored) : obs_(NULL), ok_(false), generation_(-1)
+    {
+        Handle H;
+        if (!H.h) return;
+        int n = 0;
+        if (clc_stored_observations(H.h, &n, NULL, NULL, NULL, NULL, NULL, NULL) != CLC_OK) { std::cerr << "[clc] " << clc_last_error() << std::endl; return; }
+        generation_ = clc_store_generation(H.h);
+        ok_ = true;
+    }
     explicit Session(const std::vector<Oberserve>& obs) : obs_(&obs), ok_(false), generation_(-1)
     {
         Handle H;  // locked first: flatten gathers into the process-wide pinned buffers
@@ -357,6 +372,7 @@ class Session {
         Handle H;
         ok_ = false;
         if (!H.h || !starts || n_starts == 0) return -1;
+        if (!have_observations()) return -1;
         const Flat f = flatten(*obs_);
         const int P = (int)(f.pts_off.size() - 1);
         int64_t n_rec = 0;
@@ -415,6 +431,7 @@ class Session {
         Handle H;
         ok_ = false;
         if (!H.h || !weights || !Tcls || n_subsets == 0) return false;
+        if (!have_observations()) return false;
         const Flat f = flatten(*obs_);
         const int P = (int)(f.pts_off.size() - 1);
         if (P <= 0) return false;
@@ -488,6 +505,7 @@ class Session {
         Handle H;
         ok_ = false;
         if (!H.h || n_rows == 0 || !(rms_max >= 0.0)) return false;
+        if (!have_observations()) return false;
         const Flat f = flatten(*obs_);
         const int P = (int)(f.pts_off.size() - 1);
         if (P <= 0 || (!rows && m > (size_t)P)) return false;
@@ -586,8 +604,21 @@ class Session {
     }
 
  private:
+    // CalibrationFromStarts / CalibrationSubsets / CalibrationConsensus flatten the caller's observations into records of their own;
+    // a Session that adopted stored scans holds none (ok() == false, -1 / false returned)
+    bool have_observations() const
+    {
+        if (obs_) return true;
+        std::cerr << "[clc] this Session adopted the stored scans and holds no observations: CalibrationFromStarts / CalibrationSubsets / "
+                     "CalibrationConsensus need a Session(obs) (clc_adapter::AssembleObservations returns the vector)" << std::endl;
+        return false;
+    }
     bool store(clc_handle* h)
     {
+        if (!obs_) {
+            std::cerr << "[clc] the scans this Session adopted were replaced on the shared context; it keeps no copy to store again" << std::endl;
+            return false;
+        }
         const Flat f = flatten(*obs_);
         const int P = (int)(f.pts_off.size() - 1);
         if (clc_store_observations(h, P, f.tag_q.data(), f.tag_t.data(), f.pts_off.data(), f.pts,
@@ -610,6 +641,64 @@ class Session {
     bool ok_;
     int64_t generation_;
 };
+
+}  // namespace clc_adapter
+
+namespace clc_adapter {
+
+// The data preparation of the offline node, main/calibr_offline.cpp:62-155, on the device (clc_assemble_observations): the stamped
+// tag poses of apriltag_pose.txt (T_wc, in file order) and the laser scans (scan k owns rays [offsets[k], offsets[k+1]) of ranges,
+// with its angle_min / angle_increment / range_min and stamp) -> the std::vector<Oberserve> the reference builds, in scan order.
+// The observations also stay stored on the shared context: `Session run((Session::AdoptStored()));` solves them without a second
+// upload.  The gates "fewer than 10 poses" (:56) and "fewer than 5 observations" (:158) are the caller's.  info: nullable.
+// On an error the vector is empty and *ok (nullable) false; the message goes to std::cerr.
+inline std::vector<Oberserve> AssembleObservations(const std::vector<double>& pose_stamp, const std::vector<Eigen::Quaterniond>& qwc,
+                                                   const std::vector<Eigen::Vector3d>& twc, const std::vector<float>& ranges,
+                                                   const std::vector<int64_t>& offsets, const std::vector<float>& angle_min,
+                                                   const std::vector<float>& angle_increment, const std::vector<float>& range_min,
+                                                   const std::vector<double>& scan_stamp, clc_assemble_info* info = NULL, bool* ok = NULL,
+                                                   const clc_assemble_options* opt = NULL)
+{
+    std::vector<Oberserve> obs;
+    if (ok) *ok = false;
+    const size_t n = pose_stamp.size(), S = scan_stamp.size();
+    if (qwc.size() != n || twc.size() != n || offsets.size() != S + 1 || angle_min.size() != S || angle_increment.size() != S || range_min.size() != S) {
+        std::cerr << "[clc] AssembleObservations: array sizes disagree" << std::endl;
+        return obs;
+    }
+    std::vector<double> q(4 * n + 1), t(3 * n + 1);
+    for (size_t i = 0; i < n; ++i) {
+        q[4 * i] = qwc[i].w(); q[4 * i + 1] = qwc[i].x(); q[4 * i + 2] = qwc[i].y(); q[4 * i + 3] = qwc[i].z();
+        for (int k = 0; k < 3; ++k) t[3 * i + k] = twc[i](k);
+    }
+    Handle H;
+    if (!H.h) return obs;
+    clc_assemble_info local;
+    const float fz = 0.f; const double dz = 0.0;
+    if (clc_assemble_observations(H.h, opt, n, n ? &pose_stamp[0] : &dz, &q[0], &t[0], ranges.empty() ? &fz : &ranges[0], &offsets[0], S,
+                                  S ? &angle_min[0] : &fz, S ? &angle_increment[0] : &fz, S ? &range_min[0] : &fz, S ? &scan_stamp[0] : &dz, NULL,
+                                  &local) != CLC_OK) {
+        std::cerr << "[clc] " << clc_last_error() << std::endl;
+        return obs;
+    }
+    if (info) *info = local;
+    const size_t P = (size_t)local.n_observations, M = (size_t)local.n_points, ML = (size_t)local.n_line_points;
+    std::vector<double> tq(4 * P + 1), tt(3 * P + 1), pts(3 * M + 1), ptl(3 * ML + 1);
+    std::vector<int64_t> po(P + 1), lo(P + 1);
+    if (clc_stored_observations(H.h, NULL, &tq[0], &tt[0], &po[0], &pts[0], &lo[0], &ptl[0]) != CLC_OK) {
+        std::cerr << "[clc] " << clc_last_error() << std::endl;
+        return obs;
+    }
+    obs.resize(P);
+    for (size_t i = 0; i < P; ++i) {
+        obs[i].tagPose_Qca = Eigen::Quaterniond(tq[4 * i], tq[4 * i + 1], tq[4 * i + 2], tq[4 * i + 3]);
+        obs[i].tagPose_tca = Eigen::Vector3d(tt[3 * i], tt[3 * i + 1], tt[3 * i + 2]);
+        for (int64_t k = po[i]; k < po[i + 1]; ++k) obs[i].points.push_back(Eigen::Vector3d(pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]));
+        for (int64_t k = lo[i]; k < lo[i + 1]; ++k) obs[i].points_on_line.push_back(Eigen::Vector3d(ptl[3 * k], ptl[3 * k + 1], ptl[3 * k + 2]));
+    }
+    if (ok) *ok = true;
+    return obs;
+}
 
 }  // namespace clc_adapter
 

@@ -401,6 +401,72 @@ int clc_board_segments(clc_handle* h, const double* points, const int64_t* offse
 int clc_board_segments_device(clc_handle* h, const double* points_dev, const int64_t* offsets_dev, size_t n_scans, int64_t* seg_dev,
                               int32_t* status_dev);
 
+/* ---- the offline flow (K13): stamped tag poses + raw laser scans -> stored observations, main/calibr_offline.cpp:62-155 -----
+ * Key frames (:62-78): pose 0 is kept; pose j is kept when dist > keyframe_dist_min || fabs(theta) > keyframe_theta_min against
+ * the last kept pose, dist = |older.twc - newer.twc|, theta = 2 acos(w), w = (qo . qn) / |qo|^2 the scalar part of
+ * older.qwc.inverse() * newer.qwc.  As in the reference: |w| > 1 gives NaN and the angle test is false, w < 0 gives theta > pi
+ * (antipodal quaternions: kept), a NaN dist makes the distance test false.
+ * Every scan goes through TranScanToPoints and AutoGetLinePts (clc_scan_to_points, clc_board_segments).  A scan with a segment
+ * takes the key frame with the smallest fabs(pose_stamp - scan_stamp), the first of equal minima in key-frame order (:102-113: strict
+ * <, from 10000; a NaN stamp is never chosen), accepted when that minimum < max_dt (:116).  The scans with a segment and a pose
+ * become the observations, in scan order: points = the segment's points; tagPose_Qca = qwc.inverse(), tagPose_tca =
+ * -Qca.toRotationMatrix() * twc (:145-146); a line is fitted to the points (clc_line_fit_batched under `line`, every fit started
+ * at line0) and points_on_line = the two points of that line at the first and the LAST segment point's abscissa, or ordinate when
+ * |dx| <= |dy| (:126-142; the reference reads points.end(), one past the end — the last point is used here), z = 0; a segment of
+ * fewer than 2 points gets none.  A scan on which the reference's AutoGetLinePts throws (CLC_SEG_REF_THROWS: the reference's
+ * program would terminate there) is dropped and counted.
+ * The observations are left stored on the handle exactly as clc_store_observations leaves them (clc_store_generation is bumped):
+ * clc_select_observations, clc_closed_form, clc_solve, clc_information follow as usual.  No observations at all: CLC_OK,
+ * n_observations = 0, and the store is that of clc_store_observations with n_poses = 0.  The reference's gates "fewer than 10
+ * poses" (:56) and "fewer than 5 observations" (:158) are the caller's. */
+typedef struct clc_assemble_options {
+  double keyframe_dist_min;  /* 0.20, :66 */
+  double keyframe_theta_min; /* 3.1415926 * 10 / 180, :67 */
+  double max_dt;             /* 0.02 s, :116 */
+  double line0[2];           /* start of every line fit: (0, 0) */
+  clc_options line;          /* clc_line_options_default */
+} clc_assemble_options;
+void clc_assemble_options_default(clc_assemble_options* opt);
+typedef struct clc_assemble_info {
+  int64_t n_keyframes;    /* poses the key-frame filter kept */
+  int64_t n_segments;     /* scans with a board segment (CLC_SEG_FOUND) */
+  int64_t n_ref_throws;   /* scans dropped with CLC_SEG_REF_THROWS */
+  int64_t n_unmatched;    /* scans with a segment and no key frame within max_dt */
+  int64_t n_observations; /* = n_segments - n_unmatched */
+  int64_t n_points;       /* points of all observations */
+  int64_t n_line_points;  /* points_on_line of all observations */
+} clc_assemble_info;
+#define CLC_SCAN_NO_SEGMENT (-1)
+#define CLC_SCAN_REF_THROWS (-2)
+#define CLC_SCAN_NO_POSE (-3)
+/* The key-frame filter alone, on host arrays: q_wc_wxyz[4 * n_poses], t_wc[3 * n_poses] -> keep[n_poses] (1 / 0), *n_kept
+ * (both nullable).  opt NULL: the defaults. */
+int clc_keyframes(clc_handle* h, const clc_assemble_options* opt, size_t n_poses, const double* q_wc_wxyz, const double* t_wc,
+                  uint8_t* keep, int64_t* n_kept);
+/* pose_stamp[n_poses], q_wc_wxyz[4 * n_poses], t_wc[3 * n_poses]: every stamped tag pose (T_wc as in apriltag_pose.txt), in file
+ * order.  Scan k owns rays [offsets[k], offsets[k+1]) of ranges[] (float32), with angle_min / angle_increment / range_min[k] and
+ * the stamp scan_stamp[k]; any number of scans.  scan_pose[n_scans] (nullable): the ORIGINAL index of the pose a kept scan took,
+ * or CLC_SCAN_NO_SEGMENT / CLC_SCAN_REF_THROWS / CLC_SCAN_NO_POSE.  info nullable.  Everything is uploaded once and computed on
+ * the device; the counters, the offsets and (reference-size stores) the tag poses come back, point data does not.
+ * CLC_ERR_INVALID_ARG: NULL arrays, offsets that decrease, a scan of 2^31 rays or more, 2^31 poses or more. */
+int clc_assemble_observations(clc_handle* h, const clc_assemble_options* opt, size_t n_poses, const double* pose_stamp,
+                              const double* q_wc_wxyz, const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans,
+                              const float* angle_min, const float* angle_increment, const float* range_min, const double* scan_stamp,
+                              int32_t* scan_pose, clc_assemble_info* info);
+/* The same with every array in DEVICE memory (ready on the handle's stream; complete on return — ONE synchronisation):
+ * offsets_dev[n_scans + 1] with offsets_dev[0] == 0 and n_rays = offsets_dev[n_scans], which the caller knows (not validated:
+ * monotone, fewer than 2^31 rays per scan); scan_pose_dev nullable (device memory); info on the host. */
+int clc_assemble_observations_device(clc_handle* h, const clc_assemble_options* opt, size_t n_poses, const double* pose_stamp_dev,
+                                     const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev,
+                                     const int64_t* offsets_dev, size_t n_scans, size_t n_rays, const float* angle_min_dev,
+                                     const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
+                                     int32_t* scan_pose_dev, clc_assemble_info* info);
+/* The scans stored on the handle (by clc_store_observations or clc_assemble_observations), copied back: *n_poses, tag_q_wxyz
+ * [4 P], tag_t[3 P], pts_off[P + 1], pts[3 M], ptl_off[P + 1], ptl[3 ML]; every pointer nullable (a first call with the arrays
+ * NULL gives n_poses, then the offsets give M and ML — or take them from clc_assemble_info).  CLC_ERR_NO_DATA: nothing stored. */
+int clc_stored_observations(clc_handle* h, int* n_poses, double* tag_q_wxyz, double* tag_t, int64_t* pts_off, double* pts,
+                            int64_t* ptl_off, double* ptl);
+
 /* ---- board poses from tag corners (the numeric half of CamPoseEst::calcCamPose, src/calcCamPose.cpp:270-303) -------------
  * The two camera models the reference's nodes select (main/kalibratag_detector_node.cpp:90-105), restated from camodocal:
  *   CLC_CAMERA_PINHOLE         PinholeCamera:     proj = fx fy cx cy, dist = k1 k2 p1 p2
