@@ -8,8 +8,8 @@
 //     sum r0^2,   sum log(1 + r0^2 / lf^2)   (without the loss: nothing),   #{|r0| <= tau},     r0 = n.(R p + t) + d = m.p + c0,
 // the residual before the scale, exactly as accumulate_observation (clc_device.hpp) forms it.  A lane holds points of ONE scan, so
 // scale^2 and the loss scale a = lf scale multiply its sums once:  ssq = s^2 sum r0^2,  cost = 1/2 lf^2 s^2 sum log(.)  (1/2 ssq
-// without the loss).  The logarithm is taken per point (log_ge1, < 1 ulp): one pass has no use for the running-product trick of the
-// solve kernels, and a far candidate's product would need their renormalisation.
+// without the loss).  The logarithm is taken per point (log1p_pos: log_ge1, < 1 ulp, corrected for the rounding of 1 + x): one pass
+// has no use for the running-product trick of the solve kernels, and a far candidate's product would need their renormalisation.
 //
 // Reduction over a block, in a FIXED order (two calls return the same bits; no floating-point atomics): res_build_kernel deals the
 // records to the lanes in order, so the lanes of a block are consecutive.  The lane sums go to LDS; the FIRST lane of every block
@@ -22,6 +22,16 @@
 #include "clc_resident.hpp"
 
 namespace clc {
+
+// log(1 + x) for finite x >= 0, accurate RELATIVE to the result also where x is tiny.  u = fl(1 + x) drops the low bits of a small x
+// (x = 3e-9, a residual of a few micrometres: 4e-8 of log(u) — nothing in a solve's total, but a block of ONE record is judged on its
+// own cost); log(u) x / (u - 1) puts them back: log_ge1 is accurate relative to u - 1 next to 1 (f = u - 1 is exact there), and the
+// factor x / (u - 1) is the ratio of the wanted argument to the rounded one.  u == 1: the series' first term.
+__device__ __forceinline__ double log1p_pos(double x) {
+  const double u = 1.0 + x;
+  const double d = u - 1.0;
+  return d == 0.0 ? x : log_ge1(u) * (x / d);
+}
 
 template <int NL>
 __global__ __launch_bounds__(NL) void block_scores_kernel(
@@ -65,7 +75,7 @@ __global__ __launch_bounds__(NL) void block_scores_kernel(
     const bool valid = j < cnt;
     const double r2 = valid ? r0 * r0 : 0.0;
     a_q += r2;
-    if (use_loss) a_l += log_ge1(fma(r2, inv_lf2, 1.0));  // (a padded slot: log(1) = 0)
+    if (use_loss) a_l += log1p_pos(r2 * inv_lf2);  // (a padded slot: log1p(0) = 0)
     a_i += (valid && fabs(r0) <= tau) ? 1 : 0;
   }
   const double l_q = q.s2 * a_q;

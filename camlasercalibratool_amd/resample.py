@@ -37,6 +37,26 @@ def random_subset_weights(n_blocks: int, n_subsets: int, m: int, seed: int = 0) 
     return w
 
 
+def as_weight_rows(w, n_blocks: int) -> np.ndarray:
+    """Weight rows as clc_solve_subsets reads them: [S, n_blocks] uint8, C-contiguous.  Accepts [S, n_blocks] or one row [n_blocks] of
+    integers, booleans or integral floats in 0..255.  ValueError for a value outside 0..255 (a cast to uint8 would wrap 256 to 0: a
+    block silently left out), for a non-integral or non-finite float, for a non-numeric array and for any other shape."""
+    B = int(n_blocks)
+    a = np.asarray(w)
+    if B < 1 or a.ndim not in (1, 2) or a.shape[-1] != B or a.size == 0:
+        raise ValueError(f"weights: [S, {B}] or [{B}], got {a.shape}")
+    if a.dtype == np.bool_:
+        a = a.astype(np.uint8)
+    if a.dtype.kind == "f":
+        if not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+            raise ValueError("weights: whole numbers only (a weight is a multiplicity)")
+    elif a.dtype.kind not in "iu":
+        raise ValueError(f"weights: integers, got {a.dtype}")
+    if np.any(a < 0) or np.any(a > 255):
+        raise ValueError("weights: multiplicities in 0..255")
+    return np.ascontiguousarray(a.reshape(-1, B), dtype=np.uint8)
+
+
 def materialize(records: np.ndarray, block_offsets, w) -> np.ndarray:
     """The definition of a weighted subset: the records of block b, w[b] times in a row, block after block.  For the oracle, for
     clc_solve_batched, and for problems that one workgroup does not hold."""

@@ -7,7 +7,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _capi
+from . import _capi, resample
 from ._capi import Iteration, Options, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
@@ -423,13 +423,14 @@ class Solver:
     def solve_subsets(self, block_offsets: np.ndarray, weights: np.ndarray, poses0: np.ndarray, options: Optional[Options] = None):
         """clc_solve_subsets: S resampled solves on the ONE problem uploaded as a batch of one (upload_batched(records, [0, n])).
         block_offsets [B + 1] cuts the records into consecutive blocks (one per pose), weights [S, B] uint8 says how many times subset k
-        takes block b (0: left out; resample.jackknife_weights / bootstrap_weights / random_subset_weights), poses0 [S, 7] or [7] (every
+        takes block b (0: left out; resample.jackknife_weights / bootstrap_weights / random_subset_weights) — [S, B] or one row [B], whole
+        numbers 0..255 (resample.as_weight_rows: ValueError otherwise, also for a flat [S * B] vector, which used to be accepted) —, poses0 [S, 7] or [7] (every
         subset from the same start) -> (poses [S, 7], summaries [S]).  An empty or non-finite subset: termination FAILURE, pose kept."""
         off = np.ascontiguousarray(block_offsets, dtype=np.int64).reshape(-1)
-        w = np.ascontiguousarray(weights, dtype=np.uint8)
         B = off.size - 1
-        assert B >= 1 and w.size % B == 0 and w.size > 0, "weights: [S, len(block_offsets) - 1]"
-        S = w.size // B
+        assert B >= 1, "block_offsets: [B + 1]"
+        w = resample.as_weight_rows(weights, B)   # (ValueError for 256, -1, 0.5: a plain cast to uint8 would wrap or truncate them)
+        S = w.shape[0]
         p0 = np.asarray(poses0, dtype=np.float64)
         poses = np.ascontiguousarray(np.broadcast_to(p0.reshape(-1, 7), (S, 7))).copy()
         sm = (Summary * S)()

@@ -539,7 +539,9 @@ int clc_solve_multistart(clc_handle* h, const clc_options* opt, size_t n_starts,
  * changed (clc_solve_multistart on the same upload is unaffected), the lane -> block map is kept on the handle until the offsets change
  * or the next upload.  A weight row of 1s returns the bits clc_solve_multistart returns.
  * CLC_ERR_NO_DATA unless a batch of one is uploaded.  CLC_ERR_INVALID_ARG: bad offsets; a block boundary inside a scan (the library
- * treats consecutive records with bitwise-equal planes as one scan; a block must hold whole scans); a problem that one workgroup does
+ * treats consecutive records with bitwise-equal planes as one scan; a block must hold whole scans — a boundary inside a scan is
+ * accepted only where it happens to coincide with the library's own cut of that scan into lanes, which depends on all the scans of the
+ * upload and may change between versions: do not rely on it); a problem that one workgroup does
  * not hold (clc_path_info.batched_resident == 0: materialise the subsets and use clc_solve_batched).
  * A subset with nothing in it (all weights 0) or with a non-finite end gets termination = CLC_FAILURE and keeps its pose; it does not
  * fail the call. */
@@ -558,7 +560,7 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt, size_t n_blocks, co
  * clc_solve_subsets return afterwards are unchanged; the lane -> block map is the one clc_solve_subsets keeps (built once per offsets
  * and upload, by whichever call comes first).
  * Errors as clc_solve_subsets: CLC_ERR_NO_DATA unless a batch of one is uploaded; CLC_ERR_INVALID_ARG for bad offsets, a block boundary
- * inside a scan, tau = NaN, loss_scale_factor <= 0 with use_loss, or a problem that one workgroup does not hold
+ * inside a scan (as there: whole scans per block), tau = NaN, loss_scale_factor <= 0 with use_loss, or a problem that one workgroup does not hold
  * (clc_path_info.batched_resident == 0).  A pose with a non-finite entry does not fail the call: its row is NaN / NaN / 0.  A block
  * without records scores 0 / 0 / 0. */
 int clc_score_blocks(clc_handle* h, const clc_options* opt, size_t n_blocks, const int64_t* block_offsets, size_t n_poses,

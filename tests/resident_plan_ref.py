@@ -8,7 +8,9 @@ after clc_upload_batched.  A test helper only — the package plans on the devic
     form's capacity (PR + PL); a problem with more scans than lanes, or none such c, does not fit; an empty problem: 0;
   * forms: 256 lanes (capacity 42), then 512 (capacity 22) for the whole batch when some problem does not fit 256;
     straight to 512 under flag 8192; records with p.z != 0: only the 512-lane z form (capacity 22);
-  * flag 4096 at upload, or no records at all: no lane layout."""
+  * flag 4096 at upload, or no records at all: no lane layout;
+  * the lane deal (res_build_kernel): scan s with c records takes Ls = ceil(c / ppl) lanes, lane i of them q + (i < r) records
+    (q, r = divmod(c, Ls)) from record s0 + i q + min(i, r); the lanes past the total are idle (lane_cuts)."""
 import numpy as np
 
 FLAG_NO_RESIDENT = 4096
@@ -53,6 +55,26 @@ def problem_ppl(lens, n_lanes, cap):
         if int(((lens + c - 1) // c).sum()) <= n_lanes:
             return c
     return None
+
+
+def lane_cuts(lens, nl, ppl):
+    """The lane deal of one problem at `ppl` points per lane on `nl` lanes, as res_build_kernel writes the lane descriptors:
+    -> (scan [nl], first_record [nl], cnt [nl]) np.int64; an idle lane has scan -1, cnt 0 and first_record = the record count."""
+    lens = np.asarray(lens, dtype=np.int64)
+    scan = np.full(nl, -1, dtype=np.int64)
+    first = np.full(nl, int(lens.sum()), dtype=np.int64)
+    cnt = np.zeros(nl, dtype=np.int64)
+    t, s0 = 0, 0
+    for s, c in enumerate(lens):
+        c = int(c)
+        Ls = -(-c // ppl)
+        q, r = divmod(c, Ls) if Ls else (0, 0)
+        for i in range(Ls):
+            assert t < nl, "the problem does not fit the workgroup at this many points per lane"
+            scan[t], first[t], cnt[t] = s, s0 + i * q + min(i, r), q + (1 if i < r else 0)
+            t += 1
+        s0 += c
+    return scan, first, cnt
 
 
 class Plan:

@@ -18,7 +18,10 @@ Every batch: path_info() equals the restatement's prediction; every problem agai
 count, T_cl within 1e-6 and final cost within 1e-8 — without T_cl below 7 scans, which do not pin the pose); a second solve
 bitwise equal; 16 sampled problems solved again as a batch of one, bitwise equal wherever the restatement gives them the same form
 and points per lane.  Past capacity: the same gates on the default fallback and under flags 4096, 2048 and 2048 | 1024.
-A difference in iteration count or termination passes only as a near tie of the oracle's own trace (tests/lm_near_tie.py)."""
+A difference in iteration count or termination passes only as a near tie of the oracle's own trace (tests/lm_near_tie.py).
+
+Shared with tests/subsets_fuzz_cases.py and tests/test_gpu_subsets_fuzz.py, which import this module: Pool, edge_lens, EDGES, NL, K,
+N_SCANS, _with_z, _options, _key and _path.  Change them with those callers in mind."""
 import time
 from concurrent.futures import ThreadPoolExecutor
 

@@ -11,7 +11,10 @@ is asserted first.
 
 The consensus itself: the scenario and its frozen oracle result come from tests/tools/consensus_scenario.py
 (tests/golden/consensus_oracle.json); the GPU pipeline must pick the same winning row and the same inlier mask, and its refit must lie
-within the parity gates (1e-6 on T_cl, 1e-8 on the cost) of the oracle's refit."""
+within the parity gates (1e-6 on T_cl, 1e-8 on the cost) of the oracle's refit.
+
+Shared with tests/test_gpu_subsets_fuzz.py, which imports this module: REL_TOL, TAU_MARGIN, LF, _poses, _group, _oracle_tables,
+_pick_tau, _rel, _check_case and _map_builds.  Change them with that caller in mind."""
 import ctypes as C
 import importlib.util
 import json

@@ -1,6 +1,6 @@
 """The restatement of the batched lane planner (tests/resident_plan_ref.py) on hand-computed cases: the points per lane of a
 problem, the 256 -> 512 lane fallback, the capacities 42 / 22, flags 4096 / 8192, records with z, empty problems, and the
-scan identity — equal consecutive scans merge, a problem start always starts a scan."""
+scan identity — equal consecutive scans merge, a problem start always starts a scan; and the lane deal (lane_cuts)."""
 import numpy as np
 
 import resident_plan_ref as R
@@ -104,3 +104,43 @@ def test_scan_identity():
     rec[4:, 7] = rec[0, 7]
     rec[4:, 4] += 1.0  # the points differ, the plane does not: one scan
     assert list(R.scan_lengths(rec, off)[0]) == [8]
+
+
+def test_lane_cuts_by_hand():
+    # 7 records at 3 per lane: 3 lanes of 3, 2, 2; then a scan of 3 in one lane, a scan of 1
+    scan, first, cnt = R.lane_cuts([7, 3, 1], 8, 3)
+    assert scan.tolist() == [0, 0, 0, 1, 2, -1, -1, -1]
+    assert first.tolist() == [0, 3, 5, 7, 10, 11, 11, 11]
+    assert cnt.tolist() == [3, 2, 2, 3, 1, 0, 0, 0]
+    # 10 records at 4 per lane: ceil(10 / 4) = 3 lanes of 4, 3, 3 — not 4, 4, 2
+    assert R.lane_cuts([10], 4, 4)[2].tolist() == [4, 3, 3, 0]
+    assert R.lane_cuts([], 4, 1)[2].tolist() == [0, 0, 0, 0]
+
+
+def test_lane_cuts_properties_on_seeded_problems():
+    """Counts sum to n, every count of a used lane is in [1, ppl], at most nl lanes are used, a lane's first record is the sum of the
+    counts before it, a lane holds records of one scan, and a scan's lanes differ by at most one record."""
+    rng = np.random.default_rng(11)
+    for case in range(300):
+        nl = (256, 512)[case % 2]
+        cap = R.CAP[nl]
+        ns = int(rng.integers(1, nl + 1))
+        lens = np.where(rng.random(ns) < 0.5, rng.integers(1, 4, size=ns), rng.integers(1, 3 * cap, size=ns)).astype(np.int64)
+        ppl = R.problem_ppl(lens, nl, 10**6)
+        scan, first, cnt = R.lane_cuts(lens, nl, ppl)
+        n = int(lens.sum())
+        used = cnt > 0
+        assert scan.shape == first.shape == cnt.shape == (nl,)
+        assert int(cnt.sum()) == n
+        assert used.sum() <= nl and used.sum() == int((-(-lens // ppl)).sum())
+        assert not used[int(used.sum()):].any() and np.all(scan[~used] == -1) and np.all(first[~used] == n)
+        assert np.all((cnt[used] >= 1) & (cnt[used] <= ppl))
+        assert np.array_equal(first[used], np.concatenate([[0], np.cumsum(cnt[used])[:-1]]))
+        starts = np.concatenate([[0], np.cumsum(lens)])
+        assert np.all(first[used] >= starts[scan[used]]) and np.all(first[used] + cnt[used] <= starts[scan[used] + 1])
+        assert np.array_equal(np.bincount(scan[used], weights=cnt[used], minlength=ns).astype(np.int64), lens)
+        for s in np.flatnonzero(lens > ppl)[:8]:
+            c = cnt[scan == s]
+            assert c.max() - c.min() <= 1 and np.all(np.diff(c) <= 0)
+        if ppl > 1:   # one point per lane less would need more lanes than the workgroup has
+            assert int((-(-lens // (ppl - 1))).sum()) > nl

@@ -112,3 +112,40 @@ def test_covariances_against_numpy_on_oracle_solutions_of_materialised_subsets(o
     Eb = Db - Db.mean(axis=0)
     wantb = sum(np.outer(e, e) for e in Eb) / 15.0
     assert np.abs(resample.bootstrap_covariance(full, Xb) - wantb).max() <= 1e-8 * np.abs(wantb).max()
+
+
+def test_as_weight_rows_refuses_what_a_cast_to_uint8_would_hide():
+    """Solver.solve_subsets converts its weights with resample.as_weight_rows: 256 must not become 0 (the block left out), -1 not 255,
+    2.5 not 2."""
+    B = 5
+    ok = resample.as_weight_rows([[0, 1, 2, 254, 255], [1, 1, 1, 1, 1]], B)
+    assert ok.dtype == np.uint8 and ok.shape == (2, B) and ok.flags["C_CONTIGUOUS"] and ok[0].tolist() == [0, 1, 2, 254, 255]
+    one = resample.as_weight_rows(np.array([0, 3, 0, 255, 1], dtype=np.int64), B)          # one row
+    assert one.shape == (1, B) and one.tolist() == [[0, 3, 0, 255, 1]]
+    assert resample.as_weight_rows(np.array([[0.0, 1.0, 2.0, 255.0, 7.0]]), B).tolist() == [[0, 1, 2, 255, 7]]   # integral floats
+    assert resample.as_weight_rows(np.array([[True, False, True, True, False]]), B).tolist() == [[1, 0, 1, 1, 0]]
+    sliced = np.arange(20, dtype=np.int32).reshape(2, 10)[:, ::2]                            # not contiguous
+    assert np.array_equal(resample.as_weight_rows(sliced, B), sliced) and resample.as_weight_rows(sliced, B).flags["C_CONTIGUOUS"]
+    u8 = resample.jackknife_weights(B)
+    assert np.array_equal(resample.as_weight_rows(u8, B), u8)
+    bad = [np.array([[0, 1, 2, 3, 256]]), np.array([[0, 1, 2, 3, -1]]), np.array([[0, 1, 2, 3, 2.5]]), np.array([[0, 1, 2, 3, np.nan]]),
+           np.array([[0, 1, 2, 3, np.inf]]), np.array([[0, 1, 2, 3, 1e3]]), np.zeros((2, 4), dtype=np.uint8), np.zeros((2, 6), dtype=np.uint8),
+           np.zeros(10, dtype=np.uint8), np.zeros((1, 2, B), dtype=np.uint8), np.zeros((0, B), dtype=np.uint8), np.uint8(1),
+           np.array([["1"] * B]), np.array([[1 + 0j] * B])]
+    for w in bad:
+        try:
+            resample.as_weight_rows(w, B)
+        except ValueError:
+            continue
+        raise AssertionError(w)
+    # what the plain cast did
+    assert np.ascontiguousarray(np.array([256, -1]), dtype=np.uint8).tolist() == [0, 255]
+    # Solver.solve_subsets converts before it touches the library: a Solver without a handle gets as far as the refusal
+    from camlasercalibratool_amd import solver
+    s = solver.Solver.__new__(solver.Solver)
+    for w in (np.array([[1, 1, 256, 1, 1]]), np.array([[1, 1, -1, 1, 1]]), np.array([[1, 1, 2.5, 1, 1]]), np.ones(2 * B, dtype=np.uint8)):
+        try:
+            s.solve_subsets(np.arange(B + 1), w, np.array([0, 0, 0, 0, 0, 0, 1.0]))
+        except ValueError:
+            continue
+        raise AssertionError(w)
