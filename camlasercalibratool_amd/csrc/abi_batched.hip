@@ -14,7 +14,7 @@ void warm_batched() {
   warm_kernel(reinterpret_cast<const void*>(&clc::batched_init_kernel));
 }
 
-int batched_launch_setup(clc_handle* h, const clc_options& /*opt*/, BatchedLaunch* bl) {
+int batched_launch_setup(clc_handle* h, BatchedLaunch* bl) {
   const StreamLayout& L = h->batch;
   const BatchShape b = {h->n_problems, h->batch_total_tiles, h->batch_max_tiles, L.n_rows, h->batch_max_rows, L.compact_ok, L.rows_ok, L.rows_z,
                         h->bres.ok, h->bres.with_z, h->bres.rows, h->bres.lanes};
@@ -44,23 +44,24 @@ void launch_batched_eval(clc_handle* h, const clc_options& opt, const BatchedLau
   else with_flags(launch, std::false_type{}, std::false_type{}, opt.use_loss != 0, bl.nt);
 }
 
-void launch_resident_batch(clc_handle* h, const clc_options& opt, const BatchedLaunch& bl, clc_summary* d_summaries, double* d_results,
-                           double rec_base, double* rec_host, long long seg_off, unsigned long long goal, const MultiStartLaunch* multistart) {
-  // one workgroup per problem, the problem read from HBM once and kept in registers + LDS for its whole solve
-  // (multi-start: one workgroup per START, every one of them on problem 0's points)
-  const size_t P = multistart ? multistart->n_starts : h->n_problems;
-  double* const d_poses = multistart ? multistart->d_poses : h->h_poses.dev();
-  const int uni_ppl = multistart ? -2 - h->bres.max_ppl : h->bres.uni_ppl;
+void launch_resident(clc_handle* h, const clc_options& opt, const BatchedLaunch& bl, const ResidentLaunch& w) {
+  // one workgroup per problem (start, subset), the problem read from HBM once and kept in registers + LDS for its whole solve
   // W4: the 256-lane form (4 waves); Z: 24-byte slots (p.z != 0 in some record of the batch), on 512 lanes
-  const auto launch = [&](auto Z, auto W4, auto LOSS, auto NT) {
+  const auto launch = [&](auto WEIGHTED, auto Z, auto W4, auto LOSS, auto NT) {
     constexpr int NW = W4 ? 4 : 8;
     constexpr int PR = Z ? kResPRz : W4 ? kResPR256 : kResPR512, PL = Z ? kResPLz : W4 ? kResPL256 : kResPL512;
-    hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z>), dim3((unsigned)P), dim3(NW * 64), 0,
-                       h->stream, h->bres.d_xy, h->bres.d_row, h->bres.d_desc, h->batch.d_groups, uni_ppl, opt, nullptr, 0, d_poses, d_summaries, d_results,
-                       nullptr, nullptr, rec_base, rec_host, seg_off, goal, Z ? h->bres.d_z : nullptr);
+    // The weighted form's three inputs ride in res_row, trace and trace_cap (clc_resident.hpp, WEIGHTED): a multi-start launch reads
+    // none of the three, and the kernel's argument list must not grow (profiles/subset_solves.md).  The one place they are cast.
+    const unsigned int* const res_row = WEIGHTED ? w.d_lane_block : h->bres.d_row.get();
+    clc_iteration* const trace = WEIGHTED ? reinterpret_cast<clc_iteration*>(w.d_weights) : nullptr;
+    hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z, WEIGHTED>), dim3((unsigned)w.workgroups),
+                       dim3(NW * 64), 0, h->stream, h->bres.d_xy, res_row, h->bres.d_desc, h->batch.d_groups, w.uni_ppl, opt, trace,
+                       WEIGHTED ? w.n_blocks : 0, w.d_poses, w.d_summaries, w.d_results, nullptr, nullptr, w.rec_base, w.rec_host, w.seg_off,
+                       w.goal, Z ? h->bres.d_z : nullptr);
   };
-  if (h->bres.with_z) with_flags(launch, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
-  else with_flags(launch, std::false_type{}, h->bres.lanes == 256, opt.use_loss != 0, bl.res_nt);
+  const bool weighted = w.d_weights != nullptr;
+  if (h->bres.with_z) with_flags(launch, weighted, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
+  else with_flags(launch, weighted, std::false_type{}, h->bres.lanes == 256, opt.use_loss != 0, bl.res_nt);
 }
 
 int batched_check_inputs(const char* who, const clc_options& opt, const double* poses, size_t P) {
@@ -82,25 +83,91 @@ int batched_check_inputs(const char* who, const clc_options& opt, const double* 
 
 namespace {
 
-// The end of every clc_solve_batched path: the stream synchronised (kernel completion makes the outcomes written over PCIe visible),
-// the results valid for clc_gather_results, copied out unless solved in place, the wall time (and with `timed` the kernel time of the
-// event pair around the one launch) in every summary.
+// What clc_solve_batched and the calls on a batch of one do between their own argument checks and their staging: the options (the
+// caller's or the defaults) and the n_poses start poses checked, the device made current, the wall clock started, the launch planned.
+struct BatchedCall {
+  clc_options opt;
+  BatchedLaunch bl;
+  std::chrono::steady_clock::time_point t0;
+  bool timed() const { return opt.profile_events == 1; }  // HIP event pair around the one launch -> clc_summary.eval_kernel_ms of every row
+};
+int begin_batched_call(const char* who, clc_handle* h, const clc_options* opt_in, const double* poses, size_t n_poses, BatchedCall* c) {
+  if (opt_in) c->opt = *opt_in; else clc_options_default(&c->opt);
+  CLC_TRY(batched_check_inputs(who, c->opt, poses, n_poses));
+  CLC_HIP(hipSetDevice(h->device));
+  c->t0 = std::chrono::steady_clock::now();
+  return batched_launch_setup(h, &c->bl);
+}
+
+// clc_solve_multistart / clc_solve_subsets / clc_score_blocks: the shared observations are ONE uploaded problem ...
+int require_batch_of_one(const char* who, const clc_handle* h) {
+  if (!h->batch.d_tiles || h->n_problems != 1)
+    return fail(CLC_ERR_NO_DATA, (std::string(who) + ": the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, "
+                                                     "n_problems = 1)").c_str());
+  return CLC_OK;
+}
+// ... and, for the calls without another route, one that a workgroup holds (`instead`: what the caller can do otherwise)
+int require_resident(const char* who, const BatchedLaunch& bl, const char* instead) {
+  if (bl.resident) return CLC_OK;
+  return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": the problem is not held by one workgroup (clc_path_info.batched_resident == 0, or the "
+                                                       "launch flags rule the resident kernel out): " + instead).c_str());
+}
+
+// ONE launch (launch() enqueues it on the handle's stream), between the two events when timed
+template <class Launch>
+int launch_once(clc_handle* h, bool timed, Launch&& launch) {
+  if (timed) {
+    CLC_TRY(ensure_events(h, 2));
+    CLC_HIP(hipEventRecord(h->ev[0], h->stream));
+  }
+  launch();
+  CLC_HIP(hipGetLastError());
+  if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
+  return CLC_OK;
+}
+// ... and its end: the stream synchronised (kernel completion makes the outcomes written over PCIe visible), the kernel time of the
+// event pair.  (A completion flag raised by the last workgroup to finish, polled by the host instead of this blocking synchronisation,
+// was measured: every workgroup then needs a system-scope release before it counts itself in, which on this part writes back L2 —
+// C4 shard 0.93 -> 1.28 ms, C3 0.150 -> 0.166.  The single-workgroup solve keeps its flag: one release per solve.  Polling the stream
+// with hipStreamQuery was measured too: no difference — the 70-80 us between the kernel's end event and the return are not the wake-up.)
+int wait_launch(clc_handle* h, bool timed, float* kernel_ms) {
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  *kernel_ms = 0.0f;
+  if (timed) CLC_HIP(hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]));
+  return CLC_OK;
+}
+// the wall time since t0 (and with `timed` the kernel time of the one launch) in every summary
+void stamp_summaries(clc_summary* summaries, size_t n, std::chrono::steady_clock::time_point t0, bool timed, float kernel_ms) {
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (size_t k = 0; k < n; ++k) {
+    summaries[k].solve_ms = ms;
+    if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
+  }
+}
+
+// The end of every clc_solve_batched path: the launches waited for, the results valid for clc_gather_results, copied out unless solved
+// in place, the times in every summary.
 int finish_batched(clc_handle* h, bool in_place, double* poses, clc_summary* summaries, std::chrono::steady_clock::time_point t0,
                    bool timed) {
   const size_t P = h->n_problems;
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  float kernel_ms = 0.0f;
-  if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
+  float kernel_ms;
+  CLC_TRY(wait_launch(h, timed, &kernel_ms));
   h->results_valid = P;
   if (!in_place) {
     std::memcpy(poses, h->h_poses, sizeof(double) * 7 * P);
     std::memcpy(summaries, h->h_summaries, sizeof(clc_summary) * P);
   }
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (size_t k = 0; k < P; ++k) {
-    summaries[k].solve_ms = ms;
-    if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
-  }
+  stamp_summaries(summaries, P, t0, timed, kernel_ms);
+  return CLC_OK;
+}
+
+// clc_solve_multistart / clc_solve_subsets: the n start poses into the multi-start staging arrays (pinned, device-mapped), room for
+// the n outcomes.  (The previous call ended with a stream synchronisation: nothing still reads or writes the staging buffers.)
+int stage_starts(clc_handle* h, const double* poses, size_t n) {
+  CLC_HIP(h->h_ms_poses.grow(7 * n));
+  CLC_HIP(h->h_ms_summaries.grow(n));
+  CLC_HIP(h->d_ms_results.grow(sizeof(clc_result_record) / sizeof(double) * n));
+  std::memcpy(h->h_ms_poses, poses, sizeof(double) * 7 * n);
   return CLC_OK;
 }
 
@@ -133,12 +200,11 @@ int ensure_lane_block_map(const char* who, clc_handle* h, size_t n_blocks, const
   static_assert(sizeof(long long) == sizeof(int64_t), "block offsets are copied as they are");
   CLC_HIP(hipMemcpyAsync(d_off.p, block_offsets, sizeof(int64_t) * (n_blocks + 1), hipMemcpyHostToDevice, h->stream));
   CLC_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(unsigned int), h->stream));
-  if (lanes == 256)
-    hipLaunchKernelGGL(clc::subset_lane_map_kernel<256>, dim3(1), dim3(256), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
+  const auto launch = [&](auto NL) {
+    hipLaunchKernelGGL(clc::subset_lane_map_kernel<NL>, dim3(1), dim3(NL), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
                        (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
-  else
-    hipLaunchKernelGGL(clc::subset_lane_map_kernel<512>, dim3(1), dim3(512), 0, h->stream, h->bres.d_desc, d_off.p, (int)n_blocks,
-                       (long long)h->batch_records, h->d_sub_lane_block, d_flag.p);
+  };
+  if (lanes == 256) launch(cint<256>); else launch(cint<512>);
   CLC_HIP(hipGetLastError());
   unsigned int flag = 0;
   CLC_HIP(hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, h->stream));
@@ -171,39 +237,20 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
   const bool in_place = poses == h->h_poses && summaries == h->h_summaries;
   if ((poses == h->h_poses) != (summaries == h->h_summaries))
     return fail(CLC_ERR_INVALID_ARG, "clc_solve_batched: pass both of the handle's host buffers or neither");
-  clc_options opt;
-  if (opt_in) opt = *opt_in; else clc_options_default(&opt);
   const size_t P = h->n_problems;
-  {
-    const int rc = batched_check_inputs("clc_solve_batched", opt, poses, P);
-    if (rc != CLC_OK) return rc;
-  }
-  CLC_HIP(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  BatchedLaunch bl;
-  {
-    const int rc = batched_launch_setup(h, opt, &bl);
-    if (rc != CLC_OK) return rc;
-  }
+  BatchedCall c;
+  CLC_TRY(begin_batched_call("clc_solve_batched", h, opt_in, poses, P, &c));
+  const clc_options& opt = c.opt;
+  const BatchedLaunch& bl = c.bl;
   const int bpp = bl.bpp;
   // (the previous batch ended with a stream synchronisation: nothing still reads or writes the staging buffers)
   if (!in_place) std::memcpy(h->h_poses, poses, sizeof(double) * 7 * P);
   if (bl.resident) {
-    // (A completion flag raised by the last workgroup to finish, polled by the host instead of this blocking synchronisation, was
-    // measured: every workgroup then needs a system-scope release before it counts itself in, which on this part writes back L2 —
-    // C4 shard 0.93 -> 1.28 ms, C3 0.150 -> 0.166.  The single-workgroup solve keeps its flag: one release per solve.)
-    const bool timed = opt.profile_events == 1;  // HIP event pair around the one launch -> clc_summary.eval_kernel_ms of every problem
-    if (timed) {
-      const int rc = ensure_events(h, 2);
-      if (rc != CLC_OK) return rc;
-      CLC_HIP(hipEventRecord(h->ev[0], h->stream));
-    }
-    launch_resident_batch(h, opt, bl, h->h_summaries.dev(), h->d_results, 0.0, nullptr, 0, 0);
-    CLC_HIP(hipGetLastError());
-    if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
-    // (kernel completion makes the outcomes written over PCIe visible; polling the stream with hipStreamQuery instead of this
-    // blocking call was measured: no difference — the 70-80 us between the kernel's end event and the return are not the wake-up)
-    return finish_batched(h, in_place, poses, summaries, t0, timed);
+    ResidentLaunch w = ResidentLaunch::whole_batch(h);
+    w.d_summaries = h->h_summaries.dev();
+    w.d_results = h->d_results;
+    CLC_TRY(launch_once(h, c.timed(), [&] { launch_resident(h, opt, bl, w); }));
+    return finish_batched(h, in_place, poses, summaries, c.t0, c.timed());
   }
   if (bl.whole_solve) {
     // one 256-thread workgroup per problem: the whole solve of every problem in ONE launch (batched_solve_kernel)
@@ -213,7 +260,7 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
                          h->d_prob_row, opt, h->h_poses.dev(), h->h_summaries.dev(), h->d_results);
     }, opt.use_loss != 0, bl.rows_nt);
     CLC_HIP(hipGetLastError());
-    return finish_batched(h, in_place, poses, summaries, t0, false);
+    return finish_batched(h, in_place, poses, summaries, c.t0, false);
   }
   const int lm_threads = bl.lm_threads;
   const unsigned lm_blocks = bl.lm_blocks;
@@ -224,7 +271,7 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
   // at the iteration cap the loop ends once every launch is consumed: batched_finish_kernel closes the stragglers
   const LaunchAhead la = {"clc_solve_batched", opt.max_num_iterations + 1, lookahead, LaunchAhead::kReturn, 60.0};
   int launched = 0;
-  int rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) {
+  const int rc = launch_ahead(h->h_mailbox, h->stream, la, [&](const int k) {
     launch_batched_eval(h, opt, bl);
     hipLaunchKernelGGL(clc::batched_lm_kernel, dim3(lm_blocks), dim3(lm_threads), 0, h->stream,
                        h->d_bpartials, bpp, h->d_states, opt, (int)P, h->d_queue, h->d_ticket, k,
@@ -238,8 +285,7 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
                        (int)P, h->h_poses.dev(), h->h_summaries.dev(), h->d_results);
     CLC_HIP(hipGetLastError());
   }
-  rc = finish_batched(h, in_place, poses, summaries, t0, false);
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(finish_batched(h, in_place, poses, summaries, c.t0, false));
   for (size_t k = 0; k < P; ++k)
     if (summaries[k].termination == CLC_RUNNING) summaries[k].termination = CLC_FAILURE;
   return CLC_OK;
@@ -255,56 +301,24 @@ int clc_solve_batched(clc_handle* h, const clc_options* opt_in, double* poses, c
 // streaming path.  Same kernel, same arithmetic as clc_solve_batched of n_starts uploaded copies: bit-identical results.
 int clc_solve_multistart(clc_handle* h, const clc_options* opt_in, size_t n_starts, double* poses, clc_summary* summaries) {
   if (!h || !poses || !summaries || n_starts == 0) return fail(CLC_ERR_INVALID_ARG, "clc_solve_multistart: bad argument");
-  if (!h->batch.d_tiles || h->n_problems != 1)
-    return fail(CLC_ERR_NO_DATA, "clc_solve_multistart: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
-  clc_options opt;
-  if (opt_in) opt = *opt_in; else clc_options_default(&opt);
-  {
-    const int rc = batched_check_inputs("clc_solve_multistart", opt, poses, n_starts);
-    if (rc != CLC_OK) return rc;
-  }
-  CLC_HIP(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  BatchedLaunch bl;
-  {
-    const int rc = batched_launch_setup(h, opt, &bl);
-    if (rc != CLC_OK) return rc;
-  }
-  if (!bl.resident) {  // the problem does not fit a workgroup (or explicit flags): one start after the other, still ONE copy of the data
-    for (size_t k = 0; k < n_starts; ++k) {
-      const int rc = clc_solve_batched(h, &opt, poses + 7 * k, summaries + k);
-      if (rc != CLC_OK) return rc;
-    }
+  CLC_TRY(require_batch_of_one("clc_solve_multistart", h));
+  BatchedCall c;
+  CLC_TRY(begin_batched_call("clc_solve_multistart", h, opt_in, poses, n_starts, &c));
+  if (!c.bl.resident) {  // the problem does not fit a workgroup (or explicit flags): one start after the other, still ONE copy of the data
+    for (size_t k = 0; k < n_starts; ++k) CLC_TRY(clc_solve_batched(h, &c.opt, poses + 7 * k, summaries + k));
     h->results_valid = 0;  // (the handle's result buffer holds the last start only: nothing for clc_gather_results)
     return CLC_OK;
   }
-  CLC_HIP(h->h_ms_poses.grow(7 * n_starts));
-  CLC_HIP(h->h_ms_summaries.grow(n_starts));
-  CLC_HIP(h->d_ms_results.grow(sizeof(clc_result_record) / sizeof(double) * n_starts));
-  // (the previous call ended with a stream synchronisation: nothing still reads or writes the staging buffers)
-  std::memcpy(h->h_ms_poses, poses, sizeof(double) * 7 * n_starts);
-  const bool timed = opt.profile_events == 1;
-  if (timed) {
-    const int rc = ensure_events(h, 2);
-    if (rc != CLC_OK) return rc;
-    CLC_HIP(hipEventRecord(h->ev[0], h->stream));
-  }
-  MultiStartLaunch ms;
-  ms.n_starts = n_starts;
-  ms.d_poses = h->h_ms_poses.dev();
-  launch_resident_batch(h, opt, bl, h->h_ms_summaries.dev(), h->d_ms_results, 0.0, nullptr, 0, 0, &ms);
-  CLC_HIP(hipGetLastError());
-  if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));  // (kernel completion makes the outcomes written over PCIe visible)
-  float kernel_ms = 0.0f;
-  if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
+  CLC_TRY(stage_starts(h, poses, n_starts));
+  ResidentLaunch w = ResidentLaunch::on_problem0(h, n_starts, h->h_ms_poses.dev());
+  w.d_summaries = h->h_ms_summaries.dev();
+  w.d_results = h->d_ms_results;
+  CLC_TRY(launch_once(h, c.timed(), [&] { launch_resident(h, c.opt, c.bl, w); }));
+  float kernel_ms;
+  CLC_TRY(wait_launch(h, c.timed(), &kernel_ms));
   std::memcpy(poses, h->h_ms_poses, sizeof(double) * 7 * n_starts);
   std::memcpy(summaries, h->h_ms_summaries, sizeof(clc_summary) * n_starts);
-  const double ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (size_t k = 0; k < n_starts; ++k) {
-    summaries[k].solve_ms = ms_wall;
-    if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
-  }
+  stamp_summaries(summaries, n_starts, c.t0, c.timed(), kernel_ms);
   for (size_t k = 0; k < n_starts; ++k)
     if (!all_finite(poses + 7 * k, 7)) return fail(CLC_ERR_NONFINITE, "clc_solve_multistart: non-finite result");
   return CLC_OK;
@@ -319,40 +333,15 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks,
                       const uint8_t* weights, double* poses, clc_summary* summaries) {
   if (!h || !block_offsets || !weights || !poses || !summaries || n_blocks == 0 || n_subsets == 0)
     return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: bad argument");
-  if (!h->batch.d_tiles || h->n_problems != 1)
-    return fail(CLC_ERR_NO_DATA, "clc_solve_subsets: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
+  CLC_TRY(require_batch_of_one("clc_solve_subsets", h));
   if (n_subsets > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: too many subsets");
-  {
-    const int rc = check_block_offsets("clc_solve_subsets", h, n_blocks, block_offsets);
-    if (rc != CLC_OK) return rc;
-  }
-  clc_options opt;
-  if (opt_in) opt = *opt_in; else clc_options_default(&opt);
-  {
-    const int rc = batched_check_inputs("clc_solve_subsets", opt, poses, n_subsets);
-    if (rc != CLC_OK) return rc;
-  }
-  CLC_HIP(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  BatchedLaunch bl;
-  {
-    const int rc = batched_launch_setup(h, opt, &bl);
-    if (rc != CLC_OK) return rc;
-  }
-  if (!bl.resident)
-    return fail(CLC_ERR_INVALID_ARG, "clc_solve_subsets: the problem is not held by one workgroup (clc_path_info.batched_resident == 0, or the "
-                                     "launch flags rule the resident kernel out): materialise the subsets and use clc_solve_batched");
-  const int lanes = h->bres.lanes;
-  {
-    const int rc = ensure_lane_block_map("clc_solve_subsets", h, n_blocks, block_offsets);
-    if (rc != CLC_OK) return rc;
-  }
-  CLC_HIP(h->h_ms_poses.grow(7 * n_subsets));
-  CLC_HIP(h->h_ms_summaries.grow(n_subsets));
-  CLC_HIP(h->d_ms_results.grow(sizeof(clc_result_record) / sizeof(double) * n_subsets));
+  CLC_TRY(check_block_offsets("clc_solve_subsets", h, n_blocks, block_offsets));
+  BatchedCall c;
+  CLC_TRY(begin_batched_call("clc_solve_subsets", h, opt_in, poses, n_subsets, &c));
+  CLC_TRY(require_resident("clc_solve_subsets", c.bl, "materialise the subsets and use clc_solve_batched"));
+  CLC_TRY(ensure_lane_block_map("clc_solve_subsets", h, n_blocks, block_offsets));
+  CLC_TRY(stage_starts(h, poses, n_subsets));
   CLC_HIP(h->h_sub_weights.grow(n_subsets * n_blocks));
-  // (the previous call ended with a stream synchronisation: nothing still reads or writes the staging buffers)
-  std::memcpy(h->h_ms_poses, poses, sizeof(double) * 7 * n_subsets);
   std::memcpy(h->h_sub_weights, weights, n_subsets * n_blocks);
   // a workgroup whose subset is empty writes nothing: its summary stays what it is set to here
   clc_summary none;
@@ -360,31 +349,17 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks,
   none.termination = CLC_FAILURE;
   none.num_evaluations = -1;  // (no written summary has it)
   for (size_t k = 0; k < n_subsets; ++k) h->h_ms_summaries[k] = none;
-  const bool timed = opt.profile_events == 1;
-  if (timed) {
-    const int rc = ensure_events(h, 2);
-    if (rc != CLC_OK) return rc;
-    CLC_HIP(hipEventRecord(h->ev[0], h->stream));
-  }
-  // the forms of launch_resident_batch: 256 lanes, 512 lanes, 512 lanes with z
-  const auto launch = [&](auto Z, auto W4, auto LOSS, auto NT) {
-    constexpr int NW = W4 ? 4 : 8;
-    constexpr int PR = Z ? kResPRz : W4 ? kResPR256 : kResPR512, PL = Z ? kResPLz : W4 ? kResPL256 : kResPL512;
-    // (the weighted form's three inputs ride in res_row, trace and trace_cap: clc_resident.hpp, WEIGHTED)
-    hipLaunchKernelGGL((clc::resident_solve_kernel<LOSS, NT, NW, PR, PL, W4 ? kResCtrl4 : kResCtrl8, Z, true>), dim3((unsigned)n_subsets),
-                       dim3(NW * 64), 0, h->stream, h->bres.d_xy, h->d_sub_lane_block, h->bres.d_desc, h->batch.d_groups, -2 - h->bres.max_ppl, opt,
-                       reinterpret_cast<clc_iteration*>(h->h_sub_weights.dev()), (int)n_blocks, h->h_ms_poses.dev(), h->h_ms_summaries.dev(),
-                       h->d_ms_results, nullptr, nullptr, 0.0, nullptr, 0, 0, Z ? h->bres.d_z : nullptr);
-  };
-  if (h->bres.with_z) with_flags(launch, std::true_type{}, std::false_type{}, opt.use_loss != 0, bl.res_nt);
-  else with_flags(launch, std::false_type{}, lanes == 256, opt.use_loss != 0, bl.res_nt);
-  CLC_HIP(hipGetLastError());
-  if (timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));  // (kernel completion makes the outcomes written over PCIe visible)
-  float kernel_ms = 0.0f;
-  if (timed) CLC_HIP(hipEventElapsedTime(&kernel_ms, h->ev[0], h->ev[1]));
+  ResidentLaunch w = ResidentLaunch::on_problem0(h, n_subsets, h->h_ms_poses.dev());
+  w.d_summaries = h->h_ms_summaries.dev();
+  w.d_results = h->d_ms_results;
+  w.d_lane_block = h->d_sub_lane_block;
+  w.n_blocks = (int)n_blocks;
+  w.d_weights = h->h_sub_weights.dev();
+  CLC_TRY(launch_once(h, c.timed(), [&] { launch_resident(h, c.opt, c.bl, w); }));
+  float kernel_ms;
+  CLC_TRY(wait_launch(h, c.timed(), &kernel_ms));
   std::memcpy(summaries, h->h_ms_summaries, sizeof(clc_summary) * n_subsets);
-  const double ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  stamp_summaries(summaries, n_subsets, c.t0, c.timed(), kernel_ms);
   for (size_t k = 0; k < n_subsets; ++k) {
     // an empty subset or a non-finite end: CLC_FAILURE in its summary, its pose left as the caller passed it — never the call's failure
     const double* out = h->h_ms_poses + 7 * k;
@@ -392,8 +367,6 @@ int clc_solve_subsets(clc_handle* h, const clc_options* opt_in, size_t n_blocks,
     if (written && all_finite(out, 7)) std::memcpy(poses + 7 * k, out, sizeof(double) * 7);
     else summaries[k].termination = CLC_FAILURE;
     if (!written) summaries[k].num_evaluations = 0;
-    summaries[k].solve_ms = ms_wall;
-    if (timed) { summaries[k].eval_kernel_ms = (double)kernel_ms; summaries[k].eval_kernel_launches = 1; }
   }
   return CLC_OK;
 }
@@ -408,33 +381,15 @@ int clc_score_blocks(clc_handle* h, const clc_options* opt_in, size_t n_blocks, 
                      const double* poses, double tau, double* ssq, double* cost, int32_t* inliers) {
   if (!h || !block_offsets || !poses || n_blocks == 0 || n_poses == 0 || tau != tau)
     return fail(CLC_ERR_INVALID_ARG, "clc_score_blocks: bad argument");
-  if (!h->batch.d_tiles || h->n_problems != 1)
-    return fail(CLC_ERR_NO_DATA, "clc_score_blocks: the shared observations must be uploaded as a batch of ONE problem (clc_upload_batched, n_problems = 1)");
+  CLC_TRY(require_batch_of_one("clc_score_blocks", h));
   if (n_poses > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_score_blocks: too many poses");
-  {
-    const int rc = check_block_offsets("clc_score_blocks", h, n_blocks, block_offsets);
-    if (rc != CLC_OK) return rc;
-  }
-  clc_options opt;
-  if (opt_in) opt = *opt_in; else clc_options_default(&opt);
-  {
-    // the options as clc_solve_batched checks them; a non-finite pose is not an error here: its row reports NaN / NaN / 0
-    const int rc = batched_check_inputs("clc_score_blocks", opt, poses, 0);
-    if (rc != CLC_OK) return rc;
-  }
-  CLC_HIP(hipSetDevice(h->device));
-  BatchedLaunch bl;
-  {
-    const int rc = batched_launch_setup(h, opt, &bl);
-    if (rc != CLC_OK) return rc;
-  }
-  if (!bl.resident)
-    return fail(CLC_ERR_INVALID_ARG, "clc_score_blocks: the problem is not held by one workgroup (clc_path_info.batched_resident == 0, or the "
-                                     "launch flags rule the resident kernel out): score the poses one by one with clc_factor_evaluate");
-  {
-    const int rc = ensure_lane_block_map("clc_score_blocks", h, n_blocks, block_offsets);
-    if (rc != CLC_OK) return rc;
-  }
+  CLC_TRY(check_block_offsets("clc_score_blocks", h, n_blocks, block_offsets));
+  // the options as clc_solve_batched checks them; a non-finite pose is not an error here: its row reports NaN / NaN / 0
+  BatchedCall c;
+  CLC_TRY(begin_batched_call("clc_score_blocks", h, opt_in, poses, 0, &c));
+  const clc_options& opt = c.opt;
+  CLC_TRY(require_resident("clc_score_blocks", c.bl, "score the poses one by one with clc_factor_evaluate"));
+  CLC_TRY(ensure_lane_block_map("clc_score_blocks", h, n_blocks, block_offsets));
   const size_t cells = n_poses * n_blocks;
   CLC_HIP(h->h_ms_poses.grow(7 * n_poses));
   CLC_HIP(h->h_flow.grow(2 * cells + (cells + 1) / 2));  // [ssq | cost | inliers (int32)]

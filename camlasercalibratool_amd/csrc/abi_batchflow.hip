@@ -32,10 +32,7 @@ int flow_check(clc_handle* h, const char* who) {
 extern "C" {
 
 int clc_closed_form_batched(clc_handle* h, double* poses, double* Tlc, int32_t* unobservable, double* sv9, int32_t* status) {
-  {
-    const int rc = flow_check(h, "clc_closed_form_batched");
-    if (rc != CLC_OK) return rc;
-  }
+  CLC_TRY(flow_check(h, "clc_closed_form_batched"));
   if (!status) return fail(CLC_ERR_INVALID_ARG, "clc_closed_form_batched: status is required");
   CLC_HIP(hipSetDevice(h->device));
   const size_t P = h->n_problems;
@@ -46,12 +43,10 @@ int clc_closed_form_batched(clc_handle* h, double* poses, double* Tlc, int32_t* 
   CLC_HIP(h->d_bpartials.grow(n_blocks * clc::NACC9));
   CLC_HIP(h->h_flow.grow(P * clc::bf::CF_OUT));
   if (rows) {  // 16 B per point; rows that carry z: bar_p = (x, y, 1), only the row stride differs
-    if (h->batch.rows_z)
-      hipLaunchKernelGGL((clc::bf::bf_normal9_rows_kernel<clc::ROW_DOUBLES_Z>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream,
-                         h->batch.d_rxy, h->batch.d_rdesc(), h->d_prob_row, bpp, h->d_bpartials);
-    else
-      hipLaunchKernelGGL((clc::bf::bf_normal9_rows_kernel<clc::ROW_DOUBLES>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream,
-                         h->batch.d_rxy, h->batch.d_rdesc(), h->d_prob_row, bpp, h->d_bpartials);
+    with_flags([&](auto Z) {
+      hipLaunchKernelGGL((clc::bf::bf_normal9_rows_kernel<Z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0,
+                         h->stream, h->batch.d_rxy, h->batch.d_rdesc(), h->d_prob_row, bpp, h->d_bpartials);
+    }, h->batch.rows_z);
   } else {
     hipLaunchKernelGGL(clc::bf::bf_normal9_tiles_kernel, dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream, h->batch.d_tiles,
                        h->d_tile_off, h->d_nobs, bpp, h->d_bpartials);
@@ -76,17 +71,13 @@ int clc_closed_form_batched(clc_handle* h, double* poses, double* Tlc, int32_t* 
 
 int clc_information_batched(clc_handle* h, const double* poses, double* H, double* b, double* chi2, double* sv, double* V,
                             int32_t* n_null) {
-  {
-    const int rc = flow_check(h, "clc_information_batched");
-    if (rc != CLC_OK) return rc;
-  }
+  CLC_TRY(flow_check(h, "clc_information_batched"));
   if (!poses || !chi2 || !sv || !n_null) return fail(CLC_ERR_INVALID_ARG, "clc_information_batched: bad argument");
   const size_t P = h->n_problems;
   {
     clc_options opt;
     clc_options_default(&opt);
-    const int rc = batched_check_inputs("clc_information_batched", opt, poses, P);
-    if (rc != CLC_OK) return rc;
+    CLC_TRY(batched_check_inputs("clc_information_batched", opt, poses, P));
   }
   CLC_HIP(hipSetDevice(h->device));
   const bool rows = h->batch.rows_ok;
@@ -105,12 +96,10 @@ int clc_information_batched(clc_handle* h, const double* poses, double* H, doubl
     d_poses = h->h_flow.dev() + P * clc::bf::INFO_OUT;
   }
   if (rows) {
-    if (h->batch.rows_z)
-      hipLaunchKernelGGL((clc::bf::bf_info_rows_kernel<true>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream, h->batch.d_rxy,
+    with_flags([&](auto Z) {
+      hipLaunchKernelGGL((clc::bf::bf_info_rows_kernel<Z>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream, h->batch.d_rxy,
                          h->batch.d_rdesc(), h->d_prob_row, d_poses, bpp, h->d_bpartials);
-    else
-      hipLaunchKernelGGL((clc::bf::bf_info_rows_kernel<false>), dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream, h->batch.d_rxy,
-                         h->batch.d_rdesc(), h->d_prob_row, d_poses, bpp, h->d_bpartials);
+    }, h->batch.rows_z);
   } else {
     hipLaunchKernelGGL(clc::bf::bf_info_tiles_kernel, dim3((unsigned)n_blocks), dim3(clc::BLOCK), 0, h->stream, h->batch.d_tiles, h->d_tile_off,
                        h->d_nobs, d_poses, bpp, h->d_bpartials);

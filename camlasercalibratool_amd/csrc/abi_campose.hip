@@ -18,13 +18,6 @@ int camera_check(const clc_camera* c, const char* who) {
   return CLC_OK;
 }
 
-int pose_options(const clc_options* in, clc_options* o, const char* who) {
-  if (in) *o = *in; else clc_pose_options_default(o);
-  if (o->max_num_iterations < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": max_num_iterations < 0").c_str());
-  if (o->use_loss) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": the pose refinement has no loss (use_loss must be 0)").c_str());
-  return CLC_OK;
-}
-
 unsigned lift_blocks(size_t n) { return (unsigned)((n + clc::cp::LIFT_THREADS - 1) / clc::cp::LIFT_THREADS); }
 
 // lift (rounded) into lifted_dev[2 * n_corners] (corner `first` first), then one wave per image; every array on the device, offsets
@@ -59,10 +52,7 @@ void clc_pose_options_default(clc_options* o) {
 
 int clc_camera_lift(clc_handle* h, const clc_camera* cam, const float* px, size_t n, double* xy_norm) {
   if (!h || (n > 0 && (!px || !xy_norm))) return fail(CLC_ERR_INVALID_ARG, "clc_camera_lift: bad argument");
-  {
-    const int rc = camera_check(cam, "clc_camera_lift");
-    if (rc != CLC_OK) return rc;
-  }
+  CLC_TRY(camera_check(cam, "clc_camera_lift"));
   if (n == 0) return CLC_OK;
   if (n > 0x3FFFFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_camera_lift: too many points");
   CLC_HIP(hipSetDevice(h->device));
@@ -81,10 +71,7 @@ int clc_camera_lift(clc_handle* h, const clc_camera* cam, const float* px, size_
 
 int clc_camera_project(clc_handle* h, const clc_camera* cam, const double pose7[7], const double* pts, size_t n, double* px) {
   if (!h || (n > 0 && (!pts || !px))) return fail(CLC_ERR_INVALID_ARG, "clc_camera_project: bad argument");
-  {
-    const int rc = camera_check(cam, "clc_camera_project");
-    if (rc != CLC_OK) return rc;
-  }
+  CLC_TRY(camera_check(cam, "clc_camera_project"));
   clc::cp::Pose7Arg pose{};
   if (pose7) {
     for (int i = 0; i < 7; ++i) {
@@ -112,22 +99,17 @@ int clc_board_poses(clc_handle* h, const clc_camera* cam, const clc_options* opt
                     clc_summary* summaries) {
   if (!h || (n_images > 0 && (!offsets || !q_ca_wxyz || !t_ca || !status)))
     return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: bad argument");
-  int rc = camera_check(cam, "clc_board_poses");
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(camera_check(cam, "clc_board_poses"));
   clc_options opt;
-  rc = pose_options(opt_in, &opt, "clc_board_poses");
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(pose_options(opt_in, &opt, "clc_board_poses"));
   if (n_images == 0) return CLC_OK;
   if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: too many images");
-  if (offsets[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: negative offset");
-  for (size_t k = 0; k < n_images; ++k)
-    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: offsets not monotone");
-  const size_t M = (size_t)(offsets[n_images] - offsets[0]);
+  std::vector<long long> rel;
+  size_t M;
+  CLC_TRY(host_offsets("clc_board_poses", offsets, n_images, true, nullptr, &rel, &M));
   if (M > 0 && (!corners_px || !board_xy)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: bad argument");
   CLC_HIP(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
-  std::vector<long long> rel(n_images + 1);
-  for (size_t k = 0; k <= n_images; ++k) rel[k] = offsets[k] - offsets[0];
   DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool);
   DevBuf<long long> boff(&h->pool);
   DevBuf<double> bq(&h->pool), bt(&h->pool), br(&h->pool);
@@ -162,11 +144,9 @@ int clc_board_poses_device(clc_handle* h, const clc_camera* cam, const clc_optio
                            double* t_ca_dev, double* rms_dev, int32_t* status_dev, clc_summary* summaries_dev) {
   if (!h || (n_images > 0 && (!offsets_dev || !q_ca_wxyz_dev || !t_ca_dev || !status_dev)))
     return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: bad argument");
-  int rc = camera_check(cam, "clc_board_poses_device");
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(camera_check(cam, "clc_board_poses_device"));
   clc_options opt;
-  rc = pose_options(opt_in, &opt, "clc_board_poses_device");
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(pose_options(opt_in, &opt, "clc_board_poses_device"));
   if (n_images == 0) return CLC_OK;
   if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: too many images");
   static_assert(sizeof(long long) == sizeof(int64_t), "offset type");

@@ -1,6 +1,6 @@
 // abi_comm.hip — multi-GPU: RCCL all-gather of the sharded batch's result records.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "clc_abi_internal.hpp"
+#include "abi_drive.hpp"
 
 using namespace clc_abi;
 
@@ -368,7 +368,7 @@ int step_enqueue(clc_comm* c, const clc_options& opt, const double* poses0, int6
   CLC_HIP(hipSetDevice(h->device));
   BatchedLaunch bl;
   if (P > 0 && fl.local_rc == CLC_OK) {
-    const int rc = batched_launch_setup(h, opt, &bl);
+    const int rc = batched_launch_setup(h, &bl);
     if (rc != CLC_OK) local_fail(rc, clc_last_error());
   }
   if (P > 0 && fl.local_rc == CLC_OK && !bl.resident) { fl.fused = false; return CLC_OK; }
@@ -400,7 +400,13 @@ int step_enqueue(clc_comm* c, const clc_options& opt, const double* poses0, int6
   if (fl.n_local > 0) {
     if (fl.timed) CLC_HIP(hipEventRecord(h->ev[0], h->stream));
     // the last workgroup to finish (totals' arrival count == goal) copies the totals to the host twin
-    launch_resident_batch(h, opt, bl, nullptr, c->d_base, (double)first_global_index, c->h_base[tw].dev(), seg_off, c->stats_seen[3] + (unsigned long long)P);
+    ResidentLaunch rl = ResidentLaunch::whole_batch(h);  // (records only: no summaries)
+    rl.d_results = c->d_base;
+    rl.rec_base = (double)first_global_index;
+    rl.rec_host = c->h_base[tw].dev();
+    rl.seg_off = seg_off;
+    rl.goal = c->stats_seen[3] + (unsigned long long)P;
+    launch_resident(h, opt, bl, rl);
     if (hipGetLastError() != hipSuccess) { local_fail(CLC_ERR_HIP, w + ": kernel launch failed (this rank's records are undefined)"); fl.n_local = 0; }
     else if (fl.timed) CLC_HIP(hipEventRecord(h->ev[1], h->stream));
   }

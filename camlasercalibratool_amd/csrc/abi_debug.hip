@@ -1,6 +1,6 @@
 // abi_debug.hip — test and profiling hooks (clc_debug_*, clc_time_*): NOT part of include/clc.h and not in the product library — this unit is empty without -DCLC_TEST_HOOKS.
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "clc_abi_internal.hpp"
+#include "abi_drive.hpp"
 
 using namespace clc_abi;
 
@@ -226,7 +226,7 @@ int clc_time_batched_eval(clc_handle* h, const double* poses, int reps, double* 
   clc_options opt;
   clc_options_default(&opt);
   BatchedLaunch bl;
-  rc = batched_launch_setup(h, opt, &bl);
+  rc = batched_launch_setup(h, &bl);
   if (rc != CLC_OK) return rc;
   const size_t P = h->n_problems;
   std::memcpy(h->h_poses, poses, sizeof(double) * 7 * P);

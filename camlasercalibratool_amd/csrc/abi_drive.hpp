@@ -1,11 +1,13 @@
-// abi_drive.hpp — host-side pieces of the solve drivers (abi_solve.hip, abi_batched.hip): run-time flags to template arguments,
-// and the launch-ahead loop on the pinned mailbox.  Host code only (no kernel is defined or changed here): _build.csrc_sha16(),
-// the identity of what the kernels are built from, does not cover this file.
+// abi_drive.hpp — host-side pieces the units of the C-ABI share: run-time flags to template arguments, the launch-ahead loop on
+// the pinned mailbox (abi_solve.hip, abi_batched.hip), the one launcher of the batched resident kernel (abi_batched.hip, abi_comm.hip),
+// and the front end's checks of options and host CSR offsets (abi_frontend.hip, abi_campose.hip).  Host code only (no kernel is
+// defined or changed here): _build.csrc_sha16(), the identity of what the kernels are built from, does not cover this file.
 #pragma once
 #include "clc_abi_internal.hpp"
 
 #include <string>
 #include <type_traits>
+#include <vector>
 
 namespace clc_abi {
 
@@ -80,6 +82,81 @@ int launch_ahead(clc::HostMailbox* mb, hipStream_t stream, const LaunchAhead& p,
         return fail(CLC_ERR_HIP, (std::string(p.who) + ": no progress from the device for " + std::to_string((int)p.stall_s) + " s").c_str());
     }
   }
+}
+
+// as CLC_HIP, for the calls that return CLC_OK or an error already set (fail)
+#define CLC_TRY(expr)                      \
+  do {                                     \
+    const int rc_ = (expr);                \
+    if (rc_ != CLC_OK) return rc_;         \
+  } while (0)
+
+// ---- abi_batched.hip ----
+// The launch plan of the handle's batch under its flags (plan_batched), the partial rows grown to it.
+int batched_launch_setup(clc_handle* h, BatchedLaunch* bl);
+
+// ONE launch of resident_solve_kernel on the handle's lane layout (bl.resident), on the handle's stream: what it works on.  Every
+// batched launch of that kernel is made by launch_resident (clc_solve_batched, clc_solve_multistart, clc_solve_subsets, the
+// communicator's step) — it supersedes launch_resident_batch / MultiStartLaunch, which clc_abi_internal.hpp still declares (that
+// header is part of csrc_sha16: the declarations, defined nowhere, go with the next change that re-measures the kernels).
+struct ResidentLaunch {
+  size_t workgroups = 0;       // one per problem of the batch; or one per start / subset, every one of them on problem 0's layout
+  double* d_poses = nullptr;   // start poses in, results out
+  int uni_ppl = -1;            // resident_solve_kernel's: the batch's (h->bres.uni_ppl), or <= -2: every workgroup on problem 0
+  // outcomes into d_poses / d_summaries / d_results; d_summaries == nullptr: the records-only form (clc_solve_batched_gather) —
+  // d_results / rec_host = the communicator's gather buffer and its pinned host twin ([totals record][gathered array]), this rank's
+  // segment seg_off doubles into the array, global index rec_base + k, goal = the totals' arrival count at the end of this launch
+  // (batched_write_record, clc_kernels.hpp)
+  clc_summary* d_summaries = nullptr;
+  double* d_results = nullptr;
+  double rec_base = 0.0;
+  double* rec_host = nullptr;
+  long long seg_off = 0;
+  unsigned long long goal = 0;
+  // d_weights != nullptr: the weighted form (clc_solve_subsets; on problem 0 only) — the lane -> block map, the number of blocks, the
+  // weight rows [workgroups * n_blocks]
+  const unsigned int* d_lane_block = nullptr;
+  int n_blocks = 0;
+  uint8_t* d_weights = nullptr;
+
+  // a workgroup per uploaded problem, start poses in the handle's pinned buffer / n workgroups on problem 0, each from its own pose
+  static ResidentLaunch whole_batch(const clc_handle* h) { return {h->n_problems, h->h_poses.dev(), h->bres.uni_ppl}; }
+  static ResidentLaunch on_problem0(const clc_handle* h, size_t n, double* d_poses) { return {n, d_poses, -2 - h->bres.max_ppl}; }
+};
+void launch_resident(clc_handle* h, const clc_options& opt, const BatchedLaunch& bl, const ResidentLaunch& w);
+
+// ---- the front end's argument checks (abi_frontend.hip, abi_campose.hip) ----
+// CSR offsets [n + 1] given on the host: checked in the order every caller reports — (first_nonneg) offsets[0] >= 0, then scan by
+// scan: not decreasing, and (span_unit != nullptr) fewer than 2^31 of them in the scan — and rebased: rel[k] = offsets[k] - offsets[0],
+// *total = rel[n].  n == 0: offsets is not read (rel = {0}).  CLC_OK or the error set, its text beginning with `who`.
+inline int host_offsets(const char* who, const int64_t* offsets, size_t n, bool first_nonneg, const char* span_unit,
+                        std::vector<long long>* rel, size_t* total) {
+  const std::string w(who);
+  if (n > 0 && first_nonneg && offsets[0] < 0) return fail(CLC_ERR_INVALID_ARG, (w + ": negative offset").c_str());
+  for (size_t k = 0; k < n; ++k) {
+    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, (w + ": offsets not monotone").c_str());
+    if (span_unit && offsets[k + 1] - offsets[k] > 0x7FFFFFFF)
+      return fail(CLC_ERR_INVALID_ARG, (w + ": a scan has 2^31 " + span_unit + " or more").c_str());
+  }
+  rel->assign(n + 1, 0);  // (after the checks: n itself may be what is wrong)
+  for (size_t k = 1; k <= n; ++k) (*rel)[k] = offsets[k] - offsets[0];
+  *total = (size_t)rel->back();
+  return CLC_OK;
+}
+
+// The options of a line fit / of a board-pose refinement: the caller's, or the call's defaults; checked.
+inline int line_options(const clc_options* in, clc_options* o, const char* who) {
+  if (in) *o = *in; else clc_line_options_default(o);
+  if (o->max_num_iterations < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": max_num_iterations < 0").c_str());
+  if (o->use_loss && !(o->loss_scale_factor > 0.0))
+    return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": loss_scale_factor must be > 0").c_str());
+  return CLC_OK;
+}
+inline int pose_options(const clc_options* in, clc_options* o, const char* who) {
+  if (in) *o = *in; else clc_pose_options_default(o);
+  if (o->max_num_iterations < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": max_num_iterations < 0").c_str());
+  if (o->use_loss) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": the pose refinement has no loss (use_loss must be 0)").c_str());
+  return CLC_OK;
 }
 
 }  // namespace clc_abi

@@ -96,8 +96,7 @@ int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9
   CLC_HIP(hipSetDevice(h->device));
   const StreamPlan sp = stream_plan(h);
   const int grid = sp.grid;
-  int rc = ensure_partials(h, grid);
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(ensure_partials(h, grid));
   if (sp.rows()) {  // rows that carry z: bar_p = (x, y, 1) — z is not read, only the row stride differs
     with_flags([&](auto Z, auto NT) {
       hipLaunchKernelGGL((clc::normal9_rows_kernel<NT, Z ? clc::ROW_DOUBLES_Z : clc::ROW_DOUBLES>), dim3(grid), dim3(clc::BLOCK), 0, h->stream,
@@ -123,12 +122,31 @@ int clc_closed_form(clc_handle* h, double Tlc[16], int* unobservable, double sv9
         for (int rj = 0; rj < 3; ++rj) AtA[9 * (3 * ci + ri) + (3 * cj + rj)] = r[6 * tri3(ci, cj) + tri3(ri, rj)];
       Atb[3 * ci + ri] = r[36 + 3 * ci + ri];
     }
-  rc = clc::host::closed_form_from_normal(AtA, Atb, Tlc, unobservable, sv9);
+  const int rc = clc::host::closed_form_from_normal(AtA, Atb, Tlc, unobservable, sv9);
   if (rc != CLC_OK) return fail(rc, "clc_closed_form: non-finite solution of the 9x9 normal equation");
   return CLC_OK;
 }
 
+}  // extern "C"
+
 // ---- line fitting ---------------------------------------------------------------------------
+namespace {
+// K6 on device arrays, enqueued on the handle's stream (no wait)
+void launch_line_fit(clc_handle* h, const clc_options& opt, const double* xy_dev, const long long* d_off, size_t n_scans, double* lines_dev,
+                     clc_summary* summaries_dev) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
+  const unsigned blocks = (unsigned)((n_scans + clc::LINE_SCANS_PER_BLOCK - 1) / clc::LINE_SCANS_PER_BLOCK);
+  if (opt.use_loss)
+    hipLaunchKernelGGL((clc::line_fit_kernel<true>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
+                       (int)n_scans, opt, lines_dev, summaries_dev);
+  else
+    hipLaunchKernelGGL((clc::line_fit_kernel<false>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
+                       (int)n_scans, opt, lines_dev, summaries_dev);
+}
+}  // namespace
+
+extern "C" {
+
 void clc_line_options_default(clc_options* o) {
   clc_options_default(o);
   if (!o) return;
@@ -141,21 +159,16 @@ int clc_line_fit_batched(clc_handle* h, const clc_options* opt_in, const double*
   if (!h || !offsets || !lines || (n_scans > 0 && offsets[n_scans] > offsets[0] && !xy))
     return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched: bad argument");
   clc_options opt;
-  if (opt_in) opt = *opt_in; else clc_line_options_default(&opt);
-  if (opt.max_num_iterations < 0) return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched: max_num_iterations < 0");
-  if (opt.use_loss && !(opt.loss_scale_factor > 0.0))
-    return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched: loss_scale_factor must be > 0");
+  CLC_TRY(line_options(opt_in, &opt, "clc_line_fit_batched"));
   if (n_scans == 0) return CLC_OK;
   if (n_scans > 0x7FFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched: too many scans");
-  for (size_t k = 0; k < n_scans; ++k)
-    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched: offsets not monotone");
+  std::vector<long long> rel;
+  size_t n_pts;
+  CLC_TRY(host_offsets("clc_line_fit_batched", offsets, n_scans, false, nullptr, &rel, &n_pts));
   for (size_t i = 0; i < 2 * n_scans; ++i)
     if (!std::isfinite(lines[i])) return fail(CLC_ERR_NONFINITE, "clc_line_fit_batched: non-finite initial line");
   CLC_HIP(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
-  const size_t n_pts = (size_t)(offsets[n_scans] - offsets[0]);
-  std::vector<long long> rel(n_scans + 1);
-  for (size_t k = 0; k <= n_scans; ++k) rel[k] = offsets[k] - offsets[0];
   DevBuf<double> bxy(&h->pool), blines(&h->pool);
   DevBuf<long long> boff(&h->pool);
   DevBuf<clc_summary> bsum(&h->pool);
@@ -163,28 +176,14 @@ int clc_line_fit_batched(clc_handle* h, const clc_options* opt_in, const double*
   CLC_HIP(boff.alloc(n_scans + 1));
   CLC_HIP(blines.alloc(n_scans * 2));
   if (summaries) CLC_HIP(bsum.alloc(n_scans));
-  double *d_xy = bxy.p, *d_lines = blines.p;
-  long long* d_off = boff.p;
-  clc_summary* d_sum = bsum.p;
-  hipError_t e = hipSuccess;
-  if (n_pts > 0) e = hipMemcpyAsync(d_xy, xy + 2 * offsets[0], n_pts * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_off, rel.data(), (n_scans + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_lines, lines, n_scans * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) {
-    const unsigned blocks = (unsigned)((n_scans + clc::LINE_SCANS_PER_BLOCK - 1) / clc::LINE_SCANS_PER_BLOCK);
-    if (opt.use_loss)
-      hipLaunchKernelGGL((clc::line_fit_kernel<true>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, d_xy, d_off,
-                         (int)n_scans, opt, d_lines, d_sum);
-    else
-      hipLaunchKernelGGL((clc::line_fit_kernel<false>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, d_xy, d_off,
-                         (int)n_scans, opt, d_lines, d_sum);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(lines, d_lines, n_scans * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && summaries)
-    e = hipMemcpyAsync(summaries, d_sum, n_scans * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(CLC_ERR_HIP, "clc_line_fit_batched", e);
+  if (n_pts > 0) CLC_HIP(hipMemcpyAsync(bxy.p, xy + 2 * offsets[0], n_pts * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n_scans + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemcpyAsync(blines.p, lines, n_scans * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  launch_line_fit(h, opt, bxy.p, boff.p, n_scans, blines.p, bsum.p);
+  CLC_HIP(hipGetLastError());
+  CLC_HIP(hipMemcpyAsync(lines, blines.p, n_scans * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (summaries) CLC_HIP(hipMemcpyAsync(summaries, bsum.p, n_scans * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
   if (summaries) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (size_t k = 0; k < n_scans; ++k) summaries[k].solve_ms = ms;
@@ -199,15 +198,13 @@ int clc_scan_to_points(clc_handle* h, const float* ranges, const int64_t* offset
     return fail(CLC_ERR_INVALID_ARG, "clc_scan_to_points: bad argument");
   if (n_scans == 0) return CLC_OK;
   if (n_scans > 65535) return fail(CLC_ERR_INVALID_ARG, "clc_scan_to_points: at most 65535 scans per call");
-  for (size_t k = 0; k < n_scans; ++k)
-    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_scan_to_points: offsets not monotone");
-  const size_t n = (size_t)(offsets[n_scans] - offsets[0]);
+  std::vector<long long> rel;
+  size_t n;
+  CLC_TRY(host_offsets("clc_scan_to_points", offsets, n_scans, false, nullptr, &rel, &n));
   if (n == 0) return CLC_OK;
   if (!ranges || !points) return fail(CLC_ERR_INVALID_ARG, "clc_scan_to_points: bad argument");
   CLC_HIP(hipSetDevice(h->device));
-  std::vector<long long> rel(n_scans + 1);
   long long longest = 0;
-  for (size_t k = 0; k <= n_scans; ++k) rel[k] = offsets[k] - offsets[0];
   for (size_t k = 0; k < n_scans; ++k) longest = std::max(longest, rel[k + 1] - rel[k]);
   DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
   DevBuf<long long> boff(&h->pool);
@@ -229,34 +226,12 @@ int clc_scan_to_points(clc_handle* h, const float* ranges, const int64_t* offset
   return CLC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-// K6 on device arrays, enqueued on the handle's stream (no wait)
-void launch_line_fit(clc_handle* h, const clc_options& opt, const double* xy_dev, const long long* d_off, size_t n_scans, double* lines_dev,
-                     clc_summary* summaries_dev) {
-  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
-  const unsigned blocks = (unsigned)((n_scans + clc::LINE_SCANS_PER_BLOCK - 1) / clc::LINE_SCANS_PER_BLOCK);
-  if (opt.use_loss)
-    hipLaunchKernelGGL((clc::line_fit_kernel<true>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
-                       (int)n_scans, opt, lines_dev, summaries_dev);
-  else
-    hipLaunchKernelGGL((clc::line_fit_kernel<false>), dim3(blocks), dim3(clc::BLOCK), 0, h->stream, xy_dev, d_off,
-                       (int)n_scans, opt, lines_dev, summaries_dev);
-}
-}  // namespace
-
-extern "C" {
-
 int clc_line_fit_batched_device(clc_handle* h, const clc_options* opt_in, const double* xy_dev, const int64_t* offsets_dev,
                                 size_t n_scans, double* lines_dev, clc_summary* summaries_dev) {
   if (!h || (n_scans > 0 && (!offsets_dev || !lines_dev || !xy_dev)))
     return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched_device: bad argument");
   clc_options opt;
-  if (opt_in) opt = *opt_in; else clc_line_options_default(&opt);
-  if (opt.max_num_iterations < 0) return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched_device: max_num_iterations < 0");
-  if (opt.use_loss && !(opt.loss_scale_factor > 0.0))
-    return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched_device: loss_scale_factor must be > 0");
+  CLC_TRY(line_options(opt_in, &opt, "clc_line_fit_batched_device"));
   if (n_scans == 0) return CLC_OK;
   if (n_scans > 0x7FFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_line_fit_batched_device: too many scans");
   CLC_HIP(hipSetDevice(h->device));
@@ -300,15 +275,11 @@ int clc_board_segments(clc_handle* h, const double* points, const int64_t* offse
     return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: bad argument");
   if (n_scans == 0) return CLC_OK;
   if (n_scans > 0x1FFFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: too many scans");
-  for (size_t k = 0; k < n_scans; ++k) {
-    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: offsets not monotone");
-    if (offsets[k + 1] - offsets[k] > 0x7FFFFFFF) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: a scan has 2^31 points or more");
-  }
-  const size_t n_pts = (size_t)(offsets[n_scans] - offsets[0]);
+  std::vector<long long> rel;
+  size_t n_pts;
+  CLC_TRY(host_offsets("clc_board_segments", offsets, n_scans, false, "points", &rel, &n_pts));
   if (n_pts > 0 && !points) return fail(CLC_ERR_INVALID_ARG, "clc_board_segments: bad argument");
   CLC_HIP(hipSetDevice(h->device));
-  std::vector<long long> rel(n_scans + 1);
-  for (size_t k = 0; k <= n_scans; ++k) rel[k] = offsets[k] - offsets[0];
   DevBuf<double> bp(&h->pool);
   DevBuf<long long> boff(&h->pool), bseg(&h->pool);
   DevBuf<int32_t> bst(&h->pool);
@@ -316,17 +287,13 @@ int clc_board_segments(clc_handle* h, const double* points, const int64_t* offse
   CLC_HIP(boff.alloc(n_scans + 1));
   CLC_HIP(bseg.alloc(2 * n_scans));
   if (status) CLC_HIP(bst.alloc(n_scans));
-  hipError_t e = hipSuccess;
-  if (n_pts > 0) e = hipMemcpyAsync(bp.p, points + 3 * offsets[0], 3 * n_pts * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(boff.p, rel.data(), (n_scans + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) {
-    launch_board_segments(h, bp.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, reinterpret_cast<int64_t*>(bseg.p), status ? bst.p : nullptr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(seg, bseg.p, 2 * n_scans * sizeof(long long), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && status) e = hipMemcpyAsync(status, bst.p, n_scans * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(CLC_ERR_HIP, "clc_board_segments", e);
+  if (n_pts > 0) CLC_HIP(hipMemcpyAsync(bp.p, points + 3 * offsets[0], 3 * n_pts * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n_scans + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  launch_board_segments(h, bp.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, reinterpret_cast<int64_t*>(bseg.p), status ? bst.p : nullptr);
+  CLC_HIP(hipGetLastError());
+  CLC_HIP(hipMemcpyAsync(seg, bseg.p, 2 * n_scans * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  if (status) CLC_HIP(hipMemcpyAsync(status, bst.p, n_scans * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
   return CLC_OK;
 }
 
@@ -438,8 +405,7 @@ int assemble_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_
   StoreFacts f;  // scan points have z = 0 (TranScanToPoints), the points on the line too; points_on_line is never the points
   f.tag_q = tq.data();
   f.tag_t = tt.data();
-  const int rc = adopt_store(h, (int)P, f);
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(adopt_store(h, (int)P, f));
   if (info) {
     info->n_keyframes = c[clc::ASM_N_KEYFRAMES];
     info->n_segments = c[clc::ASM_N_SEGMENTS];
@@ -469,8 +435,7 @@ int clc_keyframes(clc_handle* h, const clc_assemble_options* opt_in, size_t n_po
                   uint8_t* keep, int64_t* n_kept) {
   if (!h || (n_poses > 0 && (!q_wc_wxyz || !t_wc)) || n_poses > 0x7FFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_keyframes: bad argument");
   clc_assemble_options opt;
-  int rc = check_assemble_options("clc_keyframes: bad options", opt_in, &opt);
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(check_assemble_options("clc_keyframes: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
   DevBuf<double> bq(&h->pool), bt(&h->pool);
   DevBuf<unsigned char> bkeep(&h->pool);
@@ -503,8 +468,7 @@ int clc_assemble_observations_device(clc_handle* h, const clc_assemble_options* 
       (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
     return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations_device: bad argument");
   clc_assemble_options opt;
-  const int rc = check_assemble_options("clc_assemble_observations_device: bad options", opt_in, &opt);
-  if (rc != CLC_OK) return rc;
+  CLC_TRY(check_assemble_options("clc_assemble_observations_device: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
   return assemble_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays, angle_min_dev,
                             angle_increment_dev, range_min_dev, scan_stamp_dev, scan_pose_dev, nullptr, info);
@@ -519,16 +483,10 @@ int clc_assemble_observations(clc_handle* h, const clc_assemble_options* opt_in,
       n_scans > 0x7FFFFFF0ull)
     return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: bad argument");
   clc_assemble_options opt;
-  const int rc = check_assemble_options("clc_assemble_observations: bad options", opt_in, &opt);
-  if (rc != CLC_OK) return rc;
-  if (n_scans > 0 && offsets[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: negative offset");
-  std::vector<long long> rel(n_scans + 1, 0);
-  for (size_t k = 0; k < n_scans; ++k) {
-    if (offsets[k + 1] < offsets[k]) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: offsets not monotone");
-    if (offsets[k + 1] - offsets[k] > 0x7FFFFFFF) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: a scan has 2^31 rays or more");
-    rel[k + 1] = offsets[k + 1] - offsets[0];
-  }
-  const size_t n_rays = (size_t)rel[n_scans];
+  CLC_TRY(check_assemble_options("clc_assemble_observations: bad options", opt_in, &opt));
+  std::vector<long long> rel;
+  size_t n_rays;
+  CLC_TRY(host_offsets("clc_assemble_observations", offsets, n_scans, true, "rays", &rel, &n_rays));
   if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: NULL ranges");
   CLC_HIP(hipSetDevice(h->device));
   DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);

@@ -300,3 +300,59 @@ def _build_subsets_exe():
                                "-I", os.path.join(ROOT, "tests", "dropin", "eigen_stub"), src, "-o", exe,
                                "-L", lib_dir, "-lclc_hip", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"])
     return exe
+
+
+FLAG_RESIDENT_WG512 = 8192     # clc_set_launch: the 512-lane form even where 256 lanes hold the problem (include/clc.h)
+
+
+@pytest.mark.parametrize("use_loss", [True, False], ids=["loss", "no-loss"])
+@pytest.mark.parametrize("form", [256, 512, "z"])
+def test_subsets_in_every_form_of_the_launch(oracle_mod, form, use_loss):
+    """The three forms the weighted launch takes — 256 lanes, 512 lanes by launch flag 8192, 512 lanes with z (ONE record with p.z != 0)
+    — each with and without the loss, at the smallest shape: 6 blocks of one scan each, 4 weight rows, one of them empty.  Every
+    solved row against clc_solve_batched of the materialised subsets: the rows of weights 0 / 1 that keep every kept lane where it is
+    (all ones; the last block left out) bit for bit — weight 1 multiplies by 1.0, a lane of weight 0 adds exact zeros, the lanes in
+    front of it are dealt as in the materialised problem, so every sum has the same terms in the same order —, the row with
+    multiplicities inside the gates of test_subsets_against_the_batch_of_materialised_problems (repeated records are other lanes).
+    The all-ones row bitwise clc_solve_multistart; clc_solve_multistart before and after the subsets call: the same bits."""
+    S = sd.sim_fixed_count(21, 6, 30, noise_sigma=0.01)
+    rec = clc.flatten_observations(S, False, False)
+    off = clc.calib.pose_block_offsets(S, False, False)
+    assert np.array_equal(off, _offsets(6, 30))
+    if form == "z":
+        rec[47, 6] = 0.01
+    W = np.array([[1, 1, 1, 1, 1, 1], [2, 1, 1, 0, 1, 3], [0, 0, 0, 0, 0, 0], [1, 1, 1, 1, 1, 0]], dtype=np.uint8)
+    x0 = oracle_mod.pose_plus(_x_true(), np.array([.01, -.01, .01, .01, -.01, .01]))
+    o = clc.default_options()
+    o.use_loss = int(use_loss)
+    solved = [0, 1, 3]
+    subs = [resample.materialize(rec, off, W[k]) for k in solved]
+    boff = np.zeros(len(subs) + 1, dtype=np.int64)
+    boff[1:] = np.cumsum([r.shape[0] for r in subs])
+    with clc.Solver(0) as s:
+        if form == 512:
+            s.set_launch(0, FLAG_RESIDENT_WG512 | 2 | 16 | 32 | 128 | 256 | 512)     # (the default flags + 8192)
+        s.upload_batched(rec, np.array([0, rec.shape[0]], dtype=np.int64))
+        pi = s.path_info()
+        assert (pi.batched_resident, pi.batched_lanes, pi.batched_points_carry_z) == (1, 256 if form == 256 else 512, int(form == "z"))
+        ms_before, msm = s.solve_multistart(x0[None], o)
+        poses, sms = s.solve_subsets(off, W, x0, o)
+        again, asm = s.solve_subsets(off, W, x0, o)
+        ms_after, msm2 = s.solve_multistart(x0[None], o)
+        s.upload_batched(np.concatenate(subs), boff)
+        pb = s.path_info()
+        assert (pb.batched_resident, pb.batched_lanes, pb.batched_points_carry_z) == (1, 256 if form == 256 else 512, int(form == "z"))
+        bp, bsm = s.solve_batched(np.tile(x0, (len(subs), 1)), o)
+    key = lambda m: (m.termination, m.num_iterations, m.num_evaluations, m.initial_cost, m.final_cost)
+    assert np.array_equal(ms_before, ms_after) and key(msm[0]) == key(msm2[0])
+    assert np.array_equal(poses, again) and all(key(sms[k]) == key(asm[k]) for k in range(4))
+    assert np.array_equal(poses[0], ms_before[0]) and key(sms[0]) == key(msm[0])
+    assert sms[2].termination == _capi_termination("FAILURE") and np.array_equal(poses[2], x0)
+    for j, k in enumerate(solved):
+        bits = np.array_equal(poses[k], bp[j]) and sms[k].final_cost == bsm[j].final_cost
+        print(f"{form} {'loss' if use_loss else 'no loss'} row {k}: it {sms[k].num_iterations}/{bsm[j].num_iterations} dT {_dT(poses[k], bp[j]):.3e} "
+              f"dcost {abs(sms[k].final_cost - bsm[j].final_cost):.3e} same bits {bits}")
+        assert (sms[k].num_iterations, sms[k].termination) == (bsm[j].num_iterations, bsm[j].termination), k
+        assert _dT(poses[k], bp[j]) <= T_TOL and abs(sms[k].final_cost - bsm[j].final_cost) <= COST_TOL, k
+        if W[k].max() == 1:
+            assert bits and key(sms[k]) == key(bsm[j]), k
