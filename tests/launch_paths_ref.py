@@ -1,6 +1,7 @@
 """Pure-Python restatement of which kernels the launchers pick (csrc/abi_solve.hip launch_eval / solve_stepped / clc_solve,
 abi_frontend.hip clc_closed_form, abi_batched.hip batched_launch_setup, abi_layouts.hip's upload choices), written from the
-launchers as they stood before csrc/abi_paths.hpp gathered the rules, for tests/test_launch_paths.py.  Every function takes
+launchers as they stood before csrc/abi_paths.hpp gathered the rules, for tests/test_launch_paths.py (and, flow_blocks_per_problem,
+abi_batchflow.hip's workgroups per problem, for tests/batched_flow_cases.py).  Every other function takes
 `flags` as an np.int64 array (each -1 .. 16383, clc_set_launch) and evaluates all of them at once; the other inputs are scalars.
 
   * flags = -1: the defaults (2|16|32|128|256|512), and the size-dependent choices ("auto");
@@ -113,6 +114,15 @@ def batched(flags, grid_override, num_cus, problems, total_tiles, max_tiles, n_r
     return {"bpp": bpp * one, "n_blocks": P * bpp * one, "lm_threads": 64 * one, "lm_blocks": (P + 63) // 64 * one, "compact": compact,
             "deep": deep, "nt": nt, "rows": rows, "rows_nt": rows_nt, "rows_wave": rows_wave, "one_wave": one_wave, "whole_solve": whole,
             "resident": resident, "res_nt": res_nt}
+
+
+def flow_blocks_per_problem(num_cus, problems, units):
+    """Workgroups per problem of clc_closed_form_batched / clc_information_batched (abi_batchflow.hip flow_blocks_per_problem): four
+    workgroups per CU over the whole batch, never fewer than eight streaming units per workgroup.  units: the longest problem's rows
+    (row layout: batch_max_rows) or 128-point tiles (tile layout: batch_max_tiles).  Neither the flags nor the grid override enter."""
+    want = 4 * max(1, int(num_cus))
+    bpp = (want + int(problems) - 1) // int(problems)
+    return max(1, min(bpp, max(1, int(units) // 8)))
 
 
 def upload(flags, auto_disable, batch):

@@ -122,3 +122,15 @@ def test_upload_plan(shim):
         r = R.upload(FLAGS, ad, bool(batch))
         for k, name in enumerate(("resident", "first_lanes", "one_hop")):
             _same(t[:, k], r[name], dict(ad=ad, batch=batch), name)
+
+
+def test_flow_blocks_per_problem():
+    """The restatement of abi_batchflow.hip's flow_blocks_per_problem that tests/batched_flow_cases.py plans its batches with: values
+    worked out by hand from the rule (four workgroups per CU over the batch, at least eight units per workgroup, at least one)."""
+    f = R.flow_blocks_per_problem
+    for b in (1, 7, 8, 9, 15, 16, 17):                      # a few problems on 256 CUs: the longest problem's units decide
+        assert f(256, 4, 8 * b) == b and f(256, 4, 8 * b + 7) == b
+    assert f(256, 5, 63) == 7 and f(256, 3, 127) == 15 and f(256, 3, 7) == 1 and f(256, 3, 0) == 1
+    assert f(256, 1, 10**6 // 64) == 1024 and f(256, 1024, 10**6) == 1      # the batch size decides
+    assert f(256, 512, 24) == 2 and f(256, 513, 24) == 2 and f(256, 1023, 24) == 2 and f(256, 1024, 24) == 1 and f(256, 511, 24) == 3
+    assert f(80, 160, 24) == 2 and f(80, 320, 24) == 1 and f(0, 3, 800) == 2
