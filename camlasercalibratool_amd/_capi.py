@@ -39,6 +39,7 @@ EXPORTED = [
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
+    "clc_station_options_default", "clc_static_poses", "clc_assemble_stations", "clc_assemble_stations_device",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -47,7 +48,7 @@ HOOKS = [
     "clc_debug_wave_split", "clc_debug_resident", "clc_debug_resident_single", "clc_debug_coop", "clc_debug_coop_control",
     "clc_debug_coop_set_tag", "clc_debug_layout", "clc_debug_lm_profile", "clc_time_steps", "clc_time_batched_eval", "clc_time_eval",
     "clc_debug_comm_create_layout", "clc_debug_single_controller", "clc_debug_fast_small",
-    "clc_debug_lane_map_builds", "clc_debug_assemble_lines",
+    "clc_debug_lane_map_builds", "clc_debug_assemble_lines", "clc_debug_station_walk",
 ]
 
 
@@ -136,6 +137,21 @@ class AssembleInfo(C.Structure):
 
 
 SCAN_NO_SEGMENT, SCAN_REF_THROWS, SCAN_NO_POSE = -1, -2, -3  # CLC_SCAN_*
+
+
+class StationOptions(C.Structure):
+    """clc_station_options (include/clc.h)."""
+    _fields_ = [("center_dist_max", C.c_double), ("min_members", C.c_int64), ("close_last_run", C.c_int32), ("reserved", C.c_int32),
+                ("line0", C.c_double * 2), ("line", Options)]
+
+
+class StationInfo(C.Structure):
+    """clc_station_info (include/clc.h)."""
+    _fields_ = [(n, C.c_int64) for n in ("n_runs", "n_stations", "n_nonfinite", "n_segments", "n_ref_throws", "n_unmatched", "n_observations",
+                                         "n_points", "n_line_points")]
+
+
+STATION_OK, STATION_NONFINITE = 1, -1  # CLC_STATION_*
 
 
 class ClcError(RuntimeError):
@@ -232,6 +248,12 @@ def load(path: str):
         L.clc_assemble_observations.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V]
         L.clc_assemble_observations_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V]
         L.clc_stored_observations.argtypes = [V, V, V, V, V, V, V, V]
+        if hasattr(L, "clc_static_poses"):  # (a build of an older tree loaded through CLC_LIBRARY has none of these)
+            L.clc_station_options_default.argtypes = [V]
+            L.clc_station_options_default.restype = None
+            L.clc_static_poses.argtypes = [V, V, C.c_size_t, V, V, V, C.c_size_t, V, V, V, V, V, V, V, V]
+            L.clc_assemble_stations.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V]
+            L.clc_assemble_stations_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V]
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -290,6 +312,13 @@ def default_assemble_options() -> AssembleOptions:
     """The reference's settings, main/calibr_offline.cpp:66-67,:116: 0.20 m, 10 degrees (with pi = 3.1415926), 20 ms; line fits from (0, 0)."""
     o = AssembleOptions()
     lib().clc_assemble_options_default(C.byref(o))
+    return o
+
+
+def default_station_options() -> StationOptions:
+    """The reference's settings, src/utilities.cpp:108,:119: 2 mm, more than 30 members; the open last run dropped; line fits from (0, 0)."""
+    o = StationOptions()
+    lib().clc_station_options_default(C.byref(o))
     return o
 
 

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import simdata
-from ._capi import AssembleOptions, ClcError, Options, TERMINATION, default_line_options, default_options
+from ._capi import AssembleOptions, ClcError, Options, StationOptions, TERMINATION, default_line_options, default_options
 from .simdata import Oberserve, ObservationSet
 from .solver import SolveResult, Solver, flatten_observations
 
@@ -167,22 +167,34 @@ def pose_block_offsets(obs: ObsLike, use_linefitting_data: bool = True, use_boun
     return out
 
 
+def _group_blocks(off: np.ndarray, block_offsets) -> np.ndarray:
+    """Record offsets of blocks of consecutive observations: block_offsets [B + 1] in observations (None: one block per observation)."""
+    if block_offsets is None:
+        return off
+    b = np.asarray(block_offsets, dtype=np.int64).reshape(-1)
+    if b.size < 2 or b[0] != 0 or b[-1] != len(off) - 1 or np.any(np.diff(b) < 0):
+        raise ValueError("block_offsets: [B + 1] non-decreasing observation indices from 0 to the number of observations")
+    return np.ascontiguousarray(off[b])
+
+
 def CamLaserCalibrationResample(obs: ObsLike, Tcl: np.ndarray, use_linefitting_data: bool = True, use_boundary_constraint: bool = False,
                                 mode: str = "jackknife", n: int = 0, seed: int = 0, m: int = 0,
-                                options: Optional[Options] = None, solver: Optional[Solver] = None) -> Dict[str, object]:
+                                options: Optional[Options] = None, solver: Optional[Solver] = None, block_offsets=None) -> Dict[str, object]:
     """How much does Tcl depend on the poses that were recorded?  The full problem is solved from Tcl (refined in place), then — on the
     same upload, one launch (clc_solve_subsets) — its resampled versions from the full solution: mode "jackknife" (every pose left out
     once), "bootstrap" (n rows of P draws with replacement) or "subsets" (n random m-of-P subsets).
     -> {"pose": full solution [7], "summary", "weights" [S, P], "poses" [S, 7], "summaries", "deltas" [S, 6] (local coordinates of
     every resampled solution about the full one), "covariance" [6, 6] (jackknife / bootstrap estimate; None for "subsets"),
-    "influence" [P] (jackknife only: |delta_k|, how far leaving pose k out moves the solution)}."""
+    "influence" [P] (jackknife only: |delta_k|, how far leaving pose k out moves the solution)}.
+    block_offsets [B + 1] (optional): resample blocks of consecutive observations instead of single ones — the stations of
+    CalibrateOfflineStations (its "station_block_offsets"), whose observations share one averaged tag pose; P is then B."""
     from . import resample
     S = _as_set(obs)
     sv = solver or _shared_solver()
     rec = flatten_observations(S, use_linefitting_data, use_boundary_constraint)
-    off = pose_block_offsets(S, use_linefitting_data, use_boundary_constraint)
+    off = _group_blocks(pose_block_offsets(S, use_linefitting_data, use_boundary_constraint), block_offsets)
     sv.upload_batched(rec, np.array([0, rec.shape[0]], dtype=np.int64))
-    P = S.n_poses
+    P = len(off) - 1
     full, fsm = sv.solve_multistart(simdata.pose7_from_T(np.asarray(Tcl, dtype=np.float64).reshape(4, 4))[None], options)
     x_full = full[0]
     if mode == "jackknife":
@@ -207,7 +219,7 @@ def CamLaserCalibrationResample(obs: ObsLike, Tcl: np.ndarray, use_linefitting_d
 
 def CamLaserCalibrationConsensus(obs: ObsLike, Tcl: np.ndarray, use_linefitting_data: bool = True, use_boundary_constraint: bool = False,
                                  n: int = 256, m: int = 5, rms_max: Optional[float] = None, seed: int = 0,
-                                 options: Optional[Options] = None, solver: Optional[Solver] = None) -> Dict[str, object]:
+                                 options: Optional[Options] = None, solver: Optional[Solver] = None, block_offsets=None) -> Dict[str, object]:
     """Calibration by consensus over the recorded poses: which recordings are bad, and the answer without them.  A whole scan can be
     consistently off by centimetres (its tag pose taken from the wrong camera frame, its board segment cut wrongly); the per-point
     Cauchy loss has its largest influence exactly there and all of that scan's points pull the same way.  Steps, on ONE upload:
@@ -223,16 +235,17 @@ def CamLaserCalibrationConsensus(obs: ObsLike, Tcl: np.ndarray, use_linefitting_
     separated exactly, poses 0.05 m off slip into the support and the refit is no better than the plain solve.
     Tcl is refined in place (left alone when no candidate finds support).
     -> {"pose" [7], "summary", "inliers" [P] bool, "rms" [P] (per-pose RMS at the result), "sizes" [n] (support of every candidate),
-        "best" (the winning row; -1: none), "weights" [n, P], "candidates" [n, 7], "ssq" [n, P]}."""
+        "best" (the winning row; -1: none), "weights" [n, P], "candidates" [n, 7], "ssq" [n, P]}.
+    block_offsets [B + 1] (optional): the blocks are runs of consecutive observations (stations, see CamLaserCalibrationResample)."""
     from . import resample
     if rms_max is None:
         raise TypeError("rms_max is required: a few sigma of the scanner's range noise, in metres (see the docstring)")
     S = _as_set(obs)
     sv = solver or _shared_solver()
     rec = flatten_observations(S, use_linefitting_data, use_boundary_constraint)
-    off = pose_block_offsets(S, use_linefitting_data, use_boundary_constraint)
+    off = _group_blocks(pose_block_offsets(S, use_linefitting_data, use_boundary_constraint), block_offsets)
     sv.upload_batched(rec, np.array([0, rec.shape[0]], dtype=np.int64))
-    P = S.n_poses
+    P = len(off) - 1
     x0 = simdata.pose7_from_T(np.asarray(Tcl, dtype=np.float64).reshape(4, 4))
     W = resample.random_subset_weights(P, n, m, seed)
     cands, _ = sv.solve_subsets(off, W, x0, options)
@@ -341,6 +354,61 @@ def CalibrateOffline(pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, assemble_o
         print("\n----- Transform from Camera to Laser Tlc is: -----\n")
         print(Tlc)
     return {"Tlc_initial": Tlc0, "Tcl": Tcl, "Tlc": Tlc, "report": report, "info": info, "scan_pose": scan_pose, "session": ses}
+
+
+def GetStaticPose(pose_stamp, q_wc, t_wc, options: Optional[StationOptions] = None, solver: Optional[Solver] = None) -> dict:
+    """The static stations of a pose list — mirror of GetStaticPose(Poses, avergeStaticPoses), src/utilities.cpp:86-155: the runs
+    of poses that stay within 2 mm of their running centre, those of more than 30 members averaged into one pose each (mean
+    translation; quaternion mean by the dominant eigenvector of sum q q^T) and stamped with the run's start_time / end_time.
+    -> Solver.static_poses' dict; the member poses of station k are first[k] (twice, as in the reference) .. last[k]."""
+    return (solver or _shared_solver()).static_poses(pose_stamp, q_wc, t_wc, options)
+
+
+def station_block_offsets(scan_station: np.ndarray):
+    """Observation ranges per station [B + 1] for the observations an assemble_stations call left (one per scan with
+    scan_station >= 0, in scan order), one block per station that took a scan -> (offsets, the stations' indices), or
+    (None, None) when the observations of a station are not consecutive (scan stamps that decrease)."""
+    kept = np.asarray(scan_station)[np.asarray(scan_station) >= 0]
+    if kept.size == 0 or np.any(np.diff(kept) < 0):
+        return None, None
+    ids, start = np.unique(kept, return_index=True)
+    return np.concatenate([start, [kept.size]]).astype(np.int64), ids.astype(np.int64)
+
+
+def CalibrateOfflineStations(pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, station_options: Optional[StationOptions] = None,
+                             options: Optional[Options] = None, solver: Optional[Solver] = None, verbose: bool = True):
+    """CalibrateOffline for recordings where the board is held still at stations: the tag poses are averaged per station
+    (GetStaticPose) and every scan taken while the board stood still becomes an observation with its station's averaged pose
+    (Solver.assemble_stations) — no key frames, no 20 ms gate; then the closed form, Tcl = inv(Tlc), CamLaserCalibration(obs, Tcl,
+    false) and its analysis pass as in main/calibr_offline.cpp:166-170.  The same gates: fewer than 10 poses, fewer than 5 observations.
+    Returns None under the gates, otherwise CalibrateOffline's dict with "info" (StationInfo), "scan_station" [S] and
+    "station_block_offsets" [B + 1] / "station_block_ids" [B]: the observation ranges of the stations that took scans — blocks for
+    CamLaserCalibrationResample / CamLaserCalibrationConsensus (block_offsets=) — or None when a station's observations are not
+    consecutive (scan stamps that decrease)."""
+    if len(np.asarray(pose_stamp).reshape(-1)) < 10:
+        if verbose:
+            print("apriltag pose less than 10.")
+        return None
+    sv = solver or _shared_solver()
+    info, scan_station = sv.assemble_stations(pose_stamp, q_wc, t_wc, scans, scan_stamp, station_options)
+    if info.n_observations < 5:
+        if verbose:
+            print("Valid Calibra Data Less")
+        return None
+    if verbose:
+        print("stations: ", info.n_stations, " obs size: ", info.n_observations)
+    ses = Session.adopt(sv)
+    Tlc0 = np.eye(4)
+    ses.CamLaserCalClosedSolution(Tlc0, verbose)
+    Tcl = np.linalg.inv(Tlc0)
+    report = ses.CamLaserCalibration(Tcl, False, False, options, verbose)
+    Tlc = np.linalg.inv(Tcl)
+    if verbose:
+        print("\n----- Transform from Camera to Laser Tlc is: -----\n")
+        print(Tlc)
+    blocks, ids = station_block_offsets(scan_station)
+    return {"Tlc_initial": Tlc0, "Tcl": Tcl, "Tlc": Tlc, "report": report, "info": info, "scan_station": scan_station, "session": ses,
+            "station_block_offsets": blocks, "station_block_ids": ids}
 
 
 def LineFittingCeres(Points: np.ndarray, Line: np.ndarray, solver: Optional[Solver] = None,

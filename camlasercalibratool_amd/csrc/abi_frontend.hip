@@ -1,9 +1,10 @@
 // abi_frontend.hip — the calls either side of the solve: factor evaluation, manifold plus, information matrix and closed form, line fitting, scan conversion,
-// board-segment detection, assembly of the offline flow's observations (K13).
+// board-segment detection, assembly of the offline flow's observations (K13), static stations (K14).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 #include "clc_scanseg.hpp"
 #include "clc_assemble.hpp"
+#include "clc_stations.hpp"
 #include "abi_assemble.hpp"
 
 using namespace clc_abi;
@@ -326,13 +327,17 @@ int check_assemble_options(const char* who, const clc_assemble_options* in, clc_
   return CLC_OK;
 }
 
-// Every array in device memory; host_scan_pose (nullable): where scan_pose is copied to on the host.  The kernels run at sizes
-// the host knows — n_scans, n_rays — and learn the number of observations from the counters on the device: workgroups and rows
-// behind it leave at once, so nothing is read back before the ONE wait at the end.
-int assemble_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_poses, const double* d_stamp, const double* d_q,
-                       const double* d_t, const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am,
-                       const float* d_ai, const float* d_rm, const double* d_sstamp, int32_t* d_scan_pose, int32_t* host_scan_pose,
-                       clc_assemble_info* info) {
+// The stages every assembly shares, whatever ties a scan to a pose (K13: the nearest key frame; K14: the station that holds its
+// stamp).  Every array in device memory; host_scan_pose (nullable): where scan_pose is copied to on the host.  associate(cnt, status,
+// scan_pose) enqueues the mode's kernels: they fill scan_pose[S] with an index into (d_q, d_t) or a CLC_SCAN_* code (status: K7's, valid
+// when S > 0).  read_back() enqueues the mode's own copies to the host in front of the ONE wait.  The kernels run at sizes the host
+// knows — n_scans, n_rays — and learn the number of observations from the counters on the device: workgroups and rows behind it
+// leave at once, so nothing is read back before the wait at the end.  c: the counters (clc::AsmCounter).
+template <class Associate, class ReadBack>
+int assemble_on_device(clc_handle* h, const char* who, const double line0[2], const clc_options& line, const double* d_q, const double* d_t,
+                       const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am, const float* d_ai,
+                       const float* d_rm, int32_t* d_scan_pose, int32_t* host_scan_pose, long long c[clc::ASM_COUNTERS], Associate&& associate,
+                       ReadBack&& read_back) {
   const size_t cap_points = std::min(n_rays, S * (size_t)clc::ASM_SEG_MAX_POINTS);
   h->store_poses = -1;
   // the handle's pose-major arrays at what S scans can need at most (the number of observations is not known on the host yet)
@@ -342,19 +347,15 @@ int assemble_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_
   CLC_HIP(h->d_sptl.grow(std::max<size_t>(S * 6, 1)));
   CLC_HIP(h->d_soff.grow(3 * (S + 1)));
   DevBuf<long long> cnt(&h->pool), seg(&h->pool), obs_scan(&h->pool), fit_off(&h->pool);
-  DevBuf<unsigned char> keep(&h->pool);
-  DevBuf<int> kf(&h->pool), status(&h->pool), spose(&h->pool);
+  DevBuf<int> status(&h->pool), spose(&h->pool);
   DevBuf<double> points(&h->pool), xy(&h->pool), lines(&h->pool);
   CLC_HIP(cnt.alloc(clc::ASM_COUNTERS)); CLC_HIP(seg.alloc(2 * S)); CLC_HIP(obs_scan.alloc(S)); CLC_HIP(fit_off.alloc(S + 1));
-  CLC_HIP(keep.alloc(n_poses)); CLC_HIP(kf.alloc(n_poses)); CLC_HIP(status.alloc(S));
+  CLC_HIP(status.alloc(S));
   if (!d_scan_pose) { CLC_HIP(spose.alloc(S)); d_scan_pose = spose.p; }
   CLC_HIP(points.alloc(3 * n_rays)); CLC_HIP(xy.alloc(2 * cap_points)); CLC_HIP(lines.alloc(2 * S));
   const long long* off = reinterpret_cast<const long long*>(d_off);
   long long* soff = h->d_soff;
   CLC_HIP(hipMemsetAsync(cnt.p, 0, clc::ASM_COUNTERS * sizeof(long long), h->stream));
-  hipLaunchKernelGGL(clc::keyframe_kernel, dim3(1), dim3(64), 0, h->stream, d_q, d_t, d_stamp, (long long)n_poses, opt.keyframe_dist_min,
-                     opt.keyframe_theta_min, keep.p, kf.p, cnt.p);
-  CLC_HIP(hipGetLastError());
   const int threads = 256;
   if (S > 0) {
     if (n_rays > 0) {
@@ -364,37 +365,35 @@ int assemble_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_
     }
     launch_board_segments(h, points.p, d_off, S, reinterpret_cast<int64_t*>(seg.p), status.p);
     CLC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(clc::associate_kernel, dim3((unsigned)((S + threads - 1) / threads)), dim3(threads), 0, h->stream, status.p, d_sstamp,
-                       (long long)S, d_stamp, kf.p, cnt.p, opt.max_dt, d_scan_pose);
-    CLC_HIP(hipGetLastError());
   }
+  CLC_TRY(associate(cnt.p, status.p, d_scan_pose));
   hipLaunchKernelGGL(clc::compact_kernel, dim3(1), dim3(clc::ASM_SCAN_BLOCK), 0, h->stream, d_scan_pose, seg.p, (long long)S,
                      (long long)cap_points, obs_scan.p, fit_off.p, soff, cnt.p);
   CLC_HIP(hipGetLastError());
   if (S > 0) {
     hipLaunchKernelGGL(clc::gather_kernel, dim3((unsigned)S), dim3(256), 0, h->stream, points.p, off, seg.p, d_scan_pose, obs_scan.p, fit_off.p,
-                       cnt.p, d_q, d_t, opt.line0[0], opt.line0[1], h->d_spts.get(), xy.p, lines.p, h->d_sq.get(), h->d_st.get());
+                       cnt.p, d_q, d_t, line0[0], line0[1], h->d_spts.get(), xy.p, lines.p, h->d_sq.get(), h->d_st.get());
     CLC_HIP(hipGetLastError());
-    launch_line_fit(h, opt.line, xy.p, fit_off.p, S, lines.p, nullptr);  // rows behind the observations are empty scans
+    launch_line_fit(h, line, xy.p, fit_off.p, S, lines.p, nullptr);  // rows behind the observations are empty scans
     CLC_HIP(hipGetLastError());
     hipLaunchKernelGGL(clc::endpoints_kernel, dim3((unsigned)((S + threads - 1) / threads)), dim3(threads), 0, h->stream, h->d_spts.get(), soff,
                        cnt.p, lines.p, h->d_sptl.get());
     CLC_HIP(hipGetLastError());
   }
   // what comes back: the counters, the packed offsets, the tag poses a reference-size store keeps on the host
-  long long c[clc::ASM_COUNTERS];
   std::vector<long long> hoff(2 * (S + 1));
   const size_t n_small = std::min<size_t>(S, 4096);
   std::vector<double> tq(4 * n_small + 1), tt(3 * n_small + 1);
-  CLC_HIP(hipMemcpyAsync(c, cnt.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(c, cnt.p, clc::ASM_COUNTERS * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
   CLC_HIP(hipMemcpyAsync(hoff.data(), soff, hoff.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
   if (n_small > 0) {
     CLC_HIP(hipMemcpyAsync(tq.data(), h->d_sq.get(), 4 * n_small * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     CLC_HIP(hipMemcpyAsync(tt.data(), h->d_st.get(), 3 * n_small * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   if (host_scan_pose && S > 0) CLC_HIP(hipMemcpyAsync(host_scan_pose, d_scan_pose, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  CLC_TRY(read_back());
   CLC_HIP(hipStreamSynchronize(h->stream));
-  if (c[clc::ASM_OVERFLOW] != 0) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: the segments hold more points than the scans");
+  if (c[clc::ASM_OVERFLOW] != 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": the segments hold more points than the scans").c_str());
   const size_t P = (size_t)c[clc::ASM_N_OBS];
 #ifdef CLC_TEST_HOOKS
   g_last_lines.assign(2 * P, 0.0);  // test hook: the lines the end points were computed from (clc_debug_assemble_lines)
@@ -405,9 +404,121 @@ int assemble_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_
   StoreFacts f;  // scan points have z = 0 (TranScanToPoints), the points on the line too; points_on_line is never the points
   f.tag_q = tq.data();
   f.tag_t = tt.data();
-  CLC_TRY(adopt_store(h, (int)P, f));
+  return adopt_store(h, (int)P, f);
+}
+
+// K13: key frames, then the nearest key frame within max_dt
+int assemble_keyframes_on_device(clc_handle* h, const clc_assemble_options& opt, size_t n_poses, const double* d_stamp, const double* d_q,
+                                 const double* d_t, const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am,
+                                 const float* d_ai, const float* d_rm, const double* d_sstamp, int32_t* d_scan_pose, int32_t* host_scan_pose,
+                                 clc_assemble_info* info) {
+  DevBuf<unsigned char> keep(&h->pool);
+  DevBuf<int> kf(&h->pool);
+  CLC_HIP(keep.alloc(n_poses)); CLC_HIP(kf.alloc(n_poses));
+  long long c[clc::ASM_COUNTERS];
+  CLC_TRY(assemble_on_device(
+      h, "clc_assemble_observations", opt.line0, opt.line, d_q, d_t, d_ranges, d_off, S, n_rays, d_am, d_ai, d_rm, d_scan_pose, host_scan_pose, c,
+      [&](long long* cnt, const int* status, int32_t* scan_pose) {
+        hipLaunchKernelGGL(clc::keyframe_kernel, dim3(1), dim3(64), 0, h->stream, d_q, d_t, d_stamp, (long long)n_poses, opt.keyframe_dist_min,
+                           opt.keyframe_theta_min, keep.p, kf.p, cnt);
+        CLC_HIP(hipGetLastError());
+        if (S > 0) {
+          hipLaunchKernelGGL(clc::associate_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, status, d_sstamp, (long long)S,
+                             d_stamp, kf.p, cnt, opt.max_dt, scan_pose);
+          CLC_HIP(hipGetLastError());
+        }
+        return (int)CLC_OK;
+      },
+      [] { return (int)CLC_OK; }));
   if (info) {
     info->n_keyframes = c[clc::ASM_N_KEYFRAMES];
+    info->n_segments = c[clc::ASM_N_SEGMENTS];
+    info->n_ref_throws = c[clc::ASM_N_REF_THROWS];
+    info->n_unmatched = c[clc::ASM_N_UNMATCHED];
+    info->n_observations = c[clc::ASM_N_OBS];
+    info->n_points = c[clc::ASM_N_POINTS];
+    info->n_line_points = c[clc::ASM_N_LINE_POINTS];
+  }
+  return CLC_OK;
+}
+
+// ---- static stations (K14, clc_stations.hpp) ----------------------------------------------------------------------------------------
+int check_station_options(const char* who, const clc_station_options* in, clc_station_options* opt) {
+  if (in) *opt = *in; else clc_station_options_default(opt);
+  if (!std::isfinite(opt->center_dist_max) || opt->center_dist_max < 0.0 || opt->min_members < 0) return fail(CLC_ERR_INVALID_ARG, who);
+  if (opt->line.max_num_iterations < 0 || (opt->line.use_loss && !(opt->line.loss_scale_factor > 0.0))) return fail(CLC_ERR_INVALID_ARG, who);
+  if (!std::isfinite(opt->line0[0]) || !std::isfinite(opt->line0[1])) return fail(CLC_ERR_NONFINITE, who);
+  return CLC_OK;
+}
+
+// the stations of one call in device memory.  cap: no call can find more — a station has members > min_members, that is at least
+// max(1, min_members) poses of its own
+struct StationBufs {
+  DevBuf<long long> cnt, first, last, members;
+  DevBuf<double> q, t, start, end;
+  DevBuf<int> status;
+  size_t cap = 0;
+  explicit StationBufs(DevPool* p) : cnt(p), first(p), last(p), members(p), q(p), t(p), start(p), end(p), status(p) {}
+  hipError_t alloc(size_t n_poses, const clc_station_options& opt) {
+    cap = n_poses / (size_t)std::max<int64_t>(1, opt.min_members) + 1;
+    hipError_t e = cnt.alloc(clc::ST_COUNTERS);
+    if (e == hipSuccess) e = first.alloc(cap);
+    if (e == hipSuccess) e = last.alloc(cap);
+    if (e == hipSuccess) e = members.alloc(cap);
+    if (e == hipSuccess) e = q.alloc(4 * cap);
+    if (e == hipSuccess) e = t.alloc(3 * cap);
+    if (e == hipSuccess) e = start.alloc(cap);
+    if (e == hipSuccess) e = end.alloc(cap);
+    if (e == hipSuccess) e = status.alloc(cap);
+    return e;
+  }
+};
+
+// the walk and the averages, enqueued on the handle's stream (no wait); d_stamp nullable
+int launch_stations(clc_handle* h, const clc_station_options& opt, size_t n_poses, const double* d_stamp, const double* d_q, const double* d_t,
+                    StationBufs& b, bool average = true) {
+  hipLaunchKernelGGL(clc::station_walk_kernel, dim3(1), dim3(64), 0, h->stream, d_t, d_stamp, (long long)n_poses, opt.center_dist_max,
+                     (long long)opt.min_members, (int)(opt.close_last_run != 0), b.first.p, b.last.p, b.members.p, b.cnt.p);
+  CLC_HIP(hipGetLastError());
+  if (!average) return CLC_OK;
+  const size_t blocks = std::min<size_t>((b.cap + clc::STATION_WAVES_PER_BLOCK - 1) / clc::STATION_WAVES_PER_BLOCK, 1024);
+  hipLaunchKernelGGL(clc::station_average_kernel, dim3((unsigned)blocks), dim3(64 * clc::STATION_WAVES_PER_BLOCK), 0, h->stream, d_q, d_t, d_stamp,
+                     b.first.p, b.last.p, b.members.p, b.cnt.p, b.q.p, b.t.p, b.start.p, b.end.p, b.status.p);
+  CLC_HIP(hipGetLastError());
+  return CLC_OK;
+}
+
+// K14: stations, then the station whose [start_time, end_time] holds the scan's stamp; the gather takes the averaged poses
+int assemble_stations_on_device(clc_handle* h, const clc_station_options& opt, size_t n_poses, const double* d_stamp, const double* d_q,
+                                const double* d_t, const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am,
+                                const float* d_ai, const float* d_rm, const double* d_sstamp, int32_t* d_scan_station,
+                                int32_t* host_scan_station, clc_station_info* info) {
+  StationBufs b(&h->pool);
+  CLC_HIP(b.alloc(n_poses, opt));
+  long long c[clc::ASM_COUNTERS], sc[clc::ST_COUNTERS];
+  std::vector<int> st_status(b.cap);
+  CLC_TRY(assemble_on_device(
+      h, "clc_assemble_stations", opt.line0, opt.line, b.q.p, b.t.p, d_ranges, d_off, S, n_rays, d_am, d_ai, d_rm, d_scan_station,
+      host_scan_station, c,
+      [&](long long*, const int* status, int32_t* scan_station) {
+        CLC_TRY(launch_stations(h, opt, n_poses, d_stamp, d_q, d_t, b));
+        if (S > 0) {
+          hipLaunchKernelGGL(clc::station_associate_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, status, d_sstamp,
+                             (long long)S, b.start.p, b.end.p, b.status.p, b.cnt.p, scan_station);
+          CLC_HIP(hipGetLastError());
+        }
+        return (int)CLC_OK;
+      },
+      [&] {
+        CLC_HIP(hipMemcpyAsync(sc, b.cnt.p, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+        CLC_HIP(hipMemcpyAsync(st_status.data(), b.status.p, b.cap * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        return (int)CLC_OK;
+      }));
+  if (info) {
+    info->n_runs = sc[clc::ST_N_RUNS];
+    info->n_stations = sc[clc::ST_N_STATIONS];
+    info->n_nonfinite = 0;
+    for (long long k = 0; k < sc[clc::ST_N_STATIONS]; ++k) info->n_nonfinite += st_status[(size_t)k] == clc::STATION_NONFINITE ? 1 : 0;
     info->n_segments = c[clc::ASM_N_SEGMENTS];
     info->n_ref_throws = c[clc::ASM_N_REF_THROWS];
     info->n_unmatched = c[clc::ASM_N_UNMATCHED];
@@ -470,7 +581,7 @@ int clc_assemble_observations_device(clc_handle* h, const clc_assemble_options* 
   clc_assemble_options opt;
   CLC_TRY(check_assemble_options("clc_assemble_observations_device: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
-  return assemble_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays, angle_min_dev,
+  return assemble_keyframes_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays, angle_min_dev,
                             angle_increment_dev, range_min_dev, scan_stamp_dev, scan_pose_dev, nullptr, info);
 }
 
@@ -507,7 +618,7 @@ int clc_assemble_observations(clc_handle* h, const clc_assemble_options* opt_in,
   CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
   CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
   CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
-  return assemble_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p, bai.p,
+  return assemble_keyframes_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p, bai.p,
                             brm.p, bss.p, nullptr, scan_pose, info);
 }
 
@@ -532,6 +643,107 @@ int clc_stored_observations(clc_handle* h, int* n_poses, double* tag_q_wxyz, dou
   return CLC_OK;
 }
 
+// ---- static stations (K14) ----------------------------------------------------------------------------------------------------------
+void clc_station_options_default(clc_station_options* o) {
+  if (!o) return;
+  o->center_dist_max = 0.002;  // src/utilities.cpp:108
+  o->min_members = 30;         // :119: staticPose.size() > 30, the first pose counted twice
+  o->close_last_run = 0;       // :114-123: a run is pushed at a break only
+  o->reserved = 0;
+  o->line0[0] = o->line0[1] = 0.0;
+  clc_line_options_default(&o->line);
+}
+
+int clc_static_poses(clc_handle* h, const clc_station_options* opt_in, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                     const double* t_wc, size_t cap_stations, int64_t* first, int64_t* last, double* start_time, double* end_time,
+                     double* q_avg_wxyz, double* t_avg, int32_t* status, int64_t* n_stations) {
+  if (!h || (n_poses > 0 && (!q_wc_wxyz || !t_wc)) || n_poses > 0x7FFFFFF0ull) return fail(CLC_ERR_INVALID_ARG, "clc_static_poses: bad argument");
+  clc_station_options opt;
+  CLC_TRY(check_station_options("clc_static_poses: bad options", opt_in, &opt));
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool);
+  StationBufs b(&h->pool);
+  CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses));
+  if (pose_stamp) CLC_HIP(bstamp.alloc(n_poses));
+  CLC_HIP(b.alloc(n_poses, opt));
+  if (n_poses > 0) {
+    CLC_HIP(hipMemcpyAsync(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CLC_HIP(hipMemcpyAsync(bt.p, t_wc, 3 * n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (pose_stamp) CLC_HIP(hipMemcpyAsync(bstamp.p, pose_stamp, n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  CLC_TRY(launch_stations(h, opt, n_poses, pose_stamp ? bstamp.p : nullptr, bq.p, bt.p, b));
+  long long sc[clc::ST_COUNTERS];
+  CLC_HIP(hipMemcpyAsync(sc, b.cnt.p, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (n_stations) *n_stations = sc[clc::ST_N_STATIONS];
+  const size_t rows = std::min<size_t>((size_t)sc[clc::ST_N_STATIONS], cap_stations);  // (the count never exceeds b.cap)
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "station row types");
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    return (!dst || bytes == 0) ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+  };
+  CLC_HIP(down(first, b.first.p, rows * sizeof(int64_t)));
+  CLC_HIP(down(last, b.last.p, rows * sizeof(int64_t)));
+  CLC_HIP(down(start_time, b.start.p, rows * sizeof(double)));
+  CLC_HIP(down(end_time, b.end.p, rows * sizeof(double)));
+  CLC_HIP(down(q_avg_wxyz, b.q.p, 4 * rows * sizeof(double)));
+  CLC_HIP(down(t_avg, b.t.p, 3 * rows * sizeof(double)));
+  CLC_HIP(down(status, b.status.p, rows * sizeof(int32_t)));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+int clc_assemble_stations_device(clc_handle* h, const clc_station_options* opt_in, size_t n_poses, const double* pose_stamp_dev,
+                                 const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev, const int64_t* offsets_dev,
+                                 size_t n_scans, size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
+                                 const float* range_min_dev, const double* scan_stamp_dev, int32_t* scan_station_dev, clc_station_info* info) {
+  if (!h || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
+      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
+      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_stations_device: bad argument");
+  clc_station_options opt;
+  CLC_TRY(check_station_options("clc_assemble_stations_device: bad options", opt_in, &opt));
+  CLC_HIP(hipSetDevice(h->device));
+  return assemble_stations_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays,
+                                     angle_min_dev, angle_increment_dev, range_min_dev, scan_stamp_dev, scan_station_dev, nullptr, info);
+}
+
+int clc_assemble_stations(clc_handle* h, const clc_station_options* opt_in, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                          const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
+                          const float* angle_increment, const float* range_min, const double* scan_stamp, int32_t* scan_station,
+                          clc_station_info* info) {
+  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
+      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
+      n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_stations: bad argument");
+  clc_station_options opt;
+  CLC_TRY(check_station_options("clc_assemble_stations: bad options", opt_in, &opt));
+  std::vector<long long> rel;
+  size_t n_rays;
+  CLC_TRY(host_offsets("clc_assemble_stations", offsets, n_scans, true, "rays", &rel, &n_rays));
+  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_stations: NULL ranges");
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
+  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
+  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
+  CLC_HIP(boff.alloc(n_scans + 1));
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
+  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
+  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
+  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
+  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
+  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
+  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
+  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
+  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
+  return assemble_stations_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p,
+                                     bai.p, brm.p, bss.p, nullptr, scan_station, info);
+}
+
 }  // extern "C"
 
 #ifdef CLC_TEST_HOOKS
@@ -543,6 +755,33 @@ extern "C" int clc_debug_assemble_lines(double* lines_out, int64_t cap_lines, in
   if (lines_out) {
     if (cap_lines < *n_lines) return fail(CLC_ERR_INVALID_ARG, "clc_debug_assemble_lines: buffer too small");
     std::memcpy(lines_out, g_last_lines.data(), g_last_lines.size() * sizeof(double));
+  }
+  return CLC_OK;
+}
+// test hook: the walk of clc_static_poses alone on host translations -> the stations' first / last / members (at most cap rows each,
+// nullable), *n_stations, *n_runs (every closed run)
+extern "C" int clc_debug_station_walk(clc_handle* h, const clc_station_options* opt_in, size_t n_poses, const double* t_wc, int64_t cap,
+                                      int64_t* first, int64_t* last, int64_t* members, int64_t* n_stations, int64_t* n_runs) {
+  if (!h || (n_poses > 0 && !t_wc) || cap < 0) return fail(CLC_ERR_INVALID_ARG, "clc_debug_station_walk: bad argument");
+  clc_station_options opt;
+  CLC_TRY(check_station_options("clc_debug_station_walk: bad options", opt_in, &opt));
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bt(&h->pool);
+  StationBufs b(&h->pool);
+  CLC_HIP(bt.alloc(3 * n_poses));
+  CLC_HIP(b.alloc(n_poses, opt));
+  if (n_poses > 0) CLC_HIP(hipMemcpyAsync(bt.p, t_wc, 3 * n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CLC_TRY(launch_stations(h, opt, n_poses, nullptr, nullptr, bt.p, b, /*average=*/false));
+  long long sc[clc::ST_COUNTERS];
+  CLC_HIP(hipMemcpyAsync(sc, b.cnt.p, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (n_stations) *n_stations = sc[clc::ST_N_STATIONS];
+  if (n_runs) *n_runs = sc[clc::ST_N_RUNS];
+  const size_t rows = std::min<size_t>((size_t)sc[clc::ST_N_STATIONS], (size_t)cap);
+  if (rows > 0) {
+    if (first) CLC_HIP(hipMemcpy(first, b.first.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (last) CLC_HIP(hipMemcpy(last, b.last.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (members) CLC_HIP(hipMemcpy(members, b.members.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
   }
   return CLC_OK;
 }

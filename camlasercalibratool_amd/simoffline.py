@@ -87,6 +87,12 @@ def recording(seed: int = 1, n_stations: int = 26, move_frames: int = 20, still_
               Rlc: np.ndarray = sd.GT_RLC, tlc: np.ndarray = sd.GT_TLC) -> dict:
     """-> {pose_stamp [n], q_wc [n, 4] (w, x, y, z), t_wc [n, 3], scans (as simdata.sim_laser_scans), scan_stamp [S],
     scan_frame [S] (the camera frame every scan is tied to), has_board [S]}."""
+    rec = _record(seed, n_stations, move_frames, still_frames, side, n_rays, fov_deg, range_sigma, scan_prob, board_prob, Rlc, tlc)
+    check_margins(rec)
+    return rec
+
+
+def _record(seed, n_stations, move_frames, still_frames, side, n_rays, fov_deg, range_sigma, scan_prob, board_prob, Rlc, tlc) -> dict:
     rng = np.random.default_rng(seed)
     lo = np.array([-0.35, 0.05, 1.0, -0.6, -0.6, -0.6])
     hi = np.array([0.35, 0.55, 1.55, 0.6, 0.6, 0.6])
@@ -131,10 +137,8 @@ def recording(seed: int = 1, n_stations: int = 26, move_frames: int = 20, still_
     scans = {"ranges": ranges.ravel(), "offsets": np.arange(S + 1, dtype=np.int64) * n_rays,
              "angle_min": np.full(S, a0, dtype=np.float32), "angle_increment": np.full(S, inc, dtype=np.float32),
              "range_min": np.full(S, 0.05, dtype=np.float32)}
-    rec = {"pose_stamp": pose_stamp, "q_wc": q_wc, "t_wc": t_wc, "scans": scans, "scan_stamp": scan_stamp, "scan_frame": frames,
-           "has_board": has_board}
-    check_margins(rec)
-    return rec
+    return {"pose_stamp": pose_stamp, "q_wc": q_wc, "t_wc": t_wc, "scans": scans, "scan_stamp": scan_stamp, "scan_frame": frames,
+            "has_board": has_board}
 
 
 def check_margins(rec: dict) -> dict:
@@ -151,3 +155,73 @@ def check_margins(rec: dict) -> dict:
         m_tie = float((two[:, 1] - two[:, 0]).min())
         assert m_tie >= MARGIN, f"nearest and second-nearest |dt| are {m_tie:.3e} s apart"
     return {"keyframe": m_kf, "gate": m_gate, "tie": m_tie}
+
+
+# ---- static stations (GetStaticPose, src/utilities.cpp:86-155) --------------------------------------------------------------------
+CENTER_DIST_MAX = 0.002
+MIN_MEMBERS = 30
+
+
+def station_walk(t_wc: np.ndarray, dist_max: float = CENTER_DIST_MAX, min_members: int = MIN_MEMBERS):
+    """The walk of :96-124 -> (first [k], last [k], members [k], smallest distance of a finite membership distance from dist_max).
+    A run starts at pose a (xy_sum = t_a, size = 1); candidate j = a, a + 1, ... is a member iff |t_j - xy_sum / size| < dist_max
+    and then is added; the first non-member closes the run and is discarded; the run open at the end is dropped."""
+    t = np.asarray(t_wc, dtype=np.float64).reshape(-1, 3)
+    n = t.shape[0]
+    first, last, members, margin = [], [], [], np.inf
+    a = 0
+    while a < n:
+        xs, size, j = [float(v) for v in t[a]], 1, a
+        while j < n:
+            dx, dy, dz = float(t[j, 0]) - xs[0] / size, float(t[j, 1]) - xs[1] / size, float(t[j, 2]) - xs[2] / size
+            d = np.sqrt(dx * dx + dy * dy + dz * dz)
+            if np.isfinite(d):
+                margin = min(margin, abs(d - dist_max))
+            if not d < dist_max:
+                break
+            xs = [xs[c] + float(t[j, c]) for c in range(3)]
+            size += 1
+            j += 1
+        if j >= n:
+            break
+        if size > min_members:
+            first.append(a); last.append(max(j - 1, a)); members.append(size)
+        a = j + 1
+    return np.array(first, dtype=np.int64), np.array(last, dtype=np.int64), np.array(members, dtype=np.int64), float(margin)
+
+
+def station_recording(seed: int = 1, n_stations: int = 12, move_frames: int = 20, still_frames: int = 40, pose_sigma_t: float = 2e-4,
+                      pose_sigma_r: float = 1e-3, side: float = 1.2, n_rays: int = 1081, fov_deg: float = 270.0, range_sigma: float = 0.001,
+                      scan_prob: float = 0.85, board_prob: float = 0.9, Rlc: np.ndarray = sd.GT_RLC, tlc: np.ndarray = sd.GT_TLC) -> dict:
+    """recording() with stations long enough for GetStaticPose (more than 30 members) and seeded Gaussian jitter on the STAMPED tag
+    poses: pose_sigma_t metres on t_wc, pose_sigma_r radians (a small rotation about a random axis) on q_wc.  The scans still see the
+    board where it truly stood.  -> recording()'s dict, q_wc / t_wc the jittered poses, plus q_wc_true / t_wc_true and
+    station_first / station_last / station_members (the CPU walk on the jittered translations).  Asserts that every finite
+    membership distance is at least MARGIN from CENTER_DIST_MAX and every scan stamp at least MARGIN seconds from a station's ends."""
+    rec = _record(seed, n_stations, move_frames, still_frames, side, n_rays, fov_deg, range_sigma, scan_prob, board_prob, Rlc, tlc)
+    rng = np.random.default_rng([seed, 0x57A7])  # a stream of its own: the recording itself is recording()'s
+    n = rec["pose_stamp"].shape[0]
+    rec["q_wc_true"], rec["t_wc_true"] = rec["q_wc"], rec["t_wc"]
+    rec["t_wc"] = rec["t_wc_true"] + rng.normal(0.0, pose_sigma_t, (n, 3))
+    rv = rng.normal(0.0, pose_sigma_r, (n, 3))
+    ang = np.linalg.norm(rv, axis=1)
+    axis = rv / np.maximum(ang, 1e-300)[:, None]
+    dq = np.concatenate([np.cos(ang / 2)[:, None], np.sin(ang / 2)[:, None] * axis], axis=1)
+    w0, x0, y0, z0 = rec["q_wc_true"].T
+    w1, x1, y1, z1 = dq.T
+    q = np.stack([w0 * w1 - x0 * x1 - y0 * y1 - z0 * z1, w0 * x1 + x0 * w1 + y0 * z1 - z0 * y1, w0 * y1 - x0 * z1 + y0 * w1 + z0 * x1,
+                  w0 * z1 + x0 * y1 - y0 * x1 + z0 * w1], axis=1)
+    rec["q_wc"] = q / np.linalg.norm(q, axis=1)[:, None]
+    rec.update(check_station_margins(rec))
+    return rec
+
+
+def check_station_margins(rec: dict) -> dict:
+    """Asserts the margin conditions of station_recording -> {"station_first", "station_last", "station_members", "station_margin",
+    "stamp_margin"}."""
+    first, last, members, m_walk = station_walk(rec["t_wc"])
+    assert m_walk >= MARGIN, f"a membership distance is {m_walk:.3e} from its threshold"
+    ends = np.concatenate([rec["pose_stamp"][first], rec["pose_stamp"][last]])
+    m_stamp = float(np.abs(ends[None, :] - rec["scan_stamp"][:, None]).min()) if ends.size and rec["scan_stamp"].size else np.inf
+    assert m_stamp >= MARGIN, f"a scan stamp is {m_stamp:.3e} s from a station's end"
+    return {"station_first": first, "station_last": last, "station_members": members, "station_margin": m_walk, "stamp_margin": m_stamp}

@@ -611,6 +611,82 @@ class Solver:
                                                        scan_pose_ptr or None, C.byref(info)), "clc_assemble_observations_device")
         return info
 
+    # ---- static stations: averaged tag poses and station-mode assembly (K14) ----
+    def static_poses(self, pose_stamp, q_wc, t_wc, options: Optional["_capi.StationOptions"] = None, cap_stations: Optional[int] = None) -> dict:
+        """GetStaticPose (src/utilities.cpp:86-155) on stamped tag poses (pose_stamp [n] or None: the stamps come back 0; q_wc [n, 4]
+        (w, x, y, z), t_wc [n, 3]) -> {"n_stations" (the true count), "first", "last" [k] int64 (pose indices of the first and the
+        last member), "start_time", "end_time" [k], "q" [k, 4], "t" [k, 3], "status" [k] int32 (CLC_STATION_*)}; k = n_stations, or
+        at most cap_stations when given (0: the count alone)."""
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        ps = None if pose_stamp is None else np.ascontiguousarray(pose_stamp, dtype=np.float64).reshape(-1)
+        assert q.shape[0] == t.shape[0] and (ps is None or ps.shape[0] == q.shape[0]), "one stamp, quaternion and translation per pose"
+        o = options or _capi.default_station_options()
+        n = C.c_int64()
+        args = (self._h, C.byref(o), q.shape[0], None if ps is None else ps.ctypes.data, q.ctypes.data, t.ctypes.data)
+        if cap_stations is None:
+            check(self._L.clc_static_poses(*args, 0, None, None, None, None, None, None, None, C.byref(n)), "clc_static_poses")
+            cap_stations = n.value
+        k = int(cap_stations)
+        out = {"first": np.zeros(k, np.int64), "last": np.zeros(k, np.int64), "start_time": np.zeros(k), "end_time": np.zeros(k),
+               "q": np.zeros((k, 4)), "t": np.zeros((k, 3)), "status": np.zeros(k, np.int32)}
+        ptr = lambda a: a.ctypes.data if k > 0 else None
+        check(self._L.clc_static_poses(*args, k, ptr(out["first"]), ptr(out["last"]), ptr(out["start_time"]), ptr(out["end_time"]), ptr(out["q"]),
+                                       ptr(out["t"]), ptr(out["status"]), C.byref(n)), "clc_static_poses")
+        out["n_stations"] = n.value
+        return out
+
+    def assemble_stations(self, pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, options: Optional["_capi.StationOptions"] = None):
+        """assemble_observations in station mode: the stamped tag poses are averaged per static station (static_poses) and every scan
+        with a board segment whose stamp lies in a station's [start_time, end_time] becomes one observation with that station's
+        averaged pose -> (StationInfo, scan_station [S] int32).  The observations are left stored on the handle."""
+        ps = np.ascontiguousarray(pose_stamp, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        assert q.shape[0] == t.shape[0] == ps.shape[0], "one stamp, quaternion and translation per pose"
+        r = np.ascontiguousarray(scans["ranges"], dtype=np.float32)
+        off = np.ascontiguousarray(scans["offsets"], dtype=np.int64)
+        S = len(off) - 1
+        f = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (S,)))
+        am, ai, rm = f(scans["angle_min"]), f(scans["angle_increment"]), f(scans["range_min"])
+        ss = np.ascontiguousarray(scan_stamp, dtype=np.float64).reshape(-1)
+        assert ss.shape[0] == S, "one stamp per scan"
+        scan_station = np.zeros(S, dtype=np.int32)
+        info = _capi.StationInfo()
+        o = options or _capi.default_station_options()
+        check(self._L.clc_assemble_stations(self._h, C.byref(o), ps.shape[0], ps.ctypes.data, q.ctypes.data, t.ctypes.data, r.ctypes.data,
+                                            off.ctypes.data, S, am.ctypes.data, ai.ctypes.data, rm.ctypes.data, ss.ctypes.data,
+                                            scan_station.ctypes.data, C.byref(info)), "clc_assemble_stations")
+        return info, scan_station
+
+    def assemble_stations_device(self, n_poses: int, pose_stamp_ptr: int, q_wc_ptr: int, t_wc_ptr: int, ranges_ptr: int, offsets_ptr: int,
+                                 n_scans: int, n_rays: int, angle_min_ptr: int, angle_increment_ptr: int, range_min_ptr: int,
+                                 scan_stamp_ptr: int, scan_station_ptr: int = 0, options: Optional["_capi.StationOptions"] = None):
+        """clc_assemble_stations_device on device-resident arrays (data_ptr()s; ready on the solver's stream) -> StationInfo."""
+        info = _capi.StationInfo()
+        o = options or _capi.default_station_options()
+        check(self._L.clc_assemble_stations_device(self._h, C.byref(o), n_poses, pose_stamp_ptr or None, q_wc_ptr or None, t_wc_ptr or None,
+                                                   ranges_ptr or None, offsets_ptr or None, n_scans, n_rays, angle_min_ptr or None,
+                                                   angle_increment_ptr or None, range_min_ptr or None, scan_stamp_ptr or None,
+                                                   scan_station_ptr or None, C.byref(info)), "clc_assemble_stations_device")
+        return info
+
+    def debug_station_walk(self, t_wc, options: Optional["_capi.StationOptions"] = None) -> dict:
+        """Test hook: the walk of static_poses alone -> {"first", "last", "members" [k] int64, "n_stations", "n_runs"}."""
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        o = options or _capi.default_station_options()
+        f = self._hook("clc_debug_station_walk")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        ns, nr = C.c_int64(), C.c_int64()
+        check(f(self._h, C.byref(o), t.shape[0], t.ctypes.data, 0, None, None, None, C.byref(ns), C.byref(nr)), "clc_debug_station_walk")
+        k = ns.value
+        out = {"first": np.zeros(k, np.int64), "last": np.zeros(k, np.int64), "members": np.zeros(k, np.int64)}
+        if k > 0:
+            check(f(self._h, C.byref(o), t.shape[0], t.ctypes.data, k, out["first"].ctypes.data, out["last"].ctypes.data,
+                    out["members"].ctypes.data, C.byref(ns), C.byref(nr)), "clc_debug_station_walk")
+        out["n_stations"], out["n_runs"] = ns.value, nr.value
+        return out
+
     def stored_observations(self):
         """The scans stored on the handle (store_observations / assemble_observations), copied back -> simdata.ObservationSet."""
         from .simdata import ObservationSet

@@ -467,6 +467,69 @@ int clc_assemble_observations_device(clc_handle* h, const clc_assemble_options* 
 int clc_stored_observations(clc_handle* h, int* n_poses, double* tag_q_wxyz, double* tag_t, int64_t* pts_off, double* pts,
                             int64_t* ptl_off, double* ptl);
 
+/* ---- static stations (K14): averaged tag poses and station-mode assembly, GetStaticPose, src/utilities.cpp:86-155 ----------
+ * For recordings where the board is held still at stations.  The walk (:96-124): a run starts at pose a with xy_sum = t_a and
+ * size = 1 (the pose is pushed); candidate j = a, a + 1, ... is a member iff |t_j - xy_sum / size| < center_dist_max (norm():
+ * every square and sum rounded; the centre a per-component division) and then does xy_sum += t_j, ++size; the first candidate
+ * that is no member closes the run [a, j - 1], is discarded, and the next run starts at j + 1.  As in the reference: the first
+ * pose of a run is tested against itself and counted twice (in size, in the running centre and in the averages), so a run of k
+ * distinct poses has k + 1 members; a run is a station iff members > min_members (30: k >= 30); a NaN translation is never a
+ * member (at a run's start: a run of one member); the run still open at the end of the list is dropped, unless close_last_run.
+ * The average (:129-152) of a station with members m0 (twice), m1, ...: t = sum t / n; q = the unit eigenvector of the largest
+ * eigenvalue of A = sum q q^T / n, q as (w, x, y, z) (getAvergeQwc, :156-166; the reference takes Eigen::EigenSolver's vector,
+ * whose sign is arbitrary — here cyclic Jacobi, and the sign is fixed: w > 0, or the first non-zero component positive when
+ * w == 0); start_time / end_time = the stamps of the first and the last member (include/utilities.h:19-20).  A station whose
+ * average is not finite gets status CLC_STATION_NONFINITE, q = (1, 0, 0, 0), t = 0, and takes no scan.
+ * Station-mode assembly is clc_assemble_observations with a different tie between scans and poses: a scan with a board segment
+ * takes the FIRST station, in station order, with start_time <= scan_stamp <= end_time (both ends inclusive; a NaN stamp never
+ * matches) and becomes one observation with that station's averaged pose.  This interval matching is this library's design —
+ * the reference has no node that consumes GetStaticPose.  Everything else (segments, line fits, points_on_line, the order of the
+ * observations, how they are left stored on the handle) is as for clc_assemble_observations. */
+typedef struct clc_station_options {
+  double center_dist_max; /* 0.002 m, :108 */
+  int64_t min_members;    /* 30, :119: a station has members > 30, the first pose counted twice */
+  int32_t close_last_run; /* 0: the run open at the end of the list is dropped (the reference); 1: it is closed like any other */
+  int32_t reserved;       /* 0 */
+  double line0[2];        /* start of every line fit: (0, 0) */
+  clc_options line;       /* clc_line_options_default */
+} clc_station_options;
+void clc_station_options_default(clc_station_options* opt);
+typedef struct clc_station_info {
+  int64_t n_runs;         /* runs the walk closed */
+  int64_t n_stations;     /* those with members > min_members */
+  int64_t n_nonfinite;    /* stations with status CLC_STATION_NONFINITE */
+  int64_t n_segments;     /* scans with a board segment (CLC_SEG_FOUND) */
+  int64_t n_ref_throws;   /* scans dropped with CLC_SEG_REF_THROWS */
+  int64_t n_unmatched;    /* scans with a segment and no station that holds their stamp */
+  int64_t n_observations; /* = n_segments - n_unmatched */
+  int64_t n_points;       /* points of all observations */
+  int64_t n_line_points;  /* points_on_line of all observations */
+} clc_station_info;
+#define CLC_STATION_OK 1
+#define CLC_STATION_NONFINITE (-1)
+/* The stations alone, on host arrays: pose_stamp[n_poses] (nullable: the stamps come back 0), q_wc_wxyz[4 * n_poses],
+ * t_wc[3 * n_poses] -> *n_stations, the true count, and at most cap_stations rows of first / last (pose indices of the first and
+ * the last member), start_time / end_time, q_avg_wxyz[4 *], t_avg[3 *], status (CLC_STATION_*).  Every output is nullable:
+ * cap_stations = 0 is a count query.  n_poses = 0: 0 stations, CLC_OK (the reference asserts there).  opt NULL: the defaults.
+ * CLC_ERR_INVALID_ARG: NULL inputs, 2^31 poses or more, center_dist_max not finite or < 0, min_members < 0. */
+int clc_static_poses(clc_handle* h, const clc_station_options* opt, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                     const double* t_wc, size_t cap_stations, int64_t* first, int64_t* last, double* start_time, double* end_time,
+                     double* q_avg_wxyz, double* t_avg, int32_t* status, int64_t* n_stations);
+/* clc_assemble_observations in station mode.  The arrays are those of clc_assemble_observations; scan_station[n_scans]
+ * (nullable): the index of the station a kept scan took, or CLC_SCAN_NO_SEGMENT / CLC_SCAN_REF_THROWS / CLC_SCAN_NO_POSE (no
+ * finite station holds the stamp).  No station or no observation at all: CLC_OK and an empty store.  The same
+ * CLC_ERR_INVALID_ARG cases, and those of clc_static_poses' options. */
+int clc_assemble_stations(clc_handle* h, const clc_station_options* opt, size_t n_poses, const double* pose_stamp,
+                          const double* q_wc_wxyz, const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans,
+                          const float* angle_min, const float* angle_increment, const float* range_min, const double* scan_stamp,
+                          int32_t* scan_station, clc_station_info* info);
+/* The same with every array in DEVICE memory, as clc_assemble_observations_device (ONE synchronisation). */
+int clc_assemble_stations_device(clc_handle* h, const clc_station_options* opt, size_t n_poses, const double* pose_stamp_dev,
+                                 const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev,
+                                 const int64_t* offsets_dev, size_t n_scans, size_t n_rays, const float* angle_min_dev,
+                                 const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
+                                 int32_t* scan_station_dev, clc_station_info* info);
+
 /* ---- board poses from tag corners (the numeric half of CamPoseEst::calcCamPose, src/calcCamPose.cpp:270-303) -------------
  * The two camera models the reference's nodes select (main/kalibratag_detector_node.cpp:90-105), restated from camodocal:
  *   CLC_CAMERA_PINHOLE         PinholeCamera:     proj = fx fy cx cy, dist = k1 k2 p1 p2
