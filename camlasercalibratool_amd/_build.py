@@ -23,7 +23,7 @@ HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assembl
 # (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
 # abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md), those of abi_frontend.hip by clc_stations.hpp
 # (profiles/offline_stations.md).  They rebuild the libraries and are not part of csrc_sha16.
-SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp"]
+SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the

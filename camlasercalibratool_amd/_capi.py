@@ -40,6 +40,8 @@ EXPORTED = [
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
     "clc_station_options_default", "clc_static_poses", "clc_assemble_stations", "clc_assemble_stations_device",
+    "clc_interp_options_default", "clc_interpolate_poses", "clc_assemble_interpolated", "clc_assemble_interpolated_device",
+    "clc_clock_offset_options_default", "clc_clock_offset_best", "clc_clock_offset_sweep", "clc_clock_offset_sweep_device",
 ]
 # test / profiling hooks: NOT in include/clc.h and not in the product library; exported by the -DCLC_TEST_HOOKS builds
 # (csrc/libclc_hip_hooks.so) only (tests/test_abi_symbols.py checks both directions)
@@ -48,7 +50,7 @@ HOOKS = [
     "clc_debug_wave_split", "clc_debug_resident", "clc_debug_resident_single", "clc_debug_coop", "clc_debug_coop_control",
     "clc_debug_coop_set_tag", "clc_debug_layout", "clc_debug_lm_profile", "clc_time_steps", "clc_time_batched_eval", "clc_time_eval",
     "clc_debug_comm_create_layout", "clc_debug_single_controller", "clc_debug_fast_small",
-    "clc_debug_lane_map_builds", "clc_debug_assemble_lines", "clc_debug_station_walk",
+    "clc_debug_lane_map_builds", "clc_debug_assemble_lines", "clc_debug_station_walk", "clc_debug_sweep_records",
 ]
 
 
@@ -154,6 +156,11 @@ class StationInfo(C.Structure):
 STATION_OK, STATION_NONFINITE = 1, -1  # CLC_STATION_*
 
 
+class InterpOptions(C.Structure):
+    """clc_interp_options (include/clc.h)."""
+    _fields_ = [("time_offset", C.c_double), ("max_gap", C.c_double), ("line0", C.c_double * 2), ("line", Options)]
+
+
 class ClcError(RuntimeError):
     def __init__(self, code: int, where: str, detail: str):
         super().__init__(f"{where}: {ERRORS.get(code, code)} — {detail}")
@@ -254,6 +261,17 @@ def load(path: str):
             L.clc_static_poses.argtypes = [V, V, C.c_size_t, V, V, V, C.c_size_t, V, V, V, V, V, V, V, V]
             L.clc_assemble_stations.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V]
             L.clc_assemble_stations_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V]
+        if hasattr(L, "clc_interpolate_poses"):
+            L.clc_interp_options_default.argtypes = [V]
+            L.clc_interp_options_default.restype = None
+            L.clc_interpolate_poses.argtypes = [V, V, C.c_size_t, V, V, V, C.c_size_t, V, V, V, V, V]
+            L.clc_assemble_interpolated.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V, V]
+            L.clc_assemble_interpolated_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V, V]
+            L.clc_clock_offset_options_default.argtypes = [V]
+            L.clc_clock_offset_options_default.restype = None
+            L.clc_clock_offset_best.argtypes = [C.c_size_t, V, V, V, V, V, V]
+            L.clc_clock_offset_sweep.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V, V, V, V, V]
+            L.clc_clock_offset_sweep_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V, V, V, V, V]
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -319,6 +337,45 @@ def default_station_options() -> StationOptions:
     """The reference's settings, src/utilities.cpp:108,:119: 2 mm, more than 30 members; the open last run dropped; line fits from (0, 0)."""
     o = StationOptions()
     lib().clc_station_options_default(C.byref(o))
+    return o
+
+
+class TimeOffsetOptions(C.Structure):
+    """clc_clock_offset_options (include/clc.h)."""
+    _fields_ = [("offset_min", C.c_double), ("offset_max", C.c_double), ("n_offsets", C.c_int32), ("points_per_scan", C.c_int32),
+                ("interp", InterpOptions), ("solve", Options)]
+
+
+class TimeOffsetResult(C.Structure):
+    """clc_clock_offset_result (include/clc.h)."""
+    _fields_ = [("n_scans_used", C.c_int64), ("records_per_problem", C.c_int64), ("best_index", C.c_int32), ("at_edge", C.c_int32),
+                ("best_offset", C.c_double)]
+
+
+def default_time_offset_options() -> TimeOffsetOptions:
+    """41 candidates over -20 .. +20 ms, 16 points per scan; the interpolation's and the solve's defaults."""
+    o = TimeOffsetOptions()
+    lib().clc_clock_offset_options_default(C.byref(o))
+    return o
+
+
+def time_offset_best(offsets, final_cost, termination=None):
+    """clc_clock_offset_best (host code, no device): -> (best_index, best_offset, at_edge)."""
+    x = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(final_cost, dtype=np.float64).reshape(-1)
+    assert x.shape == c.shape
+    tm = None if termination is None else np.ascontiguousarray(termination, dtype=np.int32).reshape(-1)
+    assert tm is None or tm.shape == x.shape
+    bi, ae, bo = C.c_int32(), C.c_int32(), C.c_double()
+    check(lib().clc_clock_offset_best(x.shape[0], x.ctypes.data if x.size else None, c.ctypes.data if x.size else None,
+                                     None if tm is None else tm.ctypes.data, C.byref(bi), C.byref(bo), C.byref(ae)), "clc_clock_offset_best")
+    return bi.value, bo.value, ae.value
+
+
+def default_interp_options() -> InterpOptions:
+    """No clock offset, tag poses at most 0.1 s apart are interpolated across; line fits from (0, 0)."""
+    o = InterpOptions()
+    lib().clc_interp_options_default(C.byref(o))
     return o
 
 

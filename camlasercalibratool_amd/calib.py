@@ -16,7 +16,8 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import simdata
-from ._capi import AssembleOptions, ClcError, Options, StationOptions, TERMINATION, default_line_options, default_options
+from ._capi import (AssembleOptions, ClcError, InterpOptions, Options, StationOptions, TimeOffsetOptions, default_interp_options,
+                    default_time_offset_options, TERMINATION, default_line_options, default_options)
 from .simdata import Oberserve, ObservationSet
 from .solver import SolveResult, Solver, flatten_observations
 
@@ -409,6 +410,68 @@ def CalibrateOfflineStations(pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, st
     blocks, ids = station_block_offsets(scan_station)
     return {"Tlc_initial": Tlc0, "Tcl": Tcl, "Tlc": Tlc, "report": report, "info": info, "scan_station": scan_station, "session": ses,
             "station_block_offsets": blocks, "station_block_ids": ids}
+
+
+def CalibrateOfflineInterpolated(pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, time_offset: Union[str, float] = "estimate",
+                                 interp_options: Optional[InterpOptions] = None, sweep_options: Optional[TimeOffsetOptions] = None,
+                                 options: Optional[Options] = None, solver: Optional[Solver] = None, verbose: bool = True):
+    """CalibrateOffline for recordings where the board moves: every scan with a board segment becomes an observation with the tag
+    pose interpolated at its stamp + time_offset (Solver.assemble_interpolated) — no key frames, no 20 ms gate; then the closed form,
+    Tcl = inv(Tlc), CamLaserCalibration(obs, Tcl, false) and its analysis pass as in main/calibr_offline.cpp:166-170.
+    time_offset: seconds to add to the laser's stamps to get camera time, or "estimate": the observations are first assembled at
+    offset 0 for a closed-form start, Solver.time_offset_sweep (sweep_options; its interpolation settings are interp_options') runs
+    from that start, and the assembly is repeated at the sweep's best_offset with all points.
+    The same gates: fewer than 10 poses, fewer than 5 observations.  Returns None under the gates, otherwise CalibrateOffline's dict
+    with "info" (AssembleInfo), "scan_bracket" [S], "scan_u" [S], "time_offset" (the offset used) and "sweep" (time_offset_sweep's
+    dict — the table of offsets and final costs — or None)."""
+    if len(np.asarray(pose_stamp).reshape(-1)) < 10:
+        if verbose:
+            print("apriltag pose less than 10.")
+        return None
+    sv = solver or _shared_solver()
+    o = InterpOptions.from_buffer_copy(interp_options) if interp_options is not None else default_interp_options()
+    sweep = None
+    if isinstance(time_offset, str):
+        if time_offset != "estimate":
+            raise ValueError("CalibrateOfflineInterpolated: time_offset is a number of seconds or \"estimate\"")
+        o.time_offset = 0.0
+        info, _, _ = sv.assemble_interpolated(pose_stamp, q_wc, t_wc, scans, scan_stamp, o)
+        if info.n_observations < 5:
+            if verbose:
+                print("Valid Calibra Data Less")
+            return None
+        Tlc_start = np.eye(4)
+        Session.adopt(sv).CamLaserCalClosedSolution(Tlc_start, False)
+        so = TimeOffsetOptions.from_buffer_copy(sweep_options) if sweep_options is not None else default_time_offset_options()
+        so.interp = o
+        if options is not None:
+            so.solve = options
+        sweep = sv.time_offset_sweep(pose_stamp, q_wc, t_wc, scans, scan_stamp, simdata.pose7_from_T(np.linalg.inv(Tlc_start)), so)
+        if sweep["best_index"] < 0:
+            if verbose:
+                print("Valid Calibra Data Less")
+            return None
+        o.time_offset = float(sweep["best_offset"])
+    else:
+        o.time_offset = float(time_offset)
+    info, scan_bracket, scan_u = sv.assemble_interpolated(pose_stamp, q_wc, t_wc, scans, scan_stamp, o)
+    if info.n_observations < 5:
+        if verbose:
+            print("Valid Calibra Data Less")
+        return None
+    if verbose:
+        print("time offset: ", o.time_offset, " obs size: ", info.n_observations)
+    ses = Session.adopt(sv)
+    Tlc0 = np.eye(4)
+    ses.CamLaserCalClosedSolution(Tlc0, verbose)
+    Tcl = np.linalg.inv(Tlc0)
+    report = ses.CamLaserCalibration(Tcl, False, False, options, verbose)
+    Tlc = np.linalg.inv(Tcl)
+    if verbose:
+        print("\n----- Transform from Camera to Laser Tlc is: -----\n")
+        print(Tlc)
+    return {"Tlc_initial": Tlc0, "Tcl": Tcl, "Tlc": Tlc, "report": report, "info": info, "scan_bracket": scan_bracket, "scan_u": scan_u,
+            "time_offset": o.time_offset, "sweep": sweep, "session": ses}
 
 
 def LineFittingCeres(Points: np.ndarray, Line: np.ndarray, solver: Optional[Solver] = None,

@@ -1,10 +1,11 @@
 // abi_frontend.hip — the calls either side of the solve: factor evaluation, manifold plus, information matrix and closed form, line fitting, scan conversion,
-// board-segment detection, assembly of the offline flow's observations (K13), static stations (K14).
+// board-segment detection, assembly of the offline flow's observations (K13), static stations (K14), interpolated tag poses (K15).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 #include "clc_scanseg.hpp"
 #include "clc_assemble.hpp"
 #include "clc_stations.hpp"
+#include "clc_interp.hpp"
 #include "abi_assemble.hpp"
 
 using namespace clc_abi;
@@ -529,6 +530,144 @@ int assemble_stations_on_device(clc_handle* h, const clc_station_options& opt, s
   return CLC_OK;
 }
 
+// ---- interpolated tag poses (K15, clc_interp.hpp) -----------------------------------------------------------------------------------
+int check_interp_options(const char* who, const clc_interp_options* in, clc_interp_options* opt) {
+  if (in) *opt = *in; else clc_interp_options_default(opt);
+  if (!std::isfinite(opt->max_gap) || !(opt->max_gap > 0.0) || !std::isfinite(opt->time_offset)) return fail(CLC_ERR_INVALID_ARG, who);
+  if (opt->line.max_num_iterations < 0 || (opt->line.use_loss && !(opt->line.loss_scale_factor > 0.0))) return fail(CLC_ERR_INVALID_ARG, who);
+  if (!std::isfinite(opt->line0[0]) || !std::isfinite(opt->line0[1])) return fail(CLC_ERR_NONFINITE, who);
+  return CLC_OK;
+}
+
+// the look at the pose list and the interpolation at m query stamps, enqueued on the handle's stream (no wait); cnt: ASM_COUNTERS
+int launch_interp(clc_handle* h, const clc_interp_options& opt, size_t n_poses, const double* d_stamp, const double* d_q, const double* d_t,
+                  const int* d_status, const double* d_query, size_t m, long long* cnt, int32_t* d_bracket, double* d_u, double* d_qo, double* d_to,
+                  int32_t* d_self) {
+  hipLaunchKernelGGL(clc::interp_stamps_kernel, dim3(1), dim3(64), 0, h->stream, d_stamp, (long long)n_poses, opt.max_gap, cnt);
+  CLC_HIP(hipGetLastError());
+  if (m > 0) {
+    hipLaunchKernelGGL(clc::interp_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, d_status, d_query, (long long)m, d_stamp,
+                       d_q, d_t, (long long)n_poses, cnt, opt.time_offset, opt.max_gap, d_bracket, d_u, d_qo, d_to, d_self);
+    CLC_HIP(hipGetLastError());
+  }
+  return CLC_OK;
+}
+
+// K15: every scan with a segment takes the pose interpolated at its stamp; the gather reads the per-scan poses (scan_pose[s] = s)
+int assemble_interpolated_on_device(clc_handle* h, const clc_interp_options& opt, size_t n_poses, const double* d_stamp, const double* d_q,
+                                    const double* d_t, const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am,
+                                    const float* d_ai, const float* d_rm, const double* d_sstamp, int32_t* d_bracket, double* d_u,
+                                    int32_t* host_bracket, double* host_u, clc_assemble_info* info) {
+  DevBuf<double> sq(&h->pool), st(&h->pool), su(&h->pool);
+  DevBuf<int> sbr(&h->pool);
+  CLC_HIP(sq.alloc(4 * S)); CLC_HIP(st.alloc(3 * S));
+  if (!d_bracket && host_bracket) { CLC_HIP(sbr.alloc(S)); d_bracket = sbr.p; }
+  if (!d_u && host_u) { CLC_HIP(su.alloc(S)); d_u = su.p; }
+  long long c[clc::ASM_COUNTERS];
+  CLC_TRY(assemble_on_device(
+      h, "clc_assemble_interpolated", opt.line0, opt.line, sq.p, st.p, d_ranges, d_off, S, n_rays, d_am, d_ai, d_rm, nullptr, nullptr, c,
+      [&](long long* cnt, const int* status, int32_t* scan_pose) {
+        return launch_interp(h, opt, n_poses, d_stamp, d_q, d_t, status, d_sstamp, S, cnt, d_bracket, d_u, sq.p, st.p, scan_pose);
+      },
+      [&] {
+        if (host_bracket && S > 0) CLC_HIP(hipMemcpyAsync(host_bracket, d_bracket, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (host_u && S > 0) CLC_HIP(hipMemcpyAsync(host_u, d_u, S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        return (int)CLC_OK;
+      }));
+  if (info) {
+    info->n_keyframes = c[clc::ASM_N_KEYFRAMES];
+    info->n_segments = c[clc::ASM_N_SEGMENTS];
+    info->n_ref_throws = c[clc::ASM_N_REF_THROWS];
+    info->n_unmatched = c[clc::ASM_N_UNMATCHED];
+    info->n_observations = c[clc::ASM_N_OBS];
+    info->n_points = c[clc::ASM_N_POINTS];
+    info->n_line_points = c[clc::ASM_N_LINE_POINTS];
+  }
+  return CLC_OK;
+}
+
+// ---- the clock sweep (K15) ------------------------------------------------------------------------------------------------------------
+#ifdef CLC_TEST_HOOKS
+std::vector<double> g_last_sweep_records;  // the records of the last sweep in this process, problem-major (hooks build only)
+#endif
+
+int check_sweep_options(const char* who, const clc_clock_offset_options* in, clc_clock_offset_options* opt) {
+  if (in) *opt = *in; else clc_clock_offset_options_default(opt);
+  if (opt->n_offsets < 3 || opt->n_offsets > 1024 || !std::isfinite(opt->offset_min) || !std::isfinite(opt->offset_max) ||
+      !(opt->offset_max > opt->offset_min) || opt->points_per_scan < 0 || !std::isfinite(opt->interp.max_gap) || !(opt->interp.max_gap > 0.0))
+    return fail(CLC_ERR_INVALID_ARG, who);
+  return CLC_OK;
+}
+
+int sweep_on_device(clc_handle* h, const clc_clock_offset_options& opt, size_t n_poses, const double* d_stamp, const double* d_q, const double* d_t,
+                    const float* d_ranges, const int64_t* d_off, size_t S, size_t n_rays, const float* d_am, const float* d_ai, const float* d_rm,
+                    const double* d_sstamp, const double pose7[7], double* offsets_out, double* final_cost, double* poses, clc_summary* summaries,
+                    clc_clock_offset_result* result) {
+  const size_t J = (size_t)opt.n_offsets;
+  std::vector<double> cand(J);
+  for (size_t j = 0; j < J; ++j) cand[j] = opt.offset_min + (double)j * (opt.offset_max - opt.offset_min) / (double)(J - 1);
+  if (offsets_out) std::memcpy(offsets_out, cand.data(), J * sizeof(double));
+  result->n_scans_used = 0;
+  result->records_per_problem = 0;
+  result->best_index = -1;
+  result->at_edge = 0;
+  result->best_offset = std::nan("");
+  if (S == 0) return CLC_OK;
+  DevBuf<long long> cnt(&h->pool), sw(&h->pool), seg(&h->pool), take(&h->pool), used_scan(&h->pool), rec_off(&h->pool);
+  DevBuf<int> status(&h->pool);
+  DevBuf<double> points(&h->pool), dcand(&h->pool), rec(&h->pool);
+  CLC_HIP(cnt.alloc(clc::ASM_COUNTERS)); CLC_HIP(sw.alloc(clc::SW_COUNTERS)); CLC_HIP(seg.alloc(2 * S)); CLC_HIP(take.alloc(S));
+  CLC_HIP(used_scan.alloc(S)); CLC_HIP(rec_off.alloc(S + 1)); CLC_HIP(status.alloc(S)); CLC_HIP(points.alloc(3 * n_rays)); CLC_HIP(dcand.alloc(J));
+  const long long* off = reinterpret_cast<const long long*>(d_off);
+  const int threads = 256;
+  CLC_HIP(hipMemcpyAsync(dcand.p, cand.data(), J * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (n_rays > 0) {
+    hipLaunchKernelGGL(clc::scan_to_points_flat_kernel, dim3((unsigned)((n_rays + threads - 1) / threads)), dim3(threads), 0, h->stream, d_ranges,
+                       off, (long long)S, (long long)n_rays, d_am, d_ai, d_rm, points.p);
+    CLC_HIP(hipGetLastError());
+  }
+  launch_board_segments(h, points.p, d_off, S, reinterpret_cast<int64_t*>(seg.p), status.p);
+  CLC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(clc::interp_stamps_kernel, dim3(1), dim3(64), 0, h->stream, d_stamp, (long long)n_poses, opt.interp.max_gap, cnt.p);
+  CLC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(clc::sweep_member_kernel, dim3((unsigned)((S + threads - 1) / threads)), dim3(threads), 0, h->stream, status.p, seg.p, d_sstamp,
+                     (long long)S, d_stamp, d_q, d_t, (long long)n_poses, cnt.p, dcand.p, (int)J, opt.interp.max_gap, (long long)opt.points_per_scan,
+                     take.p);
+  CLC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(clc::sweep_offsets_kernel, dim3(1), dim3(clc::SWEEP_SCAN_BLOCK), 0, h->stream, take.p, (long long)S, used_scan.p, rec_off.p, sw.p);
+  CLC_HIP(hipGetLastError());
+  long long c[clc::SW_COUNTERS];
+  CLC_HIP(hipMemcpyAsync(c, sw.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));  // the one read-back: the sizes of the batch
+  const size_t U = (size_t)c[clc::SW_N_USED], R = (size_t)c[clc::SW_N_RECORDS];
+  result->n_scans_used = (int64_t)U;
+  result->records_per_problem = (int64_t)R;
+  if (U == 0) return CLC_OK;
+  CLC_HIP(rec.alloc(J * R * 8));
+  hipLaunchKernelGGL(clc::sweep_records_kernel, dim3((unsigned)U, (unsigned)J), dim3(128), 0, h->stream, points.p, off, seg.p, d_sstamp, used_scan.p,
+                     rec_off.p, sw.p, d_stamp, d_q, d_t, (long long)n_poses, cnt.p, dcand.p, opt.interp.max_gap, (long long)opt.points_per_scan, rec.p);
+  CLC_HIP(hipGetLastError());
+#ifdef CLC_TEST_HOOKS
+  g_last_sweep_records.assign(J * R * 8, 0.0);  // test hook: clc_debug_sweep_records
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  CLC_HIP(hipMemcpy(g_last_sweep_records.data(), rec.p, J * R * 8 * sizeof(double), hipMemcpyDeviceToHost));
+#endif
+  std::vector<int64_t> poff(J + 1);
+  for (size_t j = 0; j <= J; ++j) poff[j] = (int64_t)(j * R);
+  CLC_TRY(clc_upload_batched_device(h, reinterpret_cast<const clc_observation*>(rec.p), poff.data(), J));
+  std::vector<double> p7(7 * J);
+  std::vector<clc_summary> sm(J);
+  for (size_t j = 0; j < J; ++j) std::memcpy(&p7[7 * j], pose7, 7 * sizeof(double));
+  CLC_TRY(clc_solve_batched(h, &opt.solve, p7.data(), sm.data()));
+  std::vector<double> cost(J);
+  std::vector<int32_t> term(J);
+  for (size_t j = 0; j < J; ++j) { cost[j] = sm[j].final_cost; term[j] = sm[j].termination; }
+  if (final_cost) std::memcpy(final_cost, cost.data(), J * sizeof(double));
+  if (poses) std::memcpy(poses, p7.data(), 7 * J * sizeof(double));
+  if (summaries) std::memcpy(summaries, sm.data(), J * sizeof(clc_summary));
+  return clc_clock_offset_best(J, cand.data(), cost.data(), term.data(), &result->best_index, &result->best_offset, &result->at_edge);
+}
+
 }  // namespace
 
 extern "C" {
@@ -744,6 +883,192 @@ int clc_assemble_stations(clc_handle* h, const clc_station_options* opt_in, size
                                      bai.p, brm.p, bss.p, nullptr, scan_station, info);
 }
 
+// ---- interpolated tag poses (K15) ---------------------------------------------------------------------------------------------------
+void clc_interp_options_default(clc_interp_options* o) {
+  if (!o) return;
+  o->time_offset = 0.0;
+  o->max_gap = 0.1;
+  o->line0[0] = o->line0[1] = 0.0;
+  clc_line_options_default(&o->line);
+}
+
+int clc_interpolate_poses(clc_handle* h, const clc_interp_options* opt_in, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                          const double* t_wc, size_t n_queries, const double* query_stamp, int32_t* bracket, double* u, double* q_out_wxyz,
+                          double* t_out) {
+  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) || (n_queries > 0 && !query_stamp) || n_poses > 0x7FFFFFF0ull ||
+      n_queries > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_interpolate_poses: bad argument");
+  clc_interp_options opt;
+  CLC_TRY(check_interp_options("clc_interpolate_poses: bad options", opt_in, &opt));
+  CLC_HIP(hipSetDevice(h->device));
+  const size_t m = n_queries;
+  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bx(&h->pool), bu(&h->pool), bqo(&h->pool), bto(&h->pool);
+  DevBuf<int> bbr(&h->pool);
+  DevBuf<long long> bcnt(&h->pool);
+  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bx.alloc(m));
+  CLC_HIP(bu.alloc(m)); CLC_HIP(bqo.alloc(4 * m)); CLC_HIP(bto.alloc(3 * m)); CLC_HIP(bbr.alloc(m)); CLC_HIP(bcnt.alloc(clc::ASM_COUNTERS));
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
+  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
+  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
+  CLC_HIP(up(bx.p, query_stamp, m * sizeof(double)));
+  CLC_TRY(launch_interp(h, opt, n_poses, bstamp.p, bq.p, bt.p, nullptr, bx.p, m, bcnt.p, bbr.p, bu.p, bqo.p, bto.p, nullptr));
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    return (!dst || bytes == 0) ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+  };
+  CLC_HIP(down(bracket, bbr.p, m * sizeof(int32_t)));
+  CLC_HIP(down(u, bu.p, m * sizeof(double)));
+  CLC_HIP(down(q_out_wxyz, bqo.p, 4 * m * sizeof(double)));
+  CLC_HIP(down(t_out, bto.p, 3 * m * sizeof(double)));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+int clc_assemble_interpolated_device(clc_handle* h, const clc_interp_options* opt_in, size_t n_poses, const double* pose_stamp_dev,
+                                     const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev, const int64_t* offsets_dev,
+                                     size_t n_scans, size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
+                                     const float* range_min_dev, const double* scan_stamp_dev, int32_t* scan_bracket_dev, double* scan_u_dev,
+                                     clc_assemble_info* info) {
+  if (!h || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
+      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
+      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_interpolated_device: bad argument");
+  clc_interp_options opt;
+  CLC_TRY(check_interp_options("clc_assemble_interpolated_device: bad options", opt_in, &opt));
+  CLC_HIP(hipSetDevice(h->device));
+  return assemble_interpolated_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays,
+                                         angle_min_dev, angle_increment_dev, range_min_dev, scan_stamp_dev, scan_bracket_dev, scan_u_dev, nullptr,
+                                         nullptr, info);
+}
+
+int clc_assemble_interpolated(clc_handle* h, const clc_interp_options* opt_in, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                              const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
+                              const float* angle_increment, const float* range_min, const double* scan_stamp, int32_t* scan_bracket,
+                              double* scan_u, clc_assemble_info* info) {
+  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
+      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
+      n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_interpolated: bad argument");
+  clc_interp_options opt;
+  CLC_TRY(check_interp_options("clc_assemble_interpolated: bad options", opt_in, &opt));
+  std::vector<long long> rel;
+  size_t n_rays;
+  CLC_TRY(host_offsets("clc_assemble_interpolated", offsets, n_scans, true, "rays", &rel, &n_rays));
+  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_interpolated: NULL ranges");
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
+  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
+  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
+  CLC_HIP(boff.alloc(n_scans + 1));
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
+  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
+  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
+  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
+  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
+  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
+  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
+  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
+  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
+  return assemble_interpolated_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays,
+                                         bam.p, bai.p, brm.p, bss.p, nullptr, nullptr, scan_bracket, scan_u, info);
+}
+
+// ---- the clock sweep (K15) ------------------------------------------------------------------------------------------------------------
+void clc_clock_offset_options_default(clc_clock_offset_options* o) {
+  if (!o) return;
+  o->offset_min = -0.02;
+  o->offset_max = 0.02;
+  o->n_offsets = 41;
+  o->points_per_scan = 16;
+  clc_interp_options_default(&o->interp);
+  clc_options_default(&o->solve);
+}
+
+int clc_clock_offset_best(size_t n_offsets, const double* offsets, const double* final_cost, const int32_t* termination, int32_t* best_index,
+                         double* best_offset, int32_t* at_edge) {
+  if ((n_offsets > 0 && (!offsets || !final_cost)) || !best_index || !best_offset || !at_edge || n_offsets > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_best: bad argument");
+  auto usable = [&](size_t j) { return !(termination && termination[j] == CLC_FAILURE) && final_cost[j] == final_cost[j]; };
+  long long b = -1;
+  for (size_t j = 0; j < n_offsets; ++j)
+    if (usable(j) && (b < 0 || final_cost[j] < final_cost[(size_t)b])) b = (long long)j;
+  *best_index = (int32_t)b;
+  *at_edge = 0;
+  *best_offset = b < 0 ? std::nan("") : offsets[(size_t)b];
+  if (b < 0) return CLC_OK;
+  if (b == 0 || (size_t)b + 1 == n_offsets) { *at_edge = 1; return CLC_OK; }
+  const size_t k = (size_t)b;
+  if (!usable(k - 1) || !usable(k + 1)) return CLC_OK;
+  // the vertex of the parabola through (x0, y0), (x1, y1), (x2, y2): x1 - 1/2 (a^2 (y1 - y2) - c^2 (y1 - y0)) / (a (y1 - y2) - c (y1 - y0))
+  const double a = offsets[k] - offsets[k - 1], c = offsets[k] - offsets[k + 1];
+  const double f0 = final_cost[k] - final_cost[k - 1], f2 = final_cost[k] - final_cost[k + 1];  // both <= 0 at a minimum
+  const double den = a * f2 - c * f0;
+  const double v = offsets[k] - 0.5 * (a * a * f2 - c * c * f0) / den;
+  const double lo = std::min(offsets[k - 1], offsets[k + 1]), hi = std::max(offsets[k - 1], offsets[k + 1]);
+  if (f0 < 0.0 && f2 < 0.0 && std::isfinite(v) && v >= lo && v <= hi) *best_offset = v;
+  return CLC_OK;
+}
+
+int clc_clock_offset_sweep_device(clc_handle* h, const clc_clock_offset_options* opt_in, size_t n_poses, const double* pose_stamp_dev,
+                                 const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev, const int64_t* offsets_dev,
+                                 size_t n_scans, size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
+                                 const float* range_min_dev, const double* scan_stamp_dev, const double pose7[7], double* offsets_out,
+                                 double* final_cost, double* poses, clc_summary* summaries, clc_clock_offset_result* result) {
+  if (!h || !pose7 || !result || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
+      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
+      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_sweep_device: bad argument");
+  clc_clock_offset_options opt;
+  CLC_TRY(check_sweep_options("clc_clock_offset_sweep_device: bad options", opt_in, &opt));
+  CLC_HIP(hipSetDevice(h->device));
+  return sweep_on_device(h, opt, n_poses, pose_stamp_dev, q_wc_wxyz_dev, t_wc_dev, ranges_dev, offsets_dev, n_scans, n_rays, angle_min_dev,
+                         angle_increment_dev, range_min_dev, scan_stamp_dev, pose7, offsets_out, final_cost, poses, summaries, result);
+}
+
+int clc_clock_offset_sweep(clc_handle* h, const clc_clock_offset_options* opt_in, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                          const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
+                          const float* angle_increment, const float* range_min, const double* scan_stamp, const double pose7[7],
+                          double* offsets_out, double* final_cost, double* poses, clc_summary* summaries, clc_clock_offset_result* result) {
+  if (!h || !pose7 || !result || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
+      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
+      n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_sweep: bad argument");
+  clc_clock_offset_options opt;
+  CLC_TRY(check_sweep_options("clc_clock_offset_sweep: bad options", opt_in, &opt));
+  std::vector<long long> rel;
+  size_t n_rays;
+  CLC_TRY(host_offsets("clc_clock_offset_sweep", offsets, n_scans, true, "rays", &rel, &n_rays));
+  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_sweep: NULL ranges");
+  CLC_HIP(hipSetDevice(h->device));
+  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
+  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
+  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
+  CLC_HIP(boff.alloc(n_scans + 1));
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
+  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
+  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
+  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
+  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
+  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
+  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
+  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
+  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
+  return sweep_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p, bai.p, brm.p,
+                         bss.p, pose7, offsets_out, final_cost, poses, summaries, result);
+}
+
 }  // extern "C"
 
 #ifdef CLC_TEST_HOOKS
@@ -782,6 +1107,16 @@ extern "C" int clc_debug_station_walk(clc_handle* h, const clc_station_options* 
     if (first) CLC_HIP(hipMemcpy(first, b.first.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (last) CLC_HIP(hipMemcpy(last, b.last.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (members) CLC_HIP(hipMemcpy(members, b.members.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+  }
+  return CLC_OK;
+}
+// test hook: the records (8 doubles each, problem-major) the last clc_clock_offset_sweep[_device] of this process uploaded
+extern "C" int clc_debug_sweep_records(double* records_out, int64_t cap_doubles, int64_t* n_doubles) {
+  if (!n_doubles) return fail(CLC_ERR_INVALID_ARG, "clc_debug_sweep_records: bad argument");
+  *n_doubles = (int64_t)g_last_sweep_records.size();
+  if (records_out) {
+    if (cap_doubles < *n_doubles) return fail(CLC_ERR_INVALID_ARG, "clc_debug_sweep_records: buffer too small");
+    std::memcpy(records_out, g_last_sweep_records.data(), g_last_sweep_records.size() * sizeof(double));
   }
   return CLC_OK;
 }

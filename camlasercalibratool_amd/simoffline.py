@@ -225,3 +225,86 @@ def check_station_margins(rec: dict) -> dict:
     m_stamp = float(np.abs(ends[None, :] - rec["scan_stamp"][:, None]).min()) if ends.size and rec["scan_stamp"].size else np.inf
     assert m_stamp >= MARGIN, f"a scan stamp is {m_stamp:.3e} s from a station's end"
     return {"station_first": first, "station_last": last, "station_members": members, "station_margin": m_walk, "stamp_margin": m_stamp}
+
+
+# ---- a board that keeps moving: tag poses interpolated at the scans' stamps --------------------------------------------------------
+MAX_GAP = 0.1
+
+
+def moving_recording(seed: int = 1, n_stations: int = 26, move_frames: int = 20, still_frames: int = 8, clock_offset: float = 0.0,
+                     side: float = 1.2, n_rays: int = 1081, fov_deg: float = 270.0, range_sigma: float = 0.001, board_prob: float = 0.9,
+                     scan_rate: float = 40.0, offsets=(0.0,), Rlc: np.ndarray = sd.GT_RLC, tlc: np.ndarray = sd.GT_TLC) -> dict:
+    """A continuous board path: piecewise linear in the six station parameters of recording(), still for still_frames camera periods
+    at every station and moving for move_frames + 1 periods in between.  The camera samples the path at 30 Hz (stamps 100 + j / 30);
+    the laser runs on a clock of its own, scan_rate Hz from a seeded phase, and a scan stamped tau sees the board where it is at
+    path(tau + clock_offset) — clock_offset is what has to be ADDED to a scan's stamp to get camera time.  The scans cover the span in
+    which tau + clock_offset +- 50 ms stays inside the camera's stamps.
+    -> recording()'s dict without scan_frame, plus clock_offset and the margins of check_motion_margins(rec, offsets)."""
+    rng = np.random.default_rng([seed, 0x1D7E])
+    lo = np.array([-0.35, 0.05, 1.0, -0.6, -0.6, -0.6])
+    hi = np.array([0.35, 0.55, 1.55, 0.6, 0.6, 0.6])
+    stations = rng.uniform(lo, hi, size=(n_stations, 6))
+    knots_t, knots_p, tk = [], [], 100.0
+    for i in range(n_stations):
+        knots_t += [tk, tk + (still_frames - 1) / 30.0]
+        knots_p += [stations[i], stations[i]]
+        tk += (still_frames - 1) / 30.0 + (move_frames + 1) / 30.0
+    knots_t, knots_p = np.array(knots_t), np.array(knots_p)
+    path = lambda tau: np.stack([np.interp(tau, knots_t, knots_p[:, c]) for c in range(6)], axis=-1)
+    n = n_stations * still_frames + (n_stations - 1) * move_frames
+    pose_stamp = 100.0 + np.arange(n) / 30.0
+    params = path(pose_stamp)
+    Rca = np.empty((n, 3, 3)); tca = np.empty((n, 3))
+    for j in range(n):
+        Rca[j], tca[j] = _board_pose(params[j])
+    Rwc = np.transpose(Rca, (0, 2, 1))
+    t_wc = -np.einsum("nij,nj->ni", Rwc, tca)
+    q_wc = sd.rot_to_quat_wxyz(Rwc)
+
+    inc = np.deg2rad(fov_deg) / (n_rays - 1)
+    a0 = -np.deg2rad(fov_deg) / 2
+    th = a0 + np.arange(n_rays) * inc
+    first = pose_stamp[0] + 0.05 - min(clock_offset, 0.0) + rng.uniform(0.0, 1.0 / scan_rate)
+    last = pose_stamp[-1] - 0.05 - max(clock_offset, 0.0)
+    S = max(int(np.floor((last - first) * scan_rate)) + 1, 0)
+    scan_stamp = first + np.arange(S) / scan_rate
+    has_board = rng.random(S) < board_prob
+    ranges = np.empty((S, n_rays), dtype=np.float32)
+    seen = path(scan_stamp + clock_offset)
+    for k in range(S):
+        r = np.full(n_rays, np.inf)
+        for _ in range(3):  # walls behind the board
+            rho, phi = rng.uniform(3.0, 8.0), rng.uniform(-1.2, 1.2)
+            c = np.cos(th - phi)
+            r = np.minimum(r, np.where(c > 0.05, rho / np.maximum(c, 0.05), np.inf))
+        r = np.minimum(r, 25.0)
+        chord = _board_chord(*_board_pose(seen[k]), side, Rlc, tlc) if has_board[k] else None
+        if chord is None:
+            has_board[k] = False
+        else:
+            r = np.minimum(r, sd._ray_hits(th, chord[0], chord[1]))
+        ranges[k] = (r + rng.normal(0.0, range_sigma, n_rays)).astype(np.float32)
+    scans = {"ranges": ranges.ravel(), "offsets": np.arange(S + 1, dtype=np.int64) * n_rays,
+             "angle_min": np.full(S, a0, dtype=np.float32), "angle_increment": np.full(S, inc, dtype=np.float32),
+             "range_min": np.full(S, 0.05, dtype=np.float32)}
+    rec = {"pose_stamp": pose_stamp, "q_wc": q_wc, "t_wc": t_wc, "scans": scans, "scan_stamp": scan_stamp, "has_board": has_board,
+           "clock_offset": float(clock_offset)}
+    rec.update(check_motion_margins(rec, offsets))
+    return rec
+
+
+def check_motion_margins(rec: dict, offsets=(0.0,), max_gap: float = MAX_GAP) -> dict:
+    """Asserts that no bracket decision of the interpolated flow hinges on a last bit: every scan stamp + offset, for every offset the
+    caller is going to use, is at least MARGIN seconds from every pose stamp, and every interval between consecutive pose stamps at
+    least MARGIN seconds from max_gap -> {"stamp_margin", "gap_margin"} (the smallest margins)."""
+    ps, ss = rec["pose_stamp"], rec["scan_stamp"]
+    m_stamp = np.inf
+    for d in offsets:
+        if ps.size and ss.size:
+            x = ss + d
+            i = np.clip(np.searchsorted(ps, x), 1, len(ps) - 1)
+            m_stamp = min(m_stamp, float(np.minimum(np.abs(x - ps[i - 1]), np.abs(x - ps[i])).min()))
+    assert m_stamp >= MARGIN, f"a scan stamp + offset is {m_stamp:.3e} s from a pose stamp"
+    m_gap = float(np.abs(np.diff(ps) - max_gap).min()) if ps.size >= 2 else np.inf
+    assert m_gap >= MARGIN, f"an interval between pose stamps is {m_gap:.3e} s from max_gap"
+    return {"stamp_margin": m_stamp, "gap_margin": m_gap}

@@ -671,6 +671,117 @@ class Solver:
                                                    scan_station_ptr or None, C.byref(info)), "clc_assemble_stations_device")
         return info
 
+    # ---- interpolated tag poses: one observation per scan, the pose interpolated at the scan's stamp (K15) ----
+    def interpolate_poses(self, pose_stamp, q_wc, t_wc, query_stamp, options: Optional["_capi.InterpOptions"] = None) -> dict:
+        """The tag pose at every query stamp (+ options.time_offset), between the two stamped poses that bracket it (pose_stamp [n],
+        q_wc [n, 4] (w, x, y, z), t_wc [n, 3] in file order; include/clc.h states the rule) -> {"bracket" [m] int32 (the index of the
+        bracket's first pose, or SCAN_NO_POSE), "u" [m], "q" [m, 4] (unit), "t" [m, 3]}."""
+        ps = np.ascontiguousarray(pose_stamp, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        assert q.shape[0] == t.shape[0] == ps.shape[0], "one stamp, quaternion and translation per pose"
+        x = np.ascontiguousarray(query_stamp, dtype=np.float64).reshape(-1)
+        m = x.shape[0]
+        out = {"bracket": np.zeros(m, np.int32), "u": np.zeros(m), "q": np.zeros((m, 4)), "t": np.zeros((m, 3))}
+        o = options or _capi.default_interp_options()
+        check(self._L.clc_interpolate_poses(self._h, C.byref(o), ps.shape[0], ps.ctypes.data, q.ctypes.data, t.ctypes.data, m, x.ctypes.data,
+                                            out["bracket"].ctypes.data, out["u"].ctypes.data, out["q"].ctypes.data, out["t"].ctypes.data),
+              "clc_interpolate_poses")
+        return out
+
+    def assemble_interpolated(self, pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, options: Optional["_capi.InterpOptions"] = None):
+        """assemble_observations with the tag pose interpolated at every scan's stamp (+ options.time_offset): every scan with a board
+        segment and a bracket becomes one observation -> (AssembleInfo, scan_bracket [S] int32, scan_u [S]).  The observations are
+        left stored on the handle."""
+        ps = np.ascontiguousarray(pose_stamp, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        assert q.shape[0] == t.shape[0] == ps.shape[0], "one stamp, quaternion and translation per pose"
+        r = np.ascontiguousarray(scans["ranges"], dtype=np.float32)
+        off = np.ascontiguousarray(scans["offsets"], dtype=np.int64)
+        S = len(off) - 1
+        f = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (S,)))
+        am, ai, rm = f(scans["angle_min"]), f(scans["angle_increment"]), f(scans["range_min"])
+        ss = np.ascontiguousarray(scan_stamp, dtype=np.float64).reshape(-1)
+        assert ss.shape[0] == S, "one stamp per scan"
+        scan_bracket = np.zeros(S, dtype=np.int32)
+        scan_u = np.zeros(S)
+        info = _capi.AssembleInfo()
+        o = options or _capi.default_interp_options()
+        check(self._L.clc_assemble_interpolated(self._h, C.byref(o), ps.shape[0], ps.ctypes.data, q.ctypes.data, t.ctypes.data, r.ctypes.data,
+                                                off.ctypes.data, S, am.ctypes.data, ai.ctypes.data, rm.ctypes.data, ss.ctypes.data,
+                                                scan_bracket.ctypes.data, scan_u.ctypes.data, C.byref(info)), "clc_assemble_interpolated")
+        return info, scan_bracket, scan_u
+
+    def assemble_interpolated_device(self, n_poses: int, pose_stamp_ptr: int, q_wc_ptr: int, t_wc_ptr: int, ranges_ptr: int, offsets_ptr: int,
+                                     n_scans: int, n_rays: int, angle_min_ptr: int, angle_increment_ptr: int, range_min_ptr: int,
+                                     scan_stamp_ptr: int, scan_bracket_ptr: int = 0, scan_u_ptr: int = 0,
+                                     options: Optional["_capi.InterpOptions"] = None):
+        """clc_assemble_interpolated_device on device-resident arrays (data_ptr()s; ready on the solver's stream) -> AssembleInfo."""
+        info = _capi.AssembleInfo()
+        o = options or _capi.default_interp_options()
+        check(self._L.clc_assemble_interpolated_device(self._h, C.byref(o), n_poses, pose_stamp_ptr or None, q_wc_ptr or None, t_wc_ptr or None,
+                                                       ranges_ptr or None, offsets_ptr or None, n_scans, n_rays, angle_min_ptr or None,
+                                                       angle_increment_ptr or None, range_min_ptr or None, scan_stamp_ptr or None,
+                                                       scan_bracket_ptr or None, scan_u_ptr or None, C.byref(info)),
+              "clc_assemble_interpolated_device")
+        return info
+
+    def time_offset_sweep(self, pose_stamp, q_wc, t_wc, scans: dict, scan_stamp, pose0: np.ndarray,
+                          options: Optional["_capi.TimeOffsetOptions"] = None) -> dict:
+        """The camera-laser clock sweep (include/clc.h, K15): one calibration problem per candidate offset on the same scans and points,
+        the tag poses interpolated at scan_stamp + offset, solved as one batch from pose0 (T_cl, [tx, ty, tz, qx, qy, qz, qw]) ->
+        {"offsets" [n], "final_cost" [n], "poses" [n, 7], "summaries" (Summary array [n]), "n_scans_used", "records_per_problem",
+        "best_index", "best_offset", "at_edge"}.  The handle's batch is the sweep's afterwards; the stored observations are untouched."""
+        ps = np.ascontiguousarray(pose_stamp, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(q_wc, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)
+        assert q.shape[0] == t.shape[0] == ps.shape[0], "one stamp, quaternion and translation per pose"
+        r = np.ascontiguousarray(scans["ranges"], dtype=np.float32)
+        off = np.ascontiguousarray(scans["offsets"], dtype=np.int64)
+        S = len(off) - 1
+        f = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (S,)))
+        am, ai, rm = f(scans["angle_min"]), f(scans["angle_increment"]), f(scans["range_min"])
+        ss = np.ascontiguousarray(scan_stamp, dtype=np.float64).reshape(-1)
+        assert ss.shape[0] == S, "one stamp per scan"
+        p0 = np.ascontiguousarray(pose0, dtype=np.float64).reshape(7)
+        o = options or _capi.default_time_offset_options()
+        n = max(int(o.n_offsets), 0)
+        out = {"offsets": np.zeros(n), "final_cost": np.full(n, np.nan), "poses": np.tile(p0, (n, 1)), "summaries": (Summary * n)()}
+        res = _capi.TimeOffsetResult()
+        check(self._L.clc_clock_offset_sweep(self._h, C.byref(o), ps.shape[0], ps.ctypes.data, q.ctypes.data, t.ctypes.data, r.ctypes.data,
+                                            off.ctypes.data, S, am.ctypes.data, ai.ctypes.data, rm.ctypes.data, ss.ctypes.data, p0.ctypes.data,
+                                            out["offsets"].ctypes.data, out["final_cost"].ctypes.data, out["poses"].ctypes.data,
+                                            C.byref(out["summaries"]), C.byref(res)), "clc_clock_offset_sweep")
+        out.update({k: getattr(res, k) for k, _ in res._fields_})
+        return out
+
+    def time_offset_sweep_device(self, n_poses: int, pose_stamp_ptr: int, q_wc_ptr: int, t_wc_ptr: int, ranges_ptr: int, offsets_ptr: int,
+                                 n_scans: int, n_rays: int, angle_min_ptr: int, angle_increment_ptr: int, range_min_ptr: int,
+                                 scan_stamp_ptr: int, pose0: np.ndarray, options: Optional["_capi.TimeOffsetOptions"] = None) -> dict:
+        """clc_clock_offset_sweep_device on a device-resident recording (data_ptr()s; ready on the solver's stream) -> time_offset_sweep's dict."""
+        p0 = np.ascontiguousarray(pose0, dtype=np.float64).reshape(7)
+        o = options or _capi.default_time_offset_options()
+        n = max(int(o.n_offsets), 0)
+        out = {"offsets": np.zeros(n), "final_cost": np.full(n, np.nan), "poses": np.tile(p0, (n, 1)), "summaries": (Summary * n)()}
+        res = _capi.TimeOffsetResult()
+        check(self._L.clc_clock_offset_sweep_device(self._h, C.byref(o), n_poses, pose_stamp_ptr or None, q_wc_ptr or None, t_wc_ptr or None,
+                                                   ranges_ptr or None, offsets_ptr or None, n_scans, n_rays, angle_min_ptr or None,
+                                                   angle_increment_ptr or None, range_min_ptr or None, scan_stamp_ptr or None, p0.ctypes.data,
+                                                   out["offsets"].ctypes.data, out["final_cost"].ctypes.data, out["poses"].ctypes.data,
+                                                   C.byref(out["summaries"]), C.byref(res)), "clc_clock_offset_sweep_device")
+        out.update({k: getattr(res, k) for k, _ in res._fields_})
+        return out
+
+    def debug_sweep_records(self) -> np.ndarray:
+        """Test hook: the records [n_offsets * records_per_problem, 8] the last time_offset_sweep[_device] of this process uploaded."""
+        n = C.c_int64()
+        f = self._hook("clc_debug_sweep_records")
+        check(f(None, C.c_int64(0), C.byref(n)), "clc_debug_sweep_records")
+        out = np.zeros((n.value // 8, 8))
+        check(f(out.ctypes.data_as(C.c_void_p), C.c_int64(n.value), C.byref(n)), "clc_debug_sweep_records")
+        return out
+
     def debug_station_walk(self, t_wc, options: Optional["_capi.StationOptions"] = None) -> dict:
         """Test hook: the walk of static_poses alone -> {"first", "last", "members" [k] int64, "n_stations", "n_runs"}."""
         t = np.ascontiguousarray(t_wc, dtype=np.float64).reshape(-1, 3)

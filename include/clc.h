@@ -530,6 +530,110 @@ int clc_assemble_stations_device(clc_handle* h, const clc_station_options* opt, 
                                  const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
                                  int32_t* scan_station_dev, clc_station_info* info);
 
+/* ---- interpolated tag poses (K15): one observation per scan, the tag pose interpolated at the scan's stamp -------------------
+ * For recordings where the board moves.  Key-frame mode takes the nearest key frame (a pose error of velocity x |dt|, and most
+ * scans dropped), station mode needs the board held still; here every scan with a board segment takes the pose BETWEEN the two
+ * stamped tag poses that bracket its stamp, and a constant offset between the camera's and the laser's clock is an option.
+ * The rule below is this library's design — the reference interpolates nowhere (main/calibr_offline.cpp:102-116 takes the
+ * nearest key frame):
+ *   x = query_stamp + time_offset.  The bracket is the FIRST i in file order with both stamps finite,
+ *   0 < stamp[i+1] - stamp[i] <= max_gap and stamp[i] <= x <= stamp[i+1] (both ends inclusive); a NaN x never matches.
+ *   u = (x - stamp[i]) / (stamp[i+1] - stamp[i]);  t = t_i + u (t_{i+1} - t_i);  q on the stored (w, x, y, z) values, each
+ *   normalised first, q_{i+1} negated when the dot product is < 0: slerp while dot <= 1 - 1e-10, normalised lerp above; the
+ *   result normalised.  A result that is not finite (a NaN or zero quaternion in the bracket) counts as no bracket.
+ * Stamps that never decrease are searched by bisection, any other list by the linear walk: the same answer either way. */
+typedef struct clc_interp_options {
+  double time_offset;     /* 0: added to every query stamp (the laser's clock -> the camera's) */
+  double max_gap;         /* 0.1 s: the longest interval between two tag poses that is interpolated across */
+  double line0[2];        /* start of every line fit: (0, 0) */
+  clc_options line;       /* clc_line_options_default */
+} clc_interp_options;
+void clc_interp_options_default(clc_interp_options* opt);
+/* The interpolation alone, on host arrays: pose_stamp[n_poses], q_wc_wxyz[4 * n_poses], t_wc[3 * n_poses] in file order,
+ * query_stamp[n_queries] -> bracket[n_queries] (the index i of the bracket's first pose, or CLC_SCAN_NO_POSE), u[n_queries],
+ * q_out_wxyz[4 * n_queries] (unit), t_out[3 * n_queries]; every output nullable.  A query without a pose gets u = 0,
+ * q = (1, 0, 0, 0), t = 0.  opt NULL: the defaults (line0 / line are not looked at).  CLC_ERR_INVALID_ARG: NULL inputs, 2^31
+ * poses or queries or more, max_gap not finite or <= 0, time_offset not finite. */
+int clc_interpolate_poses(clc_handle* h, const clc_interp_options* opt, size_t n_poses, const double* pose_stamp,
+                          const double* q_wc_wxyz, const double* t_wc, size_t n_queries, const double* query_stamp, int32_t* bracket,
+                          double* u, double* q_out_wxyz, double* t_out);
+/* clc_assemble_observations with the interpolated pose: every scan with a board segment and a bracket becomes one observation,
+ * tagPose_Qca / tagPose_tca formed (:145-146) from the pose interpolated at scan_stamp + time_offset.  The arrays are those of
+ * clc_assemble_observations; scan_bracket[n_scans] (nullable): the index of the bracket's first pose, or CLC_SCAN_NO_SEGMENT /
+ * CLC_SCAN_REF_THROWS / CLC_SCAN_NO_POSE; scan_u[n_scans] (nullable): u of a kept scan, 0 elsewhere.  info: n_keyframes = the
+ * pairs (i, i + 1) of the pose list that can bracket a stamp (finite stamps, 0 < gap <= max_gap), n_unmatched = scans with a
+ * segment and no bracket; the rest as there.  Everything else (segments, line fits, points_on_line, the order of the observations,
+ * how they are left stored on the handle) is as for clc_assemble_observations.  The same CLC_ERR_INVALID_ARG cases, and those of
+ * clc_interpolate_poses' options. */
+int clc_assemble_interpolated(clc_handle* h, const clc_interp_options* opt, size_t n_poses, const double* pose_stamp,
+                              const double* q_wc_wxyz, const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans,
+                              const float* angle_min, const float* angle_increment, const float* range_min, const double* scan_stamp,
+                              int32_t* scan_bracket, double* scan_u, clc_assemble_info* info);
+/* The same with every array in DEVICE memory, as clc_assemble_observations_device (ONE synchronisation); scan_bracket_dev and
+ * scan_u_dev nullable (device memory). */
+int clc_assemble_interpolated_device(clc_handle* h, const clc_interp_options* opt, size_t n_poses, const double* pose_stamp_dev,
+                                     const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev,
+                                     const int64_t* offsets_dev, size_t n_scans, size_t n_rays, const float* angle_min_dev,
+                                     const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
+                                     int32_t* scan_bracket_dev, double* scan_u_dev, clc_assemble_info* info);
+
+/* ---- the camera-laser clock sweep (K15) -------------------------------------------------------------------------------------
+ * An estimate of the constant offset between the laser's and the camera's clock from the recording itself: n_offsets candidate
+ * offsets D_j = offset_min + j (offset_max - offset_min) / (n_offsets - 1), one calibration problem each — the same scans, the same
+ * points, the tag poses interpolated at scan_stamp + D_j — solved as ONE batch from the common start pose7 (T_cl as
+ * [tx, ty, tz, qx, qy, qz, qw]); the final cost over the offsets is smallest where the clocks agree.
+ *   Membership: a scan is used iff it has a board segment and a bracket (clc_interpolate_poses' rule, interp.max_gap;
+ *   interp.time_offset is not looked at) at EVERY D_j, so all problems hold the same records and their costs are comparable.
+ *   Decimation: from a segment of L points with L > m = points_per_scan > 0 the points at index floor((2 i + 1) L / (2 m)),
+ *   i = 0 .. m - 1, are taken; otherwise all of them.
+ *   Records: problem j's records are the reference's assembly loop (src/LaseCamCalCeres.cpp:222-254) on these scans with
+ *   use_linefitting_data = false and no edge terms: plane n = R_ca e3, d = -n . t_ca of the pose interpolated at D_j,
+ *   scale = 1 / sqrt(points taken).  They are built on the device and never cross PCIe.
+ *   Solve: clc_upload_batched_device + clc_solve_batched under `solve`, unchanged.
+ * Out (each array nullable): offsets[n_offsets], final_cost[n_offsets], poses[7 * n_offsets], summaries[n_offsets], and
+ * *result: n_scans_used, records_per_problem, and clc_clock_offset_best's choice.  No scan used: CLC_OK, n_scans_used = 0,
+ * best_index = -1, the arrays (offsets apart) untouched and nothing uploaded.
+ * What the call leaves on the handle: the uploaded batch is the sweep's (as after clc_upload_batched: clc_solve_batched,
+ * clc_information_batched ... follow on it); the observation store (clc_store_observations / clc_assemble_*) and the single
+ * problem of clc_upload are not touched.
+ * CLC_ERR_INVALID_ARG: as clc_assemble_interpolated, and n_offsets outside 3 .. 1024, offsets not finite or offset_max <=
+ * offset_min, points_per_scan < 0, NULL pose7 or result; a non-finite pose7 is refused as clc_solve_batched refuses it. */
+typedef struct clc_clock_offset_options {
+  double offset_min;        /* -0.02 s */
+  double offset_max;        /*  0.02 s */
+  int32_t n_offsets;        /* 41: 3 .. 1024 */
+  int32_t points_per_scan;  /* 16; 0 = all points of every segment */
+  clc_interp_options interp; /* clc_interp_options_default (max_gap; the rest is not looked at) */
+  clc_options solve;        /* clc_options_default */
+} clc_clock_offset_options;
+void clc_clock_offset_options_default(clc_clock_offset_options* opt);
+typedef struct clc_clock_offset_result {
+  int64_t n_scans_used;        /* scans every problem holds */
+  int64_t records_per_problem;
+  int32_t best_index;          /* clc_clock_offset_best */
+  int32_t at_edge;
+  double best_offset;
+} clc_clock_offset_result;
+/* The choice among the candidates, on host arrays (no device needed): *best_index = the argmin of final_cost over the problems
+ * whose termination (nullable: none failed) is not CLC_FAILURE, the first of equal minima, a NaN cost never chosen; -1 when there
+ * is none (*best_offset = NaN then).  *best_offset = the vertex of the parabola through best_index and its two neighbours; the
+ * candidate's own offset with *at_edge = 1 when the minimum is the first or the last candidate, and with *at_edge = 0 when a
+ * neighbour failed or the three points have no minimum of their own (not strictly convex). */
+int clc_clock_offset_best(size_t n_offsets, const double* offsets, const double* final_cost, const int32_t* termination,
+                         int32_t* best_index, double* best_offset, int32_t* at_edge);
+int clc_clock_offset_sweep(clc_handle* h, const clc_clock_offset_options* opt, size_t n_poses, const double* pose_stamp,
+                          const double* q_wc_wxyz, const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans,
+                          const float* angle_min, const float* angle_increment, const float* range_min, const double* scan_stamp,
+                          const double pose7[7], double* offsets_out, double* final_cost, double* poses, clc_summary* summaries,
+                          clc_clock_offset_result* result);
+/* The same with the recording in DEVICE memory, as clc_assemble_observations_device; pose7 and every output on the host. */
+int clc_clock_offset_sweep_device(clc_handle* h, const clc_clock_offset_options* opt, size_t n_poses, const double* pose_stamp_dev,
+                                 const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev,
+                                 const int64_t* offsets_dev, size_t n_scans, size_t n_rays, const float* angle_min_dev,
+                                 const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
+                                 const double pose7[7], double* offsets_out, double* final_cost, double* poses,
+                                 clc_summary* summaries, clc_clock_offset_result* result);
+
 /* ---- board poses from tag corners (the numeric half of CamPoseEst::calcCamPose, src/calcCamPose.cpp:270-303) -------------
  * The two camera models the reference's nodes select (main/kalibratag_detector_node.cpp:90-105), restated from camodocal:
  *   CLC_CAMERA_PINHOLE         PinholeCamera:     proj = fx fy cx cy, dist = k1 k2 p1 p2
