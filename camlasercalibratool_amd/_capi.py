@@ -36,6 +36,7 @@ EXPORTED = [
     "clc_get_path_info", "clc_device_info", "clc_comm_library", "clc_board_segments", "clc_board_segments_device",
     "clc_closed_form_batched", "clc_information_batched",
     "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
+    "clc_robust_pose_options_default", "clc_board_poses_robust", "clc_board_poses_robust_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -161,6 +162,14 @@ class InterpOptions(C.Structure):
     _fields_ = [("time_offset", C.c_double), ("max_gap", C.c_double), ("line0", C.c_double * 2), ("line", Options)]
 
 
+class RobustPoseOptions(C.Structure):
+    """clc_robust_pose_options (include/clc.h): the gates in normalized image plane units (pixels / focal)."""
+    _fields_ = [("hyp_threshold", C.c_double), ("threshold", C.c_double), ("min_inliers", C.c_int32), ("max_fits", C.c_int32)]
+
+
+POSE_OK, POSE_TOO_FEW, POSE_DEGENERATE, POSE_NONFINITE, POSE_NO_CONSENSUS = 1, 0, -1, -2, -3  # CLC_POSE_*
+
+
 class ClcError(RuntimeError):
     def __init__(self, code: int, where: str, detail: str):
         super().__init__(f"{where}: {ERRORS.get(code, code)} — {detail}")
@@ -272,6 +281,11 @@ def load(path: str):
             L.clc_clock_offset_best.argtypes = [C.c_size_t, V, V, V, V, V, V]
             L.clc_clock_offset_sweep.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, V, V, V, V, V, V, V, V, V, V]
             L.clc_clock_offset_sweep_device.argtypes = [V, V, C.c_size_t, V, V, V, V, V, C.c_size_t, C.c_size_t, V, V, V, V, V, V, V, V, V, V]
+        if hasattr(L, "clc_board_poses_robust"):
+            L.clc_robust_pose_options_default.argtypes = [V, V]
+            L.clc_robust_pose_options_default.restype = None
+            L.clc_board_poses_robust.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 9
+            L.clc_board_poses_robust_device.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 9
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -323,6 +337,15 @@ def default_pose_options() -> Options:
     """clc_pose_options_default: no loss, tolerances tight enough for the float32-rounding floor of the lifted corners."""
     o = Options()
     lib().clc_pose_options_default(C.byref(o))
+    return o
+
+
+def default_robust_pose_options(camera) -> RobustPoseOptions:
+    """clc_robust_pose_options_default: gates of 8 px (per-tag hypotheses) and 2 px (re-gate with the fitted pose) over the camera's
+    focal length — design values from the numpy experiment of DESIGN.md K16 —, at least 4 inliers, at most 4 fits."""
+    o = RobustPoseOptions()
+    c = camera.to_c()
+    lib().clc_robust_pose_options_default(C.byref(o), C.byref(c))
     return o
 
 

@@ -503,6 +503,25 @@ def CalcCamPoses(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np
     return q, t, st, rms
 
 
+def CalcCamPosesRobust(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], solver: Optional[Solver] = None,
+                       options: Optional[Options] = None, robust=None):
+    """CalcCamPoses with a consensus over the tags of every image ahead of the fit (clc_board_poses_robust, K16): a tag decoded with a
+    wrong id or a mis-refined corner is left out of the fit instead of bending the pose.  corners_px[k] must list its tags four
+    corners at a time (the order FindTargetCorner emits them).  robust: _capi.RobustPoseOptions (None: 8 px / 2 px gates over the
+    focal length).  Returns (tag_q [n, 4], tag_t [n, 3], status [n] (1 = pose, -3 = no consensus), rms [n], inlier_masks (one bool array
+    per image), info {"n_inliers", "best_group", "n_fits"})."""
+    counts = [len(np.asarray(c).reshape(-1, 2)) for c in corners_px]
+    if counts != [len(np.asarray(b).reshape(-1, 2)) for b in board_xy]:
+        raise ValueError("CalcCamPosesRobust: corners_px and board_xy differ in length")
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cat = lambda seq: (np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a in seq]) if len(seq)
+                       else np.zeros((0, 2), np.float32))
+    sv = solver or _shared_solver()
+    q, t, rms, st, _, inl, ni, bg, nf = sv.board_poses_robust(camera, cat(corners_px), cat(board_xy), off, options, robust)
+    masks = [inl[off[k]:off[k + 1]] for k in range(len(counts))]
+    return q, t, st, rms, masks, {"n_inliers": ni, "best_group": bg, "n_fits": nf}
+
+
 def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:
     """The calibration board's segment in one scan — mirror of AutoGetLinePts(points, debug), src/selectScanPoints.cpp:17-190:
     points [n,3] -> the chosen segment's points [k,3] (empty when there is none).  Raises IndexError where the reference's

@@ -1,8 +1,9 @@
 // abi_campose.hip — clc_camera_lift, clc_camera_project, clc_board_poses(_device): the camera models and the batched planar PnP
-// (K10 in clc_campose.hpp).
+// (K10 in clc_campose.hpp); clc_board_poses_robust(_device): the per-tag consensus ahead of it (K16 in clc_robustpose.hpp).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 #include "clc_campose.hpp"
+#include "clc_robustpose.hpp"
 
 using namespace clc_abi;
 
@@ -34,6 +35,59 @@ hipError_t launch_board_poses(clc_handle* h, const clc_camera& cam, const clc_op
   hipLaunchKernelGGL(clc::cp::board_pose_kernel, dim3((unsigned)n_images), dim3(64), 0, h->stream, opt, lifted_dev, board_dev, off_dev,
                      first, q_dev, t_dev, rms_dev, status_dev, sum_dev);
   return hipGetLastError();
+}
+
+// The robust call's options: the caller's or the defaults; checked.
+int robust_options(const clc_robust_pose_options* in, const clc_camera* cam, clc_robust_pose_options* o, const char* who) {
+  if (in) *o = *in; else clc_robust_pose_options_default(o, cam);
+  const std::string w(who);
+  if (!(std::isfinite(o->hyp_threshold) && o->hyp_threshold > 0.0 && std::isfinite(o->threshold) && o->threshold > 0.0))
+    return fail(CLC_ERR_INVALID_ARG, (w + ": the gates must be finite and > 0").c_str());
+  if (o->hyp_threshold < o->threshold) return fail(CLC_ERR_INVALID_ARG, (w + ": hyp_threshold < threshold").c_str());
+  if (o->min_inliers < 4) return fail(CLC_ERR_INVALID_ARG, (w + ": min_inliers < 4").c_str());
+  if (o->max_fits < 1 || o->max_fits > 8) return fail(CLC_ERR_INVALID_ARG, (w + ": max_fits outside 1..8").c_str());
+  return CLC_OK;
+}
+
+// What the robust call leaves per image, every array on the device (mask indexed by the absolute offsets; rms, summaries, best_group
+// nullable).
+struct RobustOut {
+  double *q, *t, *rms;
+  int32_t* status;
+  clc_summary* summaries;
+  unsigned char* mask;
+  int32_t *n_inliers, *best_group, *n_fits;
+};
+
+// lift -> consensus -> (fit -> re-gate) x max_fits on the handle's stream, every launch sized by n_images, no read-back in between.
+// Scratch of the caller (indexed like lifted_dev, corner `first` first): lifted_dev, sub_l, sub_b [2 * n_corners]; flag [n_images].
+hipError_t launch_board_poses_robust(clc_handle* h, const clc_camera& cam, const clc_options& opt, const clc_robust_pose_options& ro,
+                                     const float* corners_dev, const float* board_dev, const long long* off_dev, long long first,
+                                     size_t n_corners, size_t n_images, float* lifted_dev, float* sub_l, float* sub_b, int32_t* flag,
+                                     const RobustOut& o) {
+  namespace rp = clc::rp;
+  if (n_corners > 0) {
+    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<true>), dim3(lift_blocks(n_corners)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, cam,
+                       corners_dev + 2 * first, (long long)n_corners, nullptr, lifted_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid((unsigned)n_images), block(64);
+  hipLaunchKernelGGL(rp::tag_consensus_kernel, grid, block, 0, h->stream, lifted_dev, board_dev, off_dev, first, ro.hyp_threshold,
+                     (int)ro.min_inliers, o.mask, sub_l, sub_b, o.n_inliers, flag, o.n_fits, o.best_group, o.q, o.t, o.rms, o.status,
+                     o.summaries);
+  hipError_t e = hipGetLastError();
+  for (int round = 0; round < ro.max_fits && e == hipSuccess; ++round) {
+    hipLaunchKernelGGL(rp::board_pose_subset_kernel, grid, block, 0, h->stream, opt, sub_l, sub_b, off_dev, first, flag, o.n_inliers,
+                       o.n_fits, o.q, o.t, o.rms, o.status, o.summaries);
+    e = hipGetLastError();
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(rp::pose_rescore_kernel, grid, block, 0, h->stream, lifted_dev, board_dev, off_dev, first, ro.threshold,
+                       (int)ro.min_inliers, (int)ro.max_fits, o.mask, sub_l, sub_b, o.n_inliers, flag, o.n_fits, o.q, o.t, o.rms,
+                       o.status, o.summaries);
+    e = hipGetLastError();
+  }
+  return e;
 }
 
 }  // namespace
@@ -163,6 +217,113 @@ int clc_board_poses_device(clc_handle* h, const clc_camera* cam, const clc_optio
   CLC_HIP(bl.alloc(2 * M));
   CLC_HIP(launch_board_poses(h, *cam, opt, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev), ends[0], M,
                              n_images, bl.p, q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+void clc_robust_pose_options_default(clc_robust_pose_options* o, const clc_camera* cam) {
+  if (!o) return;
+  // 8 px and 2 px: design values from the numpy experiment recorded in DESIGN.md K16, in units of the focal length
+  const double f = cam ? std::sqrt(std::fabs(cam->proj[0] * cam->proj[1])) : 0.0;
+  o->hyp_threshold = f > 0.0 ? 8.0 / f : 0.0;
+  o->threshold = f > 0.0 ? 2.0 / f : 0.0;
+  o->min_inliers = 4;
+  o->max_fits = 4;
+}
+
+int clc_board_poses_robust(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const clc_robust_pose_options* ropt_in,
+                           const float* corners_px, const float* board_xy, const int64_t* offsets, size_t n_images, double* q_ca_wxyz,
+                           double* t_ca, double* rms, int32_t* status, clc_summary* summaries, uint8_t* inlier, int32_t* n_inliers,
+                           int32_t* best_group, int32_t* n_fits) {
+  const char* who = "clc_board_poses_robust";
+  // the options first: their refusals need no device
+  CLC_TRY(camera_check(cam, who));
+  clc_options opt;
+  CLC_TRY(pose_options(opt_in, &opt, who));
+  clc_robust_pose_options ro;
+  CLC_TRY(robust_options(ropt_in, cam, &ro, who));
+  if (!h || (n_images > 0 && (!offsets || !q_ca_wxyz || !t_ca || !status)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust: bad argument");
+  if (n_images == 0) return CLC_OK;
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust: too many images");
+  std::vector<long long> rel;
+  size_t M;
+  CLC_TRY(host_offsets(who, offsets, n_images, true, nullptr, &rel, &M));
+  if (M > 0 && (!corners_px || !board_xy || !inlier)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust: bad argument");
+  CLC_HIP(hipSetDevice(h->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  DevBuf<double> bq(&h->pool), bt(&h->pool), br(&h->pool);
+  DevBuf<int32_t> bs(&h->pool), bflag(&h->pool), bni(&h->pool), bnf(&h->pool), bbg(&h->pool);
+  DevBuf<clc_summary> bsum(&h->pool);
+  DevBuf<unsigned char> bm(&h->pool);
+  CLC_HIP(bc.alloc(2 * M)); CLC_HIP(bb.alloc(2 * M)); CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M));
+  CLC_HIP(bm.alloc(M)); CLC_HIP(boff.alloc(n_images + 1));
+  CLC_HIP(bq.alloc(4 * n_images)); CLC_HIP(bt.alloc(3 * n_images)); CLC_HIP(bs.alloc(n_images));
+  CLC_HIP(bflag.alloc(n_images)); CLC_HIP(bni.alloc(n_images)); CLC_HIP(bnf.alloc(n_images));
+  if (rms) CLC_HIP(br.alloc(n_images));
+  if (summaries) CLC_HIP(bsum.alloc(n_images));
+  if (best_group) CLC_HIP(bbg.alloc(n_images));
+  if (M > 0) {
+    CLC_HIP(hipMemcpyAsync(bc.p, corners_px + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    CLC_HIP(hipMemcpyAsync(bb.p, board_xy + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  }
+  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n_images + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  const RobustOut out{bq.p, bt.p, rms ? br.p : nullptr, bs.p, summaries ? bsum.p : nullptr, bm.p, bni.p, best_group ? bbg.p : nullptr,
+                      bnf.p};
+  CLC_HIP(launch_board_poses_robust(h, *cam, opt, ro, bc.p, bb.p, boff.p, 0, M, n_images, bl.p, bsl.p, bsb.p, bflag.p, out));
+  CLC_HIP(hipMemcpyAsync(q_ca_wxyz, bq.p, 4 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(t_ca, bt.p, 3 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(status, bs.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (M > 0) CLC_HIP(hipMemcpyAsync(inlier + offsets[0], bm.p, M, hipMemcpyDeviceToHost, h->stream));
+  if (rms) CLC_HIP(hipMemcpyAsync(rms, br.p, n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (summaries) CLC_HIP(hipMemcpyAsync(summaries, bsum.p, n_images * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
+  if (n_inliers) CLC_HIP(hipMemcpyAsync(n_inliers, bni.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (best_group) CLC_HIP(hipMemcpyAsync(best_group, bbg.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (n_fits) CLC_HIP(hipMemcpyAsync(n_fits, bnf.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (summaries) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (size_t k = 0; k < n_images; ++k) summaries[k].solve_ms = ms;
+  }
+  return CLC_OK;
+}
+
+int clc_board_poses_robust_device(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const clc_robust_pose_options* ropt_in,
+                                  const float* corners_px_dev, const float* board_xy_dev, const int64_t* offsets_dev, size_t n_images,
+                                  double* q_ca_wxyz_dev, double* t_ca_dev, double* rms_dev, int32_t* status_dev,
+                                  clc_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev, int32_t* best_group_dev,
+                                  int32_t* n_fits_dev) {
+  const char* who = "clc_board_poses_robust_device";
+  // the options first: their refusals need no device
+  CLC_TRY(camera_check(cam, who));
+  clc_options opt;
+  CLC_TRY(pose_options(opt_in, &opt, who));
+  clc_robust_pose_options ro;
+  CLC_TRY(robust_options(ropt_in, cam, &ro, who));
+  if (!h || (n_images > 0 && (!offsets_dev || !q_ca_wxyz_dev || !t_ca_dev || !status_dev)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: bad argument");
+  if (n_images == 0) return CLC_OK;
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: too many images");
+  CLC_HIP(hipSetDevice(h->device));
+  long long ends[2];  // the corner range, as clc_board_poses_device reads it
+  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n_images, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: offsets not monotone");
+  const size_t M = (size_t)(ends[1] - ends[0]);
+  if (M > 0 && (!corners_px_dev || !board_xy_dev || !inlier_dev))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: bad argument");
+  DevBuf<float> bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
+  DevBuf<int32_t> bflag(&h->pool), bni(&h->pool), bnf(&h->pool);
+  CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M)); CLC_HIP(bflag.alloc(n_images));
+  if (!n_inliers_dev) CLC_HIP(bni.alloc(n_images));
+  if (!n_fits_dev) CLC_HIP(bnf.alloc(n_images));
+  const RobustOut out{q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev, inlier_dev, n_inliers_dev ? n_inliers_dev : bni.p,
+                      best_group_dev, n_fits_dev ? n_fits_dev : bnf.p};
+  CLC_HIP(launch_board_poses_robust(h, *cam, opt, ro, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev),
+                                    ends[0], M, n_images, bl.p, bsl.p, bsb.p, bflag.p, out));
   CLC_HIP(hipStreamSynchronize(h->stream));
   return CLC_OK;
 }

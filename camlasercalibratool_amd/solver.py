@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import Iteration, Options, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import Iteration, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -541,6 +541,42 @@ class Solver:
         check(self._L.clc_board_poses_device(self._h, C.byref(c), o, C.c_void_p(corners_ptr), C.c_void_p(board_ptr), C.c_void_p(offsets_ptr),
                                              C.c_size_t(n_images), C.c_void_p(q_ptr), C.c_void_p(t_ptr), C.c_void_p(rms_ptr or 0),
                                              C.c_void_p(status_ptr), C.c_void_p(summaries_ptr or 0)), "clc_board_poses_device")
+
+    def board_poses_robust(self, camera, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray,
+                           options: Optional[Options] = None, robust: Optional[RobustPoseOptions] = None, want_summaries: bool = False):
+        """clc_board_poses_robust (K16): per image a consensus over its tags (groups of four corners), the K10 fit on the consensus set,
+        re-gate and refit until the set stops changing.  Arrays as board_poses -> (q_ca_wxyz [n, 4], t_ca [n, 3], rms [n], status [n]
+        (CLC_POSE_*, -3 = no consensus), summaries or None, inlier [M] bool, n_inliers [n], best_group [n], n_fits [n])."""
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        q = np.empty((n, 4)); t = np.empty((n, 3)); rms = np.empty(n); st = np.empty(n, dtype=np.int32)
+        inl = np.zeros(cp.shape[0], dtype=np.uint8)
+        ni = np.empty(n, dtype=np.int32); bg = np.empty(n, dtype=np.int32); nf = np.empty(n, dtype=np.int32)
+        sm = (Summary * n)() if want_summaries and n > 0 else None
+        c = camera.to_c()
+        o = C.byref(options) if options is not None else None
+        ro = C.byref(robust) if robust is not None else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_board_poses_robust(self._h, C.byref(c), o, ro, vp(cp), vp(bx), vp(offsets), C.c_size_t(n), vp(q), vp(t), vp(rms),
+                                             vp(st), sm, vp(inl), vp(ni), vp(bg), vp(nf)), "clc_board_poses_robust")
+        return q, t, rms, st, sm, inl.astype(bool), ni, bg, nf
+
+    def board_poses_robust_device(self, camera, corners_ptr: int, board_ptr: int, offsets_ptr: int, n_images: int, q_ptr: int, t_ptr: int,
+                                  rms_ptr: int = 0, status_ptr: int = 0, summaries_ptr: int = 0, inlier_ptr: int = 0,
+                                  n_inliers_ptr: int = 0, best_group_ptr: int = 0, n_fits_ptr: int = 0,
+                                  options: Optional[Options] = None, robust: Optional[RobustPoseOptions] = None):
+        """clc_board_poses_robust_device on device-resident arrays (data_ptr()s; ready on the solver's stream); inlier: uint8,
+        indexed like the corners."""
+        c = camera.to_c()
+        o = C.byref(options) if options is not None else None
+        ro = C.byref(robust) if robust is not None else None
+        V = C.c_void_p
+        check(self._L.clc_board_poses_robust_device(self._h, C.byref(c), o, ro, V(corners_ptr), V(board_ptr), V(offsets_ptr),
+                                                    C.c_size_t(n_images), V(q_ptr), V(t_ptr), V(rms_ptr or 0), V(status_ptr),
+                                                    V(summaries_ptr or 0), V(inlier_ptr), V(n_inliers_ptr or 0), V(best_group_ptr or 0),
+                                                    V(n_fits_ptr or 0)), "clc_board_poses_robust_device")
 
     # ---- board-segment detection ----
     def board_segments(self, points: np.ndarray, offsets: np.ndarray):

@@ -838,6 +838,68 @@ int clc_solve_batched_gather_pipelined(clc_comm* c, const clc_options* opt, cons
                                        size_t cap_per_rank, const clc_result_record** prev_records, clc_batch_stats* prev_stats);
 int clc_gather_flush(clc_comm* c, const clc_result_record** records, clc_batch_stats* stats);
 
+/* ---- robust board poses (K16): a consensus over the tags of an image ahead of clc_board_poses' planar PnP ------------------
+ * clc_board_poses is a plain least-squares fit over every corner of an image: one AprilTag decoded with a wrong id (four corners
+ * at the wrong place of the board) or one mis-refined corner bends the pose, and nothing downstream can tell.  The reference
+ * left cv::solvePnPRansac commented out beside cv::solvePnP (src/calcCamPose.cpp:226-227).  A tag board needs no random
+ * sampling: every tag is four corners of a planar square, and four planar correspondences fix a homography in closed form.
+ * Per image, after clc_board_poses' own lift (fp64, x/z and y/z rounded to float32):
+ *  1. Groups: group g = the image's corners 4g .. 4g+3 (the order FindTargetCorner emits tags).  A tail of 1-3 corners belongs
+ *     to no group but is scored like every other corner.
+ *  2. Hypothesis: H_g = S(lifted quad) adj(S(board quad)), S(p) the closed-form unit-square -> quad map: with
+ *     sigma = p0 - p1 + p2 - p3, d1 = p1 - p2, d2 = p3 - p2, den = d1 x d2, g = (sigma x d2) / den, h = (d1 x sigma) / den its
+ *     rows are (x1 - x0 + g x1, x3 - x0 + h x3, x0), (y1 - y0 + g y1, y3 - y0 + h y3, y0), (g, h, 1).  No pivoting, no
+ *     iteration.  A group is invalid when either den is zero or not finite or an entry of H_g is not finite — so the groups
+ *     of a chessboard, four consecutive collinear corners, are all invalid and a chessboard image ends CLC_POSE_NO_CONSENSUS:
+ *     this call is for tag boards.
+ *  3. Score: corner k under group g: (u, v, w) = H_g (X, Y, 1), e = (u/w - x)^2 + (v/w - y)^2; an inlier iff e is finite,
+ *     e < hyp_threshold^2 and w w0 > 0, w0 the w of the group's first corner.  count_g = the inliers, cost_g = the sum of
+ *     min(e, hyp_threshold^2) in corner order (a non-finite e adds the cap).  The winner: the largest count, then the smallest
+ *     cost, then the smallest g.  Every product and sum is rounded on its own and the divisions are IEEE: counts, costs and
+ *     the winner do not depend on the device.
+ *  4. First set = the winner's inliers.  No valid group, or fewer than min_inliers of them: CLC_POSE_NO_CONSENSUS.
+ *  5. Fit: clc_board_poses' per-image fit on the set's corners, compacted in corner order — the same code on the same input
+ *     as clc_board_poses given those corners alone, hence the same bits.  A status other than CLC_POSE_OK ends the image
+ *     with that status.
+ *  6. Re-gate: with the fitted (R, t), P = R (X, Y, 0) + t, e = (P_x / P_z - x)^2 + (P_y / P_z - y)^2; an inlier iff P_z > 0, e
+ *     finite and e < threshold^2.  Then, in this order: the set equals the one just fitted — done; fewer than min_inliers —
+ *     CLC_POSE_NO_CONSENSUS; n_fits == max_fits — done with the last fit; otherwise a refit (5.) on the new set.
+ * Outputs, per image: q / t / rms / summaries of the LAST fit (rms over the set it was fitted on); inlier[] = that set, indexed
+ * like the corners (entries [offsets[0], offsets[n_images]) are written, 1 / 0); n_inliers = its size; best_group = the winner
+ * (-1: none, or its set was too small); n_fits = the fits that ran.  An image that ends without a pose has q = (1, 0, 0, 0), t = 0,
+ * rms = NaN, an all-zero mask and n_inliers = 0.  An image never fails the call and never affects another image.  A non-finite
+ * corner is never an inlier; it does not condemn its image, as it does in clc_board_poses.
+ * The default gates, 8 px and 2 px over the focal length, are DESIGN VALUES from a numpy experiment (6x6 board, tag 0.055 m, spacing
+ * 0.3, f = 367 px, 0.3 px noise, 0.6-1.5 m): the best single-tag homography explains >= 126 of 144 clean corners within 8 px but only
+ * about half within 3 px — a single tag extrapolates poorly, so the hypothesis gate is loose and the fitted pose re-gates tightly. */
+#define CLC_POSE_NO_CONSENSUS (-3)   /* no valid hypothesis, or the best set has fewer than min_inliers corners */
+
+typedef struct clc_robust_pose_options {
+  double hyp_threshold;  /* gate of the per-tag hypotheses, normalized image plane units (pixels / focal) */
+  double threshold;      /* gate of the re-scoring with the fitted pose, same units */
+  int32_t min_inliers;   /* >= 4 */
+  int32_t max_fits;      /* 1..8: fits per image at most */
+} clc_robust_pose_options; /* 24 bytes */
+
+/* hyp_threshold = 8 / sqrt(|proj[0] proj[1]|), threshold = 2 / sqrt(|proj[0] proj[1]|), min_inliers 4, max_fits 4 (cam NULL: both
+ * gates 0, which the calls refuse — set them). */
+void clc_robust_pose_options_default(clc_robust_pose_options* ropt, const clc_camera* cam);
+
+/* Arrays as clc_board_poses; inlier[] required; rms, summaries, n_inliers, best_group, n_fits nullable; opt NULL =
+ * clc_pose_options_default(), ropt NULL = clc_robust_pose_options_default().  CLC_ERR_INVALID_ARG: a gate that is not finite and
+ * positive, hyp_threshold < threshold, min_inliers < 4, max_fits outside 1..8.  One enqueue — lift, consensus, (fit, re-gate) x
+ * max_fits on the handle's stream, every launch sized by n_images — and one synchronisation at the end. */
+int clc_board_poses_robust(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_robust_pose_options* ropt,
+                           const float* corners_px, const float* board_xy, const int64_t* offsets, size_t n_images,
+                           double* q_ca_wxyz, double* t_ca, double* rms, int32_t* status, clc_summary* summaries,
+                           uint8_t* inlier, int32_t* n_inliers, int32_t* best_group, int32_t* n_fits);
+/* The same with every array in DEVICE memory (as clc_board_poses_device: offsets_dev[0] may be > 0; not validated: monotone). */
+int clc_board_poses_robust_device(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_robust_pose_options* ropt,
+                                  const float* corners_px_dev, const float* board_xy_dev, const int64_t* offsets_dev, size_t n_images,
+                                  double* q_ca_wxyz_dev, double* t_ca_dev, double* rms_dev, int32_t* status_dev,
+                                  clc_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev, int32_t* best_group_dev,
+                                  int32_t* n_fits_dev);
+
 #ifdef __cplusplus
 }
 #endif
