@@ -37,6 +37,7 @@ EXPORTED = [
     "clc_closed_form_batched", "clc_information_batched",
     "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
     "clc_robust_pose_options_default", "clc_board_poses_robust", "clc_board_poses_robust_device",
+    "clc_alt_pose_options_default", "clc_board_poses_alternate", "clc_board_poses_alternate_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -167,7 +168,13 @@ class RobustPoseOptions(C.Structure):
     _fields_ = [("hyp_threshold", C.c_double), ("threshold", C.c_double), ("min_inliers", C.c_int32), ("max_fits", C.c_int32)]
 
 
+class AltPoseOptions(C.Structure):
+    """clc_alt_pose_options (include/clc.h): same_angle in rad, ratio_gate a cost ratio."""
+    _fields_ = [("same_angle", C.c_double), ("ratio_gate", C.c_double)]
+
+
 POSE_OK, POSE_TOO_FEW, POSE_DEGENERATE, POSE_NONFINITE, POSE_NO_CONSENSUS = 1, 0, -1, -2, -3  # CLC_POSE_*
+ALT_NONE, ALT_SAME, ALT_DISTINCT = 0, 1, 2  # CLC_ALT_*
 
 
 class ClcError(RuntimeError):
@@ -286,6 +293,11 @@ def load(path: str):
             L.clc_robust_pose_options_default.restype = None
             L.clc_board_poses_robust.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 9
             L.clc_board_poses_robust_device.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 9
+        if hasattr(L, "clc_board_poses_alternate"):
+            L.clc_alt_pose_options_default.argtypes = [V]
+            L.clc_alt_pose_options_default.restype = None
+            L.clc_board_poses_alternate.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 16
+            L.clc_board_poses_alternate_device.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 16
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -346,6 +358,13 @@ def default_robust_pose_options(camera) -> RobustPoseOptions:
     o = RobustPoseOptions()
     c = camera.to_c()
     lib().clc_robust_pose_options_default(C.byref(o), C.byref(c))
+    return o
+
+
+def default_alt_pose_options() -> AltPoseOptions:
+    """clc_alt_pose_options_default: same_angle 0.01 rad, ratio_gate 2 — design values."""
+    o = AltPoseOptions()
+    lib().clc_alt_pose_options_default(C.byref(o))
     return o
 
 

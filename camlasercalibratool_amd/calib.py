@@ -522,6 +522,39 @@ def CalcCamPosesRobust(camera, corners_px: Sequence[np.ndarray], board_xy: Seque
     return q, t, st, rms, masks, {"n_inliers": ni, "best_group": bg, "n_fits": nf}
 
 
+def checked_poses(q, t, status, alt):
+    """The host half of BoardPosesChecked from the outputs of the two calls (alt: the dict of Solver.board_poses_alternate): the
+    lower-cost solution where `better`, and keep = status OK and not ambiguous.  -> (q [n, 4], t [n, 3], keep [n] bool)"""
+    q, t = np.array(q, dtype=np.float64, copy=True), np.array(t, dtype=np.float64, copy=True)
+    swap = np.asarray(alt["better"], dtype=bool)
+    q[swap], t[swap] = alt["q"][swap], alt["t"][swap]
+    keep = (np.asarray(status) == 1) & ~np.asarray(alt["ambiguous"], dtype=bool)
+    return q, t, keep
+
+
+def BoardPosesChecked(camera, corners, board, offsets, robust: bool = True, ratio_gate: float = 2.0, solver: Optional[Solver] = None):
+    """Board poses with the planar ambiguity checked (K17): clc_board_poses_robust (robust=False: clc_board_poses) and then
+    clc_board_poses_alternate on its poses and mask.  corners [M, 2] pixels, board [M, 2] board-plane points, CSR offsets [n+1].
+    Returns (q [n, 4] (w, x, y, z), t [n, 3], status [n], keep [n] bool, table): where the other minimum has the lower cost (`better`)
+    it is the pose returned; keep = status OK and not ambiguous (the mirror pose does not fit within ratio_gate of the cost) — the mask
+    to select the images fed to CalibrateOffline*; table: the per-image dict of Solver.board_poses_alternate plus "rms" of the first
+    call as "rms_in" and, with robust, "inlier", "n_inliers"."""
+    from ._capi import default_alt_pose_options
+    sv = solver or _shared_solver()
+    ao = default_alt_pose_options()
+    ao.ratio_gate = float(ratio_gate)
+    extra = {}
+    if robust:
+        q, t, rms, st, _, inl, ni, _, _ = sv.board_poses_robust(camera, corners, board, offsets)
+        extra = {"inlier": inl, "n_inliers": ni}
+    else:
+        q, t, rms, st, _ = sv.board_poses(camera, corners, board, offsets)
+        inl = None
+    alt = sv.board_poses_alternate(camera, corners, board, offsets, q, t, st, inlier=inl, alt=ao)
+    q2, t2, keep = checked_poses(q, t, st, alt)
+    return q2, t2, st, keep, dict(alt, rms_in=rms, **extra)
+
+
 def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:
     """The calibration board's segment in one scan — mirror of AutoGetLinePts(points, debug), src/selectScanPoints.cpp:17-190:
     points [n,3] -> the chosen segment's points [k,3] (empty when there is none).  Raises IndexError where the reference's

@@ -1,9 +1,11 @@
 // abi_campose.hip — clc_camera_lift, clc_camera_project, clc_board_poses(_device): the camera models and the batched planar PnP
-// (K10 in clc_campose.hpp); clc_board_poses_robust(_device): the per-tag consensus ahead of it (K16 in clc_robustpose.hpp).
+// (K10 in clc_campose.hpp); clc_board_poses_robust(_device): the per-tag consensus ahead of it (K16 in clc_robustpose.hpp);
+// clc_board_poses_alternate(_device): the planar fit's second minimum (K17 in clc_altpose.hpp).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 #include "clc_campose.hpp"
 #include "clc_robustpose.hpp"
+#include "clc_altpose.hpp"
 
 using namespace clc_abi;
 
@@ -88,6 +90,45 @@ hipError_t launch_board_poses_robust(clc_handle* h, const clc_camera& cam, const
     e = hipGetLastError();
   }
   return e;
+}
+
+// The alternate call's options: the caller's or the defaults; checked.
+int alt_options(const clc_alt_pose_options* in, clc_alt_pose_options* o, const char* who) {
+  if (in) *o = *in; else clc_alt_pose_options_default(o);
+  const std::string w(who);
+  if (!(std::isfinite(o->same_angle) && o->same_angle > 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": same_angle must be finite and > 0").c_str());
+  if (!(std::isfinite(o->ratio_gate) && o->ratio_gate >= 1.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": ratio_gate must be finite and >= 1").c_str());
+  return CLC_OK;
+}
+
+// What the alternate call reads per image, every array on the device (inlier nullable, indexed by the absolute offsets).
+struct AltIn {
+  const unsigned char* inlier;
+  const double *q, *t;
+  const int32_t* status;
+};
+
+// lift -> start -> fit on the handle's stream, every launch sized by n_images, no read-back in between.  Scratch of the caller
+// (indexed like lifted_dev, corner `first` first): lifted_dev, sub_l, sub_b [2 * n_corners]; cnt, flag [n_images]; start7 [7 * n_images].
+hipError_t launch_board_poses_alternate(clc_handle* h, const clc_camera& cam, const clc_options& opt, const clc_alt_pose_options& ao,
+                                        const float* corners_dev, const float* board_dev, const long long* off_dev, long long first,
+                                        size_t n_corners, size_t n_images, const AltIn& in, float* lifted_dev, float* sub_l, float* sub_b,
+                                        int32_t* cnt, int32_t* flag, double* start7, const clc::ap::AltOut& o) {
+  namespace ap = clc::ap;
+  if (n_corners > 0) {
+    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<true>), dim3(lift_blocks(n_corners)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, cam,
+                       corners_dev + 2 * first, (long long)n_corners, nullptr, lifted_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid((unsigned)n_images), block(64);
+  hipLaunchKernelGGL(ap::alt_start_kernel, grid, block, 0, h->stream, lifted_dev, board_dev, off_dev, first, in.inlier, in.q, in.t,
+                     in.status, sub_l, sub_b, cnt, flag, start7, o);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ap::board_pose_from_start_kernel, grid, block, 0, h->stream, opt, ao, sub_l, sub_b, off_dev, first, flag, cnt, start7,
+                     in.q, in.t, o);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -324,6 +365,128 @@ int clc_board_poses_robust_device(clc_handle* h, const clc_camera* cam, const cl
                       best_group_dev, n_fits_dev ? n_fits_dev : bnf.p};
   CLC_HIP(launch_board_poses_robust(h, *cam, opt, ro, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev),
                                     ends[0], M, n_images, bl.p, bsl.p, bsb.p, bflag.p, out));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  return CLC_OK;
+}
+
+void clc_alt_pose_options_default(clc_alt_pose_options* o) {
+  if (!o) return;
+  // design values (include/clc.h): between the two clusters of rot_angle; a mirror within a factor two of the cost
+  o->same_angle = 0.01;
+  o->ratio_gate = 2.0;
+}
+
+int clc_board_poses_alternate(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const clc_alt_pose_options* aopt_in,
+                              const float* corners_px, const float* board_xy, const int64_t* offsets, size_t n_images,
+                              const uint8_t* inlier, const double* q_in_wxyz, const double* t_in, const int32_t* status_in,
+                              double* q_alt_wxyz, double* t_alt, double* rms_alt, double* cost_in, double* cost_alt, double* ratio,
+                              double* rot_angle, double* normal_angle, int32_t* kind, uint8_t* ambiguous, uint8_t* better,
+                              clc_summary* summaries_alt) {
+  const char* who = "clc_board_poses_alternate";
+  // the options first: their refusals need no device
+  CLC_TRY(camera_check(cam, who));
+  clc_options opt;
+  CLC_TRY(pose_options(opt_in, &opt, who));
+  clc_alt_pose_options ao;
+  CLC_TRY(alt_options(aopt_in, &ao, who));
+  if (!h || (n_images > 0 && (!offsets || !q_in_wxyz || !t_in || !status_in || !kind)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate: bad argument");
+  if (n_images == 0) return CLC_OK;
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate: too many images");
+  std::vector<long long> rel;
+  size_t M;
+  CLC_TRY(host_offsets(who, offsets, n_images, true, nullptr, &rel, &M));
+  if (M > 0 && (!corners_px || !board_xy)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate: bad argument");
+  CLC_HIP(hipSetDevice(h->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t n = n_images;
+  DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
+  DevBuf<long long> boff(&h->pool);
+  DevBuf<unsigned char> bm(&h->pool), bamb(&h->pool), bbet(&h->pool);
+  DevBuf<double> bqi(&h->pool), bti(&h->pool), bq(&h->pool), bt(&h->pool), bst7(&h->pool);
+  DevBuf<double> breal(&h->pool);  // rms, cost_in, cost_alt, ratio, rot_angle, normal_angle: n each
+  DevBuf<int32_t> bsi(&h->pool), bkind(&h->pool), bcnt(&h->pool), bflag(&h->pool);
+  DevBuf<clc_summary> bsum(&h->pool);
+  CLC_HIP(bc.alloc(2 * M)); CLC_HIP(bb.alloc(2 * M)); CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M));
+  CLC_HIP(boff.alloc(n + 1));
+  if (inlier) CLC_HIP(bm.alloc(M));
+  CLC_HIP(bqi.alloc(4 * n)); CLC_HIP(bti.alloc(3 * n)); CLC_HIP(bsi.alloc(n)); CLC_HIP(bkind.alloc(n)); CLC_HIP(bcnt.alloc(n));
+  CLC_HIP(bflag.alloc(n)); CLC_HIP(bst7.alloc(7 * n)); CLC_HIP(breal.alloc(6 * n));
+  if (q_alt_wxyz) CLC_HIP(bq.alloc(4 * n));
+  if (t_alt) CLC_HIP(bt.alloc(3 * n));
+  if (ambiguous) CLC_HIP(bamb.alloc(n));
+  if (better) CLC_HIP(bbet.alloc(n));
+  if (summaries_alt) CLC_HIP(bsum.alloc(n));
+  if (M > 0) {
+    CLC_HIP(hipMemcpyAsync(bc.p, corners_px + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    CLC_HIP(hipMemcpyAsync(bb.p, board_xy + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (inlier) CLC_HIP(hipMemcpyAsync(bm.p, inlier + offsets[0], M, hipMemcpyHostToDevice, h->stream));
+  }
+  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemcpyAsync(bqi.p, q_in_wxyz, 4 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemcpyAsync(bti.p, t_in, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CLC_HIP(hipMemcpyAsync(bsi.p, status_in, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  double* const host_real[6] = {rms_alt, cost_in, cost_alt, ratio, rot_angle, normal_angle};
+  double* dev_real[6];
+  for (int i = 0; i < 6; ++i) dev_real[i] = host_real[i] ? breal.p + (size_t)i * n : nullptr;
+  const AltIn in{(inlier && M > 0) ? bm.p : nullptr, bqi.p, bti.p, bsi.p};
+  const clc::ap::AltOut out{q_alt_wxyz ? bq.p : nullptr, t_alt ? bt.p : nullptr, dev_real[0], dev_real[1], dev_real[2],
+                            dev_real[3], dev_real[4], dev_real[5], bkind.p, ambiguous ? bamb.p : nullptr, better ? bbet.p : nullptr,
+                            summaries_alt ? bsum.p : nullptr};
+  CLC_HIP(launch_board_poses_alternate(h, *cam, opt, ao, bc.p, bb.p, boff.p, 0, M, n, in, bl.p, bsl.p, bsb.p, bcnt.p, bflag.p, bst7.p,
+                                       out));
+  CLC_HIP(hipMemcpyAsync(kind, bkind.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (q_alt_wxyz) CLC_HIP(hipMemcpyAsync(q_alt_wxyz, bq.p, 4 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (t_alt) CLC_HIP(hipMemcpyAsync(t_alt, bt.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  for (int i = 0; i < 6; ++i)
+    if (host_real[i]) CLC_HIP(hipMemcpyAsync(host_real[i], dev_real[i], n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (ambiguous) CLC_HIP(hipMemcpyAsync(ambiguous, bamb.p, n, hipMemcpyDeviceToHost, h->stream));
+  if (better) CLC_HIP(hipMemcpyAsync(better, bbet.p, n, hipMemcpyDeviceToHost, h->stream));
+  if (summaries_alt) CLC_HIP(hipMemcpyAsync(summaries_alt, bsum.p, n * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (summaries_alt) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (size_t k = 0; k < n; ++k) summaries_alt[k].solve_ms = ms;
+  }
+  return CLC_OK;
+}
+
+int clc_board_poses_alternate_device(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const clc_alt_pose_options* aopt_in,
+                                     const float* corners_px_dev, const float* board_xy_dev, const int64_t* offsets_dev,
+                                     size_t n_images, const uint8_t* inlier_dev, const double* q_in_wxyz_dev, const double* t_in_dev,
+                                     const int32_t* status_in_dev, double* q_alt_wxyz_dev, double* t_alt_dev, double* rms_alt_dev,
+                                     double* cost_in_dev, double* cost_alt_dev, double* ratio_dev, double* rot_angle_dev,
+                                     double* normal_angle_dev, int32_t* kind_dev, uint8_t* ambiguous_dev, uint8_t* better_dev,
+                                     clc_summary* summaries_alt_dev) {
+  const char* who = "clc_board_poses_alternate_device";
+  // the options first: their refusals need no device
+  CLC_TRY(camera_check(cam, who));
+  clc_options opt;
+  CLC_TRY(pose_options(opt_in, &opt, who));
+  clc_alt_pose_options ao;
+  CLC_TRY(alt_options(aopt_in, &ao, who));
+  if (!h || (n_images > 0 && (!offsets_dev || !q_in_wxyz_dev || !t_in_dev || !status_in_dev || !kind_dev)))
+    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: bad argument");
+  if (n_images == 0) return CLC_OK;
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: too many images");
+  CLC_HIP(hipSetDevice(h->device));
+  long long ends[2];  // the corner range, as clc_board_poses_device reads it
+  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n_images, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: offsets not monotone");
+  const size_t M = (size_t)(ends[1] - ends[0]);
+  if (M > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: bad argument");
+  DevBuf<float> bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
+  DevBuf<int32_t> bcnt(&h->pool), bflag(&h->pool);
+  DevBuf<double> bst7(&h->pool);
+  CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M)); CLC_HIP(bcnt.alloc(n_images));
+  CLC_HIP(bflag.alloc(n_images)); CLC_HIP(bst7.alloc(7 * n_images));
+  const AltIn in{inlier_dev, q_in_wxyz_dev, t_in_dev, status_in_dev};
+  const clc::ap::AltOut out{q_alt_wxyz_dev, t_alt_dev, rms_alt_dev, cost_in_dev, cost_alt_dev, ratio_dev, rot_angle_dev, normal_angle_dev,
+                            kind_dev, ambiguous_dev, better_dev, summaries_alt_dev};
+  CLC_HIP(launch_board_poses_alternate(h, *cam, opt, ao, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev),
+                                       ends[0], M, n_images, in, bl.p, bsl.p, bsb.p, bcnt.p, bflag.p, bst7.p, out));
   CLC_HIP(hipStreamSynchronize(h->stream));
   return CLC_OK;
 }

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import Iteration, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, Iteration, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -577,6 +577,53 @@ class Solver:
                                                     C.c_size_t(n_images), V(q_ptr), V(t_ptr), V(rms_ptr or 0), V(status_ptr),
                                                     V(summaries_ptr or 0), V(inlier_ptr), V(n_inliers_ptr or 0), V(best_group_ptr or 0),
                                                     V(n_fits_ptr or 0)), "clc_board_poses_robust_device")
+
+    def board_poses_alternate(self, camera, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray, q_in_wxyz: np.ndarray,
+                              t_in: np.ndarray, status_in: np.ndarray, inlier: Optional[np.ndarray] = None,
+                              options: Optional[Options] = None, alt: Optional[AltPoseOptions] = None, want_summaries: bool = False):
+        """clc_board_poses_alternate (K17): per image the other minimum of the planar fit, from the mirror of the input pose about the
+        line of sight, and how ambiguous the choice is.  Arrays as board_poses; (q_in_wxyz [n, 4], t_in [n, 3], status_in [n]) from
+        board_poses / board_poses_robust, inlier [M] (bool / uint8, None: every corner) the robust call's mask -> dict: q [n, 4], t
+        [n, 3], rms, cost_in, cost_alt, ratio, rot_angle, normal_angle [n], kind [n] int32 (CLC_ALT_*: 0 none, 1 same, 2 distinct),
+        ambiguous, better [n] bool, summaries (or None)."""
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        qi = np.ascontiguousarray(q_in_wxyz, dtype=np.float64).reshape(n, 4)
+        ti = np.ascontiguousarray(t_in, dtype=np.float64).reshape(n, 3)
+        si = np.ascontiguousarray(status_in, dtype=np.int32).reshape(n)
+        m = None if inlier is None else np.ascontiguousarray(np.asarray(inlier).astype(np.uint8)).reshape(cp.shape[0])
+        real = {k: np.empty(n) for k in ("rms", "cost_in", "cost_alt", "ratio", "rot_angle", "normal_angle")}
+        q = np.empty((n, 4)); t = np.empty((n, 3)); kind = np.empty(n, dtype=np.int32)
+        amb = np.zeros(n, dtype=np.uint8); bet = np.zeros(n, dtype=np.uint8)
+        sm = (Summary * n)() if want_summaries and n > 0 else None
+        c = camera.to_c()
+        o = C.byref(options) if options is not None else None
+        ao = C.byref(alt) if alt is not None else None
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_board_poses_alternate(self._h, C.byref(c), o, ao, vp(cp), vp(bx), vp(offsets), C.c_size_t(n), vp(m), vp(qi), vp(ti),
+                                                vp(si), vp(q), vp(t), vp(real["rms"]), vp(real["cost_in"]), vp(real["cost_alt"]),
+                                                vp(real["ratio"]), vp(real["rot_angle"]), vp(real["normal_angle"]), vp(kind), vp(amb),
+                                                vp(bet), sm), "clc_board_poses_alternate")
+        return dict(real, q=q, t=t, kind=kind, ambiguous=amb.astype(bool), better=bet.astype(bool), summaries=sm)
+
+    def board_poses_alternate_device(self, camera, corners_ptr: int, board_ptr: int, offsets_ptr: int, n_images: int, q_in_ptr: int,
+                                     t_in_ptr: int, status_in_ptr: int, kind_ptr: int, inlier_ptr: int = 0, q_ptr: int = 0, t_ptr: int = 0,
+                                     rms_ptr: int = 0, cost_in_ptr: int = 0, cost_alt_ptr: int = 0, ratio_ptr: int = 0,
+                                     rot_angle_ptr: int = 0, normal_angle_ptr: int = 0, ambiguous_ptr: int = 0, better_ptr: int = 0,
+                                     summaries_ptr: int = 0, options: Optional[Options] = None, alt: Optional[AltPoseOptions] = None):
+        """clc_board_poses_alternate_device on device-resident arrays (data_ptr()s; ready on the solver's stream); inlier, ambiguous,
+        better: uint8; kind is required, a zero pointer leaves any other output out."""
+        c = camera.to_c()
+        o = C.byref(options) if options is not None else None
+        ao = C.byref(alt) if alt is not None else None
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_board_poses_alternate_device(self._h, C.byref(c), o, ao, V(corners_ptr), V(board_ptr), V(offsets_ptr),
+                                                       C.c_size_t(n_images), V(inlier_ptr), V(q_in_ptr), V(t_in_ptr), V(status_in_ptr),
+                                                       V(q_ptr), V(t_ptr), V(rms_ptr), V(cost_in_ptr), V(cost_alt_ptr), V(ratio_ptr),
+                                                       V(rot_angle_ptr), V(normal_angle_ptr), V(kind_ptr), V(ambiguous_ptr),
+                                                       V(better_ptr), V(summaries_ptr)), "clc_board_poses_alternate_device")
 
     # ---- board-segment detection ----
     def board_segments(self, points: np.ndarray, offsets: np.ndarray):

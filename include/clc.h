@@ -900,6 +900,69 @@ int clc_board_poses_robust_device(clc_handle* h, const clc_camera* cam, const cl
                                   clc_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev, int32_t* best_group_dev,
                                   int32_t* n_fits_dev);
 
+/* ---- the planar fit's second minimum (K17): the other pose of every image and how ambiguous the choice is -------------------
+ * The reprojection cost of a planar target has two local minima: the true pose and its mirror about the line of sight
+ * (Schweighofer-Pinz; IPPE; AprilTag's estimate_tag_pose returns both for this reason).  clc_board_poses returns the one its DLT
+ * start leads to.  With the board far away or only a few tags decoded the two costs come close and noise decides which is lower:
+ * the plane's normal is then wrong by twice the tilt while rms looks clean.  This call takes the poses of clc_board_poses or
+ * clc_board_poses_robust and returns, per image k (corners [offsets[k], offsets[k+1]), status_in[k] the earlier call's status):
+ *  1. Set: the corners with inlier[i] != 0, compacted in corner order (inlier NULL: all corners), after clc_board_poses' lift
+ *     (fp64, x/z and y/z rounded to float32).  status_in[k] != CLC_POSE_OK, fewer than 4 corners in the set, or a non-finite
+ *     lifted corner or board point in it: CLC_ALT_NONE.  A non-finite corner outside the set is ignored.
+ *  2. Mirror start: Xbar = the set's mean board point, c = R Xbar + t, s = c / |c|, R' = (I - 2 s s^T) R diag(1, 1, -1),
+ *     t' = c - R' Xbar.  R' is a rotation, the centroid stays where it is and every corner's offset from it is reflected through the
+ *     plane perpendicular to the line of sight — the same image under weak perspective; the new normal is 2 (s.n) s - n.
+ *     c zero or not finite, or a non-finite start: CLC_ALT_NONE.
+ *  3. Fit: clc_board_poses' LM stage (K = I reprojection error, the same clc_options, opt NULL = clc_pose_options_default(), the
+ *     same rule for a point behind the camera) from (R', t') on the set; no DLT.  A failed or non-finite fit: CLC_ALT_NONE.
+ *  4. Costs: cost_in = 1/2 sum |r|^2 of the INPUT pose on the compacted set through the same evaluation — the per-corner
+ *     arithmetic AND the summation order of the fit's own evaluations, so that `better` and a ratio near 1 compare like with
+ *     like; cost_alt = the fit's final cost; ratio = cost_alt / cost_in (NaN when cost_in is zero or either cost is not finite).
+ *  5. rot_angle = the angle of R^T R_alt, normal_angle = the angle between R e_z and R_alt e_z.  rot_angle < same_angle:
+ *     CLC_ALT_SAME — the mirror start fell back into the input's minimum, the view is unambiguous; otherwise CLC_ALT_DISTINCT.
+ *  6. ambiguous = 1 iff DISTINCT and ratio < ratio_gate; better = 1 iff DISTINCT and cost_alt < cost_in.
+ * Outputs per image: q_alt_wxyz (w >= 0), t_alt, rms_alt (over the set), cost_in, cost_alt, ratio, rot_angle, normal_angle, kind,
+ * ambiguous, better, summaries_alt.  A CLC_ALT_NONE image gets q = (1, 0, 0, 0), t = 0, NaN for every real output and 0 for both
+ * flags.  An image never fails the call and never affects another image.  No existing call changes.
+ * The defaults are DESIGN VALUES.  same_angle = 0.01 rad lies between the two clusters of a numpy / scipy experiment (DESIGN.md
+ * K17): both starts in one minimum — rotations within 3.7e-4 rad (scipy's stopping); distinct minima — at least 0.18 rad apart;
+ * with this library's LM the clusters are 3.4e-9 rad at most and 0.35 rad at least on the seeded test sets, 7.8e-3 and 1.8e-2 rad on
+ * 4 x 10^4 random views whose tilt goes down to zero (profiles/board_poses_alternate.md).
+ * A rot_angle near the gate is NOT a sharp classification: the two minima lie twice the tilt apart and merge as the board turns to
+ * face the camera, the cost between them is flat, and the fit stops somewhere on the flat.  Below about half a degree of tilt SAME
+ * and DISTINCT shade into each other (the normals then differ by a degree at most); move same_angle to class such views one way.
+ * ratio_gate = 2: a pose whose mirror fits within a factor two is not a clean observation. */
+#define CLC_ALT_NONE 0
+#define CLC_ALT_SAME 1
+#define CLC_ALT_DISTINCT 2
+
+typedef struct clc_alt_pose_options {
+  double same_angle; /* rad: below it the two fits are the same minimum; finite, > 0 */
+  double ratio_gate; /* cost_alt / cost_in below it: ambiguous; finite, >= 1 */
+} clc_alt_pose_options; /* 16 bytes */
+
+/* same_angle 0.01, ratio_gate 2 (design values, see above). */
+void clc_alt_pose_options_default(clc_alt_pose_options* aopt);
+
+/* corners_px, board_xy, offsets as clc_board_poses; inlier (nullable) indexed like the corners; q_in_wxyz[4 n], t_in[3 n],
+ * status_in[n]: the earlier call's results.  kind[n] required, every other output nullable (ambiguous, better: uint8).
+ * CLC_ERR_INVALID_ARG: a same_angle that is not finite and positive, a ratio_gate that is not finite and >= 1 (checked before the
+ * handle).  One enqueue — lift, start, fit on the handle's stream, every launch sized by n_images — and one synchronisation. */
+int clc_board_poses_alternate(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_alt_pose_options* aopt,
+                              const float* corners_px, const float* board_xy, const int64_t* offsets, size_t n_images,
+                              const uint8_t* inlier, const double* q_in_wxyz, const double* t_in, const int32_t* status_in,
+                              double* q_alt_wxyz, double* t_alt, double* rms_alt, double* cost_in, double* cost_alt, double* ratio,
+                              double* rot_angle, double* normal_angle, int32_t* kind, uint8_t* ambiguous, uint8_t* better,
+                              clc_summary* summaries_alt);
+/* The same with every array in DEVICE memory (as clc_board_poses_device: offsets_dev[0] may be > 0; not validated: monotone). */
+int clc_board_poses_alternate_device(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_alt_pose_options* aopt,
+                                     const float* corners_px_dev, const float* board_xy_dev, const int64_t* offsets_dev,
+                                     size_t n_images, const uint8_t* inlier_dev, const double* q_in_wxyz_dev, const double* t_in_dev,
+                                     const int32_t* status_in_dev, double* q_alt_wxyz_dev, double* t_alt_dev, double* rms_alt_dev,
+                                     double* cost_in_dev, double* cost_alt_dev, double* ratio_dev, double* rot_angle_dev,
+                                     double* normal_angle_dev, int32_t* kind_dev, uint8_t* ambiguous_dev, uint8_t* better_dev,
+                                     clc_summary* summaries_alt_dev);
+
 #ifdef __cplusplus
 }
 #endif
