@@ -38,6 +38,7 @@ EXPORTED = [
     "clc_pose_options_default", "clc_camera_lift", "clc_camera_project", "clc_board_poses", "clc_board_poses_device",
     "clc_robust_pose_options_default", "clc_board_poses_robust", "clc_board_poses_robust_device",
     "clc_alt_pose_options_default", "clc_board_poses_alternate", "clc_board_poses_alternate_device",
+    "clc_joint_options_default", "clc_joint_refine", "clc_joint_refine_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -173,6 +174,12 @@ class AltPoseOptions(C.Structure):
     _fields_ = [("same_angle", C.c_double), ("ratio_gate", C.c_double)]
 
 
+class JointOptions(C.Structure):
+    """clc_joint_options (include/clc.h): sigma_corner in normalized image units (pixels / focal), sigma_laser in metres."""
+    _fields_ = [("sigma_corner", C.c_double), ("sigma_laser", C.c_double), ("hold_board_poses", C.c_int32), ("hold_extrinsic", C.c_int32)]
+
+
+JOINT_OK, JOINT_TOO_FEW, JOINT_NOT_KEPT, JOINT_NONFINITE = 1, 0, -1, -2  # CLC_JOINT_*
 POSE_OK, POSE_TOO_FEW, POSE_DEGENERATE, POSE_NONFINITE, POSE_NO_CONSENSUS = 1, 0, -1, -2, -3  # CLC_POSE_*
 ALT_NONE, ALT_SAME, ALT_DISTINCT = 0, 1, 2  # CLC_ALT_*
 
@@ -298,6 +305,11 @@ def load(path: str):
             L.clc_alt_pose_options_default.restype = None
             L.clc_board_poses_alternate.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 16
             L.clc_board_poses_alternate_device.argtypes = [V, V, V, V, V, V, V, C.c_size_t] + [V] * 16
+        if hasattr(L, "clc_joint_refine"):
+            L.clc_joint_options_default.argtypes = [V, V]
+            L.clc_joint_options_default.restype = None
+            L.clc_joint_refine.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 7
+            L.clc_joint_refine_device.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 7
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -365,6 +377,14 @@ def default_alt_pose_options() -> AltPoseOptions:
     """clc_alt_pose_options_default: same_angle 0.01 rad, ratio_gate 2 — design values."""
     o = AltPoseOptions()
     lib().clc_alt_pose_options_default(C.byref(o))
+    return o
+
+
+def default_joint_options(camera) -> JointOptions:
+    """clc_joint_options_default: 0.3 px over the camera's focal length and 0.01 m, nothing held."""
+    o = JointOptions()
+    c = camera.to_c()
+    lib().clc_joint_options_default(C.byref(o), C.byref(c))
     return o
 
 

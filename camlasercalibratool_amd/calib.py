@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import simdata
+from . import _capi, simdata
 from ._capi import (AssembleOptions, ClcError, InterpOptions, Options, StationOptions, TimeOffsetOptions, default_interp_options,
                     default_time_offset_options, TERMINATION, default_line_options, default_options)
 from .simdata import Oberserve, ObservationSet
@@ -553,6 +553,64 @@ def BoardPosesChecked(camera, corners, board, offsets, robust: bool = True, rati
     alt = sv.board_poses_alternate(camera, corners, board, offsets, q, t, st, inlier=inl, alt=ao)
     q2, t2, keep = checked_poses(q, t, st, alt)
     return q2, t2, st, keep, dict(alt, rms_in=rms, **extra)
+
+
+def _joint_arrays(corners_px, board_xy, sets: Sequence[ObservationSet], use_linefitting_data: bool):
+    """The CSR arrays of Solver.joint_refine over a list of problems: corners_px / board_xy one list of per-image arrays per problem."""
+    imgs_c = [np.asarray(c, np.float32).reshape(-1, 2) for prob in corners_px for c in prob]
+    imgs_b = [np.asarray(b, np.float32).reshape(-1, 2) for prob in board_xy for b in prob]
+    co = np.concatenate([[0], np.cumsum([len(c) for c in imgs_c])]).astype(np.int64)
+    pts, po = [], [0]
+    for s in sets:
+        off, P = (s.ptl_off, s.ptl) if use_linefitting_data else (s.pts_off, s.pts)
+        pts.append(P[off[0]:off[-1]])
+        po += list(po[-1] + (off[1:] - off[0]))
+    pr = np.concatenate([[0], np.cumsum([s.n_poses for s in sets])]).astype(np.int64)
+    if not (len(imgs_c) == len(imgs_b) == pr[-1]) or any(len(c) != len(b) for c, b in zip(imgs_c, imgs_b)):
+        raise ValueError("CamLaserCalibrationJoint: one image (corners and as many board points) per pose of the observation set")
+    cat = lambda xs, w, dt: np.concatenate(xs) if len(xs) else np.zeros((0, w), dt)
+    return (cat(imgs_c, 2, np.float32), cat(imgs_b, 2, np.float32), co, cat(pts, 3, np.float64), np.asarray(po, np.int64), pr,
+            cat([s.tag_q for s in sets], 4, np.float64), cat([s.tag_t for s in sets], 3, np.float64))
+
+
+def CamLaserCalibrationJointBatch(camera, problems: Sequence[dict], use_linefitting_data: bool = False, sigma_px: float = 0.3,
+                                  sigma_laser: float = 0.01, solver: Optional[Solver] = None, options: Optional[Options] = None):
+    """CamLaserCalibrationJoint for a list of problems in one call (one workgroup each): every problem a dict(corners_px, board_xy — one
+    array per image —, obs, Tcl [4, 4], keep (optional)).  -> list of (Tcl, ObservationSet, report)."""
+    sv = solver or _shared_solver()
+    sets = [_as_set(p["obs"]) for p in problems]
+    cp, bx, co, pts, po, pr, q0, t0 = _joint_arrays([p["corners_px"] for p in problems], [p["board_xy"] for p in problems], sets,
+                                                    use_linefitting_data)
+    keep = None
+    if any(p.get("keep") is not None for p in problems):
+        keep = np.concatenate([np.ones(s.n_poses, bool) if p.get("keep") is None else np.asarray(p["keep"], bool) for p, s in zip(problems, sets)])
+    jo = _capi.default_joint_options(camera)
+    jo.sigma_corner = sigma_px / float(np.sqrt(abs(camera.proj[0] * camera.proj[1])))
+    jo.sigma_laser = sigma_laser
+    cl0 = np.stack([simdata.pose7_from_T(np.asarray(p["Tcl"], np.float64)) for p in problems]) if problems else np.zeros((0, 7))
+    r = sv.joint_refine(camera, cp, bx, co, pts, po, q0, t0, cl0, problem_offsets=pr, keep=keep, options=options, joint=jo)
+    out = []
+    for k, s in enumerate(sets):
+        sl = slice(pr[k], pr[k + 1])
+        H = r["H_cl"][k]
+        report = dict(summary=r["summaries"][k], termination=_capi.TERMINATION.get(r["summaries"][k].termination, "?"), H_cl=H,
+                      singular_values=np.linalg.svd(H, compute_uv=False) if np.all(np.isfinite(H)) else np.full(6, np.nan),
+                      cost_corner=float(r["cost_parts"][k, 0]), cost_laser=float(r["cost_parts"][k, 1]), status=r["status"][sl].copy())
+        refined = ObservationSet(r["q"][sl].copy(), r["t"][sl].copy(), s.pts_off, s.pts, s.ptl_off, s.ptl)
+        out.append((simdata.T_from_pose7(r["poses_cl"][k]), refined, report))
+    return out
+
+
+def CamLaserCalibrationJoint(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], obs: ObsLike, Tcl: np.ndarray,
+                             use_linefitting_data: bool = False, keep=None, sigma_px: float = 0.3, sigma_laser: float = 0.01,
+                             solver: Optional[Solver] = None, options: Optional[Options] = None):
+    """Joint refinement of the board poses and T_cl (K18): image i belongs to pose i of `obs` — its start pose is that pose's tag pose,
+    its laser points that pose's `points` (or `points_on_line`).  Minimises the corner reprojection error over sigma_px (pixels) plus
+    the laser point-to-board-plane distance over sigma_laser (metres) over T_cl and every board pose.
+    -> (Tcl [4, 4], the observation set with the refined tag poses, report: summary, termination, H_cl — the information on T_cl
+    with the board poses marginalised —, its singular_values, cost_corner, cost_laser, status per image)."""
+    return CamLaserCalibrationJointBatch(camera, [dict(corners_px=corners_px, board_xy=board_xy, obs=obs, Tcl=Tcl, keep=keep)],
+                                         use_linefitting_data, sigma_px, sigma_laser, solver, options)[0]
 
 
 def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:

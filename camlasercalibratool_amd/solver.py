@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, Iteration, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, Iteration, JointOptions, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -624,6 +624,60 @@ class Solver:
                                                        V(q_ptr), V(t_ptr), V(rms_ptr), V(cost_in_ptr), V(cost_alt_ptr), V(ratio_ptr),
                                                        V(rot_angle_ptr), V(normal_angle_ptr), V(kind_ptr), V(ambiguous_ptr),
                                                        V(better_ptr), V(summaries_ptr)), "clc_board_poses_alternate_device")
+
+    # ---- joint refinement (K18) ----
+    def joint_refine(self, camera, corners_px: np.ndarray, board_xy: np.ndarray, corner_offsets: np.ndarray, pts: np.ndarray,
+                     pts_offsets: np.ndarray, q_ca_wxyz: np.ndarray, t_ca: np.ndarray, poses_cl: np.ndarray,
+                     problem_offsets: Optional[np.ndarray] = None, keep: Optional[np.ndarray] = None, options: Optional[Options] = None,
+                     joint: Optional[JointOptions] = None) -> dict:
+        """clc_joint_refine (K18): one cost over T_cl and every board pose of a problem — corner reprojection over sigma_corner plus laser
+        point-to-board-plane distance over sigma_laser.  Image i owns corners [corner_offsets[i], corner_offsets[i+1]) and laser points
+        [pts_offsets[i], pts_offsets[i+1]); problem k owns images [problem_offsets[k], problem_offsets[k+1]) (None: one problem).
+        q_ca_wxyz [n, 4], t_ca [n, 3], poses_cl [n_problems, 7] are the start poses (not modified).
+        -> dict(q [n, 4], t [n, 3], poses_cl [n_problems, 7], summaries, H_cl [n_problems, 6, 6], cost_parts [n_problems, 2] (corner,
+        laser), status [n] int32 (CLC_JOINT_*))."""
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        co = np.ascontiguousarray(corner_offsets, dtype=np.int64)
+        P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        po = np.ascontiguousarray(pts_offsets, dtype=np.int64)
+        n = len(co) - 1
+        if n < 0 or len(po) != n + 1:
+            raise ValueError("joint_refine: corner_offsets and pts_offsets need one entry per image plus one")
+        if n > 0 and (co[-1] > len(cp) or co[-1] > len(bx) or po[-1] > len(P) or co[0] < 0 or po[0] < 0):
+            raise ValueError("joint_refine: offsets run past corners_px, board_xy or pts")
+        pr = None if problem_offsets is None else np.ascontiguousarray(problem_offsets, dtype=np.int64)
+        npb = 1 if pr is None else len(pr) - 1
+        q = np.array(q_ca_wxyz, dtype=np.float64, order="C").reshape(n, 4)
+        t = np.array(t_ca, dtype=np.float64, order="C").reshape(n, 3)
+        cl = np.array(poses_cl, dtype=np.float64, order="C").reshape(npb, 7)
+        kp = None if keep is None else np.ascontiguousarray(np.asarray(keep).astype(np.uint8))
+        if kp is not None and kp.shape != (n,):
+            raise ValueError("joint_refine: keep needs one entry per image")
+        if pr is not None and (len(pr) < 1 or (len(pr) > 1 and pr[-1] > n)):
+            raise ValueError("joint_refine: problem_offsets run past the images")
+        sm = (Summary * max(npb, 1))()
+        H = np.empty((npb, 6, 6)); parts = np.empty((npb, 2)); st = np.empty(n, dtype=np.int32)
+        c = camera.to_c()
+        V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_joint_refine(self._h, C.byref(c), C.byref(options) if options is not None else None,
+                                       C.byref(joint) if joint is not None else None, V(cp), V(bx), V(co), V(P), V(po), V(kp), C.c_size_t(n),
+                                       V(pr), C.c_size_t(npb), V(q), V(t), V(cl), sm, V(H), V(parts), V(st)), "clc_joint_refine")
+        return dict(q=q, t=t, poses_cl=cl, summaries=sm, H_cl=H, cost_parts=parts, status=st)
+
+    def joint_refine_device(self, camera, corners_ptr: int, board_ptr: int, corner_offsets_ptr: int, pts_ptr: int, pts_offsets_ptr: int,
+                            n_images: int, n_problems: int, q_ptr: int, t_ptr: int, poses_cl_ptr: int, summaries_ptr: int, status_ptr: int,
+                            problem_offsets_ptr: int = 0, keep_ptr: int = 0, H_cl_ptr: int = 0, cost_parts_ptr: int = 0,
+                            options: Optional[Options] = None, joint: Optional[JointOptions] = None):
+        """clc_joint_refine_device on device-resident arrays (data_ptr()s; ready on the solver's stream): the per-image arrays are
+        indexed by the absolute image index, the call covers n_images images from problem_offsets[0] on; q, t, poses_cl in / out."""
+        c = camera.to_c()
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_joint_refine_device(self._h, C.byref(c), C.byref(options) if options is not None else None,
+                                              C.byref(joint) if joint is not None else None, V(corners_ptr), V(board_ptr),
+                                              V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
+                                              V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
+                                              V(summaries_ptr), V(H_cl_ptr), V(cost_parts_ptr), V(status_ptr)), "clc_joint_refine_device")
 
     # ---- board-segment detection ----
     def board_segments(self, points: np.ndarray, offsets: np.ndarray):

@@ -963,6 +963,57 @@ int clc_board_poses_alternate_device(clc_handle* h, const clc_camera* cam, const
                                      double* normal_angle_dev, int32_t* kind_dev, uint8_t* ambiguous_dev, uint8_t* better_dev,
                                      clc_summary* summaries_alt_dev);
 
+/* ---- joint refinement of the board poses and the camera-laser extrinsic (K18) ------------------------------------------
+ * One cost over T_cl and every board pose T_ca,i of a problem of P images:
+ *   corner  ((R_i X + t_i)_xy / (R_i X + t_i)_z - x_lifted) / sigma_corner     x_lifted: the float32-rounded lift of clc_board_poses
+ *   laser   e3^T R_i^T (R_cl p + t_cl - t_i) / sigma_laser                     the point-to-plane factor with n = R_i e3, d = -n.t_i
+ * cost = 1/2 sum r^2, no loss; tangent [dt, dtheta] with t += dt, R <- R Exp(dtheta) for every pose.  The whole Levenberg-Marquardt
+ * solve of a problem runs in one kernel launch (one workgroup per problem): per-image 6x6 blocks, a Schur complement onto the 6x6
+ * system of T_cl, clc_options with the semantics of the other solves (opt NULL = clc_pose_options_default()).  Deterministic: the
+ * same bits on every run, and a problem's result does not depend on the other problems of the call. */
+typedef struct clc_joint_options {
+  double sigma_corner;      /* normalized image units (pixels / focal), finite, > 0 */
+  double sigma_laser;       /* metres, finite, > 0 */
+  int32_t hold_board_poses; /* 1: only T_cl moves */
+  int32_t hold_extrinsic;   /* 1: only the board poses move */
+} clc_joint_options;        /* 24 bytes */
+
+/* 0.3 px / sqrt(|proj0 proj1|) and 0.01 m, the noise levels of the project's simulations; cam NULL: sigma_corner 0 (refused). */
+void clc_joint_options_default(clc_joint_options* jopt, const clc_camera* cam);
+
+/* Image status of clc_joint_refine. */
+#define CLC_JOINT_OK 1
+#define CLC_JOINT_TOO_FEW 0      /* fewer than 4 corners */
+#define CLC_JOINT_NOT_KEPT (-1)  /* keep[i] == 0, or the image belongs to no problem */
+#define CLC_JOINT_NONFINITE (-2) /* a non-finite corner, board point, laser point or start pose */
+
+/* Image i owns corners [corner_offsets[i], corner_offsets[i+1]) of corners_px / board_xy (as clc_board_poses) and laser points
+ * [pts_offsets[i], pts_offsets[i+1]) of pts[3 N] (laser frame; none is allowed); problem k owns images [problem_offsets[k],
+ * problem_offsets[k+1]) (NULL: one problem of all images).  keep[n_images] (nullable): 0 drops an image.  In / out: q_ca_wxyz[4 n]
+ * (out: w >= 0), t_ca[3 n] — the start poses, e.g. clc_board_poses' — and poses_cl[7 n_problems] = [t, qx, qy, qz, qw] with
+ * p_c = R_cl p + t_cl.  An image that takes no part (image_status != CLC_JOINT_OK) keeps its pose bit for bit.  A problem with no
+ * participating image, a non-finite T_cl or a failed solve ends CLC_FAILURE with every pose untouched.  With no laser point in a
+ * problem T_cl is returned bit for bit.  summaries[n_problems]: final_cost is the cost at the returned poses.  H_cl[36 n_problems]
+ * (nullable): the information on T_cl with the board poses marginalised, C - sum B_i^T A_i^-1 B_i at the returned poses (undamped;
+ * C itself with hold_board_poses; NaN where an A_i is not positive definite).  cost_parts[2 n_problems] (nullable): the corner and
+ * the laser share of final_cost.  CLC_ERR_INVALID_ARG before any device work: NULL required pointers, a sigma that is not finite
+ * and positive, both hold flags, offsets that decrease.  One enqueue (lift, then the solve) and one synchronisation. */
+int clc_joint_refine(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_joint_options* jopt,
+                     const float* corners_px, const float* board_xy, const int64_t* corner_offsets, const double* pts,
+                     const int64_t* pts_offsets, const uint8_t* keep, size_t n_images, const int64_t* problem_offsets, size_t n_problems,
+                     double* q_ca_wxyz, double* t_ca, double* poses_cl, clc_summary* summaries, double* H_cl, double* cost_parts,
+                     int32_t* image_status);
+/* The same with every array in DEVICE memory.  The per-image arrays (offsets, keep, q, t, image_status) are indexed by the
+ * absolute image index: the call covers the n_images images from problem_offsets_dev[0] on (from 0 when it is NULL); corner and
+ * point offsets are absolute too.  The per-problem arrays start at problem 0.  Offsets are not validated beyond the ends of the
+ * ranges, which are read back once to size the call's scratch ahead of its one enqueue. */
+int clc_joint_refine_device(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_joint_options* jopt,
+                            const float* corners_px_dev, const float* board_xy_dev, const int64_t* corner_offsets_dev,
+                            const double* pts_dev, const int64_t* pts_offsets_dev, const uint8_t* keep_dev, size_t n_images,
+                            const int64_t* problem_offsets_dev, size_t n_problems, double* q_ca_wxyz_dev, double* t_ca_dev,
+                            double* poses_cl_dev, clc_summary* summaries_dev, double* H_cl_dev, double* cost_parts_dev,
+                            int32_t* image_status_dev);
+
 #ifdef __cplusplus
 }
 #endif
