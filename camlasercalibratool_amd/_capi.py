@@ -39,6 +39,7 @@ EXPORTED = [
     "clc_robust_pose_options_default", "clc_board_poses_robust", "clc_board_poses_robust_device",
     "clc_alt_pose_options_default", "clc_board_poses_alternate", "clc_board_poses_alternate_device",
     "clc_joint_options_default", "clc_joint_refine", "clc_joint_refine_device",
+    "clc_camcal_options_default", "clc_camera_guess", "clc_camera_guess_device", "clc_camera_calibrate", "clc_camera_calibrate_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -179,7 +180,13 @@ class JointOptions(C.Structure):
     _fields_ = [("sigma_corner", C.c_double), ("sigma_laser", C.c_double), ("hold_board_poses", C.c_int32), ("hold_extrinsic", C.c_int32)]
 
 
+class CamcalOptions(C.Structure):
+    """clc_camcal_options (include/clc.h): sigma_px in pixels; bit j of hold_mask holds intrinsic j (proj[0..3], dist[0..3])."""
+    _fields_ = [("sigma_px", C.c_double), ("hold_mask", C.c_uint32), ("hold_board_poses", C.c_int32)]
+
+
 JOINT_OK, JOINT_TOO_FEW, JOINT_NOT_KEPT, JOINT_NONFINITE = 1, 0, -1, -2  # CLC_JOINT_*
+CAMCAL_OK, CAMCAL_TOO_FEW, CAMCAL_NOT_KEPT, CAMCAL_NONFINITE = 1, 0, -1, -2  # CLC_CAMCAL_*
 POSE_OK, POSE_TOO_FEW, POSE_DEGENERATE, POSE_NONFINITE, POSE_NO_CONSENSUS = 1, 0, -1, -2, -3  # CLC_POSE_*
 ALT_NONE, ALT_SAME, ALT_DISTINCT = 0, 1, 2  # CLC_ALT_*
 
@@ -310,6 +317,13 @@ def load(path: str):
             L.clc_joint_options_default.restype = None
             L.clc_joint_refine.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 7
             L.clc_joint_refine_device.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 7
+        if hasattr(L, "clc_camera_calibrate"):
+            L.clc_camcal_options_default.argtypes = [V, C.c_int32]
+            L.clc_camcal_options_default.restype = None
+            L.clc_camera_guess.argtypes = [V, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_size_t, V, V]
+            L.clc_camera_guess_device.argtypes = [V, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_size_t, V, V]
+            L.clc_camera_calibrate.argtypes = [V] * 7 + [C.c_size_t, V, C.c_size_t] + [V] * 7
+            L.clc_camera_calibrate_device.argtypes = [V] * 7 + [C.c_size_t, V, C.c_size_t] + [V] * 7
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -385,6 +399,13 @@ def default_joint_options(camera) -> JointOptions:
     o = JointOptions()
     c = camera.to_c()
     lib().clc_joint_options_default(C.byref(o), C.byref(c))
+    return o
+
+
+def default_camcal_options(model: int) -> CamcalOptions:
+    """clc_camcal_options_default: 0.3 px; nothing held for PINHOLE, k4 and k5 (bits 6, 7) held for KANNALA_BRANDT."""
+    o = CamcalOptions()
+    lib().clc_camcal_options_default(C.byref(o), C.c_int32(model))
     return o
 
 

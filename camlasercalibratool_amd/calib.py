@@ -613,6 +613,52 @@ def CamLaserCalibrationJoint(camera, corners_px: Sequence[np.ndarray], board_xy:
                                          use_linefitting_data, sigma_px, sigma_laser, solver, options)[0]
 
 
+def CalibrateCamera(model: int, width: int, height: int, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], hold=None,
+                    sigma_px: float = 0.3, camera0=None, solver: Optional[Solver] = None, options: Optional[Options] = None):
+    """The camera's intrinsics from images of the board (K19): corners_px[i] [n_i, 2] pixels and board_xy[i] [n_i, 2] board-plane
+    points of image i.  The start is `camera0` or the closed-form guess (clc_camera_guess: fx = fy from the images' homographies, the
+    principal point at the image centre, zero distortion); the start poses are clc_board_poses' under that camera, images without
+    one are dropped; then clc_camera_calibrate over the free intrinsics and every board pose.  hold: the intrinsics to hold — a bit
+    mask or a sequence of indices into (proj[0..3], dist[0..3]); None = the model's default (Kannala-Brandt: k4, k5).
+    -> (Camera, q_ca [n, 4] (w, x, y, z), t_ca [n, 3], report: summary, termination, cost, rms_px, iterations, H_cam [8, 8], sigma [8]
+    (1 sigma of the free intrinsics from inv(H_cam restricted to the free set), NaN for a held one), hold_mask, camera0, status per
+    image (CLC_CAMCAL_*), n_used)."""
+    from .camera import Camera
+    sv = solver or _shared_solver()
+    cp = [np.asarray(c, dtype=np.float32).reshape(-1, 2) for c in corners_px]
+    bx = [np.asarray(b, dtype=np.float32).reshape(-1, 2) for b in board_xy]
+    if len(cp) != len(bx) or any(len(a) != len(b) for a, b in zip(cp, bx)):
+        raise ValueError("CalibrateCamera: one board point per corner, image by image")
+    off = np.zeros(len(cp) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in cp])
+    C_ = np.concatenate(cp) if cp else np.zeros((0, 2), np.float32)
+    B_ = np.concatenate(bx) if bx else np.zeros((0, 2), np.float32)
+    co = _capi.default_camcal_options(model)
+    co.sigma_px = float(sigma_px)
+    if hold is not None:
+        co.hold_mask = int(hold) if np.isscalar(hold) else int(sum(1 << int(j) for j in set(hold)))
+    if camera0 is None:
+        camera0, _ = sv.camera_guess(model, width, height, C_, B_, off)
+    else:
+        camera0 = Camera(camera0.model, tuple(camera0.proj), tuple(camera0.dist), int(width), int(height))
+    q0, t0, _, st0, _ = sv.board_poses(camera0, C_, B_, off)
+    keep = st0 == _capi.POSE_OK
+    res = sv.camera_calibrate(camera0, C_, B_, off, q0, t0, keep=keep, options=options, camcal=co)
+    sm = res["summaries"][0]
+    H = res["H_cam"][0]
+    free = [j for j in range(8) if not (co.hold_mask >> j) & 1]
+    sigma = np.full(8, np.nan)
+    if free and np.isfinite(H).all():
+        try:
+            sigma[free] = np.sqrt(np.diag(np.linalg.inv(H[np.ix_(free, free)])))
+        except np.linalg.LinAlgError:
+            pass
+    report = dict(summary=sm, termination=_capi.TERMINATION.get(sm.termination, str(sm.termination)), cost=sm.final_cost,
+                  rms_px=float(res["rms_px"][0]), iterations=sm.num_iterations, H_cam=H, sigma=sigma, hold_mask=int(co.hold_mask),
+                  camera0=camera0, status=res["status"], n_used=int(np.count_nonzero(res["status"] == _capi.CAMCAL_OK)))
+    return res["cameras"][0], res["q"], res["t"], report
+
+
 def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:
     """The calibration board's segment in one scan — mirror of AutoGetLinePts(points, debug), src/selectScanPoints.cpp:17-190:
     points [n,3] -> the chosen segment's points [k,3] (empty when there is none).  Raises IndexError where the reference's

@@ -74,6 +74,26 @@ class Camera:
             return Camera.kannala_brandt(g("mu"), g("mv"), g("u0"), g("v0"), g("k2"), g("k3"), g("k4"), g("k5"), w, h)
         raise ValueError(f"{path}: model_type {model!r} is not supported (PINHOLE, KANNALA_BRANDT)")
 
+    def to_yaml(self, path: str, camera_name: str = "cam0") -> None:
+        """Writes the camera in the reference's config format, the one from_yaml reads (%YAML:1.0, model_type, image size, the
+        projection_parameters / distortion_parameters blocks; Kannala-Brandt keeps all eight under projection_parameters, as the
+        reference's file does).  repr() of a float round-trips: from_yaml returns an equal Camera."""
+        if self.model == PINHOLE:
+            blocks = [("distortion_parameters", zip(("k1", "k2", "p1", "p2"), self.dist)),
+                      ("projection_parameters", zip(("fx", "fy", "cx", "cy"), self.proj))]
+            name = "PINHOLE"
+        elif self.model == KANNALA_BRANDT:
+            blocks = [("projection_parameters", zip(("mu", "mv", "u0", "v0", "k2", "k3", "k4", "k5"), tuple(self.proj) + tuple(self.dist)))]
+            name = "KANNALA_BRANDT"
+        else:
+            raise ValueError(f"model {self.model!r} is not supported (PINHOLE, KANNALA_BRANDT)")
+        lines = ["%YAML:1.0", "", "#camera calibration", f"model_type: {name}", f"camera_name: {camera_name}",
+                 f"image_width: {int(self.width)}", f"image_height: {int(self.height)}"]
+        for block, items in blocks:
+            lines += ["", f"{block}:"] + [f"   {k}: {float(v)!r}" for k, v in items]
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
     def to_c(self) -> ClcCamera:
         c = ClcCamera()
         c.model = self.model

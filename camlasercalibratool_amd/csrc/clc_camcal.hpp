@@ -1,0 +1,998 @@
+// clc_camcal.hpp — K19: the camera's intrinsics from the board images.  One problem = one camera seen in P images of the board; the cost
+//
+//   1/2 sum |(project(cam, R_i X + t_i) - u) / sigma_px|^2          project: cam_project of clc_campose.hpp, pixels, no lift
+//
+// is minimised over the 8 intrinsics (clc_camera order: proj[0..3], dist[0..3]; moved additively) and the tangent [dt, dtheta] of every
+// board pose (t += dt, R <- R Exp(dtheta)).  The normal matrix is K18's arrow with an 8-wide shared block: A_i (6x6) per image, B_i
+// (6x8) to the block C (8x8) of the intrinsics; the Schur complement over the images leaves an 8x8 system, less the held intrinsics.
+//
+//   camcal_kernel   one 256-thread workgroup (4 waves) per problem, the whole Levenberg-Marquardt solve in one launch; the shape and
+//                   the helpers (each_image, each_image_wave, each_lane, chol_factor6, chol_apply6, block_candidate, ...) are those of
+//                   joint_refine_kernel (clc_joint.hpp).
+//     evaluation   the waves take the images round-robin; per image a wave all-reduces, in four passes over the corners (the cheap
+//                  residual recomputed), {A_i, g_i, sum r^2} (28), {B_i[:, 0:4], g_c} (32), B_i[:, 4:8] (24) and the image's share of
+//                  C (36): 120 sums, never more than 36 live.  The shares are added over the images in image order.
+//     step         one image per lane: the scaled, damped A_i + D_i factored, Y_i = (A_i + D_i)^-1 B_i, S_i = B_i^T Y_i (8x8), s_i; S
+//                  and s added in image order; thread 0 compacts the reduced system to the free intrinsics and solves it with
+//                  chol_solve<n_free>; the lanes back-substitute.  A rejected step repeats only this.
+//     controller   thread 0, state in LDS: the semantics of clc_lm.hpp over the arrow (Jacobi scaling fixed at the first evaluation —
+//                  focal lengths and k-coefficients differ by five orders of magnitude —, the diagonal clamp, the radius rule, the
+//                  three tolerances, the iteration cap).  An evaluation with a corner at P_z <= 0 is invalid (a rejected candidate).
+//   homography_kernel   one wave per image: the pixel-space homography of the image's corners about the image centre (K10's normalized
+//                       DLT and jacobi_rows, the same degeneracy ratio), scaled to unit Frobenius norm: the closed-form focal start's
+//                       per-image half (guess_focal is the host's half).
+// Per-image state (CalImage) lives in a workspace in device memory indexed by image; every access goes through pointers (no scratch).
+// Every sum has a fixed shape: no atomics, the same bits on every run, and a problem never reads another problem's state.
+//
+// Everything numeric is CLC_HD: tests/shim/camcal_shim.cpp compiles this header for the host with g++ and runs the same code with the
+// threads as loops, in the same summation order.
+#pragma once
+#include "clc_joint.hpp"
+
+namespace clc {
+namespace cc {
+
+using jt::each_image;
+using jt::each_image_wave;
+using jt::each_lane;
+using jt::finite_d;
+using jt::wg_barrier;
+using jt::wg_lead;
+
+constexpr int CAL_THREADS = jt::JOINT_THREADS;  // each_image / each_image_wave stride by the joint kernel's workgroup
+constexpr int NK = 8;                           // intrinsics
+
+// offsets into an evaluation record E[EVAL_DOUBLES] of one image: A tri<6>, B[8 p + q] (pose row p, intrinsic q), g_i, C tri<8>, g_c
+constexpr int E_A = 0, E_B = 21, E_G = 69, E_C = 75, E_GC = 111, E_COST = 119, EVAL_DOUBLES = 120;
+constexpr int TOTAL_DOUBLES = EVAL_DOUBLES - E_C;  // C, g_c, the cost
+constexpr int SS_DOUBLES = 36 + NK;                // S_i (tri<8>) and s_i
+
+struct CalImage {
+  double x[7], xe[7];            // accepted pose, pose the next evaluation uses: [t, qx, qy, qz, qw]
+  double E[2][EVAL_DOUBLES];     // the blocks at the accepted point (sh.cur) and at the candidate
+  double scale[6], diag[6];      // Jacobi scaling, clamped diagonal of the scaled A
+  double As[36], Md[36], L[36];  // scaled A, scaled damped A, its Cholesky factor (inverse diagonal)
+  double Bs[48], Y[48];          // scaled B, (A + D)^-1 B
+  double gs[6], yg[6], z[6];     // scaled g, (A + D)^-1 g, substitution scratch
+  double Ss[SS_DOUBLES];         // S_i and s_i
+  double step[6];                // delta_i in the scaled space
+  double red[6];                 // shares: step.g, step^T H step, |x - xe|^2, |xe|^2, gradient max norm, bad-step flag
+  int32_t st;                    // CLC_CAMCAL_*
+  int32_t pad_;
+};
+
+struct CalShared {
+  double kc[NK], kce[NK];  // intrinsics accepted / to evaluate
+  double tot[2][TOTAL_DOUBLES];
+  double scale_c[NK], diag_c[NK], step_c[NK], gs_c[NK], rhs[NK];
+  double Ss[SS_DOUBLES], red[6];
+  double Hs[64], A[64], L[64], z[NK];
+  double Af[64], rf[NK], yf[NK];  // the reduced system of the free intrinsics, compact
+  double x_cost, x_norm, initial_cost, min_iter_cost, radius, decrease_factor, model_cost_change, gmax;
+  double it_cost, it_gmax;
+  long long n_evals, n_corners;
+  int32_t status, n_invalid, reuse_diagonal, num_successful, num_unsuccessful, n_trace, cur, step_ok, move_c, move_i, n_part;
+  int32_t it_iteration, it_successful, model, n_free;
+  int32_t free_idx[NK];
+};
+
+struct CalArgs {
+  clc_options opt;
+  double sigma_px;
+  uint32_t hold_mask;
+  int32_t hold_board_poses;
+  const float* corners;       // pixels, indexed by the absolute corner offsets
+  const float* board;
+  const long long* coff;      // [image] absolute
+  const unsigned char* keep;  // nullable
+  const long long* prob_off;  // nullable: one problem over every image
+  long long n_images;         // images from prob_off[0] (0 without it) on
+  double *q, *t;
+  clc_camera* cams;
+  clc_summary* summaries;
+  double *H_cam, *rms;        // nullable
+  int32_t* status;
+  CalImage* ws;               // [n_images], the call's first image first
+};
+
+// ---- the projection's derivatives -----------------------------------------------------------------------------------------
+// JP[3 i + j] = d px_i / d P_j, JK[8 i + q] = d px_i / d intrinsic q (proj[0..3], dist[0..3]) of cam_project at the camera-frame
+// point P.  PINHOLE: radial-tangential distortion of x = P_x / P_z, y = P_y / P_z.  KANNALA_BRANDT: through theta = acos(P_z / |P|)
+// and phi; on the optical axis (rho = 0) phi is undefined and the limit d px / d P_xy = f / P_z is taken.
+CLC_HD void project_jacobian(const clc_camera& c, const double* P, double* JP, double* JK) {
+  CLC_BF_NO_CONTRACT
+  const double fx = c.proj[0], fy = c.proj[1];
+  if (c.model == CLC_CAMERA_PINHOLE) {
+    const double k1 = c.dist[0], k2 = c.dist[1], p1 = c.dist[2], p2 = c.dist[3];
+    const double iz = 1.0 / P[2];
+    const double x = P[0] * iz, y = P[1] * iz;
+    const double x2 = x * x, y2 = y * y, xy = x * y, r2 = x2 + y2;
+    const double rad = k1 * r2 + k2 * r2 * r2, drad = 2.0 * (k1 + 2.0 * k2 * r2);  // d rad / d r2, doubled
+    const double xd = x + (x * rad + 2.0 * p1 * xy + p2 * (r2 + 2.0 * x2));
+    const double yd = y + (y * rad + 2.0 * p2 * xy + p1 * (r2 + 2.0 * y2));
+    const double xd_x = 1.0 + rad + x2 * drad + 2.0 * p1 * y + 6.0 * p2 * x;
+    const double xd_y = xy * drad + 2.0 * p1 * x + 2.0 * p2 * y;
+    const double yd_x = xy * drad + 2.0 * p2 * y + 2.0 * p1 * x;
+    const double yd_y = 1.0 + rad + y2 * drad + 2.0 * p2 * x + 6.0 * p1 * y;
+    JP[0] = fx * xd_x * iz; JP[1] = fx * xd_y * iz; JP[2] = -fx * (xd_x * x + xd_y * y) * iz;
+    JP[3] = fy * yd_x * iz; JP[4] = fy * yd_y * iz; JP[5] = -fy * (yd_x * x + yd_y * y) * iz;
+    JK[0] = xd; JK[1] = 0.0; JK[2] = 1.0; JK[3] = 0.0;
+    JK[4] = fx * x * r2; JK[5] = fx * x * r2 * r2; JK[6] = fx * 2.0 * xy; JK[7] = fx * (r2 + 2.0 * x2);
+    JK[8] = 0.0; JK[9] = yd; JK[10] = 0.0; JK[11] = 1.0;
+    JK[12] = fy * y * r2; JK[13] = fy * y * r2 * r2; JK[14] = fy * (r2 + 2.0 * y2); JK[15] = fy * 2.0 * xy;
+  } else {
+    const double rho2 = P[0] * P[0] + P[1] * P[1];
+    const double n2 = rho2 + P[2] * P[2];
+    const double nrm = sqrt(n2), rho = sqrt(rho2);
+    const double th = acos(P[2] / nrm), t2 = th * th;
+    const double t3 = t2 * th, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
+    const double r = th + c.dist[0] * t3 + c.dist[1] * t5 + c.dist[2] * t7 + c.dist[3] * t9;
+    const double dr = 1.0 + t2 * (3.0 * c.dist[0] + t2 * (5.0 * c.dist[1] + t2 * (7.0 * c.dist[2] + t2 * 9.0 * c.dist[3])));
+    if (rho > 1e-12 * nrm) {
+      const double cph = P[0] / rho, sph = P[1] / rho;
+      // d theta / d P = (x z, y z, -rho^2) / (|P|^2 rho); d phi / d P = (-y, x, 0) / rho^2
+      const double a = P[2] / (n2 * rho);
+      const double th0 = P[0] * a, th1 = P[1] * a, th2 = -rho / n2;
+      const double ph0 = -P[1] / rho2, ph1 = P[0] / rho2;
+      JP[0] = fx * (dr * cph * th0 - r * sph * ph0); JP[1] = fx * (dr * cph * th1 - r * sph * ph1); JP[2] = fx * (dr * cph * th2);
+      JP[3] = fy * (dr * sph * th0 + r * cph * ph0); JP[4] = fy * (dr * sph * th1 + r * cph * ph1); JP[5] = fy * (dr * sph * th2);
+      JK[0] = r * cph; JK[1] = 0.0; JK[2] = 1.0; JK[3] = 0.0;
+      JK[4] = fx * t3 * cph; JK[5] = fx * t5 * cph; JK[6] = fx * t7 * cph; JK[7] = fx * t9 * cph;
+      JK[8] = 0.0; JK[9] = r * sph; JK[10] = 0.0; JK[11] = 1.0;
+      JK[12] = fy * t3 * sph; JK[13] = fy * t5 * sph; JK[14] = fy * t7 * sph; JK[15] = fy * t9 * sph;
+    } else {
+      const double iz = 1.0 / P[2];
+      JP[0] = fx * iz; JP[1] = 0.0; JP[2] = 0.0;
+      JP[3] = 0.0; JP[4] = fy * iz; JP[5] = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) JK[i] = 0.0;
+      JK[2] = 1.0;
+      JK[11] = 1.0;
+    }
+  }
+}
+
+// The two residuals of board point (X, Y, 0) against pixel (u, v) at (R, t), scaled by inv_s, their Jacobians over the image's
+// tangent (J[6 i + a]) and over the intrinsics (JK[8 i + q]); false when the point is not in front of the camera.
+CLC_HD bool corner_terms(const clc_camera& c, const double* R, const double* t, double X, double Y, double u, double v, double inv_s,
+                         double* r, double* J, double* JK) {
+  CLC_BF_NO_CONTRACT
+  const double P[3] = {(R[0] * X + R[1] * Y) + t[0], (R[3] * X + R[4] * Y) + t[1], (R[6] * X + R[7] * Y) + t[2]};
+  double px[2], JP[6];
+  cp::cam_project(c, P, px);
+  project_jacobian(c, P, JP, JK);
+  r[0] = (px[0] - u) * inv_s;
+  r[1] = (px[1] - v) * inv_s;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const double a0 = JP[3 * i] * inv_s, a1 = JP[3 * i + 1] * inv_s, a2 = JP[3 * i + 2] * inv_s;
+    // dP/dt = I, dP/dtheta = -R [X]x
+    const double B0 = (a0 * R[0] + a1 * R[3]) + a2 * R[6];
+    const double B1 = (a0 * R[1] + a1 * R[4]) + a2 * R[7];
+    const double B2 = (a0 * R[2] + a1 * R[5]) + a2 * R[8];
+    J[6 * i] = a0; J[6 * i + 1] = a1; J[6 * i + 2] = a2;
+    J[6 * i + 3] = B2 * Y;
+    J[6 * i + 4] = -(B2 * X);
+    J[6 * i + 5] = B1 * X - B0 * Y;
+#pragma unroll
+    for (int q = 0; q < NK; ++q) JK[8 * i + q] *= inv_s;
+  }
+  return P[2] > 0.0;
+}
+
+// One image's evaluation record at pose7 under camera c: every lane of the image's wave calls it (host: once); the lead lane stores.
+CLC_HD void eval_image(const CalArgs& a, const clc_camera& c, long long img, const double* pose7, double* E) {
+  CLC_BF_NO_CONTRACT
+  double xe[7], R[9];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) xe[i] = pose7[i];
+  quat_to_rot(xe + 3, R);
+  const long long cb = a.coff[img], n = a.coff[img + 1] - cb;
+  const float* __restrict__ px = a.corners + 2 * cb;
+  const float* __restrict__ board = a.board + 2 * cb;
+  const double inv_s = 1.0 / a.sigma_px;
+  {  // A_i, g_i, sum r^2
+    double s[28];
+    cp::wave_sum<28>([&](int lane, double* acc) {
+      for (long long k = lane; k < n; k += cp::POSE_LANES) {
+        double r[2], J[12], JK[16];
+        const bool front = corner_terms(c, R, xe, board[2 * k], board[2 * k + 1], px[2 * k], px[2 * k + 1], inv_s, r, J, JK);
+        int idx = 0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+          for (int q = p; q < 6; ++q) {
+            acc[idx] = fma(J[p], J[q], acc[idx]);
+            acc[idx] = fma(J[6 + p], J[6 + q], acc[idx]);
+            ++idx;
+          }
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+          acc[21 + p] = fma(J[p], r[0], acc[21 + p]);
+          acc[21 + p] = fma(J[6 + p], r[1], acc[21 + p]);
+        }
+        acc[27] = fma(r[0], r[0], acc[27]);
+        acc[27] = fma(r[1], r[1], acc[27]);
+        if (!front) acc[27] += __builtin_inf();  // an invalid evaluation, as reproj_accumulate's
+      }
+    }, s);
+    if (bf::lead_lane()) {
+#pragma unroll
+      for (int i = 0; i < 21; ++i) E[E_A + i] = s[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) E[E_G + i] = s[21 + i];
+      E[E_COST] = 0.5 * s[27];
+    }
+  }
+  {  // B_i[:, 0:4], g_c
+    double s[32];
+    cp::wave_sum<32>([&](int lane, double* acc) {
+      for (long long k = lane; k < n; k += cp::POSE_LANES) {
+        double r[2], J[12], JK[16];
+        corner_terms(c, R, xe, board[2 * k], board[2 * k + 1], px[2 * k], px[2 * k + 1], inv_s, r, J, JK);
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            acc[4 * p + q] = fma(J[p], JK[q], acc[4 * p + q]);
+            acc[4 * p + q] = fma(J[6 + p], JK[8 + q], acc[4 * p + q]);
+          }
+#pragma unroll
+        for (int q = 0; q < NK; ++q) {
+          acc[24 + q] = fma(JK[q], r[0], acc[24 + q]);
+          acc[24 + q] = fma(JK[8 + q], r[1], acc[24 + q]);
+        }
+      }
+    }, s);
+    if (bf::lead_lane()) {
+#pragma unroll
+      for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) E[E_B + 8 * p + q] = s[4 * p + q];
+#pragma unroll
+      for (int q = 0; q < NK; ++q) E[E_GC + q] = s[24 + q];
+    }
+  }
+  {  // B_i[:, 4:8]
+    double s[24];
+    cp::wave_sum<24>([&](int lane, double* acc) {
+      for (long long k = lane; k < n; k += cp::POSE_LANES) {
+        double r[2], J[12], JK[16];
+        corner_terms(c, R, xe, board[2 * k], board[2 * k + 1], px[2 * k], px[2 * k + 1], inv_s, r, J, JK);
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            acc[4 * p + q] = fma(J[p], JK[4 + q], acc[4 * p + q]);
+            acc[4 * p + q] = fma(J[6 + p], JK[12 + q], acc[4 * p + q]);
+          }
+      }
+    }, s);
+    if (bf::lead_lane()) {
+#pragma unroll
+      for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) E[E_B + 8 * p + 4 + q] = s[4 * p + q];
+    }
+  }
+  {  // the image's share of C
+    double s[36];
+    cp::wave_sum<36>([&](int lane, double* acc) {
+      for (long long k = lane; k < n; k += cp::POSE_LANES) {
+        double r[2], J[12], JK[16];
+        corner_terms(c, R, xe, board[2 * k], board[2 * k + 1], px[2 * k], px[2 * k + 1], inv_s, r, J, JK);
+        int idx = 0;
+#pragma unroll
+        for (int p = 0; p < NK; ++p)
+#pragma unroll
+          for (int q = p; q < NK; ++q) {
+            acc[idx] = fma(JK[p], JK[q], acc[idx]);
+            acc[idx] = fma(JK[8 + p], JK[8 + q], acc[idx]);
+            ++idx;
+          }
+      }
+    }, s);
+    if (bf::lead_lane()) {
+#pragma unroll
+      for (int i = 0; i < 36; ++i) E[E_C + i] = s[i];
+    }
+  }
+}
+
+// Y = M^-1 B (6x8) and S = B^T Y (tri<8> order) of one image, from im.L.
+CLC_HD void schur_share(CalImage& im, const double* B) {
+  CLC_JT_ROLLED for (int b = 0; b < NK; ++b) jt::chol_apply6(im.L, B + b, NK, im.Y + b, NK, im.z);
+  int idx = 0;
+  CLC_JT_ROLLED for (int p = 0; p < NK; ++p)
+    CLC_JT_ROLLED for (int q = p; q < NK; ++q) {
+      double s = 0.0;
+      CLC_JT_ROLLED for (int k = 0; k < 6; ++k) s += B[NK * k + p] * im.Y[NK * k + q];
+      im.Ss[idx++] = s;
+    }
+}
+
+struct Problem {
+  long long i0, P;  // first image (absolute), images
+  CalImage* ws;     // image i0 first
+};
+
+// Adds the images' shares in image order: sh.red (sums of 0..3, maxima of 4..5).
+CLC_HD void reduce_red(const Problem& pr, CalShared& sh) {
+  each_lane(6, [&](int k) {
+    double s = 0.0;
+    for (long long j = 0; j < pr.P; ++j) {
+      const CalImage& im = pr.ws[j];
+      if (im.st != CLC_CAMCAL_OK) continue;
+      s = k < 4 ? s + im.red[k] : fmax(s, im.red[k]);
+    }
+    sh.red[k] = s;
+  });
+}
+
+CLC_HD void camera_of(const CalShared& sh, const double* k, clc_camera& c) {
+  c.model = sh.model;
+  c.reserved = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { c.proj[i] = k[i]; c.dist[i] = k[4 + i]; }
+}
+
+// Evaluates every participating image at its xe under the intrinsics sh.kce into record `set`; the totals into sh.tot[set].
+CLC_HD void evaluate(const CalArgs& a, const Problem& pr, CalShared& sh, int set) {
+  clc_camera c;
+  camera_of(sh, sh.kce, c);
+  each_image_wave(pr.P, [&](long long j) {
+    CalImage& im = pr.ws[j];
+    if (im.st != CLC_CAMCAL_OK) return;
+    eval_image(a, c, pr.i0 + j, im.xe, im.E[set]);
+  });
+  wg_barrier();
+  each_lane(TOTAL_DOUBLES, [&](int k) {
+    double s = 0.0;
+    for (long long j = 0; j < pr.P; ++j) {
+      const CalImage& im = pr.ws[j];
+      if (im.st != CLC_CAMCAL_OK) continue;
+      s += im.E[set][E_C + k];
+    }
+    sh.tot[set][k] = s;
+  });
+  wg_barrier();
+}
+
+// The gradient max norm over the moving blocks at the accepted point (record sh.cur) -> sh.gmax.
+CLC_HD void gradient_norm(const Problem& pr, CalShared& sh) {
+  each_image(pr.P, [&](long long j) {
+    CalImage& im = pr.ws[j];
+    if (im.st != CLC_CAMCAL_OK) return;
+    im.red[4] = sh.move_i ? jt::block_gradient_norm(im.x, im.E[sh.cur] + E_G) : 0.0;
+    im.red[5] = 0.0;
+  });
+  wg_barrier();
+  reduce_red(pr, sh);
+  wg_barrier();
+  if (wg_lead()) {
+    double m = sh.red[4];
+    CLC_JT_ROLLED for (int f = 0; f < sh.n_free; ++f) m = fmax(m, fabs(sh.tot[sh.cur][(E_GC - E_C) + sh.free_idx[f]]));
+    sh.gmax = m;
+  }
+  wg_barrier();
+}
+
+// The reduced system sh.A / sh.rhs without the rows and columns of the held intrinsics, solved: sh.yf[0..N).
+template <int N>
+CLC_HD bool solve_free(CalShared& sh) {
+  CLC_JT_ROLLED for (int p = 0; p < N; ++p) {
+    CLC_JT_ROLLED for (int q = 0; q < N; ++q) sh.Af[N * p + q] = sh.A[NK * sh.free_idx[p] + sh.free_idx[q]];
+    sh.rf[p] = sh.rhs[sh.free_idx[p]];
+  }
+  return chol_solve<N>(sh.Af, sh.rf, sh.yf, sh.L, sh.z);
+}
+
+// The trust-region step at the accepted point for sh.radius: every image's xe and sh.kce become the candidate, sh.step_ok says
+// whether it is valid (LevenbergMarquardtStrategy::ComputeStep + the model-cost test, over the arrow).
+CLC_HD void compute_step(const CalArgs& a, const Problem& pr, CalShared& sh) {
+  const clc_options& o = a.opt;
+  const double inv_radius = rcp_pos(sh.radius);
+  const int reuse = sh.reuse_diagonal, cur = sh.cur;
+  if (sh.move_i) {
+    each_image(pr.P, [&](long long j) {
+      CalImage& im = pr.ws[j];
+      if (im.st != CLC_CAMCAL_OK) return;
+      const double* E = im.E[cur];
+      int idx = 0;
+      CLC_JT_ROLLED for (int p = 0; p < 6; ++p)
+        CLC_JT_ROLLED for (int q = p; q < 6; ++q) {
+          const double v = E[E_A + idx++] * (im.scale[p] * im.scale[q]);
+          im.As[6 * p + q] = v;
+          im.As[6 * q + p] = v;
+        }
+      if (!reuse) {
+        CLC_JT_ROLLED for (int c = 0; c < 6; ++c) {
+          double d = im.As[7 * c];
+          d = d > o.min_lm_diagonal ? d : o.min_lm_diagonal;
+          d = d < o.max_lm_diagonal ? d : o.max_lm_diagonal;
+          im.diag[c] = d;
+        }
+      }
+      CLC_JT_ROLLED for (int i = 0; i < 36; ++i) im.Md[i] = im.As[i];
+      CLC_JT_ROLLED for (int c = 0; c < 6; ++c) im.Md[7 * c] += im.diag[c] * inv_radius;
+      CLC_JT_ROLLED for (int p = 0; p < 6; ++p) im.gs[p] = E[E_G + p] * im.scale[p];
+      CLC_JT_ROLLED for (int p = 0; p < 6; ++p)
+        CLC_JT_ROLLED for (int q = 0; q < NK; ++q) im.Bs[NK * p + q] = E[E_B + NK * p + q] * (im.scale[p] * sh.scale_c[q]);
+      im.red[5] = 0.0;
+      CLC_JT_ROLLED for (int i = 0; i < SS_DOUBLES; ++i) im.Ss[i] = 0.0;
+      if (!jt::chol_factor6(im.Md, im.L)) { im.red[5] = 1.0; return; }
+      jt::chol_apply6(im.L, im.gs, 1, im.yg, 1, im.z);
+      if (sh.move_c) {
+        schur_share(im, im.Bs);
+        CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
+          double s = 0.0;
+          CLC_JT_ROLLED for (int k = 0; k < 6; ++k) s += im.Bs[NK * k + p] * im.yg[k];
+          im.Ss[36 + p] = s;
+        }
+      }
+    });
+    wg_barrier();
+    each_lane(SS_DOUBLES, [&](int k) {
+      double s = 0.0;
+      for (long long j = 0; j < pr.P; ++j) {
+        const CalImage& im = pr.ws[j];
+        if (im.st != CLC_CAMCAL_OK) continue;
+        s += im.Ss[k];
+      }
+      sh.Ss[k] = s;
+    });
+    wg_barrier();
+  }
+  // ---- the reduced system, thread 0 ----
+  if (wg_lead()) {
+    bool ok = true;
+    const double* T = sh.tot[cur];
+    int idx = 0;
+    CLC_JT_ROLLED for (int p = 0; p < NK; ++p)
+      CLC_JT_ROLLED for (int q = p; q < NK; ++q) {
+        const double v = T[idx++] * (sh.scale_c[p] * sh.scale_c[q]);
+        sh.Hs[NK * p + q] = v;
+        sh.Hs[NK * q + p] = v;
+      }
+    CLC_JT_ROLLED for (int p = 0; p < NK; ++p) { sh.step_c[p] = 0.0; sh.gs_c[p] = sh.rhs[p] = T[(E_GC - E_C) + p] * sh.scale_c[p]; }
+    if (sh.move_c) {
+      if (!reuse) {
+        CLC_JT_ROLLED for (int c = 0; c < NK; ++c) {
+          double d = sh.Hs[(NK + 1) * c];
+          d = d > o.min_lm_diagonal ? d : o.min_lm_diagonal;
+          d = d < o.max_lm_diagonal ? d : o.max_lm_diagonal;
+          sh.diag_c[c] = d;
+        }
+      }
+      CLC_JT_ROLLED for (int i = 0; i < 64; ++i) sh.A[i] = sh.Hs[i];
+      CLC_JT_ROLLED for (int c = 0; c < NK; ++c) sh.A[(NK + 1) * c] += sh.diag_c[c] * inv_radius;
+      if (sh.move_i) {
+        CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
+          CLC_JT_ROLLED for (int q = 0; q < NK; ++q) sh.A[NK * p + q] -= sh.Ss[p <= q ? tri<NK>(p, q) : tri<NK>(q, p)];
+          sh.rhs[p] -= sh.Ss[36 + p];
+        }
+      }
+      // held intrinsics lose their rows and columns: chol_solve at the number of free ones
+      switch (sh.n_free) {
+        case 1: ok = solve_free<1>(sh); break;
+        case 2: ok = solve_free<2>(sh); break;
+        case 3: ok = solve_free<3>(sh); break;
+        case 4: ok = solve_free<4>(sh); break;
+        case 5: ok = solve_free<5>(sh); break;
+        case 6: ok = solve_free<6>(sh); break;
+        case 7: ok = solve_free<7>(sh); break;
+        default: ok = solve_free<8>(sh); break;
+      }
+      CLC_JT_ROLLED for (int f = 0; f < sh.n_free; ++f) {
+        sh.step_c[sh.free_idx[f]] = -sh.yf[f];
+        if (!finite_d(sh.yf[f])) ok = false;
+      }
+    }
+    sh.step_ok = ok ? 1 : 0;
+  }
+  wg_barrier();
+  // ---- back-substitution and the candidates ----
+  each_image(pr.P, [&](long long j) {
+    CalImage& im = pr.ws[j];
+    if (im.st != CLC_CAMCAL_OK) return;
+    im.red[0] = im.red[1] = im.red[2] = im.red[3] = 0.0;
+    if (!sh.move_i || im.red[5] != 0.0 || !sh.step_ok) return;
+    bool fin = true;
+    CLC_JT_ROLLED for (int p = 0; p < 6; ++p) {
+      double s = im.yg[p];
+      if (sh.move_c) CLC_JT_ROLLED for (int q = 0; q < NK; ++q) s += im.Y[NK * p + q] * sh.step_c[q];
+      im.step[p] = -s;
+      fin = fin && finite_d(s);
+    }
+    if (!fin) { im.red[5] = 1.0; return; }
+    double sg = 0.0, shs = 0.0;
+    CLC_JT_ROLLED for (int p = 0; p < 6; ++p) {
+      sg += im.step[p] * im.gs[p];
+      double row = 0.0;
+      CLC_JT_ROLLED for (int q = 0; q < 6; ++q) row += im.As[6 * p + q] * im.step[q];
+      if (sh.move_c) CLC_JT_ROLLED for (int q = 0; q < NK; ++q) row += 2.0 * (im.Bs[NK * p + q] * sh.step_c[q]);
+      shs += im.step[p] * row;
+    }
+    im.red[0] = sg;
+    im.red[1] = shs;
+    double n2;
+    im.red[2] = jt::block_candidate(im.x, im.step, im.scale, im.xe, &n2);
+    im.red[3] = n2;
+  });
+  wg_barrier();
+  reduce_red(pr, sh);
+  wg_barrier();
+  if (wg_lead()) {
+    bool ok = sh.step_ok && sh.red[5] == 0.0;
+    double sg = sh.red[0], shs = sh.red[1], sn = sh.red[2], xn = sh.red[3];
+    if (sh.move_c) {
+      CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
+        sg += sh.step_c[p] * sh.gs_c[p];
+        double row = 0.0;
+        CLC_JT_ROLLED for (int q = 0; q < NK; ++q) row += sh.Hs[NK * p + q] * sh.step_c[q];
+        shs += sh.step_c[p] * row;
+      }
+      CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
+        // a held intrinsic (scale 0, step 0) keeps its bits
+        const double d = sh.step_c[p] * sh.scale_c[p];
+        const double v = sh.scale_c[p] != 0.0 ? sh.kc[p] + d : sh.kc[p];
+        sh.kce[p] = v;
+        sn += (sh.kc[p] - v) * (sh.kc[p] - v);
+        xn += v * v;
+      }
+    }
+    sh.model_cost_change = -(sg + 0.5 * shs);
+    sh.red[2] = sn;
+    sh.red[3] = xn;
+    sh.reuse_diagonal = 1;
+    sh.step_ok = (ok && sh.model_cost_change > 0.0) ? 1 : 0;
+  }
+  wg_barrier();
+}
+
+// H_cam = C - sum B_i^T A_i^-1 B_i at the accepted point (undamped, unscaled), rows and columns of held intrinsics zero; with the
+// board poses held, C itself; NaN where an A_i is not positive definite.
+CLC_HD void marginal_information(const CalArgs& a, const Problem& pr, CalShared& sh, double* H) {
+  const int cur = sh.cur;
+  if (sh.move_i) {
+    each_image(pr.P, [&](long long j) {
+      CalImage& im = pr.ws[j];
+      if (im.st != CLC_CAMCAL_OK) return;
+      const double* E = im.E[cur];
+      int idx = 0;
+      CLC_JT_ROLLED for (int p = 0; p < 6; ++p)
+        CLC_JT_ROLLED for (int q = p; q < 6; ++q) {
+          const double v = E[E_A + idx++];
+          im.Md[6 * p + q] = v;
+          im.Md[6 * q + p] = v;
+        }
+      im.red[5] = 0.0;
+      CLC_JT_ROLLED for (int i = 0; i < SS_DOUBLES; ++i) im.Ss[i] = 0.0;
+      if (!jt::chol_factor6(im.Md, im.L)) { im.red[5] = 1.0; return; }
+      schur_share(im, E + E_B);
+    });
+    wg_barrier();
+    each_lane(37, [&](int k) {
+      double s = 0.0;
+      for (long long j = 0; j < pr.P; ++j) {
+        const CalImage& im = pr.ws[j];
+        if (im.st != CLC_CAMCAL_OK) continue;
+        s = k < 36 ? s + im.Ss[k] : fmax(s, im.red[5]);
+      }
+      sh.Ss[k] = s;
+    });
+    wg_barrier();
+  }
+  if (wg_lead()) {
+    const bool bad = sh.move_i && sh.Ss[36] != 0.0;
+    CLC_JT_ROLLED for (int p = 0; p < NK; ++p)
+      CLC_JT_ROLLED for (int q = 0; q < NK; ++q) {
+        const int k = p <= q ? tri<NK>(p, q) : tri<NK>(q, p);
+        const bool held = ((a.hold_mask >> p) & 1u) || ((a.hold_mask >> q) & 1u);
+        H[NK * p + q] = held ? 0.0 : bad ? __builtin_nan("") : sh.tot[cur][k] - (sh.move_i ? sh.Ss[k] : 0.0);
+      }
+  }
+  wg_barrier();
+}
+
+// Why an image takes no part (wave-uniform; every lane of the image's wave calls it).
+CLC_HD int image_status(const CalArgs& a, long long img) {
+  if (a.keep && !a.keep[img]) return CLC_CAMCAL_NOT_KEPT;
+  const long long cb = a.coff[img], n = a.coff[img + 1] - cb;
+  if (n < 4) return CLC_CAMCAL_TOO_FEW;
+  if (cb < 0) return CLC_CAMCAL_NONFINITE;
+  const float* px = a.corners + 2 * cb;
+  const float* board = a.board + 2 * cb;
+  double bad[1];
+  cp::wave_sum<1>([&](int lane, double* acc) {
+    for (long long k = lane; k < n; k += cp::POSE_LANES)
+      if (!(isfinite(px[2 * k]) && isfinite(px[2 * k + 1]) && isfinite(board[2 * k]) && isfinite(board[2 * k + 1]))) acc[0] += 1.0;
+    if (lane < 4 && !finite_d(a.q[4 * img + lane])) acc[0] += 1.0;
+    if (lane < 3 && !finite_d(a.t[3 * img + lane])) acc[0] += 1.0;
+  }, bad);
+  if (bad[0] != 0.0) return CLC_CAMCAL_NONFINITE;
+  const double w = a.q[4 * img], x = a.q[4 * img + 1], y = a.q[4 * img + 2], z = a.q[4 * img + 3];
+  if (!((w * w + x * x) + (y * y + z * z) > 0.0)) return CLC_CAMCAL_NONFINITE;
+  return CLC_CAMCAL_OK;
+}
+
+// One problem: every thread of its workgroup calls it (host: once).
+CLC_HD void camcal_problem(const CalArgs& a, long long pb, CalShared& sh) {
+  const clc_options& o = a.opt;
+  Problem pr;
+  {
+    const long long first = a.prob_off ? a.prob_off[0] : 0;
+    long long i0 = a.prob_off ? a.prob_off[pb] : 0, i1 = a.prob_off ? a.prob_off[pb + 1] : a.n_images;
+    if (i0 < first) i0 = first;
+    if (i1 > first + a.n_images) i1 = first + a.n_images;
+    pr.i0 = i0;
+    pr.P = i1 > i0 ? i1 - i0 : 0;
+    pr.ws = a.ws + (i0 - first);
+  }
+  // ---- which images take part; their start poses ----
+  each_image_wave(pr.P, [&](long long j) {
+    const long long img = pr.i0 + j;
+    const int st = image_status(a, img);
+    if (bf::lead_lane()) {
+      CalImage& im = pr.ws[j];
+      im.st = st;
+      a.status[img] = st;
+      if (st == CLC_CAMCAL_OK) {
+        const double w = a.q[4 * img], x = a.q[4 * img + 1], y = a.q[4 * img + 2], z = a.q[4 * img + 3];
+        const double inv = 1.0 / sqrt((w * w + x * x) + (y * y + z * z));
+        const double p7[7] = {a.t[3 * img], a.t[3 * img + 1], a.t[3 * img + 2], x * inv, y * inv, z * inv, w * inv};
+#pragma unroll
+        for (int i = 0; i < 7; ++i) im.x[i] = im.xe[i] = p7[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { im.scale[i] = 1.0; im.diag[i] = 0.0; im.red[i] = 0.0; }
+      }
+    }
+  });
+  wg_barrier();
+  if (wg_lead()) {
+    int n_part = 0;
+    long long n_corners = 0;
+    double xn = 0.0;
+    for (long long j = 0; j < pr.P; ++j) {
+      if (pr.ws[j].st != CLC_CAMCAL_OK) continue;
+      ++n_part;
+      n_corners += a.coff[pr.i0 + j + 1] - a.coff[pr.i0 + j];
+    }
+    const clc_camera& cam = a.cams[pb];
+    bool ok = n_part > 0 && (cam.model == CLC_CAMERA_PINHOLE || cam.model == CLC_CAMERA_KANNALA_BRANDT);
+    CLC_JT_ROLLED for (int i = 0; i < 4; ++i) {
+      sh.kc[i] = sh.kce[i] = cam.proj[i];
+      sh.kc[4 + i] = sh.kce[4 + i] = cam.dist[i];
+      ok = ok && finite_d(cam.proj[i]) && finite_d(cam.dist[i]);
+    }
+    sh.model = cam.model;
+    int nf = 0;
+    CLC_JT_ROLLED for (int i = 0; i < NK; ++i) {
+      sh.free_idx[i] = 0;
+      if (!((a.hold_mask >> i) & 1u)) sh.free_idx[nf++] = i;
+    }
+    sh.n_free = nf;
+    sh.n_part = n_part;
+    sh.n_corners = n_corners;
+    sh.move_i = a.hold_board_poses ? 0 : 1;
+    sh.move_c = nf > 0 ? 1 : 0;
+    if (sh.move_i)
+      for (long long j = 0; j < pr.P; ++j) {
+        if (pr.ws[j].st != CLC_CAMCAL_OK) continue;
+        CLC_JT_ROLLED for (int i = 0; i < 7; ++i) xn += pr.ws[j].x[i] * pr.ws[j].x[i];
+      }
+    if (sh.move_c) CLC_JT_ROLLED for (int i = 0; i < NK; ++i) xn += sh.kc[i] * sh.kc[i];
+    sh.x_norm = sqrt_pos(xn);
+    sh.status = ok ? CLC_RUNNING : CLC_FAILURE;
+    sh.n_invalid = 0; sh.reuse_diagonal = 0; sh.num_successful = 0; sh.num_unsuccessful = 0; sh.n_trace = 0; sh.n_evals = 0;
+    sh.cur = 0; sh.step_ok = 0;
+    sh.x_cost = 0.0; sh.initial_cost = 0.0; sh.min_iter_cost = 0.0;
+    sh.radius = o.initial_trust_region_radius; sh.decrease_factor = 2.0; sh.model_cost_change = 0.0; sh.gmax = 0.0;
+    CLC_JT_ROLLED for (int i = 0; i < NK; ++i) {
+      sh.scale_c[i] = ((a.hold_mask >> i) & 1u) ? 0.0 : 1.0;
+      sh.diag_c[i] = 0.0;
+      sh.step_c[i] = 0.0;
+    }
+    CLC_JT_ROLLED for (int i = 0; i < TOTAL_DOUBLES; ++i) sh.tot[0][i] = sh.tot[1][i] = 0.0;
+    sh.it_iteration = 0; sh.it_successful = 1; sh.it_cost = 0.0; sh.it_gmax = 0.0;
+  }
+  wg_barrier();
+  if (sh.status == CLC_RUNNING) {
+    // ---- IterationZero ----
+    evaluate(a, pr, sh, 0);
+    if (wg_lead()) {
+      sh.n_evals = 1;
+      const double cost = sh.tot[0][E_COST - E_C];
+      if (!finite_d(cost)) sh.status = CLC_FAILURE;
+      sh.x_cost = sh.initial_cost = sh.min_iter_cost = cost;
+      if (o.jacobi_scaling)
+        CLC_JT_ROLLED for (int c = 0; c < NK; ++c)
+          if (sh.scale_c[c] != 0.0) sh.scale_c[c] = 1.0 / (1.0 + sqrt(sh.tot[0][tri<NK>(c, c)]));
+    }
+    if (o.jacobi_scaling)
+      each_image(pr.P, [&](long long j) {
+        CalImage& im = pr.ws[j];
+        if (im.st != CLC_CAMCAL_OK) return;
+        CLC_JT_ROLLED for (int c = 0; c < 6; ++c) im.scale[c] = 1.0 / (1.0 + sqrt(im.E[0][E_A + tri<6>(c, c)]));
+      });
+    wg_barrier();
+  }
+  if (sh.status == CLC_RUNNING) {
+    gradient_norm(pr, sh);
+    if (wg_lead()) { sh.it_cost = sh.x_cost; sh.it_gmax = sh.gmax; }
+    wg_barrier();
+  }
+  // ---- TrustRegionMinimizer::Minimize, as joint_problem (clc_joint.hpp): the same barrier rule for every word of `sh` that thread 0
+  // writes and the others read ----
+  while (sh.status == CLC_RUNNING) {
+    for (;;) {
+      wg_barrier();  // every thread has read sh.status (the loop conditions above and below) before thread 0 may change it
+      if (wg_lead()) {
+        // FinalizeIterationAndCheckIfMinimizerCanContinue
+        if (sh.it_successful) sh.num_successful++; else sh.num_unsuccessful++;
+        sh.n_trace++;
+        sh.min_iter_cost = sh.it_cost < sh.min_iter_cost ? sh.it_cost : sh.min_iter_cost;
+        if (sh.it_iteration >= o.max_num_iterations) sh.status = CLC_NO_CONVERGENCE;
+        else if (sh.it_successful && sh.it_gmax <= o.gradient_tolerance) sh.status = CLC_CONVERGENCE_GRADIENT;
+        else if (sh.radius <= o.min_trust_region_radius) sh.status = CLC_CONVERGENCE_RADIUS;
+        sh.it_iteration++;
+        sh.it_successful = 0;
+      }
+      wg_barrier();
+      if (sh.status != CLC_RUNNING) break;
+      compute_step(a, pr, sh);
+      if (sh.step_ok) {
+        if (wg_lead()) sh.n_invalid = 0;
+        wg_barrier();
+        break;
+      }
+      wg_barrier();  // (every thread has read step_ok)
+      if (wg_lead()) {
+        // HandleInvalidStep
+        if (++sh.n_invalid >= o.max_num_consecutive_invalid_steps) sh.status = CLC_FAILURE;
+        sh.radius = sh.radius / sh.decrease_factor;
+        sh.decrease_factor *= 2.0;
+        sh.reuse_diagonal = 1;
+        sh.it_cost = sh.x_cost;
+        sh.it_gmax = sh.gmax;
+      }
+      wg_barrier();
+      if (sh.status != CLC_RUNNING) break;
+    }
+    if (sh.status != CLC_RUNNING) break;
+    // ---- the candidate ----
+    evaluate(a, pr, sh, 1 - sh.cur);
+    if (wg_lead()) {
+      sh.n_evals++;
+      const double cost_e = sh.tot[1 - sh.cur][E_COST - E_C];
+      const double candidate_cost = finite_d(cost_e) ? cost_e : 1.7976931348623157e308;
+      const double step_norm = sqrt_pos(sh.red[2]);
+      const double cost_change = sh.x_cost - candidate_cost;
+      sh.step_ok = 0;  // from here: 1 = accepted
+      if (step_norm <= o.parameter_tolerance * (sh.x_norm + o.parameter_tolerance)) {
+        sh.status = CLC_CONVERGENCE_PARAMETER;
+      } else if (fabs(cost_change) <= o.function_tolerance * sh.x_cost) {
+        sh.status = CLC_CONVERGENCE_FUNCTION;
+      } else {
+        const double relative_decrease = cost_change * rcp_pos_safe(sh.model_cost_change);
+        if (relative_decrease > o.min_relative_decrease) {
+          // HandleSuccessfulStep
+          sh.step_ok = 1;
+          sh.x_norm = sqrt_pos(sh.red[3]);
+          sh.x_cost = candidate_cost;
+          const double q = 2.0 * relative_decrease - 1.0;
+          double den = 1.0 - q * q * q;
+          den = den > (1.0 / 3.0) ? den : (1.0 / 3.0);
+          sh.radius = sh.radius * rcp_pos(den);
+          sh.radius = sh.radius < o.max_trust_region_radius ? sh.radius : o.max_trust_region_radius;
+          sh.decrease_factor = 2.0;
+          sh.reuse_diagonal = 0;
+          sh.it_successful = 1;
+          sh.it_cost = candidate_cost;
+        } else {
+          // HandleUnsuccessfulStep
+          sh.radius = sh.radius / sh.decrease_factor;
+          sh.decrease_factor *= 2.0;
+          sh.reuse_diagonal = 1;
+          sh.it_cost = candidate_cost;
+          sh.it_gmax = sh.gmax;
+        }
+      }
+    }
+    wg_barrier();
+    if (sh.status != CLC_RUNNING) break;
+    if (sh.step_ok) {
+      if (sh.move_i)
+        each_image(pr.P, [&](long long j) {
+          CalImage& im = pr.ws[j];
+          if (im.st != CLC_CAMCAL_OK) return;
+#pragma unroll
+          for (int i = 0; i < 7; ++i) im.x[i] = im.xe[i];
+        });
+      wg_barrier();  // (every thread has read step_ok and cur)
+      if (wg_lead()) {
+        sh.cur = 1 - sh.cur;
+        CLC_JT_ROLLED for (int i = 0; i < NK; ++i) sh.kc[i] = sh.kce[i];
+      }
+      wg_barrier();
+      gradient_norm(pr, sh);
+      if (wg_lead()) sh.it_gmax = sh.gmax;
+      wg_barrier();
+    } else {
+      wg_barrier();
+    }
+  }
+  // ---- the outputs: a candidate that was not accepted leaves no trace ----
+  wg_barrier();
+  const bool failed = sh.status == CLC_FAILURE;
+  if (!failed && sh.move_i)
+    each_image(pr.P, [&](long long j) {
+      const CalImage& im = pr.ws[j];
+      if (im.st != CLC_CAMCAL_OK) return;
+      const long long img = pr.i0 + j;
+      const double sgn = im.x[6] < 0.0 ? -1.0 : 1.0;
+      a.q[4 * img] = sgn * im.x[6];
+      a.q[4 * img + 1] = sgn * im.x[3];
+      a.q[4 * img + 2] = sgn * im.x[4];
+      a.q[4 * img + 3] = sgn * im.x[5];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) a.t[3 * img + i] = im.x[i];
+    });
+  if (wg_lead()) {
+    clc_summary sm;
+    cp::summary_empty(sm);
+    sm.termination = sh.status;
+    if (sh.n_evals > 0) {
+      sm.num_iterations = sh.n_trace > 0 ? sh.n_trace - 1 : 0;
+      sm.num_successful_steps = sh.num_successful;
+      sm.num_unsuccessful_steps = sh.num_unsuccessful;
+      sm.num_evaluations = sh.n_evals;
+      sm.initial_cost = sh.initial_cost;
+      sm.final_cost = sh.x_cost;
+    }
+    a.summaries[pb] = sm;
+    if (!failed && sh.move_c)
+      CLC_JT_ROLLED for (int f = 0; f < sh.n_free; ++f) {
+        const int i = sh.free_idx[f];
+        if (i < 4) a.cams[pb].proj[i] = sh.kc[i]; else a.cams[pb].dist[i - 4] = sh.kc[i];
+      }
+    if (a.rms) {
+      const bool have = sh.n_evals > 0 && !failed && sh.n_corners > 0;
+      a.rms[pb] = have ? a.sigma_px * sqrt(2.0 * sh.x_cost / (double)sh.n_corners) : __builtin_nan("");
+    }
+  }
+  if (a.H_cam) {
+    if (!failed && sh.n_evals > 0) {
+      marginal_information(a, pr, sh, a.H_cam + 64 * pb);
+    } else if (wg_lead()) {
+      CLC_JT_ROLLED for (int i = 0; i < 64; ++i) a.H_cam[64 * pb + i] = __builtin_nan("");
+    }
+  }
+}
+
+// ---- the closed-form focal start ---------------------------------------------------------------------------------------------
+struct GuessShared {
+  double acc45[45];
+};
+
+// The homography board (X, Y, 1) -> pixel - (cx0, cy0) of one image, unit Frobenius norm: H[9] row-major.  Every lane calls it
+// (device: the image's wave; host: once).  Returns a CLC_POSE_* status (wave-uniform).  board_pose_image's DLT on pixels.
+CLC_HD int homography_image(const float* __restrict__ px, const float* __restrict__ board, long long n, double cx0, double cy0,
+                            GuessShared& sh, double* H) {
+  CLC_BF_NO_CONTRACT
+  if (n < 4) return CLC_POSE_TOO_FEW;
+  double m[9];
+  cp::wave_sum<9>([&](int lane, double* a) {
+    for (long long k = lane; k < n; k += cp::POSE_LANES) {
+      const double x = (double)px[2 * k] - cx0, y = (double)px[2 * k + 1] - cy0, X = board[2 * k], Y = board[2 * k + 1];
+      if (!(isfinite(x) && isfinite(y) && isfinite(X) && isfinite(Y))) { a[8] += 1.0; continue; }
+      a[0] += x; a[1] += y; a[2] = fma(x, x, a[2]); a[3] = fma(y, y, a[3]);
+      a[4] += X; a[5] += Y; a[6] = fma(X, X, a[6]); a[7] = fma(Y, Y, a[7]);
+    }
+  }, m);
+  if (m[8] != 0.0) return CLC_POSE_NONFINITE;
+  const double inv_n = 1.0 / (double)n;
+  const double cx = m[0] * inv_n, cy = m[1] * inv_n, cX = m[4] * inv_n, cY = m[5] * inv_n;
+  const double var_i = (m[2] + m[3]) * inv_n - (cx * cx + cy * cy), var_b = (m[6] + m[7]) * inv_n - (cX * cX + cY * cY);
+  if (!(var_i > 0.0 && var_b > 0.0)) return CLC_POSE_DEGENERATE;
+  const double si = sqrt(2.0 / var_i), sb = sqrt(2.0 / var_b);
+  double acc[45];
+  cp::wave_sum<45>([&](int lane, double* a) {
+    for (long long k = lane; k < n; k += cp::POSE_LANES)
+      cp::dlt_accumulate((((double)px[2 * k] - cx0) - cx) * si, (((double)px[2 * k + 1] - cy0) - cy) * si, (board[2 * k] - cX) * sb,
+                         (board[2 * k + 1] - cY) * sb, a);
+  }, acc);
+  if (bf::lead_lane())
+    for (int i = 0; i < 45; ++i) sh.acc45[i] = acc[i];
+  cp::wave_barrier();
+  bf::LaneRows<9> A, V;
+  A.each([&](int k, double* row) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) row[j] = sh.acc45[cp::tri9(k, j)];
+  });
+  double w[9];
+  bf::jacobi_rows<9, true>(A, V, w);
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) finite = finite && isfinite(w[i]);
+  if (!finite) return CLC_POSE_NONFINITE;
+  if (!(w[7] > cp::POSE_DEGENERATE_RATIO * w[0])) return CLC_POSE_DEGENERATE;
+  double hn[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) hn[i] = V.at(i, 8);
+  double Hb[9];  // Hn Tb
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    Hb[3 * r] = hn[3 * r] * sb;
+    Hb[3 * r + 1] = hn[3 * r + 1] * sb;
+    Hb[3 * r + 2] = (hn[3 * r + 2] - hn[3 * r] * sb * cX) - hn[3 * r + 1] * sb * cY;
+  }
+  double f2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    H[j] = Hb[j] / si + cx * Hb[6 + j];
+    H[3 + j] = Hb[3 + j] / si + cy * Hb[6 + j];
+    H[6 + j] = Hb[6 + j];
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) f2 += H[i] * H[i];
+  if (!(f2 > 0.0) || !finite_d(f2)) return CLC_POSE_NONFINITE;
+  const double inv = 1.0 / sqrt(f2);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) H[i] *= inv;
+  return CLC_POSE_OK;
+}
+
+// The host's half: the one-unknown least squares for u = 1 / f^2 over the usable images' homographies, in image order (Zhang's two
+// constraints h1^T w h2 = 0, h1^T w h1 = h2^T w h2 with w = diag(u, u, 1)).  Returns the focal length, NaN when u is not positive and
+// finite or fewer than 2 images are usable; *n_used = the usable images.
+inline double guess_focal(const double* H, const int32_t* status, long long n_images, int32_t* n_used) {
+  double sab = 0.0, saa = 0.0;
+  int32_t used = 0;
+  for (long long k = 0; k < n_images; ++k) {
+    if (status[k] != CLC_POSE_OK) continue;
+    const double* h = H + 9 * k;
+    const double h1x = h[0], h1y = h[3], h1z = h[6], h2x = h[1], h2y = h[4], h2z = h[7];
+    const double a1 = h1x * h2x + h1y * h2y, b1 = h1z * h2z;
+    const double a2 = (h1x * h1x + h1y * h1y) - (h2x * h2x + h2y * h2y), b2 = h1z * h1z - h2z * h2z;
+    sab += a1 * b1;
+    sab += a2 * b2;
+    saa += a1 * a1;
+    saa += a2 * a2;
+    ++used;
+  }
+  if (n_used) *n_used = used;
+  if (used < 2) return __builtin_nan("");
+  const double u = -sab / saa;
+  if (!(u > 0.0) || !finite_d(u)) return __builtin_nan("");
+  const double f = 1.0 / sqrt(u);
+  return finite_d(f) ? f : __builtin_nan("");
+}
+
+#if defined(__HIPCC__)
+
+// K19: one 256-thread workgroup per problem.
+static __global__ __launch_bounds__(CAL_THREADS) void camcal_kernel(const CalArgs a) {
+  __shared__ CalShared sh;
+  camcal_problem(a, (long long)blockIdx.x, sh);
+}
+
+// The closed-form start's per-image half: one 64-thread workgroup (one wave) per image; off absolute, image `first` first in H / status.
+static __global__ __launch_bounds__(64) void homography_kernel(const float* __restrict__ px, const float* __restrict__ board,
+                                                               const long long* __restrict__ off, const double cx0, const double cy0,
+                                                               double* __restrict__ H, int32_t* __restrict__ status) {
+  __shared__ GuessShared sh;
+  const long long img = blockIdx.x;
+  const long long b = off[img], n = off[img + 1] - b;
+  double h[9];
+  const int st = (b >= 0 && n >= 0) ? homography_image(px + 2 * b, board + 2 * b, n, cx0, cy0, sh, h) : CLC_POSE_NONFINITE;
+  if (threadIdx.x == 0) {
+    status[img] = st;
+    for (int i = 0; i < 9; ++i) H[9 * img + i] = st == CLC_POSE_OK ? h[i] : __builtin_nan("");
+  }
+}
+
+#endif  // __HIPCC__
+
+}  // namespace cc
+}  // namespace clc

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, Iteration, JointOptions, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, Iteration, JointOptions, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -678,6 +678,83 @@ class Solver:
                                               V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
                                               V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
                                               V(summaries_ptr), V(H_cl_ptr), V(cost_parts_ptr), V(status_ptr)), "clc_joint_refine_device")
+
+    # ---- camera intrinsics from the board images (K19) ----
+    def camera_guess(self, model: int, width: int, height: int, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray):
+        """clc_camera_guess: the closed-form start -> (Camera with fx = fy, the principal point at the image centre and zero distortion,
+        n_used).  Raises ClcError where the images give no focal length."""
+        from .camera import Camera, ClcCamera
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(off) - 1
+        if n < 0 or (n > 0 and (off[0] < 0 or off[-1] > len(cp) or off[-1] > len(bx))):
+            raise ValueError("camera_guess: offsets run past corners_px or board_xy")
+        c, used = ClcCamera(), C.c_int32(0)
+        V = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_camera_guess(self._h, C.c_int32(model), C.c_int32(width), C.c_int32(height), V(cp), V(bx), V(off), C.c_size_t(n),
+                                       C.byref(c), C.byref(used)), "clc_camera_guess")
+        return Camera(c.model, tuple(c.proj), tuple(c.dist), int(width), int(height)), used.value
+
+    def camera_guess_device(self, model: int, width: int, height: int, corners_ptr: int, board_ptr: int, offsets_ptr: int, n_images: int):
+        """clc_camera_guess_device on device-resident corners, board points and offsets (data_ptr()s) -> (Camera, n_used)."""
+        from .camera import Camera, ClcCamera
+        c, used = ClcCamera(), C.c_int32(0)
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_camera_guess_device(self._h, C.c_int32(model), C.c_int32(width), C.c_int32(height), V(corners_ptr), V(board_ptr),
+                                              V(offsets_ptr), C.c_size_t(n_images), C.byref(c), C.byref(used)), "clc_camera_guess_device")
+        return Camera(c.model, tuple(c.proj), tuple(c.dist), int(width), int(height)), used.value
+
+    def camera_calibrate(self, cameras, corners_px: np.ndarray, board_xy: np.ndarray, corner_offsets: np.ndarray, q_ca_wxyz: np.ndarray,
+                         t_ca: np.ndarray, problem_offsets: Optional[np.ndarray] = None, keep: Optional[np.ndarray] = None,
+                         options: Optional[Options] = None, camcal: Optional[CamcalOptions] = None) -> dict:
+        """clc_camera_calibrate (K19): per problem the reprojection error in pixels over sigma_px, minimised over the free intrinsics and
+        every board pose.  cameras: one Camera (one problem) or a sequence, one per problem: the starts.  Image i owns corners
+        [corner_offsets[i], corner_offsets[i+1]); problem k owns images [problem_offsets[k], problem_offsets[k+1]) (None: one problem).
+        q_ca_wxyz [n, 4], t_ca [n, 3]: the start poses (not modified).
+        -> dict(cameras [list of Camera], q [n, 4], t [n, 3], summaries, H_cam [n_problems, 8, 8], rms_px [n_problems], status [n] int32
+        (CLC_CAMCAL_*))."""
+        from .camera import Camera, ClcCamera
+        cams_in = [cameras] if isinstance(cameras, Camera) else list(cameras)
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        co = np.ascontiguousarray(corner_offsets, dtype=np.int64)
+        n = len(co) - 1
+        if n < 0 or (n > 0 and (co[-1] > len(cp) or co[-1] > len(bx) or co[0] < 0)):
+            raise ValueError("camera_calibrate: offsets run past corners_px or board_xy")
+        pr = None if problem_offsets is None else np.ascontiguousarray(problem_offsets, dtype=np.int64)
+        npb = 1 if pr is None else len(pr) - 1
+        if len(cams_in) != npb:
+            raise ValueError("camera_calibrate: one camera per problem")
+        if pr is not None and (len(pr) < 1 or (len(pr) > 1 and pr[-1] > n)):
+            raise ValueError("camera_calibrate: problem_offsets run past the images")
+        q = np.array(q_ca_wxyz, dtype=np.float64, order="C").reshape(n, 4)
+        t = np.array(t_ca, dtype=np.float64, order="C").reshape(n, 3)
+        kp = None if keep is None else np.ascontiguousarray(np.asarray(keep).astype(np.uint8))
+        if kp is not None and kp.shape != (n,):
+            raise ValueError("camera_calibrate: keep needs one entry per image")
+        cams = (ClcCamera * max(npb, 1))(*[c.to_c() for c in cams_in])
+        sm = (Summary * max(npb, 1))()
+        H = np.empty((npb, 8, 8)); rms = np.empty(npb); st = np.empty(n, dtype=np.int32)
+        V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_camera_calibrate(self._h, C.byref(options) if options is not None else None,
+                                           C.byref(camcal) if camcal is not None else None, V(cp), V(bx), V(co), V(kp), C.c_size_t(n), V(pr),
+                                           C.c_size_t(npb), cams, V(q), V(t), sm, V(H), V(rms), V(st)), "clc_camera_calibrate")
+        out = [Camera(cams[k].model, tuple(cams[k].proj), tuple(cams[k].dist), cams_in[k].width, cams_in[k].height) for k in range(npb)]
+        return dict(cameras=out, q=q, t=t, summaries=sm, H_cam=H, rms_px=rms, status=st)
+
+    def camera_calibrate_device(self, corners_ptr: int, board_ptr: int, corner_offsets_ptr: int, n_images: int, n_problems: int,
+                                cameras_ptr: int, q_ptr: int, t_ptr: int, summaries_ptr: int, status_ptr: int, problem_offsets_ptr: int = 0,
+                                keep_ptr: int = 0, H_cam_ptr: int = 0, rms_ptr: int = 0, options: Optional[Options] = None,
+                                camcal: Optional[CamcalOptions] = None):
+        """clc_camera_calibrate_device on device-resident arrays (data_ptr()s; ready on the solver's stream): cameras as clc_camera
+        records (72 bytes each), in / out like q and t; the per-image arrays are indexed by the absolute image index."""
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_camera_calibrate_device(self._h, C.byref(options) if options is not None else None,
+                                                  C.byref(camcal) if camcal is not None else None, V(corners_ptr), V(board_ptr),
+                                                  V(corner_offsets_ptr), V(keep_ptr), C.c_size_t(n_images), V(problem_offsets_ptr),
+                                                  C.c_size_t(n_problems), V(cameras_ptr), V(q_ptr), V(t_ptr), V(summaries_ptr), V(H_cam_ptr),
+                                                  V(rms_ptr), V(status_ptr)), "clc_camera_calibrate_device")
 
     # ---- board-segment detection ----
     def board_segments(self, points: np.ndarray, offsets: np.ndarray):

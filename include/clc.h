@@ -1014,6 +1014,72 @@ int clc_joint_refine_device(clc_handle* h, const clc_camera* cam, const clc_opti
                             double* poses_cl_dev, clc_summary* summaries_dev, double* H_cl_dev, double* cost_parts_dev,
                             int32_t* image_status_dev);
 
+/* ---- camera intrinsics from the board images (K19) ------------------------------------------------------------------------
+ * One problem = one camera seen in P images of the board.  The cost 1/2 sum |(project(cam, R_i X + t_i) - u) / sigma_px|^2 (project:
+ * spaceToPlane as clc_camera_project, pixels; no lift, no loss) is minimised over the 8 intrinsics in clc_camera order (proj[0..3],
+ * dist[0..3], moved additively) and the tangent [dt, dtheta] of every board pose (t += dt, R <- R Exp(dtheta)).  The whole
+ * Levenberg-Marquardt solve of a problem runs in one kernel launch (one workgroup per problem): per-image 6x6 blocks and a Schur
+ * complement onto the system of the free intrinsics, clc_options with the semantics of the other solves (opt NULL =
+ * clc_pose_options_default()), Jacobi scaling fixed at the first evaluation.  An evaluation with a corner at P_z <= 0 is invalid.
+ * Deterministic: the same bits on every run, and a problem's result does not depend on the other problems of the call.
+ * Kannala-Brandt's k4 and k5 are not observable in an ordinary field of view: they are held by default. */
+typedef struct clc_camcal_options {
+  double sigma_px;          /* pixels, finite, > 0 */
+  uint32_t hold_mask;       /* bit j: intrinsic j (proj[0..3], dist[0..3]) is held */
+  int32_t hold_board_poses; /* 1: only the free intrinsics move */
+} clc_camcal_options;       /* 16 bytes */
+
+/* 0.3 px; mask 0 for CLC_CAMERA_PINHOLE, bits 6 | 7 (k4, k5) for CLC_CAMERA_KANNALA_BRANDT. */
+void clc_camcal_options_default(clc_camcal_options* copt, int32_t model);
+
+/* Image status of clc_camera_calibrate. */
+#define CLC_CAMCAL_OK 1
+#define CLC_CAMCAL_TOO_FEW 0      /* fewer than 4 corners */
+#define CLC_CAMCAL_NOT_KEPT (-1)  /* keep[i] == 0, or the image belongs to no problem */
+#define CLC_CAMCAL_NONFINITE (-2) /* a non-finite corner, board point or start pose */
+
+/* The closed-form start: per image (corners [offsets[k], offsets[k+1]) of corners_px / board_xy, as clc_board_poses) the homography
+ * board -> pixel - (width / 2, height / 2) by clc_board_poses' normalized DLT (same degeneracy ratio), scaled to unit Frobenius
+ * norm; then, over the usable images in image order, the one-unknown least squares for u = 1 / f^2 of h1^T w h2 = 0 and
+ * h1^T w h1 = h2^T w h2, w = diag(u, u, 1), h1 and h2 the first two columns.  cam_out: model, fx = fy = 1 / sqrt(u), the principal
+ * point at the image centre, zero distortion (for Kannala-Brandt a small-angle approximation: a start only).  *n_used (nullable):
+ * the usable images.  CLC_ERR_LINALG when fewer than 2 images are usable or u is not positive and finite (cam_out untouched);
+ * CLC_ERR_INVALID_ARG: a model that is neither of the two, width or height <= 0, NULL pointers, decreasing offsets. */
+int clc_camera_guess(clc_handle* h, int32_t model, int32_t width, int32_t height, const float* corners_px, const float* board_xy,
+                     const int64_t* offsets, size_t n_images, clc_camera* cam_out, int32_t* n_used);
+/* The same with corners_px, board_xy and offsets in DEVICE memory (offsets_dev[0] may be > 0; not validated); cam_out and n_used on
+ * the host.  The same bits as the host-array form. */
+int clc_camera_guess_device(clc_handle* h, int32_t model, int32_t width, int32_t height, const float* corners_px_dev,
+                            const float* board_xy_dev, const int64_t* offsets_dev, size_t n_images, clc_camera* cam_out,
+                            int32_t* n_used);
+
+/* Image i owns corners [corner_offsets[i], corner_offsets[i+1]) of corners_px / board_xy; problem k owns images
+ * [problem_offsets[k], problem_offsets[k+1]) (NULL: one problem of all images) and the camera cams[k] (in: the start, e.g.
+ * clc_camera_guess's; out: the minimiser; a held intrinsic keeps its bits).  keep[n_images] (nullable): 0 drops an image.  In / out:
+ * q_ca_wxyz[4 n] (out: w >= 0), t_ca[3 n]: the start poses, e.g. clc_board_poses' under the start camera.  An image that takes no
+ * part (image_status != CLC_CAMCAL_OK) keeps its pose bit for bit.  A problem with no participating image, a non-finite camera or a
+ * failed solve ends CLC_FAILURE with its camera and every pose untouched.  summaries[n_problems]: final_cost is the cost at the
+ * returned point.  H_cam[64 n_problems] (nullable): the information on the intrinsics with the board poses marginalised,
+ * C - sum B_i^T A_i^-1 B_i at the returned point (undamped, unscaled; rows and columns of held intrinsics zero; C itself with
+ * hold_board_poses; NaN where an A_i is not positive definite).  rms_px[n_problems] (nullable): sqrt(sum |project - u|^2 / corners)
+ * over the participating images.  copt NULL: clc_camcal_options_default of cams[0].model.  CLC_ERR_INVALID_ARG before any device
+ * work: NULL required pointers, a sigma_px that is not finite and positive, mask bits beyond the 8, all 8 bits together with
+ * hold_board_poses, offsets that decrease, a camera whose model is neither of the two.  One enqueue, one synchronisation. */
+int clc_camera_calibrate(clc_handle* h, const clc_options* opt, const clc_camcal_options* copt, const float* corners_px,
+                         const float* board_xy, const int64_t* corner_offsets, const uint8_t* keep, size_t n_images,
+                         const int64_t* problem_offsets, size_t n_problems, clc_camera* cams, double* q_ca_wxyz, double* t_ca,
+                         clc_summary* summaries, double* H_cam, double* rms_px, int32_t* image_status);
+/* The same with every array, cams included, in DEVICE memory; indexing as clc_joint_refine_device: the per-image arrays by the
+ * absolute image index (the call covers the n_images images from problem_offsets_dev[0] on, from 0 when it is NULL), corner offsets
+ * absolute, the per-problem arrays from problem 0.  Nothing is read back ahead of the enqueue: offsets are not validated, and a
+ * camera with an unknown model ends its problem CLC_FAILURE.  copt NULL: sigma 0.3 px, nothing held (the models are not known to
+ * the host). */
+int clc_camera_calibrate_device(clc_handle* h, const clc_options* opt, const clc_camcal_options* copt, const float* corners_px_dev,
+                                const float* board_xy_dev, const int64_t* corner_offsets_dev, const uint8_t* keep_dev, size_t n_images,
+                                const int64_t* problem_offsets_dev, size_t n_problems, clc_camera* cams_dev, double* q_ca_wxyz_dev,
+                                double* t_ca_dev, clc_summary* summaries_dev, double* H_cam_dev, double* rms_px_dev,
+                                int32_t* image_status_dev);
+
 #ifdef __cplusplus
 }
 #endif
