@@ -23,9 +23,10 @@ HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assembl
 # (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
 # abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md), those of abi_frontend.hip by clc_stations.hpp
 # (profiles/offline_stations.md), those of abi_campose.hip by clc_robustpose.hpp (tests/test_robustpose_resources.py holds
-# board_pose_kernel's figures) or by clc_altpose.hpp (tests/test_altpose_resources.py); clc_joint.hpp is included by abi_joint.hip
-# (tests/test_joint_resources.py) and by clc_camcal.hpp, which abi_camcal.hip alone includes (tests/test_camcal_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
-SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_joint.hpp", "clc_camcal.hpp"]
+# board_pose_kernel's figures) or by clc_altpose.hpp (tests/test_altpose_resources.py); clc_arrow.hpp (the arrow solve) is included by clc_joint.hpp,
+# which abi_joint.hip alone includes (tests/test_joint_resources.py), and by clc_camcal.hpp, which abi_camcal.hip alone includes
+# (tests/test_camcal_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
+SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_joint.hpp", "clc_camcal.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the

@@ -11,8 +11,6 @@ namespace {
 
 namespace cc = clc::cc;
 
-bool known_model(int32_t model) { return model == CLC_CAMERA_PINHOLE || model == CLC_CAMERA_KANNALA_BRANDT; }
-
 // The calibration's options: the caller's or the defaults for `model`; checked.
 int camcal_options(const clc_camcal_options* in, int32_t model, clc_camcal_options* o, const char* who) {
   if (in) *o = *in; else clc_camcal_options_default(o, model);

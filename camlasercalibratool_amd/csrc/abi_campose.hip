@@ -11,16 +11,6 @@ using namespace clc_abi;
 
 namespace {
 
-int camera_check(const clc_camera* c, const char* who) {
-  if (!c || (c->model != CLC_CAMERA_PINHOLE && c->model != CLC_CAMERA_KANNALA_BRANDT))
-    return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": unknown camera model").c_str());
-  for (int i = 0; i < 4; ++i)
-    if (!std::isfinite(c->proj[i]) || !std::isfinite(c->dist[i]))
-      return fail(CLC_ERR_NONFINITE, (std::string(who) + ": non-finite camera parameter").c_str());
-  if (c->proj[0] == 0.0 || c->proj[1] == 0.0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": zero focal length").c_str());
-  return CLC_OK;
-}
-
 unsigned lift_blocks(size_t n) { return (unsigned)((n + clc::cp::LIFT_THREADS - 1) / clc::cp::LIFT_THREADS); }
 
 // lift (rounded) into lifted_dev[2 * n_corners] (corner `first` first), then one wave per image; every array on the device, offsets

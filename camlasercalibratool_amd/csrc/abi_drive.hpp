@@ -158,5 +158,15 @@ inline int pose_options(const clc_options* in, clc_options* o, const char* who) 
   if (o->use_loss) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": the pose refinement has no loss (use_loss must be 0)").c_str());
   return CLC_OK;
 }
+inline bool known_model(int32_t model) { return model == CLC_CAMERA_PINHOLE || model == CLC_CAMERA_KANNALA_BRANDT; }
+// A camera the lift and the projection can use: a known model, finite parameters, focal lengths not 0.
+inline int camera_check(const clc_camera* c, const char* who) {
+  if (!c || !known_model(c->model)) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": unknown camera model").c_str());
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(c->proj[i]) || !std::isfinite(c->dist[i]))
+      return fail(CLC_ERR_NONFINITE, (std::string(who) + ": non-finite camera parameter").c_str());
+  if (c->proj[0] == 0.0 || c->proj[1] == 0.0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": zero focal length").c_str());
+  return CLC_OK;
+}
 
 }  // namespace clc_abi

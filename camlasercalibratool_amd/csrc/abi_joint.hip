@@ -11,16 +11,6 @@ namespace {
 
 namespace jt = clc::jt;
 
-int joint_camera_check(const clc_camera* c, const char* who) {
-  if (!c || (c->model != CLC_CAMERA_PINHOLE && c->model != CLC_CAMERA_KANNALA_BRANDT))
-    return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": unknown camera model").c_str());
-  for (int i = 0; i < 4; ++i)
-    if (!std::isfinite(c->proj[i]) || !std::isfinite(c->dist[i]))
-      return fail(CLC_ERR_NONFINITE, (std::string(who) + ": non-finite camera parameter").c_str());
-  if (c->proj[0] == 0.0 || c->proj[1] == 0.0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": zero focal length").c_str());
-  return CLC_OK;
-}
-
 // The joint call's options: the caller's or the defaults; checked.
 int joint_options(const clc_joint_options* in, const clc_camera* cam, clc_joint_options* o, const char* who) {
   if (in) *o = *in; else clc_joint_options_default(o, cam);
@@ -76,7 +66,7 @@ int clc_joint_refine(clc_handle* h, const clc_camera* cam, const clc_options* op
                      int32_t* image_status) {
   const char* who = "clc_joint_refine";
   // everything that can be refused without the device first
-  CLC_TRY(joint_camera_check(cam, who));
+  CLC_TRY(camera_check(cam, who));
   clc_options opt;
   CLC_TRY(pose_options(opt_in, &opt, who));
   clc_joint_options jo;
@@ -161,7 +151,7 @@ int clc_joint_refine_device(clc_handle* h, const clc_camera* cam, const clc_opti
                             double* poses_cl_dev, clc_summary* summaries_dev, double* H_cl_dev, double* cost_parts_dev,
                             int32_t* image_status_dev) {
   const char* who = "clc_joint_refine_device";
-  CLC_TRY(joint_camera_check(cam, who));
+  CLC_TRY(camera_check(cam, who));
   clc_options opt;
   CLC_TRY(pose_options(opt_in, &opt, who));
   clc_joint_options jo;

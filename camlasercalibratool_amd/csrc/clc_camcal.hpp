@@ -3,76 +3,45 @@
 //   1/2 sum |(project(cam, R_i X + t_i) - u) / sigma_px|^2          project: cam_project of clc_campose.hpp, pixels, no lift
 //
 // is minimised over the 8 intrinsics (clc_camera order: proj[0..3], dist[0..3]; moved additively) and the tangent [dt, dtheta] of every
-// board pose (t += dt, R <- R Exp(dtheta)).  The normal matrix is K18's arrow with an 8-wide shared block: A_i (6x6) per image, B_i
-// (6x8) to the block C (8x8) of the intrinsics; the Schur complement over the images leaves an 8x8 system, less the held intrinsics.
+// board pose.  The arrow of clc_arrow.hpp with the intrinsics as its 8-wide shared block: the solve (step, controller, outputs) is
+// aw::arrow_problem; this file holds the cost, what is the intrinsics' own and the closed-form start.
 //
-//   camcal_kernel   one 256-thread workgroup (4 waves) per problem, the whole Levenberg-Marquardt solve in one launch; the shape and
-//                   the helpers (each_image, each_image_wave, each_lane, chol_factor6, chol_apply6, block_candidate, ...) are those of
-//                   joint_refine_kernel (clc_joint.hpp).
-//     evaluation   the waves take the images round-robin; per image a wave all-reduces, in four passes over the corners (the cheap
-//                  residual recomputed), {A_i, g_i, sum r^2} (28), {B_i[:, 0:4], g_c} (32), B_i[:, 4:8] (24) and the image's share of
-//                  C (36): 120 sums, never more than 36 live.  The shares are added over the images in image order.
-//     step         one image per lane: the scaled, damped A_i + D_i factored, Y_i = (A_i + D_i)^-1 B_i, S_i = B_i^T Y_i (8x8), s_i; S
-//                  and s added in image order; thread 0 compacts the reduced system to the free intrinsics and solves it with
-//                  chol_solve<n_free>; the lanes back-substitute.  A rejected step repeats only this.
-//     controller   thread 0, state in LDS: the semantics of clc_lm.hpp over the arrow (Jacobi scaling fixed at the first evaluation —
-//                  focal lengths and k-coefficients differ by five orders of magnitude —, the diagonal clamp, the radius rule, the
-//                  three tolerances, the iteration cap).  An evaluation with a corner at P_z <= 0 is invalid (a rejected candidate).
+//   camcal_kernel   one 256-thread workgroup (4 waves) per problem, the whole Levenberg-Marquardt solve in one launch.
+//     evaluation   per image a wave all-reduces, in four passes over the corners (the cheap residual recomputed), {A_i, g_i, sum r^2}
+//                  (28), {B_i[:, 0:4], g_c} (32), B_i[:, 4:8] (24) and the image's share of C (36): 120 sums, never more than 36 live.
+//                  An evaluation with a corner at P_z <= 0 is invalid (a rejected candidate).
+//     reduced 8x8  thread 0 compacts it to the free intrinsics and solves it with chol_solve<n_free>.  A held intrinsic has scale 0
+//                  (Jacobi scaling matters here: focal lengths and k-coefficients differ by five orders of magnitude).
 //   homography_kernel   one wave per image: the pixel-space homography of the image's corners about the image centre (K10's normalized
 //                       DLT and jacobi_rows, the same degeneracy ratio), scaled to unit Frobenius norm: the closed-form focal start's
 //                       per-image half (guess_focal is the host's half).
-// Per-image state (CalImage) lives in a workspace in device memory indexed by image; every access goes through pointers (no scratch).
-// Every sum has a fixed shape: no atomics, the same bits on every run, and a problem never reads another problem's state.
+//   Per-image state: CalImage, 4.4 KB.
 //
 // Everything numeric is CLC_HD: tests/shim/camcal_shim.cpp compiles this header for the host with g++ and runs the same code with the
 // threads as loops, in the same summation order.
 #pragma once
-#include "clc_joint.hpp"
+#include "clc_arrow.hpp"
 
 namespace clc {
 namespace cc {
 
-using jt::each_image;
-using jt::each_image_wave;
-using jt::each_lane;
-using jt::finite_d;
-using jt::wg_barrier;
-using jt::wg_lead;
+using aw::finite_d;
 
-constexpr int CAL_THREADS = jt::JOINT_THREADS;  // each_image / each_image_wave stride by the joint kernel's workgroup
-constexpr int NK = 8;                           // intrinsics
+constexpr int CAL_THREADS = aw::ARROW_THREADS;
+constexpr int NK = 8;  // intrinsics
 
-// offsets into an evaluation record E[EVAL_DOUBLES] of one image: A tri<6>, B[8 p + q] (pose row p, intrinsic q), g_i, C tri<8>, g_c
+// offsets into an evaluation record E[EVAL_DOUBLES] of one image (aw::ArrowRecord<8> and the cost)
 constexpr int E_A = 0, E_B = 21, E_G = 69, E_C = 75, E_GC = 111, E_COST = 119, EVAL_DOUBLES = 120;
-constexpr int TOTAL_DOUBLES = EVAL_DOUBLES - E_C;  // C, g_c, the cost
-constexpr int SS_DOUBLES = 36 + NK;                // S_i (tri<8>) and s_i
+static_assert(E_G == aw::ArrowRecord<NK>::E_G && E_C == aw::ArrowRecord<NK>::E_C && E_GC == aw::ArrowRecord<NK>::E_GC &&
+                  E_COST == aw::ArrowRecord<NK>::E_COST, "the record of K19 is the arrow's");
 
-struct CalImage {
-  double x[7], xe[7];            // accepted pose, pose the next evaluation uses: [t, qx, qy, qz, qw]
-  double E[2][EVAL_DOUBLES];     // the blocks at the accepted point (sh.cur) and at the candidate
-  double scale[6], diag[6];      // Jacobi scaling, clamped diagonal of the scaled A
-  double As[36], Md[36], L[36];  // scaled A, scaled damped A, its Cholesky factor (inverse diagonal)
-  double Bs[48], Y[48];          // scaled B, (A + D)^-1 B
-  double gs[6], yg[6], z[6];     // scaled g, (A + D)^-1 g, substitution scratch
-  double Ss[SS_DOUBLES];         // S_i and s_i
-  double step[6];                // delta_i in the scaled space
-  double red[6];                 // shares: step.g, step^T H step, |x - xe|^2, |xe|^2, gradient max norm, bad-step flag
-  int32_t st;                    // CLC_CAMCAL_*
-  int32_t pad_;
-};
+using CalImage = aw::ArrowImage<NK, EVAL_DOUBLES>;
 
-struct CalShared {
-  double kc[NK], kce[NK];  // intrinsics accepted / to evaluate
-  double tot[2][TOTAL_DOUBLES];
-  double scale_c[NK], diag_c[NK], step_c[NK], gs_c[NK], rhs[NK];
-  double Ss[SS_DOUBLES], red[6];
-  double Hs[64], A[64], L[64], z[NK];
+struct CalShared : aw::ArrowShared<NK, EVAL_DOUBLES> {
+  double kc[NK], kce[NK];         // intrinsics accepted / to evaluate
   double Af[64], rf[NK], yf[NK];  // the reduced system of the free intrinsics, compact
-  double x_cost, x_norm, initial_cost, min_iter_cost, radius, decrease_factor, model_cost_change, gmax;
-  double it_cost, it_gmax;
-  long long n_evals, n_corners;
-  int32_t status, n_invalid, reuse_diagonal, num_successful, num_unsuccessful, n_trace, cur, step_ok, move_c, move_i, n_part;
-  int32_t it_iteration, it_successful, model, n_free;
+  long long n_corners;
+  int32_t model, n_free;
   int32_t free_idx[NK];
 };
 
@@ -299,36 +268,6 @@ CLC_HD void eval_image(const CalArgs& a, const clc_camera& c, long long img, con
   }
 }
 
-// Y = M^-1 B (6x8) and S = B^T Y (tri<8> order) of one image, from im.L.
-CLC_HD void schur_share(CalImage& im, const double* B) {
-  CLC_JT_ROLLED for (int b = 0; b < NK; ++b) jt::chol_apply6(im.L, B + b, NK, im.Y + b, NK, im.z);
-  int idx = 0;
-  CLC_JT_ROLLED for (int p = 0; p < NK; ++p)
-    CLC_JT_ROLLED for (int q = p; q < NK; ++q) {
-      double s = 0.0;
-      CLC_JT_ROLLED for (int k = 0; k < 6; ++k) s += B[NK * k + p] * im.Y[NK * k + q];
-      im.Ss[idx++] = s;
-    }
-}
-
-struct Problem {
-  long long i0, P;  // first image (absolute), images
-  CalImage* ws;     // image i0 first
-};
-
-// Adds the images' shares in image order: sh.red (sums of 0..3, maxima of 4..5).
-CLC_HD void reduce_red(const Problem& pr, CalShared& sh) {
-  each_lane(6, [&](int k) {
-    double s = 0.0;
-    for (long long j = 0; j < pr.P; ++j) {
-      const CalImage& im = pr.ws[j];
-      if (im.st != CLC_CAMCAL_OK) continue;
-      s = k < 4 ? s + im.red[k] : fmax(s, im.red[k]);
-    }
-    sh.red[k] = s;
-  });
-}
-
 CLC_HD void camera_of(const CalShared& sh, const double* k, clc_camera& c) {
   c.model = sh.model;
   c.reserved = 0;
@@ -336,263 +275,14 @@ CLC_HD void camera_of(const CalShared& sh, const double* k, clc_camera& c) {
   for (int i = 0; i < 4; ++i) { c.proj[i] = k[i]; c.dist[i] = k[4 + i]; }
 }
 
-// Evaluates every participating image at its xe under the intrinsics sh.kce into record `set`; the totals into sh.tot[set].
-CLC_HD void evaluate(const CalArgs& a, const Problem& pr, CalShared& sh, int set) {
-  clc_camera c;
-  camera_of(sh, sh.kce, c);
-  each_image_wave(pr.P, [&](long long j) {
-    CalImage& im = pr.ws[j];
-    if (im.st != CLC_CAMCAL_OK) return;
-    eval_image(a, c, pr.i0 + j, im.xe, im.E[set]);
-  });
-  wg_barrier();
-  each_lane(TOTAL_DOUBLES, [&](int k) {
-    double s = 0.0;
-    for (long long j = 0; j < pr.P; ++j) {
-      const CalImage& im = pr.ws[j];
-      if (im.st != CLC_CAMCAL_OK) continue;
-      s += im.E[set][E_C + k];
-    }
-    sh.tot[set][k] = s;
-  });
-  wg_barrier();
-}
-
-// The gradient max norm over the moving blocks at the accepted point (record sh.cur) -> sh.gmax.
-CLC_HD void gradient_norm(const Problem& pr, CalShared& sh) {
-  each_image(pr.P, [&](long long j) {
-    CalImage& im = pr.ws[j];
-    if (im.st != CLC_CAMCAL_OK) return;
-    im.red[4] = sh.move_i ? jt::block_gradient_norm(im.x, im.E[sh.cur] + E_G) : 0.0;
-    im.red[5] = 0.0;
-  });
-  wg_barrier();
-  reduce_red(pr, sh);
-  wg_barrier();
-  if (wg_lead()) {
-    double m = sh.red[4];
-    CLC_JT_ROLLED for (int f = 0; f < sh.n_free; ++f) m = fmax(m, fabs(sh.tot[sh.cur][(E_GC - E_C) + sh.free_idx[f]]));
-    sh.gmax = m;
-  }
-  wg_barrier();
-}
-
 // The reduced system sh.A / sh.rhs without the rows and columns of the held intrinsics, solved: sh.yf[0..N).
 template <int N>
 CLC_HD bool solve_free(CalShared& sh) {
-  CLC_JT_ROLLED for (int p = 0; p < N; ++p) {
-    CLC_JT_ROLLED for (int q = 0; q < N; ++q) sh.Af[N * p + q] = sh.A[NK * sh.free_idx[p] + sh.free_idx[q]];
+  CLC_AW_ROLLED for (int p = 0; p < N; ++p) {
+    CLC_AW_ROLLED for (int q = 0; q < N; ++q) sh.Af[N * p + q] = sh.A[NK * sh.free_idx[p] + sh.free_idx[q]];
     sh.rf[p] = sh.rhs[sh.free_idx[p]];
   }
   return chol_solve<N>(sh.Af, sh.rf, sh.yf, sh.L, sh.z);
-}
-
-// The trust-region step at the accepted point for sh.radius: every image's xe and sh.kce become the candidate, sh.step_ok says
-// whether it is valid (LevenbergMarquardtStrategy::ComputeStep + the model-cost test, over the arrow).
-CLC_HD void compute_step(const CalArgs& a, const Problem& pr, CalShared& sh) {
-  const clc_options& o = a.opt;
-  const double inv_radius = rcp_pos(sh.radius);
-  const int reuse = sh.reuse_diagonal, cur = sh.cur;
-  if (sh.move_i) {
-    each_image(pr.P, [&](long long j) {
-      CalImage& im = pr.ws[j];
-      if (im.st != CLC_CAMCAL_OK) return;
-      const double* E = im.E[cur];
-      int idx = 0;
-      CLC_JT_ROLLED for (int p = 0; p < 6; ++p)
-        CLC_JT_ROLLED for (int q = p; q < 6; ++q) {
-          const double v = E[E_A + idx++] * (im.scale[p] * im.scale[q]);
-          im.As[6 * p + q] = v;
-          im.As[6 * q + p] = v;
-        }
-      if (!reuse) {
-        CLC_JT_ROLLED for (int c = 0; c < 6; ++c) {
-          double d = im.As[7 * c];
-          d = d > o.min_lm_diagonal ? d : o.min_lm_diagonal;
-          d = d < o.max_lm_diagonal ? d : o.max_lm_diagonal;
-          im.diag[c] = d;
-        }
-      }
-      CLC_JT_ROLLED for (int i = 0; i < 36; ++i) im.Md[i] = im.As[i];
-      CLC_JT_ROLLED for (int c = 0; c < 6; ++c) im.Md[7 * c] += im.diag[c] * inv_radius;
-      CLC_JT_ROLLED for (int p = 0; p < 6; ++p) im.gs[p] = E[E_G + p] * im.scale[p];
-      CLC_JT_ROLLED for (int p = 0; p < 6; ++p)
-        CLC_JT_ROLLED for (int q = 0; q < NK; ++q) im.Bs[NK * p + q] = E[E_B + NK * p + q] * (im.scale[p] * sh.scale_c[q]);
-      im.red[5] = 0.0;
-      CLC_JT_ROLLED for (int i = 0; i < SS_DOUBLES; ++i) im.Ss[i] = 0.0;
-      if (!jt::chol_factor6(im.Md, im.L)) { im.red[5] = 1.0; return; }
-      jt::chol_apply6(im.L, im.gs, 1, im.yg, 1, im.z);
-      if (sh.move_c) {
-        schur_share(im, im.Bs);
-        CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
-          double s = 0.0;
-          CLC_JT_ROLLED for (int k = 0; k < 6; ++k) s += im.Bs[NK * k + p] * im.yg[k];
-          im.Ss[36 + p] = s;
-        }
-      }
-    });
-    wg_barrier();
-    each_lane(SS_DOUBLES, [&](int k) {
-      double s = 0.0;
-      for (long long j = 0; j < pr.P; ++j) {
-        const CalImage& im = pr.ws[j];
-        if (im.st != CLC_CAMCAL_OK) continue;
-        s += im.Ss[k];
-      }
-      sh.Ss[k] = s;
-    });
-    wg_barrier();
-  }
-  // ---- the reduced system, thread 0 ----
-  if (wg_lead()) {
-    bool ok = true;
-    const double* T = sh.tot[cur];
-    int idx = 0;
-    CLC_JT_ROLLED for (int p = 0; p < NK; ++p)
-      CLC_JT_ROLLED for (int q = p; q < NK; ++q) {
-        const double v = T[idx++] * (sh.scale_c[p] * sh.scale_c[q]);
-        sh.Hs[NK * p + q] = v;
-        sh.Hs[NK * q + p] = v;
-      }
-    CLC_JT_ROLLED for (int p = 0; p < NK; ++p) { sh.step_c[p] = 0.0; sh.gs_c[p] = sh.rhs[p] = T[(E_GC - E_C) + p] * sh.scale_c[p]; }
-    if (sh.move_c) {
-      if (!reuse) {
-        CLC_JT_ROLLED for (int c = 0; c < NK; ++c) {
-          double d = sh.Hs[(NK + 1) * c];
-          d = d > o.min_lm_diagonal ? d : o.min_lm_diagonal;
-          d = d < o.max_lm_diagonal ? d : o.max_lm_diagonal;
-          sh.diag_c[c] = d;
-        }
-      }
-      CLC_JT_ROLLED for (int i = 0; i < 64; ++i) sh.A[i] = sh.Hs[i];
-      CLC_JT_ROLLED for (int c = 0; c < NK; ++c) sh.A[(NK + 1) * c] += sh.diag_c[c] * inv_radius;
-      if (sh.move_i) {
-        CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
-          CLC_JT_ROLLED for (int q = 0; q < NK; ++q) sh.A[NK * p + q] -= sh.Ss[p <= q ? tri<NK>(p, q) : tri<NK>(q, p)];
-          sh.rhs[p] -= sh.Ss[36 + p];
-        }
-      }
-      // held intrinsics lose their rows and columns: chol_solve at the number of free ones
-      switch (sh.n_free) {
-        case 1: ok = solve_free<1>(sh); break;
-        case 2: ok = solve_free<2>(sh); break;
-        case 3: ok = solve_free<3>(sh); break;
-        case 4: ok = solve_free<4>(sh); break;
-        case 5: ok = solve_free<5>(sh); break;
-        case 6: ok = solve_free<6>(sh); break;
-        case 7: ok = solve_free<7>(sh); break;
-        default: ok = solve_free<8>(sh); break;
-      }
-      CLC_JT_ROLLED for (int f = 0; f < sh.n_free; ++f) {
-        sh.step_c[sh.free_idx[f]] = -sh.yf[f];
-        if (!finite_d(sh.yf[f])) ok = false;
-      }
-    }
-    sh.step_ok = ok ? 1 : 0;
-  }
-  wg_barrier();
-  // ---- back-substitution and the candidates ----
-  each_image(pr.P, [&](long long j) {
-    CalImage& im = pr.ws[j];
-    if (im.st != CLC_CAMCAL_OK) return;
-    im.red[0] = im.red[1] = im.red[2] = im.red[3] = 0.0;
-    if (!sh.move_i || im.red[5] != 0.0 || !sh.step_ok) return;
-    bool fin = true;
-    CLC_JT_ROLLED for (int p = 0; p < 6; ++p) {
-      double s = im.yg[p];
-      if (sh.move_c) CLC_JT_ROLLED for (int q = 0; q < NK; ++q) s += im.Y[NK * p + q] * sh.step_c[q];
-      im.step[p] = -s;
-      fin = fin && finite_d(s);
-    }
-    if (!fin) { im.red[5] = 1.0; return; }
-    double sg = 0.0, shs = 0.0;
-    CLC_JT_ROLLED for (int p = 0; p < 6; ++p) {
-      sg += im.step[p] * im.gs[p];
-      double row = 0.0;
-      CLC_JT_ROLLED for (int q = 0; q < 6; ++q) row += im.As[6 * p + q] * im.step[q];
-      if (sh.move_c) CLC_JT_ROLLED for (int q = 0; q < NK; ++q) row += 2.0 * (im.Bs[NK * p + q] * sh.step_c[q]);
-      shs += im.step[p] * row;
-    }
-    im.red[0] = sg;
-    im.red[1] = shs;
-    double n2;
-    im.red[2] = jt::block_candidate(im.x, im.step, im.scale, im.xe, &n2);
-    im.red[3] = n2;
-  });
-  wg_barrier();
-  reduce_red(pr, sh);
-  wg_barrier();
-  if (wg_lead()) {
-    bool ok = sh.step_ok && sh.red[5] == 0.0;
-    double sg = sh.red[0], shs = sh.red[1], sn = sh.red[2], xn = sh.red[3];
-    if (sh.move_c) {
-      CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
-        sg += sh.step_c[p] * sh.gs_c[p];
-        double row = 0.0;
-        CLC_JT_ROLLED for (int q = 0; q < NK; ++q) row += sh.Hs[NK * p + q] * sh.step_c[q];
-        shs += sh.step_c[p] * row;
-      }
-      CLC_JT_ROLLED for (int p = 0; p < NK; ++p) {
-        // a held intrinsic (scale 0, step 0) keeps its bits
-        const double d = sh.step_c[p] * sh.scale_c[p];
-        const double v = sh.scale_c[p] != 0.0 ? sh.kc[p] + d : sh.kc[p];
-        sh.kce[p] = v;
-        sn += (sh.kc[p] - v) * (sh.kc[p] - v);
-        xn += v * v;
-      }
-    }
-    sh.model_cost_change = -(sg + 0.5 * shs);
-    sh.red[2] = sn;
-    sh.red[3] = xn;
-    sh.reuse_diagonal = 1;
-    sh.step_ok = (ok && sh.model_cost_change > 0.0) ? 1 : 0;
-  }
-  wg_barrier();
-}
-
-// H_cam = C - sum B_i^T A_i^-1 B_i at the accepted point (undamped, unscaled), rows and columns of held intrinsics zero; with the
-// board poses held, C itself; NaN where an A_i is not positive definite.
-CLC_HD void marginal_information(const CalArgs& a, const Problem& pr, CalShared& sh, double* H) {
-  const int cur = sh.cur;
-  if (sh.move_i) {
-    each_image(pr.P, [&](long long j) {
-      CalImage& im = pr.ws[j];
-      if (im.st != CLC_CAMCAL_OK) return;
-      const double* E = im.E[cur];
-      int idx = 0;
-      CLC_JT_ROLLED for (int p = 0; p < 6; ++p)
-        CLC_JT_ROLLED for (int q = p; q < 6; ++q) {
-          const double v = E[E_A + idx++];
-          im.Md[6 * p + q] = v;
-          im.Md[6 * q + p] = v;
-        }
-      im.red[5] = 0.0;
-      CLC_JT_ROLLED for (int i = 0; i < SS_DOUBLES; ++i) im.Ss[i] = 0.0;
-      if (!jt::chol_factor6(im.Md, im.L)) { im.red[5] = 1.0; return; }
-      schur_share(im, E + E_B);
-    });
-    wg_barrier();
-    each_lane(37, [&](int k) {
-      double s = 0.0;
-      for (long long j = 0; j < pr.P; ++j) {
-        const CalImage& im = pr.ws[j];
-        if (im.st != CLC_CAMCAL_OK) continue;
-        s = k < 36 ? s + im.Ss[k] : fmax(s, im.red[5]);
-      }
-      sh.Ss[k] = s;
-    });
-    wg_barrier();
-  }
-  if (wg_lead()) {
-    const bool bad = sh.move_i && sh.Ss[36] != 0.0;
-    CLC_JT_ROLLED for (int p = 0; p < NK; ++p)
-      CLC_JT_ROLLED for (int q = 0; q < NK; ++q) {
-        const int k = p <= q ? tri<NK>(p, q) : tri<NK>(q, p);
-        const bool held = ((a.hold_mask >> p) & 1u) || ((a.hold_mask >> q) & 1u);
-        H[NK * p + q] = held ? 0.0 : bad ? __builtin_nan("") : sh.tot[cur][k] - (sh.move_i ? sh.Ss[k] : 0.0);
-      }
-  }
-  wg_barrier();
 }
 
 // Why an image takes no part (wave-uniform; every lane of the image's wave calls it).
@@ -616,243 +306,90 @@ CLC_HD int image_status(const CalArgs& a, long long img) {
   return CLC_CAMCAL_OK;
 }
 
-// One problem: every thread of its workgroup calls it (host: once).
-CLC_HD void camcal_problem(const CalArgs& a, long long pb, CalShared& sh) {
-  const clc_options& o = a.opt;
-  Problem pr;
-  {
+// What K19 gives the arrow solve (clc_arrow.hpp): the shared block is the 8 intrinsics, moved additively, those of hold_mask held.
+struct CalTraits {
+  static constexpr int NC = NK, EVAL_DOUBLES = cc::EVAL_DOUBLES;
+  using Args = CalArgs;
+  using Image = CalImage;
+  using Shared = CalShared;
+  using Ctx = clc_camera;
+
+  // clamped to the call's images: n_images from prob_off[0] on
+  static CLC_HD aw::Problem<Image> problem(const Args& a, long long pb) {
     const long long first = a.prob_off ? a.prob_off[0] : 0;
     long long i0 = a.prob_off ? a.prob_off[pb] : 0, i1 = a.prob_off ? a.prob_off[pb + 1] : a.n_images;
     if (i0 < first) i0 = first;
     if (i1 > first + a.n_images) i1 = first + a.n_images;
-    pr.i0 = i0;
-    pr.P = i1 > i0 ? i1 - i0 : 0;
-    pr.ws = a.ws + (i0 - first);
+    return {i0, i1 > i0 ? i1 - i0 : 0, a.ws + (i0 - first)};
   }
-  // ---- which images take part; their start poses ----
-  each_image_wave(pr.P, [&](long long j) {
-    const long long img = pr.i0 + j;
-    const int st = image_status(a, img);
-    if (bf::lead_lane()) {
-      CalImage& im = pr.ws[j];
-      im.st = st;
-      a.status[img] = st;
-      if (st == CLC_CAMCAL_OK) {
-        const double w = a.q[4 * img], x = a.q[4 * img + 1], y = a.q[4 * img + 2], z = a.q[4 * img + 3];
-        const double inv = 1.0 / sqrt((w * w + x * x) + (y * y + z * z));
-        const double p7[7] = {a.t[3 * img], a.t[3 * img + 1], a.t[3 * img + 2], x * inv, y * inv, z * inv, w * inv};
-#pragma unroll
-        for (int i = 0; i < 7; ++i) im.x[i] = im.xe[i] = p7[i];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { im.scale[i] = 1.0; im.diag[i] = 0.0; im.red[i] = 0.0; }
-      }
-    }
-  });
-  wg_barrier();
-  if (wg_lead()) {
-    int n_part = 0;
-    long long n_corners = 0;
-    double xn = 0.0;
-    for (long long j = 0; j < pr.P; ++j) {
-      if (pr.ws[j].st != CLC_CAMCAL_OK) continue;
-      ++n_part;
-      n_corners += a.coff[pr.i0 + j + 1] - a.coff[pr.i0 + j];
-    }
+  static CLC_HD int image_status(const Args& a, long long img) { return cc::image_status(a, img); }
+  static CLC_HD long long observations(const Args& a, long long img) { return a.coff[img + 1] - a.coff[img]; }
+  static CLC_HD void context(const Shared& sh, Ctx& c) { camera_of(sh, sh.kce, c); }
+  static CLC_HD void eval_image(const Args& a, const Ctx& c, long long img, const double* pose7, double* E) {
+    cc::eval_image(a, c, img, pose7, E);
+  }
+  static CLC_HD bool init_block(const Args& a, long long pb, long long n_corners, Shared& sh, double& xn) {
     const clc_camera& cam = a.cams[pb];
-    bool ok = n_part > 0 && (cam.model == CLC_CAMERA_PINHOLE || cam.model == CLC_CAMERA_KANNALA_BRANDT);
-    CLC_JT_ROLLED for (int i = 0; i < 4; ++i) {
+    bool ok = cam.model == CLC_CAMERA_PINHOLE || cam.model == CLC_CAMERA_KANNALA_BRANDT;
+    CLC_AW_ROLLED for (int i = 0; i < 4; ++i) {
       sh.kc[i] = sh.kce[i] = cam.proj[i];
       sh.kc[4 + i] = sh.kce[4 + i] = cam.dist[i];
       ok = ok && finite_d(cam.proj[i]) && finite_d(cam.dist[i]);
     }
     sh.model = cam.model;
     int nf = 0;
-    CLC_JT_ROLLED for (int i = 0; i < NK; ++i) {
+    CLC_AW_ROLLED for (int i = 0; i < NK; ++i) {
       sh.free_idx[i] = 0;
-      if (!((a.hold_mask >> i) & 1u)) sh.free_idx[nf++] = i;
+      if (!held(a, i)) sh.free_idx[nf++] = i;
     }
     sh.n_free = nf;
-    sh.n_part = n_part;
     sh.n_corners = n_corners;
-    sh.move_i = a.hold_board_poses ? 0 : 1;
     sh.move_c = nf > 0 ? 1 : 0;
-    if (sh.move_i)
-      for (long long j = 0; j < pr.P; ++j) {
-        if (pr.ws[j].st != CLC_CAMCAL_OK) continue;
-        CLC_JT_ROLLED for (int i = 0; i < 7; ++i) xn += pr.ws[j].x[i] * pr.ws[j].x[i];
-      }
-    if (sh.move_c) CLC_JT_ROLLED for (int i = 0; i < NK; ++i) xn += sh.kc[i] * sh.kc[i];
-    sh.x_norm = sqrt_pos(xn);
-    sh.status = ok ? CLC_RUNNING : CLC_FAILURE;
-    sh.n_invalid = 0; sh.reuse_diagonal = 0; sh.num_successful = 0; sh.num_unsuccessful = 0; sh.n_trace = 0; sh.n_evals = 0;
-    sh.cur = 0; sh.step_ok = 0;
-    sh.x_cost = 0.0; sh.initial_cost = 0.0; sh.min_iter_cost = 0.0;
-    sh.radius = o.initial_trust_region_radius; sh.decrease_factor = 2.0; sh.model_cost_change = 0.0; sh.gmax = 0.0;
-    CLC_JT_ROLLED for (int i = 0; i < NK; ++i) {
-      sh.scale_c[i] = ((a.hold_mask >> i) & 1u) ? 0.0 : 1.0;
-      sh.diag_c[i] = 0.0;
-      sh.step_c[i] = 0.0;
-    }
-    CLC_JT_ROLLED for (int i = 0; i < TOTAL_DOUBLES; ++i) sh.tot[0][i] = sh.tot[1][i] = 0.0;
-    sh.it_iteration = 0; sh.it_successful = 1; sh.it_cost = 0.0; sh.it_gmax = 0.0;
+    if (sh.move_c) CLC_AW_ROLLED for (int i = 0; i < NK; ++i) xn += sh.kc[i] * sh.kc[i];
+    return ok;
   }
-  wg_barrier();
-  if (sh.status == CLC_RUNNING) {
-    // ---- IterationZero ----
-    evaluate(a, pr, sh, 0);
-    if (wg_lead()) {
-      sh.n_evals = 1;
-      const double cost = sh.tot[0][E_COST - E_C];
-      if (!finite_d(cost)) sh.status = CLC_FAILURE;
-      sh.x_cost = sh.initial_cost = sh.min_iter_cost = cost;
-      if (o.jacobi_scaling)
-        CLC_JT_ROLLED for (int c = 0; c < NK; ++c)
-          if (sh.scale_c[c] != 0.0) sh.scale_c[c] = 1.0 / (1.0 + sqrt(sh.tot[0][tri<NK>(c, c)]));
-    }
-    if (o.jacobi_scaling)
-      each_image(pr.P, [&](long long j) {
-        CalImage& im = pr.ws[j];
-        if (im.st != CLC_CAMCAL_OK) return;
-        CLC_JT_ROLLED for (int c = 0; c < 6; ++c) im.scale[c] = 1.0 / (1.0 + sqrt(im.E[0][E_A + tri<6>(c, c)]));
-      });
-    wg_barrier();
+  static CLC_HD bool held(const Args& a, int p) { return (a.hold_mask >> p) & 1u; }
+  static CLC_HD double cost(const double* tot) { return tot[E_COST - E_C]; }
+  static CLC_HD double block_gradient(const Shared& sh, double m) {
+    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) m = fmax(m, fabs(sh.tot[sh.cur][(E_GC - E_C) + sh.free_idx[f]]));
+    return m;
   }
-  if (sh.status == CLC_RUNNING) {
-    gradient_norm(pr, sh);
-    if (wg_lead()) { sh.it_cost = sh.x_cost; sh.it_gmax = sh.gmax; }
-    wg_barrier();
+  // held intrinsics lose their rows and columns: chol_solve at the number of free ones
+  static CLC_HD bool solve_block(Shared& sh) {
+    bool ok;
+    switch (sh.n_free) {
+      case 1: ok = solve_free<1>(sh); break;
+      case 2: ok = solve_free<2>(sh); break;
+      case 3: ok = solve_free<3>(sh); break;
+      case 4: ok = solve_free<4>(sh); break;
+      case 5: ok = solve_free<5>(sh); break;
+      case 6: ok = solve_free<6>(sh); break;
+      case 7: ok = solve_free<7>(sh); break;
+      default: ok = solve_free<8>(sh); break;
+    }
+    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) {
+      sh.step_c[sh.free_idx[f]] = -sh.yf[f];
+      if (!finite_d(sh.yf[f])) ok = false;
+    }
+    return ok;
   }
-  // ---- TrustRegionMinimizer::Minimize, as joint_problem (clc_joint.hpp): the same barrier rule for every word of `sh` that thread 0
-  // writes and the others read ----
-  while (sh.status == CLC_RUNNING) {
-    for (;;) {
-      wg_barrier();  // every thread has read sh.status (the loop conditions above and below) before thread 0 may change it
-      if (wg_lead()) {
-        // FinalizeIterationAndCheckIfMinimizerCanContinue
-        if (sh.it_successful) sh.num_successful++; else sh.num_unsuccessful++;
-        sh.n_trace++;
-        sh.min_iter_cost = sh.it_cost < sh.min_iter_cost ? sh.it_cost : sh.min_iter_cost;
-        if (sh.it_iteration >= o.max_num_iterations) sh.status = CLC_NO_CONVERGENCE;
-        else if (sh.it_successful && sh.it_gmax <= o.gradient_tolerance) sh.status = CLC_CONVERGENCE_GRADIENT;
-        else if (sh.radius <= o.min_trust_region_radius) sh.status = CLC_CONVERGENCE_RADIUS;
-        sh.it_iteration++;
-        sh.it_successful = 0;
-      }
-      wg_barrier();
-      if (sh.status != CLC_RUNNING) break;
-      compute_step(a, pr, sh);
-      if (sh.step_ok) {
-        if (wg_lead()) sh.n_invalid = 0;
-        wg_barrier();
-        break;
-      }
-      wg_barrier();  // (every thread has read step_ok)
-      if (wg_lead()) {
-        // HandleInvalidStep
-        if (++sh.n_invalid >= o.max_num_consecutive_invalid_steps) sh.status = CLC_FAILURE;
-        sh.radius = sh.radius / sh.decrease_factor;
-        sh.decrease_factor *= 2.0;
-        sh.reuse_diagonal = 1;
-        sh.it_cost = sh.x_cost;
-        sh.it_gmax = sh.gmax;
-      }
-      wg_barrier();
-      if (sh.status != CLC_RUNNING) break;
-    }
-    if (sh.status != CLC_RUNNING) break;
-    // ---- the candidate ----
-    evaluate(a, pr, sh, 1 - sh.cur);
-    if (wg_lead()) {
-      sh.n_evals++;
-      const double cost_e = sh.tot[1 - sh.cur][E_COST - E_C];
-      const double candidate_cost = finite_d(cost_e) ? cost_e : 1.7976931348623157e308;
-      const double step_norm = sqrt_pos(sh.red[2]);
-      const double cost_change = sh.x_cost - candidate_cost;
-      sh.step_ok = 0;  // from here: 1 = accepted
-      if (step_norm <= o.parameter_tolerance * (sh.x_norm + o.parameter_tolerance)) {
-        sh.status = CLC_CONVERGENCE_PARAMETER;
-      } else if (fabs(cost_change) <= o.function_tolerance * sh.x_cost) {
-        sh.status = CLC_CONVERGENCE_FUNCTION;
-      } else {
-        const double relative_decrease = cost_change * rcp_pos_safe(sh.model_cost_change);
-        if (relative_decrease > o.min_relative_decrease) {
-          // HandleSuccessfulStep
-          sh.step_ok = 1;
-          sh.x_norm = sqrt_pos(sh.red[3]);
-          sh.x_cost = candidate_cost;
-          const double q = 2.0 * relative_decrease - 1.0;
-          double den = 1.0 - q * q * q;
-          den = den > (1.0 / 3.0) ? den : (1.0 / 3.0);
-          sh.radius = sh.radius * rcp_pos(den);
-          sh.radius = sh.radius < o.max_trust_region_radius ? sh.radius : o.max_trust_region_radius;
-          sh.decrease_factor = 2.0;
-          sh.reuse_diagonal = 0;
-          sh.it_successful = 1;
-          sh.it_cost = candidate_cost;
-        } else {
-          // HandleUnsuccessfulStep
-          sh.radius = sh.radius / sh.decrease_factor;
-          sh.decrease_factor *= 2.0;
-          sh.reuse_diagonal = 1;
-          sh.it_cost = candidate_cost;
-          sh.it_gmax = sh.gmax;
-        }
-      }
-    }
-    wg_barrier();
-    if (sh.status != CLC_RUNNING) break;
-    if (sh.step_ok) {
-      if (sh.move_i)
-        each_image(pr.P, [&](long long j) {
-          CalImage& im = pr.ws[j];
-          if (im.st != CLC_CAMCAL_OK) return;
-#pragma unroll
-          for (int i = 0; i < 7; ++i) im.x[i] = im.xe[i];
-        });
-      wg_barrier();  // (every thread has read step_ok and cur)
-      if (wg_lead()) {
-        sh.cur = 1 - sh.cur;
-        CLC_JT_ROLLED for (int i = 0; i < NK; ++i) sh.kc[i] = sh.kce[i];
-      }
-      wg_barrier();
-      gradient_norm(pr, sh);
-      if (wg_lead()) sh.it_gmax = sh.gmax;
-      wg_barrier();
-    } else {
-      wg_barrier();
+  static CLC_HD void block_candidate(Shared& sh, double& sn, double& xn) {
+    CLC_AW_ROLLED for (int p = 0; p < NK; ++p) {
+      // a held intrinsic (scale 0, step 0) keeps its bits
+      const double d = sh.step_c[p] * sh.scale_c[p];
+      const double v = sh.scale_c[p] != 0.0 ? sh.kc[p] + d : sh.kc[p];
+      sh.kce[p] = v;
+      sn += (sh.kc[p] - v) * (sh.kc[p] - v);
+      xn += v * v;
     }
   }
-  // ---- the outputs: a candidate that was not accepted leaves no trace ----
-  wg_barrier();
-  const bool failed = sh.status == CLC_FAILURE;
-  if (!failed && sh.move_i)
-    each_image(pr.P, [&](long long j) {
-      const CalImage& im = pr.ws[j];
-      if (im.st != CLC_CAMCAL_OK) return;
-      const long long img = pr.i0 + j;
-      const double sgn = im.x[6] < 0.0 ? -1.0 : 1.0;
-      a.q[4 * img] = sgn * im.x[6];
-      a.q[4 * img + 1] = sgn * im.x[3];
-      a.q[4 * img + 2] = sgn * im.x[4];
-      a.q[4 * img + 3] = sgn * im.x[5];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) a.t[3 * img + i] = im.x[i];
-    });
-  if (wg_lead()) {
-    clc_summary sm;
-    cp::summary_empty(sm);
-    sm.termination = sh.status;
-    if (sh.n_evals > 0) {
-      sm.num_iterations = sh.n_trace > 0 ? sh.n_trace - 1 : 0;
-      sm.num_successful_steps = sh.num_successful;
-      sm.num_unsuccessful_steps = sh.num_unsuccessful;
-      sm.num_evaluations = sh.n_evals;
-      sm.initial_cost = sh.initial_cost;
-      sm.final_cost = sh.x_cost;
-    }
-    a.summaries[pb] = sm;
+  static CLC_HD void accept_block(Shared& sh) {
+    CLC_AW_ROLLED for (int i = 0; i < NK; ++i) sh.kc[i] = sh.kce[i];
+  }
+  static CLC_HD double* information(const Args& a) { return a.H_cam; }
+  static CLC_HD void write_outputs(const Args& a, long long pb, const Shared& sh, bool failed) {
     if (!failed && sh.move_c)
-      CLC_JT_ROLLED for (int f = 0; f < sh.n_free; ++f) {
+      CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) {
         const int i = sh.free_idx[f];
         if (i < 4) a.cams[pb].proj[i] = sh.kc[i]; else a.cams[pb].dist[i - 4] = sh.kc[i];
       }
@@ -861,14 +398,10 @@ CLC_HD void camcal_problem(const CalArgs& a, long long pb, CalShared& sh) {
       a.rms[pb] = have ? a.sigma_px * sqrt(2.0 * sh.x_cost / (double)sh.n_corners) : __builtin_nan("");
     }
   }
-  if (a.H_cam) {
-    if (!failed && sh.n_evals > 0) {
-      marginal_information(a, pr, sh, a.H_cam + 64 * pb);
-    } else if (wg_lead()) {
-      CLC_JT_ROLLED for (int i = 0; i < 64; ++i) a.H_cam[64 * pb + i] = __builtin_nan("");
-    }
-  }
-}
+};
+
+// One problem: every thread of its workgroup calls it (host: once).
+CLC_HD void camcal_problem(const CalArgs& a, long long pb, CalShared& sh) { aw::arrow_problem<CalTraits>(a, pb, sh); }
 
 // ---- the closed-form focal start ---------------------------------------------------------------------------------------------
 struct GuessShared {

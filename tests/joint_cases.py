@@ -81,7 +81,7 @@ def seeded(name):
     return [problem(name, seed + (0 if name == "radtan" else 1000), *shape) for seed, *shape in SEEDED]
 
 
-WAVES, THREADS = 4, 256  # csrc/clc_joint.hpp: JOINT_WAVES, JOINT_THREADS
+WAVES, THREADS = 4, 256  # csrc/clc_arrow.hpp: ARROW_WAVES, ARROW_THREADS
 
 
 def edge_problems(name, seed=7):

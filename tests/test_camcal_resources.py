@@ -1,4 +1,4 @@
-"""Build-time guard of the kernels of the intrinsic calibration (K19, csrc/clc_camcal.hpp), without a GPU: hipcc's
+"""Build-time guard of the kernels of the intrinsic calibration (K19, csrc/clc_camcal.hpp, clc_arrow.hpp), without a GPU: hipcc's
 kernel-resource-usage remarks for gfx950 over abi_camcal.hip only.  camcal_kernel — the evaluation waves, the per-lane Schur step and
 the controller in one kernel — and homography_kernel use no scratch memory and spill no VGPR.  The register and LDS figures they are
 built with are printed and recorded in DESIGN.md (K19), not fixed here."""

@@ -1,4 +1,4 @@
-"""K18 (csrc/clc_joint.hpp) on the host: the evaluation blocks, the Schur step, the controller and the outputs compiled with g++
+"""K18 (csrc/clc_joint.hpp, clc_arrow.hpp) on the host: the evaluation blocks, the Schur step, the controller and the outputs compiled with g++
 (tests/shim/joint_shim.cpp) against the numpy / scipy restatement tests/joint_ref.py on the seeded sets of tests/joint_cases.py:
 Jacobians against central differences through Plus; the minimiser, the final cost, H_cl and the cost shares; inv(H_cl) against the
 dense normal matrix; the held-board-poses route against the oracle's solve of the records; no laser points; noise-free data;

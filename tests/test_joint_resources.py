@@ -1,4 +1,4 @@
-"""Build-time guard of the kernel of the joint refinement (K18, csrc/clc_joint.hpp), without a GPU: hipcc's kernel-resource-usage
+"""Build-time guard of the kernel of the joint refinement (K18, csrc/clc_joint.hpp, clc_arrow.hpp), without a GPU: hipcc's kernel-resource-usage
 remarks for gfx950 over abi_joint.hip only.  joint_refine_kernel — the evaluation waves, the per-lane Schur step and the controller
 in one kernel — uses no scratch memory, spills no VGPR and stays within the figures it was built with; the small kernel that reads
 the ranges of a device-array call stays small."""
