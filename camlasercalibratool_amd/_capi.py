@@ -40,6 +40,8 @@ EXPORTED = [
     "clc_alt_pose_options_default", "clc_board_poses_alternate", "clc_board_poses_alternate_device",
     "clc_joint_options_default", "clc_joint_refine", "clc_joint_refine_device",
     "clc_camcal_options_default", "clc_camera_guess", "clc_camera_guess_device", "clc_camera_calibrate", "clc_camera_calibrate_device",
+    "clc_guidance_options_default", "clc_score_board_poses", "clc_score_board_poses_device", "clc_select_board_poses",
+    "clc_select_board_poses_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -55,6 +57,7 @@ HOOKS = [
     "clc_debug_coop_set_tag", "clc_debug_layout", "clc_debug_lm_profile", "clc_time_steps", "clc_time_batched_eval", "clc_time_eval",
     "clc_debug_comm_create_layout", "clc_debug_single_controller", "clc_debug_fast_small",
     "clc_debug_lane_map_builds", "clc_debug_assemble_lines", "clc_debug_station_walk", "clc_debug_sweep_records",
+    "clc_debug_guidance_dirs", "clc_debug_guidance_score_rows",
 ]
 
 
@@ -185,6 +188,14 @@ class CamcalOptions(C.Structure):
     _fields_ = [("sigma_px", C.c_double), ("hold_mask", C.c_uint32), ("hold_board_poses", C.c_int32)]
 
 
+class GuidanceOptions(C.Structure):
+    """clc_guidance_options (include/clc.h): the scan model, the board rectangle in board coordinates and the criterion of K20."""
+    _fields_ = [("n_rays", C.c_int32), ("min_points", C.c_int32), ("angle_min", C.c_double), ("angle_increment", C.c_double),
+                ("range_min", C.c_double), ("range_max", C.c_double), ("board_min", C.c_double * 2), ("board_max", C.c_double * 2),
+                ("eig_floor", C.c_double), ("criterion", C.c_int32), ("reserved", C.c_int32)]
+
+
+GUIDE_LOGDET, GUIDE_MIN_EIG = 0, 1  # CLC_GUIDE_*
 JOINT_OK, JOINT_TOO_FEW, JOINT_NOT_KEPT, JOINT_NONFINITE = 1, 0, -1, -2  # CLC_JOINT_*
 CAMCAL_OK, CAMCAL_TOO_FEW, CAMCAL_NOT_KEPT, CAMCAL_NONFINITE = 1, 0, -1, -2  # CLC_CAMCAL_*
 POSE_OK, POSE_TOO_FEW, POSE_DEGENERATE, POSE_NONFINITE, POSE_NO_CONSENSUS = 1, 0, -1, -2, -3  # CLC_POSE_*
@@ -324,6 +335,13 @@ def load(path: str):
             L.clc_camera_guess_device.argtypes = [V, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_size_t, V, V]
             L.clc_camera_calibrate.argtypes = [V] * 7 + [C.c_size_t, V, C.c_size_t] + [V] * 7
             L.clc_camera_calibrate_device.argtypes = [V] * 7 + [C.c_size_t, V, C.c_size_t] + [V] * 7
+        if hasattr(L, "clc_score_board_poses"):
+            L.clc_guidance_options_default.argtypes = [V]
+            L.clc_guidance_options_default.restype = None
+            L.clc_score_board_poses.argtypes = [V, V, V, V, C.c_size_t] + [V] * 6
+            L.clc_score_board_poses_device.argtypes = [V, V, V, V, C.c_size_t] + [V] * 6
+            L.clc_select_board_poses.argtypes = [V, V, V, V, C.c_size_t, V, V, C.c_size_t] + [V] * 5
+            L.clc_select_board_poses_device.argtypes = [V, V, V, V, C.c_size_t, V, V, C.c_size_t] + [V] * 5
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -399,6 +417,14 @@ def default_joint_options(camera) -> JointOptions:
     o = JointOptions()
     c = camera.to_c()
     lib().clc_joint_options_default(C.byref(o), C.byref(c))
+    return o
+
+
+def default_guidance_options() -> GuidanceOptions:
+    """clc_guidance_options_default: 1 081 rays over 270 degrees, ranges [0.05, 30), 50 points, the board [-0.043, 0.457]^2, floor 1e-8,
+    the floored log-determinant."""
+    o = GuidanceOptions()
+    lib().clc_guidance_options_default(C.byref(o))
     return o
 
 

@@ -613,6 +613,62 @@ def CamLaserCalibrationJoint(camera, corners_px: Sequence[np.ndarray], board_xy:
                                          use_linefitting_data, sigma_px, sigma_laser, solver, options)[0]
 
 
+@dataclass
+class GuidanceReport:
+    """What SuggestBoardPoses returns; indices in the caller's numbering of the candidates."""
+    chosen: np.ndarray        # [k] int64, in the order chosen, -1 padded
+    sv_after: np.ndarray      # [k, 6] eigenvalues of H after each round (NaN in the padding)
+    score_after: np.ndarray   # [k]
+    n_hits: np.ndarray        # [n] int32: rays on the board per candidate (-1: non-finite; 0 for a candidate outside the image)
+    in_image: np.ndarray      # [n] bool: every corner of the board rectangle projects inside the image (all True without a camera)
+    H0: np.ndarray            # [6, 6] the information of the recording at Tcl
+    sv0: np.ndarray           # [6] its eigenvalues, as the analysis pass prints them
+    H_after: np.ndarray       # [6, 6] H0 plus the chosen poses' predicted information
+
+
+def SuggestBoardPoses(obs: ObsLike, Tcl: np.ndarray, cand_q: np.ndarray, cand_t: np.ndarray, k: int = 5,
+                      options: Optional[_capi.GuidanceOptions] = None, camera=None, use_linefitting_data: bool = False,
+                      solver: Optional[Solver] = None) -> GuidanceReport:
+    """Pose guidance (K20): where to hold the board next.  Uploads the recording `obs`, takes H0 from the analysis pass at Tcl (4x4,
+    laser -> camera) and picks greedily k of the candidate board poses (cand_q [n, 4] w x y z, cand_t [n, 3], board in the camera
+    frame) by the predicted information of clc_select_board_poses.  camera (with a width and a height): candidates whose four
+    board-rectangle corners do not all project inside the image with P_z > 0 are dropped first.  H mixes metres and radians, and the
+    prediction is taken at Tcl, which a degenerate recording leaves loose along its null directions."""
+    sv = solver or _shared_solver()
+    ses = Session(obs, sv)
+    ses._ensure_stored()
+    sv.select_observations(use_linefitting_data, False)
+    pose = simdata.pose7_from_T(np.asarray(Tcl, dtype=np.float64))
+    H0, _, _, sv0, _, _ = sv.information(pose)
+    q = np.ascontiguousarray(cand_q, dtype=np.float64).reshape(-1, 4)
+    t = np.ascontiguousarray(cand_t, dtype=np.float64).reshape(-1, 3)
+    n = q.shape[0]
+    o = options or _capi.default_guidance_options()
+    in_image = np.ones(n, dtype=bool)
+    if camera is not None and camera.width > 0 and camera.height > 0 and n > 0:
+        R = simdata.quat_wxyz_to_rot(q).reshape(n, 3, 3)
+        X = np.array([[o.board_min[0], o.board_min[1]], [o.board_max[0], o.board_min[1]], [o.board_max[0], o.board_max[1]],
+                      [o.board_min[0], o.board_max[1]]])
+        P = R[:, None, :, 0] * X[None, :, 0, None] + R[:, None, :, 1] * X[None, :, 1, None] + t[:, None, :]  # [n, 4, 3]
+        with np.errstate(invalid="ignore"):
+            fin = np.isfinite(P).all(axis=(1, 2))
+            px = sv.camera_project(camera, np.where(fin[:, None, None], P, 1.0).reshape(-1, 3)).reshape(n, 4, 2)
+            ok = (P[:, :, 2] > 0) & (px[:, :, 0] >= 0) & (px[:, :, 0] < camera.width) & (px[:, :, 1] >= 0) & (px[:, :, 1] < camera.height)
+        in_image = fin & ok.all(axis=1)
+    idx = np.flatnonzero(in_image)
+    n_hits = np.zeros(n, dtype=np.int32)
+    kk = int(k)
+    chosen = np.full(kk, -1, dtype=np.int64)
+    if idx.size:
+        qs, ts = np.ascontiguousarray(q[idx]), np.ascontiguousarray(t[idx])
+        n_hits[idx] = sv.score_board_poses(pose, qs, ts, H0, o)["n_hits"]
+        r = sv.select_board_poses(pose, qs, ts, kk, H0, o)
+        got = r["chosen"] >= 0
+        chosen[got] = idx[r["chosen"][got]]
+        return GuidanceReport(chosen, r["sv_after"], r["score_after"], n_hits, in_image, H0, sv0, r["H_after"])
+    return GuidanceReport(chosen, np.full((kk, 6), np.nan), np.full(kk, np.nan), n_hits, in_image, H0, sv0, H0.copy())
+
+
 def CalibrateCamera(model: int, width: int, height: int, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], hold=None,
                     sigma_px: float = 0.3, camera0=None, solver: Optional[Solver] = None, options: Optional[Options] = None):
     """The camera's intrinsics from images of the board (K19): corners_px[i] [n_i, 2] pixels and board_xy[i] [n_i, 2] board-plane

@@ -672,3 +672,29 @@ def scan_points_host(scans: dict) -> np.ndarray:
             pts[off[k]:off[k + 1], 0] = np.where(ok, rr * np.cos(t), 1000.0)
             pts[off[k]:off[k + 1], 1] = np.where(ok, rr * np.sin(t), 1000.0)
     return pts
+
+
+# ----------------------------------------------------------------------------------
+# candidate board poses for the pose guidance (K20)
+# ----------------------------------------------------------------------------------
+def candidate_board_poses(seed: int, n: int, Tcl: np.ndarray, dist: Tuple[float, float] = (0.8, 3.0), bearing: float = 0.7,
+                          height: float = 0.15, max_angle: float = np.pi / 4,
+                          board_centre: Tuple[float, float] = (0.207, 0.207)) -> Tuple[np.ndarray, np.ndarray]:
+    """Seeded candidate board poses T_ca for clc_score_board_poses / clc_select_board_poses: the board's centre (board_centre in board
+    coordinates: the middle of the default rectangle [-0.043, 0.457]^2) is placed near the laser's scan plane — dist m from the laser,
+    within +-bearing rad of its x axis, +-height m off the plane — and the board is turned by R_ca = rot_zyx(U, U, U),
+    U ~ +-max_angle, from facing the camera squarely.  Tcl: 4x4 laser -> camera, or the pose [t, qx, qy, qz, qw].
+    -> (q_ca_wxyz [n, 4], t_ca [n, 3]).  With the defaults about half the candidates gather the 50 hits of a seen pose."""
+    T = np.asarray(Tcl, dtype=np.float64)
+    if T.shape == (7,):
+        T = T_from_pose7(T)
+    rng = np.random.default_rng(seed)
+    u = rng.random((n, 6))
+    r = dist[0] + u[:, 0] * (dist[1] - dist[0])
+    phi = (u[:, 1] * 2.0 - 1.0) * bearing
+    centre_l = np.stack([r * np.cos(phi), r * np.sin(phi), (u[:, 2] * 2.0 - 1.0) * height], 1)
+    ang = (u[:, 3:] * 2.0 - 1.0) * max_angle
+    Rca = rot_zyx(ang[:, 0], ang[:, 1], ang[:, 2])
+    centre_c = centre_l @ T[:3, :3].T + T[:3, 3]
+    t = centre_c - Rca[:, :, 0] * board_centre[0] - Rca[:, :, 1] * board_centre[1]
+    return _rot_to_quat_wxyz_vec(Rca), np.ascontiguousarray(t)

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, Iteration, JointOptions, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, GuidanceOptions, Iteration, JointOptions, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -678,6 +678,73 @@ class Solver:
                                               V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
                                               V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
                                               V(summaries_ptr), V(H_cl_ptr), V(cost_parts_ptr), V(status_ptr)), "clc_joint_refine_device")
+
+    # ---- pose guidance (K20) ----
+    @staticmethod
+    def _guidance_args(pose_cl, H0, options):
+        pose = np.ascontiguousarray(pose_cl, dtype=np.float64).reshape(7)
+        H = None if H0 is None else np.ascontiguousarray(H0, dtype=np.float64).reshape(36)
+        return pose, H, (C.byref(options) if options is not None else None)
+
+    def score_board_poses(self, pose_cl: np.ndarray, q_ca_wxyz: np.ndarray, t_ca: np.ndarray, H0: Optional[np.ndarray] = None,
+                          options: Optional[GuidanceOptions] = None) -> dict:
+        """clc_score_board_poses (K20): for every candidate board pose (q_ca_wxyz [n, 4], t_ca [n, 3], the board in the camera frame)
+        the scanner's rays are cast through T_cl = pose_cl onto the board; H_add is the information clc_information's H would gain if
+        the pose were recorded, sv the eigenvalues of H0 + H_add (descending), score the criterion of `options` (None: the defaults).
+        H0 [6, 6] or None (zeros).  -> dict(n_hits [n] int32 (-1: a non-finite candidate), H_add [n, 6, 6], sv [n, 6], score [n])."""
+        q = np.ascontiguousarray(q_ca_wxyz, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_ca, dtype=np.float64).reshape(-1, 3)
+        if q.shape[0] != t.shape[0]:
+            raise ValueError("score_board_poses: q_ca_wxyz and t_ca need one row per candidate")
+        n = q.shape[0]
+        pose, H, o = self._guidance_args(pose_cl, H0, options)
+        nh = np.empty(n, dtype=np.int32); Ha = np.empty((n, 6, 6)); sv = np.empty((n, 6)); sc = np.empty(n)
+        V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_score_board_poses(self._h, o, V(pose), V(H), C.c_size_t(n), V(q), V(t), V(nh), V(Ha), V(sv), V(sc)),
+              "clc_score_board_poses")
+        return dict(n_hits=nh, H_add=Ha, sv=sv, score=sc)
+
+    def score_board_poses_device(self, pose_cl: np.ndarray, n_cand: int, q_ptr: int, t_ptr: int, n_hits_ptr: int = 0, H_add_ptr: int = 0,
+                                 sv_ptr: int = 0, score_ptr: int = 0, H0: Optional[np.ndarray] = None,
+                                 options: Optional[GuidanceOptions] = None):
+        """clc_score_board_poses_device: the candidates and the per-candidate outputs (each optional) are device arrays (data_ptr()s;
+        ready on the solver's stream); pose_cl, H0 and the options on the host."""
+        pose, H, o = self._guidance_args(pose_cl, H0, options)
+        V = lambda p: C.c_void_p(p or 0)
+        A = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_score_board_poses_device(self._h, o, A(pose), A(H), C.c_size_t(n_cand), V(q_ptr), V(t_ptr), V(n_hits_ptr),
+                                                   V(H_add_ptr), V(sv_ptr), V(score_ptr)), "clc_score_board_poses_device")
+
+    def _select_board_poses(self, name: str, pose_cl, H0, options, n: int, q, t, k: int) -> dict:
+        pose, H, o = self._guidance_args(pose_cl, H0, options)
+        kk = max(int(k), 0)
+        ch = np.full(kk, -1, dtype=np.int64); sva = np.full((kk, 6), np.nan); sca = np.full(kk, np.nan)
+        Hf = np.zeros((6, 6)) if H is None else H.reshape(6, 6).copy()
+        nc = C.c_int32(0)
+        A = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(getattr(self._L, name)(self._h, o, A(pose), A(H), C.c_size_t(n), q, t, C.c_size_t(kk), A(ch) if kk else None, A(sva), A(sca),
+                                     A(Hf), C.byref(nc)), name)
+        return dict(chosen=ch, sv_after=sva, score_after=sca, H_after=Hf, n_chosen=nc.value)
+
+    def select_board_poses(self, pose_cl: np.ndarray, q_ca_wxyz: np.ndarray, t_ca: np.ndarray, k: int, H0: Optional[np.ndarray] = None,
+                           options: Optional[GuidanceOptions] = None) -> dict:
+        """clc_select_board_poses (K20): a greedy choice of k candidates without replacement — every round picks the seen candidate not
+        yet chosen with the largest score of M + H_add (ties: the lowest index), then M += H_add[chosen]; M starts at H0.
+        -> dict(chosen [k] int64 in order, -1 padded; sv_after [k, 6] and score_after [k] of M after each round (NaN in the padding);
+        H_after [6, 6]; n_chosen)."""
+        q = np.ascontiguousarray(q_ca_wxyz, dtype=np.float64).reshape(-1, 4)
+        t = np.ascontiguousarray(t_ca, dtype=np.float64).reshape(-1, 3)
+        if q.shape[0] != t.shape[0]:
+            raise ValueError("select_board_poses: q_ca_wxyz and t_ca need one row per candidate")
+        return self._select_board_poses("clc_select_board_poses", pose_cl, H0, options, q.shape[0], q.ctypes.data_as(C.c_void_p),
+                                        t.ctypes.data_as(C.c_void_p), k)
+
+    def select_board_poses_device(self, pose_cl: np.ndarray, n_cand: int, q_ptr: int, t_ptr: int, k: int, H0: Optional[np.ndarray] = None,
+                                  options: Optional[GuidanceOptions] = None) -> dict:
+        """clc_select_board_poses_device: the candidates are device arrays (data_ptr()s; ready on the solver's stream); the results
+        come back to the host as select_board_poses' do."""
+        return self._select_board_poses("clc_select_board_poses_device", pose_cl, H0, options, n_cand, C.c_void_p(q_ptr or 0),
+                                        C.c_void_p(t_ptr or 0), k)
 
     # ---- camera intrinsics from the board images (K19) ----
     def camera_guess(self, model: int, width: int, height: int, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray):

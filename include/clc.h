@@ -1080,6 +1080,69 @@ int clc_camera_calibrate_device(clc_handle* h, const clc_options* opt, const clc
                                 double* t_ca_dev, clc_summary* summaries_dev, double* H_cam_dev, double* rms_px_dev,
                                 int32_t* image_status_dev);
 
+/* ---- pose guidance: rank candidate board poses by predicted information (K20) ---------------------------------------------
+ * clc_information's H = sum J^T J depends on the laser points and the poses, not on the residuals.  So for a candidate board pose
+ * T_ca (board in the camera frame, the convention of clc_store_observations' tag_q_wxyz / tag_t) the H_add that H would gain at
+ * the current T_cl = pose_cl ([t, qx qy qz qw]) if that pose were recorded is computed exactly, without a noise model:
+ *   per candidate  n = R_ca e3, d = -n.t_ca, m = R_cl^T n, d_l = n.t_cl + d   (R_ca from q without normalisation, as Eigen)
+ *   per ray i      dir_i = (cos th_i, sin th_i, 0), th_i = angle_min + i angle_increment in double;  rho_i = -d_l / (m.dir_i);
+ *                  p_i = rho_i dir_i (laser frame);  X_i = R_ca^T (R_cl p_i + t_cl - t_ca) (board frame)
+ *   hit            rho_i finite, range_min <= rho_i < range_max (TranScanToPoints), board_min <= (X_x, X_y) <= board_max (closed)
+ *   c hits; seen when c >= min_points:  H_add = (1 / c) sum_hits u u^T, u = [n, p x m]  (the factor's Jacobian row with the
+ *   reference's per-pose scale 1 / sqrt(c));  unseen: H_add = 0;  a candidate with a non-finite entry: unseen, n_hits = -1.
+ * sv: the eigenvalues of M = H0 + H_add, descending, as clc_information reports them.  score: CLC_GUIDE_LOGDET
+ * sum_k log max(sv_k, eig_floor), or CLC_GUIDE_MIN_EIG sv[5].  An unseen candidate scores as H0 itself.
+ * H mixes metres and radians, as the reference's printed singular values do; the prediction is taken at pose_cl, which on a
+ * degenerate recording is itself loose along the null directions. */
+#define CLC_GUIDE_LOGDET 0
+#define CLC_GUIDE_MIN_EIG 1
+typedef struct clc_guidance_options {
+  int32_t n_rays;         /* rays of a scan, 1 .. 2^24 */
+  int32_t min_points;     /* fewest hits of a seen candidate, >= 1 */
+  double angle_min;       /* rad */
+  double angle_increment; /* rad */
+  double range_min;       /* m; range_min < range_max */
+  double range_max;
+  double board_min[2];    /* the board rectangle in board coordinates, m; board_min <= board_max */
+  double board_max[2];
+  double eig_floor;       /* > 0 */
+  int32_t criterion;      /* CLC_GUIDE_* */
+  int32_t reserved;
+} clc_guidance_options;   /* 88 bytes */
+
+/* 1 081 rays over 270 degrees from -135 degrees, ranges [0.05, 30) (src/utilities.cpp:201), 50 points (the shortest segment
+ * AutoGetLinePts accepts), the board [-0.043, 0.457]^2 (src/LaseCamCalCeres.cpp:262-268), floor 1e-8 (the reference's null-space
+ * threshold, :371), CLC_GUIDE_LOGDET. */
+void clc_guidance_options_default(clc_guidance_options* gopt);
+
+/* n_cand candidates q_ca_wxyz[4 n], t_ca[3 n].  H0[36] (row-major, symmetric): the information already collected, clc_information's
+ * H at pose_cl; NULL: zeros.  Outputs, every one nullable: n_hits[n], H_add[36 n] row-major, sv[6 n], score[n].  gopt NULL: the
+ * defaults.  CLC_ERR_INVALID_ARG before any device work: NULL h, pose_cl or candidate arrays, n_rays <= 0 or > 2^24, min_points < 1,
+ * range_min >= range_max or NaN, a non-finite angle, an empty board rectangle, eig_floor <= 0, an unknown criterion;
+ * CLC_ERR_NONFINITE: a non-finite pose_cl or H0.  n_cand = 0: CLC_OK, nothing written.  One bad candidate never fails the call.
+ * Deterministic: the same bits on every run, and for a candidate alone or in a batch.  One enqueue, one synchronisation. */
+int clc_score_board_poses(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0, size_t n_cand,
+                          const double* q_ca_wxyz, const double* t_ca, int32_t* n_hits, double* H_add, double* sv, double* score);
+/* The same with the candidate arrays and the per-candidate outputs in DEVICE memory (ready on the handle's stream); gopt, pose_cl
+ * and H0 on the host.  The same bits as the host-array form. */
+int clc_score_board_poses_device(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0,
+                                 size_t n_cand, const double* q_ca_wxyz_dev, const double* t_ca_dev, int32_t* n_hits_dev,
+                                 double* H_add_dev, double* sv_dev, double* score_dev);
+
+/* A greedy choice of k candidates without replacement: M_0 = H0; round r picks the seen candidate not yet chosen with the largest
+ * score of M_r + H_add (ties: the lowest index; a score that is NaN is never picked), then M_{r+1} = M_r + H_add[chosen], a plain
+ * add in chosen order.  It stops when no such candidate remains.  chosen[k]: the indices in order, padded with -1;
+ * sv_after[6 k], score_after[k] (nullable): the eigenvalues and the score of M_{r+1} (NaN in the padding); H_after[36] (nullable):
+ * the last M; *n_chosen (nullable).  The rays are cast once; the k rounds are enqueued back to back and the call synchronises once.
+ * Errors as clc_score_board_poses, and k < 1 or chosen NULL: CLC_ERR_INVALID_ARG.  n_cand = 0: CLC_OK, nothing written. */
+int clc_select_board_poses(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0, size_t n_cand,
+                           const double* q_ca_wxyz, const double* t_ca, size_t k, int64_t* chosen, double* sv_after,
+                           double* score_after, double* H_after, int32_t* n_chosen);
+/* The same with the candidate arrays in DEVICE memory; the k-sized results and H_after on the host. */
+int clc_select_board_poses_device(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0,
+                                  size_t n_cand, const double* q_ca_wxyz_dev, const double* t_ca_dev, size_t k, int64_t* chosen,
+                                  double* sv_after, double* score_after, double* H_after, int32_t* n_chosen);
+
 #ifdef __cplusplus
 }
 #endif
