@@ -18,7 +18,7 @@ UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip",
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
            "clc_batchflow.hpp", "clc_campose.hpp"]
-HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
+HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
 # kernels of their own that include HEADERS and are included by none of them: the kernels whose measured constants csrc_sha16 guards
 # (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
 # abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md), those of abi_frontend.hip by clc_stations.hpp

@@ -3,6 +3,7 @@
 // clc_board_poses_alternate(_device): the planar fit's second minimum (K17 in clc_altpose.hpp).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
+#include "abi_lift.hpp"
 #include "clc_campose.hpp"
 #include "clc_robustpose.hpp"
 #include "clc_altpose.hpp"
@@ -11,22 +12,64 @@ using namespace clc_abi;
 
 namespace {
 
-unsigned lift_blocks(size_t n) { return (unsigned)((n + clc::cp::LIFT_THREADS - 1) / clc::cp::LIFT_THREADS); }
+// What every board-pose call works on, in device memory: the images' corner ranges off[n_images + 1] inside px / board, of which
+// the call covers the corners [first, first + n_corners).
+struct Corners {
+  const float *px, *board;
+  const long long* off;
+  long long first;
+  size_t n_corners, n_images;
+};
 
-// lift (rounded) into lifted_dev[2 * n_corners] (corner `first` first), then one wave per image; every array on the device, offsets
-// absolute
-hipError_t launch_board_poses(clc_handle* h, const clc_camera& cam, const clc_options& opt, const float* corners_dev, const float* board_dev,
-                              const long long* off_dev, long long first, size_t n_corners, size_t n_images, float* lifted_dev,
-                              double* q_dev, double* t_dev, double* rms_dev, int32_t* status_dev, clc_summary* sum_dev) {
-  if (n_corners > 0) {
-    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<true>), dim3(lift_blocks(n_corners)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, cam,
-                       corners_dev + 2 * first, (long long)n_corners, nullptr, lifted_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(clc::cp::board_pose_kernel, dim3((unsigned)n_images), dim3(64), 0, h->stream, opt, lifted_dev, board_dev, off_dev,
-                     first, q_dev, t_dev, rms_dev, status_dev, sum_dev);
-  return hipGetLastError();
+// The host arrays of a call up: the corners and board points from offsets[0] on and the rebased offsets (host_offsets), so first = 0.
+Corners upload_corners(Staging& st, const float* corners_px, const float* board_xy, const int64_t* offsets, const std::vector<long long>& rel,
+                       size_t n_corners) {
+  const long long first = n_corners > 0 ? (long long)offsets[0] : 0;  // (the arrays may be NULL when there is no corner)
+  const float* px = st.in(n_corners > 0 ? corners_px + 2 * first : nullptr, 2 * n_corners);
+  const float* board = st.in(n_corners > 0 ? board_xy + 2 * first : nullptr, 2 * n_corners);
+  return {px, board, st.in(rel.data(), rel.size()), 0, n_corners, rel.size() - 1};
+}
+
+// The corner range of a _device call: the two ends of its offsets (a small read and a synchronise ahead of the call's enqueue; the
+// lifted corners go to a scratch array of that size).  The offsets in between are not validated.
+int device_offset_ends(clc_handle* h, const char* who, const int64_t* offsets_dev, size_t n, long long ends[2]) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
+  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": offsets not monotone").c_str());
+  return CLC_OK;
+}
+Corners device_corners(const float* corners_px_dev, const float* board_xy_dev, const int64_t* offsets_dev, const long long ends[2], size_t n_images) {
+  return {corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev), ends[0], (size_t)(ends[1] - ends[0]), n_images};
+}
+
+// K10 on device arrays: the lift, then one wave per image.
+void enqueue_board_poses(Staging& st, const clc_camera& cam, const clc_options& opt, const Corners& c, double* q_dev, double* t_dev,
+                         double* rms_dev, int32_t* status_dev, clc_summary* sum_dev) {
+  const float* lifted = enqueue_lift(st, cam, c.px, c.first, c.n_corners);
+  if (!st.ok()) return;
+  hipLaunchKernelGGL(clc::cp::board_pose_kernel, dim3((unsigned)c.n_images), dim3(64), 0, st.stream(), opt, lifted, c.board, c.off, c.first,
+                     q_dev, t_dev, rms_dev, status_dev, sum_dev);
+  st.launched();
+}
+
+// The checks that clc_board_poses and its _device form make in the same order, up to the empty call.
+int board_pose_checks(const char* who, const clc_handle* h, bool required, const clc_camera* cam, const clc_options* opt_in, size_t n_images,
+                      clc_options* opt) {
+  const std::string w(who);
+  if (!h || (n_images > 0 && !required)) return fail(CLC_ERR_INVALID_ARG, (w + ": bad argument").c_str());
+  CLC_TRY(camera_check(cam, who));
+  CLC_TRY(pose_options(opt_in, opt, who));
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, (w + ": too many images").c_str());
+  return CLC_OK;
+}
+// The robust and the alternate calls check their options first (those refusals need no device), then the handle and the counts.
+int count_checks(const char* who, const clc_handle* h, bool required, size_t n_images) {
+  const std::string w(who);
+  if (!h || (n_images > 0 && !required)) return fail(CLC_ERR_INVALID_ARG, (w + ": bad argument").c_str());
+  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, (w + ": too many images").c_str());
+  return CLC_OK;
 }
 
 // The robust call's options: the caller's or the defaults; checked.
@@ -41,6 +84,15 @@ int robust_options(const clc_robust_pose_options* in, const clc_camera* cam, clc
   return CLC_OK;
 }
 
+// Every refusal of clc_board_poses_robust and its _device form up to the empty call: the options first (they need no device).
+int robust_checks(const char* who, const clc_handle* h, bool required, const clc_camera* cam, const clc_options* opt_in,
+                  const clc_robust_pose_options* ropt_in, size_t n_images, clc_options* opt, clc_robust_pose_options* ro) {
+  CLC_TRY(camera_check(cam, who));
+  CLC_TRY(pose_options(opt_in, opt, who));
+  CLC_TRY(robust_options(ropt_in, cam, ro, who));
+  return count_checks(who, h, required, n_images);
+}
+
 // What the robust call leaves per image, every array on the device (mask indexed by the absolute offsets; rms, summaries, best_group
 // nullable).
 struct RobustOut {
@@ -51,35 +103,33 @@ struct RobustOut {
   int32_t *n_inliers, *best_group, *n_fits;
 };
 
-// lift -> consensus -> (fit -> re-gate) x max_fits on the handle's stream, every launch sized by n_images, no read-back in between.
-// Scratch of the caller (indexed like lifted_dev, corner `first` first): lifted_dev, sub_l, sub_b [2 * n_corners]; flag [n_images].
-hipError_t launch_board_poses_robust(clc_handle* h, const clc_camera& cam, const clc_options& opt, const clc_robust_pose_options& ro,
-                                     const float* corners_dev, const float* board_dev, const long long* off_dev, long long first,
-                                     size_t n_corners, size_t n_images, float* lifted_dev, float* sub_l, float* sub_b, int32_t* flag,
-                                     const RobustOut& o) {
+// K16 on device arrays: lift -> consensus -> (fit -> re-gate) x max_fits on the handle's stream, every launch sized by n_images, no
+// read-back in between.  The counts are needed whether or not the caller takes them: o.n_inliers / o.n_fits NULL -> scratch.
+void enqueue_board_poses_robust(Staging& st, const clc_camera& cam, const clc_options& opt, const clc_robust_pose_options& ro,
+                                const Corners& c, RobustOut o) {
   namespace rp = clc::rp;
-  if (n_corners > 0) {
-    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<true>), dim3(lift_blocks(n_corners)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, cam,
-                       corners_dev + 2 * first, (long long)n_corners, nullptr, lifted_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  const dim3 grid((unsigned)n_images), block(64);
-  hipLaunchKernelGGL(rp::tag_consensus_kernel, grid, block, 0, h->stream, lifted_dev, board_dev, off_dev, first, ro.hyp_threshold,
+  const float* lifted = enqueue_lift(st, cam, c.px, c.first, c.n_corners);
+  float* sub_l = st.scratch<float>(2 * c.n_corners);  // indexed like lifted: corner `first` first
+  float* sub_b = st.scratch<float>(2 * c.n_corners);
+  int32_t* flag = st.scratch<int32_t>(c.n_images);
+  if (!o.n_inliers) o.n_inliers = st.scratch<int32_t>(c.n_images);
+  if (!o.n_fits) o.n_fits = st.scratch<int32_t>(c.n_images);
+  if (!st.ok()) return;
+  const dim3 grid((unsigned)c.n_images), block(64);
+  hipLaunchKernelGGL(rp::tag_consensus_kernel, grid, block, 0, st.stream(), lifted, c.board, c.off, c.first, ro.hyp_threshold,
                      (int)ro.min_inliers, o.mask, sub_l, sub_b, o.n_inliers, flag, o.n_fits, o.best_group, o.q, o.t, o.rms, o.status,
                      o.summaries);
-  hipError_t e = hipGetLastError();
-  for (int round = 0; round < ro.max_fits && e == hipSuccess; ++round) {
-    hipLaunchKernelGGL(rp::board_pose_subset_kernel, grid, block, 0, h->stream, opt, sub_l, sub_b, off_dev, first, flag, o.n_inliers,
+  st.launched();
+  for (int round = 0; round < ro.max_fits && st.ok(); ++round) {
+    hipLaunchKernelGGL(rp::board_pose_subset_kernel, grid, block, 0, st.stream(), opt, sub_l, sub_b, c.off, c.first, flag, o.n_inliers,
                        o.n_fits, o.q, o.t, o.rms, o.status, o.summaries);
-    e = hipGetLastError();
-    if (e != hipSuccess) break;
-    hipLaunchKernelGGL(rp::pose_rescore_kernel, grid, block, 0, h->stream, lifted_dev, board_dev, off_dev, first, ro.threshold,
+    st.launched();
+    if (!st.ok()) return;
+    hipLaunchKernelGGL(rp::pose_rescore_kernel, grid, block, 0, st.stream(), lifted, c.board, c.off, c.first, ro.threshold,
                        (int)ro.min_inliers, (int)ro.max_fits, o.mask, sub_l, sub_b, o.n_inliers, flag, o.n_fits, o.q, o.t, o.rms,
                        o.status, o.summaries);
-    e = hipGetLastError();
+    st.launched();
   }
-  return e;
 }
 
 // The alternate call's options: the caller's or the defaults; checked.
@@ -91,6 +141,15 @@ int alt_options(const clc_alt_pose_options* in, clc_alt_pose_options* o, const c
   return CLC_OK;
 }
 
+// Every refusal of clc_board_poses_alternate and its _device form up to the empty call: the options first.
+int alt_checks(const char* who, const clc_handle* h, bool required, const clc_camera* cam, const clc_options* opt_in,
+               const clc_alt_pose_options* aopt_in, size_t n_images, clc_options* opt, clc_alt_pose_options* ao) {
+  CLC_TRY(camera_check(cam, who));
+  CLC_TRY(pose_options(opt_in, opt, who));
+  CLC_TRY(alt_options(aopt_in, ao, who));
+  return count_checks(who, h, required, n_images);
+}
+
 // What the alternate call reads per image, every array on the device (inlier nullable, indexed by the absolute offsets).
 struct AltIn {
   const unsigned char* inlier;
@@ -98,27 +157,25 @@ struct AltIn {
   const int32_t* status;
 };
 
-// lift -> start -> fit on the handle's stream, every launch sized by n_images, no read-back in between.  Scratch of the caller
-// (indexed like lifted_dev, corner `first` first): lifted_dev, sub_l, sub_b [2 * n_corners]; cnt, flag [n_images]; start7 [7 * n_images].
-hipError_t launch_board_poses_alternate(clc_handle* h, const clc_camera& cam, const clc_options& opt, const clc_alt_pose_options& ao,
-                                        const float* corners_dev, const float* board_dev, const long long* off_dev, long long first,
-                                        size_t n_corners, size_t n_images, const AltIn& in, float* lifted_dev, float* sub_l, float* sub_b,
-                                        int32_t* cnt, int32_t* flag, double* start7, const clc::ap::AltOut& o) {
+// K17 on device arrays: lift -> start -> fit on the handle's stream, every launch sized by n_images, no read-back in between.
+void enqueue_board_poses_alternate(Staging& st, const clc_camera& cam, const clc_options& opt, const clc_alt_pose_options& ao,
+                                   const Corners& c, const AltIn& in, const clc::ap::AltOut& o) {
   namespace ap = clc::ap;
-  if (n_corners > 0) {
-    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<true>), dim3(lift_blocks(n_corners)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, cam,
-                       corners_dev + 2 * first, (long long)n_corners, nullptr, lifted_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  const dim3 grid((unsigned)n_images), block(64);
-  hipLaunchKernelGGL(ap::alt_start_kernel, grid, block, 0, h->stream, lifted_dev, board_dev, off_dev, first, in.inlier, in.q, in.t,
-                     in.status, sub_l, sub_b, cnt, flag, start7, o);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ap::board_pose_from_start_kernel, grid, block, 0, h->stream, opt, ao, sub_l, sub_b, off_dev, first, flag, cnt, start7,
+  const float* lifted = enqueue_lift(st, cam, c.px, c.first, c.n_corners);
+  float* sub_l = st.scratch<float>(2 * c.n_corners);  // indexed like lifted: corner `first` first
+  float* sub_b = st.scratch<float>(2 * c.n_corners);
+  int32_t* cnt = st.scratch<int32_t>(c.n_images);
+  int32_t* flag = st.scratch<int32_t>(c.n_images);
+  double* start7 = st.scratch<double>(7 * c.n_images);
+  if (!st.ok()) return;
+  const dim3 grid((unsigned)c.n_images), block(64);
+  hipLaunchKernelGGL(ap::alt_start_kernel, grid, block, 0, st.stream(), lifted, c.board, c.off, c.first, in.inlier, in.q, in.t, in.status,
+                     sub_l, sub_b, cnt, flag, start7, o);
+  st.launched();
+  if (!st.ok()) return;
+  hipLaunchKernelGGL(ap::board_pose_from_start_kernel, grid, block, 0, st.stream(), opt, ao, sub_l, sub_b, c.off, c.first, flag, cnt, start7,
                      in.q, in.t, o);
-  return hipGetLastError();
+  st.launched();
 }
 
 }  // namespace
@@ -141,17 +198,15 @@ int clc_camera_lift(clc_handle* h, const clc_camera* cam, const float* px, size_
   if (n == 0) return CLC_OK;
   if (n > 0x3FFFFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_camera_lift: too many points");
   CLC_HIP(hipSetDevice(h->device));
-  DevBuf<float> bp(&h->pool);
-  DevBuf<double> bo(&h->pool);
-  CLC_HIP(bp.alloc(2 * n));
-  CLC_HIP(bo.alloc(2 * n));
-  CLC_HIP(hipMemcpyAsync(bp.p, px, 2 * n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL((clc::cp::campose_lift_kernel<false>), dim3(lift_blocks(n)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, *cam, bp.p,
-                     (long long)n, bo.p, nullptr);
-  CLC_HIP(hipGetLastError());
-  CLC_HIP(hipMemcpyAsync(xy_norm, bo.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  Staging st(h);
+  const float* px_dev = st.in(px, 2 * n);
+  double* out_dev = st.out(xy_norm, 2 * n);
+  if (st.ok()) {
+    hipLaunchKernelGGL((clc::cp::campose_lift_kernel<false>), dim3(lift_blocks(n)), dim3(clc::cp::LIFT_THREADS), 0, st.stream(), *cam, px_dev,
+                       (long long)n, out_dev, nullptr);
+    st.launched();
+  }
+  return st.finish("clc_camera_lift");
 }
 
 int clc_camera_project(clc_handle* h, const clc_camera* cam, const double pose7[7], const double* pts, size_t n, double* px) {
@@ -167,89 +222,57 @@ int clc_camera_project(clc_handle* h, const clc_camera* cam, const double pose7[
   if (n == 0) return CLC_OK;
   if (n > 0x3FFFFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_camera_project: too many points");
   CLC_HIP(hipSetDevice(h->device));
-  DevBuf<double> bp(&h->pool), bo(&h->pool);
-  CLC_HIP(bp.alloc(3 * n));
-  CLC_HIP(bo.alloc(2 * n));
-  CLC_HIP(hipMemcpyAsync(bp.p, pts, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(clc::cp::campose_project_kernel, dim3(lift_blocks(n)), dim3(clc::cp::LIFT_THREADS), 0, h->stream, *cam, pose,
-                     pose7 ? 1 : 0, bp.p, (long long)n, bo.p);
-  CLC_HIP(hipGetLastError());
-  CLC_HIP(hipMemcpyAsync(px, bo.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  Staging st(h);
+  const double* pts_dev = st.in(pts, 3 * n);
+  double* px_dev = st.out(px, 2 * n);
+  if (st.ok()) {
+    hipLaunchKernelGGL(clc::cp::campose_project_kernel, dim3(lift_blocks(n)), dim3(clc::cp::LIFT_THREADS), 0, st.stream(), *cam, pose,
+                       pose7 ? 1 : 0, pts_dev, (long long)n, px_dev);
+    st.launched();
+  }
+  return st.finish("clc_camera_project");
 }
 
 int clc_board_poses(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const float* corners_px, const float* board_xy,
                     const int64_t* offsets, size_t n_images, double* q_ca_wxyz, double* t_ca, double* rms, int32_t* status,
                     clc_summary* summaries) {
-  if (!h || (n_images > 0 && (!offsets || !q_ca_wxyz || !t_ca || !status)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: bad argument");
-  CLC_TRY(camera_check(cam, "clc_board_poses"));
+  const char* who = "clc_board_poses";
   clc_options opt;
-  CLC_TRY(pose_options(opt_in, &opt, "clc_board_poses"));
+  CLC_TRY(board_pose_checks(who, h, offsets && q_ca_wxyz && t_ca && status, cam, opt_in, n_images, &opt));
   if (n_images == 0) return CLC_OK;
-  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: too many images");
   std::vector<long long> rel;
   size_t M;
-  CLC_TRY(host_offsets("clc_board_poses", offsets, n_images, true, nullptr, &rel, &M));
+  CLC_TRY(host_offsets(who, offsets, n_images, true, nullptr, &rel, &M));
   if (M > 0 && (!corners_px || !board_xy)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses: bad argument");
   CLC_HIP(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  DevBuf<double> bq(&h->pool), bt(&h->pool), br(&h->pool);
-  DevBuf<int32_t> bs(&h->pool);
-  DevBuf<clc_summary> bsum(&h->pool);
-  CLC_HIP(bc.alloc(2 * M)); CLC_HIP(bb.alloc(2 * M)); CLC_HIP(bl.alloc(2 * M)); CLC_HIP(boff.alloc(n_images + 1));
-  CLC_HIP(bq.alloc(4 * n_images)); CLC_HIP(bt.alloc(3 * n_images)); CLC_HIP(bs.alloc(n_images));
-  if (rms) CLC_HIP(br.alloc(n_images));
-  if (summaries) CLC_HIP(bsum.alloc(n_images));
-  if (M > 0) {
-    CLC_HIP(hipMemcpyAsync(bc.p, corners_px + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    CLC_HIP(hipMemcpyAsync(bb.p, board_xy + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  }
-  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n_images + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(launch_board_poses(h, *cam, opt, bc.p, bb.p, boff.p, 0, M, n_images, bl.p, bq.p, bt.p, rms ? br.p : nullptr, bs.p,
-                             summaries ? bsum.p : nullptr));
-  CLC_HIP(hipMemcpyAsync(q_ca_wxyz, bq.p, 4 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(t_ca, bt.p, 3 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(status, bs.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (rms) CLC_HIP(hipMemcpyAsync(rms, br.p, n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (summaries) CLC_HIP(hipMemcpyAsync(summaries, bsum.p, n_images * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (summaries) {
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (size_t k = 0; k < n_images; ++k) summaries[k].solve_ms = ms;
-  }
+  const auto t0 = Clock::now();
+  Staging st(h);
+  const Corners c = upload_corners(st, corners_px, board_xy, offsets, rel, M);
+  double* q_dev = st.out(q_ca_wxyz, 4 * n_images);
+  double* t_dev = st.out(t_ca, 3 * n_images);
+  double* rms_dev = st.out_opt(rms, n_images);
+  int32_t* status_dev = st.out(status, n_images);
+  enqueue_board_poses(st, *cam, opt, c, q_dev, t_dev, rms_dev, status_dev, st.out_opt(summaries, n_images));
+  CLC_TRY(st.finish(who));
+  stamp_solve_ms(summaries, n_images, t0);
   return CLC_OK;
 }
 
 int clc_board_poses_device(clc_handle* h, const clc_camera* cam, const clc_options* opt_in, const float* corners_px_dev,
                            const float* board_xy_dev, const int64_t* offsets_dev, size_t n_images, double* q_ca_wxyz_dev,
                            double* t_ca_dev, double* rms_dev, int32_t* status_dev, clc_summary* summaries_dev) {
-  if (!h || (n_images > 0 && (!offsets_dev || !q_ca_wxyz_dev || !t_ca_dev || !status_dev)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: bad argument");
-  CLC_TRY(camera_check(cam, "clc_board_poses_device"));
+  const char* who = "clc_board_poses_device";
   clc_options opt;
-  CLC_TRY(pose_options(opt_in, &opt, "clc_board_poses_device"));
+  CLC_TRY(board_pose_checks(who, h, offsets_dev && q_ca_wxyz_dev && t_ca_dev && status_dev, cam, opt_in, n_images, &opt));
   if (n_images == 0) return CLC_OK;
-  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: too many images");
-  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
   CLC_HIP(hipSetDevice(h->device));
-  // the corner range: the two ends of the offsets (a small read; the lifted corners go to a scratch array of the same indexing)
   long long ends[2];
-  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n_images, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: offsets not monotone");
-  const size_t M = (size_t)(ends[1] - ends[0]);
-  if (M > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: bad argument");
-  DevBuf<float> bl(&h->pool);
-  CLC_HIP(bl.alloc(2 * M));
-  CLC_HIP(launch_board_poses(h, *cam, opt, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev), ends[0], M,
-                             n_images, bl.p, q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  CLC_TRY(device_offset_ends(h, who, offsets_dev, n_images, ends));
+  const Corners c = device_corners(corners_px_dev, board_xy_dev, offsets_dev, ends, n_images);
+  if (c.n_corners > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_device: bad argument");
+  Staging st(h);
+  enqueue_board_poses(st, *cam, opt, c, q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev);
+  return st.finish(who);
 }
 
 void clc_robust_pose_options_default(clc_robust_pose_options* o, const clc_camera* cam) {
@@ -267,57 +290,32 @@ int clc_board_poses_robust(clc_handle* h, const clc_camera* cam, const clc_optio
                            double* t_ca, double* rms, int32_t* status, clc_summary* summaries, uint8_t* inlier, int32_t* n_inliers,
                            int32_t* best_group, int32_t* n_fits) {
   const char* who = "clc_board_poses_robust";
-  // the options first: their refusals need no device
-  CLC_TRY(camera_check(cam, who));
   clc_options opt;
-  CLC_TRY(pose_options(opt_in, &opt, who));
   clc_robust_pose_options ro;
-  CLC_TRY(robust_options(ropt_in, cam, &ro, who));
-  if (!h || (n_images > 0 && (!offsets || !q_ca_wxyz || !t_ca || !status)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust: bad argument");
+  CLC_TRY(robust_checks(who, h, offsets && q_ca_wxyz && t_ca && status, cam, opt_in, ropt_in, n_images, &opt, &ro));
   if (n_images == 0) return CLC_OK;
-  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust: too many images");
   std::vector<long long> rel;
   size_t M;
   CLC_TRY(host_offsets(who, offsets, n_images, true, nullptr, &rel, &M));
   if (M > 0 && (!corners_px || !board_xy || !inlier)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust: bad argument");
   CLC_HIP(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  DevBuf<double> bq(&h->pool), bt(&h->pool), br(&h->pool);
-  DevBuf<int32_t> bs(&h->pool), bflag(&h->pool), bni(&h->pool), bnf(&h->pool), bbg(&h->pool);
-  DevBuf<clc_summary> bsum(&h->pool);
-  DevBuf<unsigned char> bm(&h->pool);
-  CLC_HIP(bc.alloc(2 * M)); CLC_HIP(bb.alloc(2 * M)); CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M));
-  CLC_HIP(bm.alloc(M)); CLC_HIP(boff.alloc(n_images + 1));
-  CLC_HIP(bq.alloc(4 * n_images)); CLC_HIP(bt.alloc(3 * n_images)); CLC_HIP(bs.alloc(n_images));
-  CLC_HIP(bflag.alloc(n_images)); CLC_HIP(bni.alloc(n_images)); CLC_HIP(bnf.alloc(n_images));
-  if (rms) CLC_HIP(br.alloc(n_images));
-  if (summaries) CLC_HIP(bsum.alloc(n_images));
-  if (best_group) CLC_HIP(bbg.alloc(n_images));
-  if (M > 0) {
-    CLC_HIP(hipMemcpyAsync(bc.p, corners_px + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    CLC_HIP(hipMemcpyAsync(bb.p, board_xy + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  }
-  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n_images + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const RobustOut out{bq.p, bt.p, rms ? br.p : nullptr, bs.p, summaries ? bsum.p : nullptr, bm.p, bni.p, best_group ? bbg.p : nullptr,
-                      bnf.p};
-  CLC_HIP(launch_board_poses_robust(h, *cam, opt, ro, bc.p, bb.p, boff.p, 0, M, n_images, bl.p, bsl.p, bsb.p, bflag.p, out));
-  CLC_HIP(hipMemcpyAsync(q_ca_wxyz, bq.p, 4 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(t_ca, bt.p, 3 * n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(status, bs.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (M > 0) CLC_HIP(hipMemcpyAsync(inlier + offsets[0], bm.p, M, hipMemcpyDeviceToHost, h->stream));
-  if (rms) CLC_HIP(hipMemcpyAsync(rms, br.p, n_images * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (summaries) CLC_HIP(hipMemcpyAsync(summaries, bsum.p, n_images * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
-  if (n_inliers) CLC_HIP(hipMemcpyAsync(n_inliers, bni.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (best_group) CLC_HIP(hipMemcpyAsync(best_group, bbg.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (n_fits) CLC_HIP(hipMemcpyAsync(n_fits, bnf.p, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (summaries) {
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (size_t k = 0; k < n_images; ++k) summaries[k].solve_ms = ms;
-  }
+  const auto t0 = Clock::now();
+  Staging st(h);
+  const Corners c = upload_corners(st, corners_px, board_xy, offsets, rel, M);
+  const size_t n = n_images;
+  RobustOut out{};
+  out.q = st.out(q_ca_wxyz, 4 * n);
+  out.t = st.out(t_ca, 3 * n);
+  out.rms = st.out_opt(rms, n);
+  out.status = st.out(status, n);
+  out.summaries = st.out_opt(summaries, n);
+  out.mask = st.out(M > 0 ? inlier + offsets[0] : nullptr, M);  // indexed by the absolute offsets
+  out.n_inliers = st.out_opt(n_inliers, n);
+  out.best_group = st.out_opt(best_group, n);
+  out.n_fits = st.out_opt(n_fits, n);
+  enqueue_board_poses_robust(st, *cam, opt, ro, c, out);
+  CLC_TRY(st.finish(who));
+  stamp_solve_ms(summaries, n, t0);
   return CLC_OK;
 }
 
@@ -327,36 +325,20 @@ int clc_board_poses_robust_device(clc_handle* h, const clc_camera* cam, const cl
                                   clc_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev, int32_t* best_group_dev,
                                   int32_t* n_fits_dev) {
   const char* who = "clc_board_poses_robust_device";
-  // the options first: their refusals need no device
-  CLC_TRY(camera_check(cam, who));
   clc_options opt;
-  CLC_TRY(pose_options(opt_in, &opt, who));
   clc_robust_pose_options ro;
-  CLC_TRY(robust_options(ropt_in, cam, &ro, who));
-  if (!h || (n_images > 0 && (!offsets_dev || !q_ca_wxyz_dev || !t_ca_dev || !status_dev)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: bad argument");
+  CLC_TRY(robust_checks(who, h, offsets_dev && q_ca_wxyz_dev && t_ca_dev && status_dev, cam, opt_in, ropt_in, n_images, &opt, &ro));
   if (n_images == 0) return CLC_OK;
-  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: too many images");
   CLC_HIP(hipSetDevice(h->device));
-  long long ends[2];  // the corner range, as clc_board_poses_device reads it
-  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n_images, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: offsets not monotone");
-  const size_t M = (size_t)(ends[1] - ends[0]);
-  if (M > 0 && (!corners_px_dev || !board_xy_dev || !inlier_dev))
+  long long ends[2];
+  CLC_TRY(device_offset_ends(h, who, offsets_dev, n_images, ends));
+  const Corners c = device_corners(corners_px_dev, board_xy_dev, offsets_dev, ends, n_images);
+  if (c.n_corners > 0 && (!corners_px_dev || !board_xy_dev || !inlier_dev))
     return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_robust_device: bad argument");
-  DevBuf<float> bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
-  DevBuf<int32_t> bflag(&h->pool), bni(&h->pool), bnf(&h->pool);
-  CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M)); CLC_HIP(bflag.alloc(n_images));
-  if (!n_inliers_dev) CLC_HIP(bni.alloc(n_images));
-  if (!n_fits_dev) CLC_HIP(bnf.alloc(n_images));
-  const RobustOut out{q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev, inlier_dev, n_inliers_dev ? n_inliers_dev : bni.p,
-                      best_group_dev, n_fits_dev ? n_fits_dev : bnf.p};
-  CLC_HIP(launch_board_poses_robust(h, *cam, opt, ro, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev),
-                                    ends[0], M, n_images, bl.p, bsl.p, bsb.p, bflag.p, out));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  Staging st(h);
+  enqueue_board_poses_robust(st, *cam, opt, ro, c, RobustOut{q_ca_wxyz_dev, t_ca_dev, rms_dev, status_dev, summaries_dev, inlier_dev,
+                                                            n_inliers_dev, best_group_dev, n_fits_dev});
+  return st.finish(who);
 }
 
 void clc_alt_pose_options_default(clc_alt_pose_options* o) {
@@ -373,71 +355,40 @@ int clc_board_poses_alternate(clc_handle* h, const clc_camera* cam, const clc_op
                               double* rot_angle, double* normal_angle, int32_t* kind, uint8_t* ambiguous, uint8_t* better,
                               clc_summary* summaries_alt) {
   const char* who = "clc_board_poses_alternate";
-  // the options first: their refusals need no device
-  CLC_TRY(camera_check(cam, who));
   clc_options opt;
-  CLC_TRY(pose_options(opt_in, &opt, who));
   clc_alt_pose_options ao;
-  CLC_TRY(alt_options(aopt_in, &ao, who));
-  if (!h || (n_images > 0 && (!offsets || !q_in_wxyz || !t_in || !status_in || !kind)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate: bad argument");
+  CLC_TRY(alt_checks(who, h, offsets && q_in_wxyz && t_in && status_in && kind, cam, opt_in, aopt_in, n_images, &opt, &ao));
   if (n_images == 0) return CLC_OK;
-  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate: too many images");
   std::vector<long long> rel;
   size_t M;
   CLC_TRY(host_offsets(who, offsets, n_images, true, nullptr, &rel, &M));
   if (M > 0 && (!corners_px || !board_xy)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate: bad argument");
   CLC_HIP(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = Clock::now();
+  Staging st(h);
+  const Corners c = upload_corners(st, corners_px, board_xy, offsets, rel, M);
   const size_t n = n_images;
-  DevBuf<float> bc(&h->pool), bb(&h->pool), bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  DevBuf<unsigned char> bm(&h->pool), bamb(&h->pool), bbet(&h->pool);
-  DevBuf<double> bqi(&h->pool), bti(&h->pool), bq(&h->pool), bt(&h->pool), bst7(&h->pool);
-  DevBuf<double> breal(&h->pool);  // rms, cost_in, cost_alt, ratio, rot_angle, normal_angle: n each
-  DevBuf<int32_t> bsi(&h->pool), bkind(&h->pool), bcnt(&h->pool), bflag(&h->pool);
-  DevBuf<clc_summary> bsum(&h->pool);
-  CLC_HIP(bc.alloc(2 * M)); CLC_HIP(bb.alloc(2 * M)); CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M));
-  CLC_HIP(boff.alloc(n + 1));
-  if (inlier) CLC_HIP(bm.alloc(M));
-  CLC_HIP(bqi.alloc(4 * n)); CLC_HIP(bti.alloc(3 * n)); CLC_HIP(bsi.alloc(n)); CLC_HIP(bkind.alloc(n)); CLC_HIP(bcnt.alloc(n));
-  CLC_HIP(bflag.alloc(n)); CLC_HIP(bst7.alloc(7 * n)); CLC_HIP(breal.alloc(6 * n));
-  if (q_alt_wxyz) CLC_HIP(bq.alloc(4 * n));
-  if (t_alt) CLC_HIP(bt.alloc(3 * n));
-  if (ambiguous) CLC_HIP(bamb.alloc(n));
-  if (better) CLC_HIP(bbet.alloc(n));
-  if (summaries_alt) CLC_HIP(bsum.alloc(n));
-  if (M > 0) {
-    CLC_HIP(hipMemcpyAsync(bc.p, corners_px + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    CLC_HIP(hipMemcpyAsync(bb.p, board_xy + 2 * offsets[0], 2 * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (inlier) CLC_HIP(hipMemcpyAsync(bm.p, inlier + offsets[0], M, hipMemcpyHostToDevice, h->stream));
-  }
-  CLC_HIP(hipMemcpyAsync(boff.p, rel.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(hipMemcpyAsync(bqi.p, q_in_wxyz, 4 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(hipMemcpyAsync(bti.p, t_in, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(hipMemcpyAsync(bsi.p, status_in, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-  double* const host_real[6] = {rms_alt, cost_in, cost_alt, ratio, rot_angle, normal_angle};
-  double* dev_real[6];
-  for (int i = 0; i < 6; ++i) dev_real[i] = host_real[i] ? breal.p + (size_t)i * n : nullptr;
-  const AltIn in{(inlier && M > 0) ? bm.p : nullptr, bqi.p, bti.p, bsi.p};
-  const clc::ap::AltOut out{q_alt_wxyz ? bq.p : nullptr, t_alt ? bt.p : nullptr, dev_real[0], dev_real[1], dev_real[2],
-                            dev_real[3], dev_real[4], dev_real[5], bkind.p, ambiguous ? bamb.p : nullptr, better ? bbet.p : nullptr,
-                            summaries_alt ? bsum.p : nullptr};
-  CLC_HIP(launch_board_poses_alternate(h, *cam, opt, ao, bc.p, bb.p, boff.p, 0, M, n, in, bl.p, bsl.p, bsb.p, bcnt.p, bflag.p, bst7.p,
-                                       out));
-  CLC_HIP(hipMemcpyAsync(kind, bkind.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (q_alt_wxyz) CLC_HIP(hipMemcpyAsync(q_alt_wxyz, bq.p, 4 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (t_alt) CLC_HIP(hipMemcpyAsync(t_alt, bt.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  for (int i = 0; i < 6; ++i)
-    if (host_real[i]) CLC_HIP(hipMemcpyAsync(host_real[i], dev_real[i], n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (ambiguous) CLC_HIP(hipMemcpyAsync(ambiguous, bamb.p, n, hipMemcpyDeviceToHost, h->stream));
-  if (better) CLC_HIP(hipMemcpyAsync(better, bbet.p, n, hipMemcpyDeviceToHost, h->stream));
-  if (summaries_alt) CLC_HIP(hipMemcpyAsync(summaries_alt, bsum.p, n * sizeof(clc_summary), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (summaries_alt) {
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (size_t k = 0; k < n; ++k) summaries_alt[k].solve_ms = ms;
-  }
+  AltIn in{};
+  in.inlier = st.in_opt(inlier && M > 0 ? inlier + offsets[0] : nullptr, M);  // indexed by the absolute offsets; none without corners
+  in.q = st.in(q_in_wxyz, 4 * n);
+  in.t = st.in(t_in, 3 * n);
+  in.status = st.in(status_in, n);
+  clc::ap::AltOut out{};
+  out.q = st.out_opt(q_alt_wxyz, 4 * n);
+  out.t = st.out_opt(t_alt, 3 * n);
+  out.rms = st.out_opt(rms_alt, n);
+  out.cost_in = st.out_opt(cost_in, n);
+  out.cost_alt = st.out_opt(cost_alt, n);
+  out.ratio = st.out_opt(ratio, n);
+  out.rot_angle = st.out_opt(rot_angle, n);
+  out.normal_angle = st.out_opt(normal_angle, n);
+  out.kind = st.out(kind, n);
+  out.ambiguous = st.out_opt(ambiguous, n);
+  out.better = st.out_opt(better, n);
+  out.summaries = st.out_opt(summaries_alt, n);
+  enqueue_board_poses_alternate(st, *cam, opt, ao, c, in, out);
+  CLC_TRY(st.finish(who));
+  stamp_solve_ms(summaries_alt, n, t0);
   return CLC_OK;
 }
 
@@ -449,36 +400,22 @@ int clc_board_poses_alternate_device(clc_handle* h, const clc_camera* cam, const
                                      double* normal_angle_dev, int32_t* kind_dev, uint8_t* ambiguous_dev, uint8_t* better_dev,
                                      clc_summary* summaries_alt_dev) {
   const char* who = "clc_board_poses_alternate_device";
-  // the options first: their refusals need no device
-  CLC_TRY(camera_check(cam, who));
   clc_options opt;
-  CLC_TRY(pose_options(opt_in, &opt, who));
   clc_alt_pose_options ao;
-  CLC_TRY(alt_options(aopt_in, &ao, who));
-  if (!h || (n_images > 0 && (!offsets_dev || !q_in_wxyz_dev || !t_in_dev || !status_in_dev || !kind_dev)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: bad argument");
+  CLC_TRY(alt_checks(who, h, offsets_dev && q_in_wxyz_dev && t_in_dev && status_in_dev && kind_dev, cam, opt_in, aopt_in, n_images, &opt,
+                     &ao));
   if (n_images == 0) return CLC_OK;
-  if (n_images > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: too many images");
   CLC_HIP(hipSetDevice(h->device));
-  long long ends[2];  // the corner range, as clc_board_poses_device reads it
-  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n_images, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: offsets not monotone");
-  const size_t M = (size_t)(ends[1] - ends[0]);
-  if (M > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: bad argument");
-  DevBuf<float> bl(&h->pool), bsl(&h->pool), bsb(&h->pool);
-  DevBuf<int32_t> bcnt(&h->pool), bflag(&h->pool);
-  DevBuf<double> bst7(&h->pool);
-  CLC_HIP(bl.alloc(2 * M)); CLC_HIP(bsl.alloc(2 * M)); CLC_HIP(bsb.alloc(2 * M)); CLC_HIP(bcnt.alloc(n_images));
-  CLC_HIP(bflag.alloc(n_images)); CLC_HIP(bst7.alloc(7 * n_images));
+  long long ends[2];
+  CLC_TRY(device_offset_ends(h, who, offsets_dev, n_images, ends));
+  const Corners c = device_corners(corners_px_dev, board_xy_dev, offsets_dev, ends, n_images);
+  if (c.n_corners > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_board_poses_alternate_device: bad argument");
+  Staging st(h);
   const AltIn in{inlier_dev, q_in_wxyz_dev, t_in_dev, status_in_dev};
   const clc::ap::AltOut out{q_alt_wxyz_dev, t_alt_dev, rms_alt_dev, cost_in_dev, cost_alt_dev, ratio_dev, rot_angle_dev, normal_angle_dev,
                             kind_dev, ambiguous_dev, better_dev, summaries_alt_dev};
-  CLC_HIP(launch_board_poses_alternate(h, *cam, opt, ao, corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev),
-                                       ends[0], M, n_images, in, bl.p, bsl.p, bsb.p, bcnt.p, bflag.p, bst7.p, out));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  enqueue_board_poses_alternate(st, *cam, opt, ao, c, in, out);
+  return st.finish(who);
 }
 
 }  // extern "C"

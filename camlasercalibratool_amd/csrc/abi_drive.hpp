@@ -1,7 +1,8 @@
 // abi_drive.hpp — host-side pieces the units of the C-ABI share: run-time flags to template arguments, the launch-ahead loop on
 // the pinned mailbox (abi_solve.hip, abi_batched.hip), the one launcher of the batched resident kernel (abi_batched.hip, abi_comm.hip),
-// and the front end's checks of options and host CSR offsets (abi_frontend.hip, abi_campose.hip).  Host code only (no kernel is
-// defined or changed here): _build.csrc_sha16(), the identity of what the kernels are built from, does not cover this file.
+// and the checks of options, host CSR offsets and problem offsets (abi_frontend.hip, abi_campose.hip, abi_joint.hip, abi_camcal.hip,
+// abi_guidance.hip).  The device memory of one call — uploads, scratch, copies back — is abi_staging.hpp's.  Host code only (no kernel
+// is defined or changed here): _build.csrc_sha16(), the identity of what the kernels are built from, does not cover this file.
 #pragma once
 #include "clc_abi_internal.hpp"
 
@@ -141,6 +142,24 @@ inline int host_offsets(const char* who, const int64_t* offsets, size_t n, bool 
   rel->assign(n + 1, 0);  // (after the checks: n itself may be what is wrong)
   for (size_t k = 1; k <= n; ++k) (*rel)[k] = offsets[k] - offsets[0];
   *total = (size_t)rel->back();
+  return CLC_OK;
+}
+
+// The counts and the problem offsets of the calls over problems of images (abi_joint.hip, abi_camcal.hip): what both forms of a
+// pair refuse alike, then (host form) the offsets [n_problems + 1] themselves, NULL being one problem over every image.
+inline int problem_count_checks(const char* who, size_t n_images, bool has_problem_offsets, size_t n_problems) {
+  const std::string w(who);
+  if (n_images > 0x7FFFFFFFull || n_problems > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, (w + ": too many images").c_str());
+  if (!has_problem_offsets && n_problems > 1) return fail(CLC_ERR_INVALID_ARG, (w + ": bad argument").c_str());
+  return CLC_OK;
+}
+inline int host_problem_offsets(const char* who, const int64_t* problem_offsets, size_t n_problems, size_t n_images) {
+  if (!problem_offsets) return CLC_OK;
+  std::vector<long long> rel;
+  size_t span = 0;
+  CLC_TRY(host_offsets(who, problem_offsets, n_problems, true, nullptr, &rel, &span));
+  if (n_problems > 0 && (size_t)problem_offsets[n_problems] > n_images)
+    return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": problem_offsets beyond n_images").c_str());
   return CLC_OK;
 }
 

@@ -2,6 +2,7 @@
 // board-segment detection, assembly of the offline flow's observations (K13), static stations (K14), interpolated tag poses (K15).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
+#include "abi_staging.hpp"
 #include "clc_scanseg.hpp"
 #include "clc_assemble.hpp"
 #include "clc_stations.hpp"
@@ -320,6 +321,41 @@ namespace {
 #ifdef CLC_TEST_HOOKS
 std::vector<double> g_last_lines;  // (m0, m1) per observation of the last assembly in this process (hooks build only)
 #endif
+
+// The one argument check of the assemble and sweep calls, host and _device forms (host forms: n_rays = 0, not known yet).
+int scan_call_check(const char* who, bool handles, size_t n_poses, bool poses, size_t n_scans, bool scans, size_t n_rays, const void* ranges) {
+  if (!handles || (n_poses > 0 && !poses) || (n_scans > 0 && !scans) || (n_rays > 0 && (!ranges || n_scans == 0)) ||
+      n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
+    return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": bad argument").c_str());
+  return CLC_OK;
+}
+
+// The stamped poses and the scans of such a call in device memory: offsets from 0, ranges from the first ray.
+struct ScanCall {
+  const double *stamp, *q, *t, *sstamp;
+  const float *ranges, *am, *ai, *rm;
+  const int64_t* off;
+  size_t n_rays;
+};
+// The host arrays of a host form: the offsets checked and rebased, then everything up into blocks of st.
+int upload_scan_call(clc_handle* h, Staging& st, const char* who, size_t n_poses, const double* pose_stamp, const double* q_wc_wxyz,
+                     const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
+                     const float* angle_increment, const float* range_min, const double* scan_stamp, ScanCall* c) {
+  std::vector<long long> rel;
+  CLC_TRY(host_offsets(who, offsets, n_scans, true, "rays", &rel, &c->n_rays));
+  if (c->n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": NULL ranges").c_str());
+  CLC_HIP(hipSetDevice(h->device));
+  c->stamp = st.in(pose_stamp, n_poses);
+  c->q = st.in(q_wc_wxyz, 4 * n_poses);
+  c->t = st.in(t_wc, 3 * n_poses);
+  c->sstamp = st.in(scan_stamp, n_scans);
+  c->ranges = st.in(c->n_rays ? ranges + offsets[0] : nullptr, c->n_rays);
+  c->am = st.in(angle_min, n_scans);
+  c->ai = st.in(angle_increment, n_scans);
+  c->rm = st.in(range_min, n_scans);
+  c->off = reinterpret_cast<const int64_t*>(st.in(rel.data(), n_scans + 1));
+  return st.status(who);
+}
 
 int check_assemble_options(const char* who, const clc_assemble_options* in, clc_assemble_options* opt) {
   if (in) *opt = *in; else clc_assemble_options_default(opt);
@@ -713,10 +749,8 @@ int clc_assemble_observations_device(clc_handle* h, const clc_assemble_options* 
                                      const int64_t* offsets_dev, size_t n_scans, size_t n_rays, const float* angle_min_dev,
                                      const float* angle_increment_dev, const float* range_min_dev, const double* scan_stamp_dev,
                                      int32_t* scan_pose_dev, clc_assemble_info* info) {
-  if (!h || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
-      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
-      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations_device: bad argument");
+  CLC_TRY(scan_call_check("clc_assemble_observations_device", h != nullptr, n_poses, pose_stamp_dev && q_wc_wxyz_dev && t_wc_dev, n_scans,
+                          offsets_dev && angle_min_dev && angle_increment_dev && range_min_dev && scan_stamp_dev, n_rays, ranges_dev));
   clc_assemble_options opt;
   CLC_TRY(check_assemble_options("clc_assemble_observations_device: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
@@ -728,37 +762,17 @@ int clc_assemble_observations(clc_handle* h, const clc_assemble_options* opt_in,
                               const double* q_wc_wxyz, const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans,
                               const float* angle_min, const float* angle_increment, const float* range_min, const double* scan_stamp,
                               int32_t* scan_pose, clc_assemble_info* info) {
-  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
-      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
-      n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: bad argument");
+  const char* who = "clc_assemble_observations";
+  CLC_TRY(scan_call_check(who, h != nullptr, n_poses, pose_stamp && q_wc_wxyz && t_wc, n_scans,
+                          offsets && angle_min && angle_increment && range_min && scan_stamp, 0, nullptr));
   clc_assemble_options opt;
   CLC_TRY(check_assemble_options("clc_assemble_observations: bad options", opt_in, &opt));
-  std::vector<long long> rel;
-  size_t n_rays;
-  CLC_TRY(host_offsets("clc_assemble_observations", offsets, n_scans, true, "rays", &rel, &n_rays));
-  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_observations: NULL ranges");
-  CLC_HIP(hipSetDevice(h->device));
-  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
-  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
-  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
-  CLC_HIP(boff.alloc(n_scans + 1));
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
-  };
-  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
-  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
-  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
-  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
-  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
-  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
-  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
-  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
-  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
-  return assemble_keyframes_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p, bai.p,
-                            brm.p, bss.p, nullptr, scan_pose, info);
+  Staging st(h);
+  ScanCall c;
+  CLC_TRY(upload_scan_call(h, st, who, n_poses, pose_stamp, q_wc_wxyz, t_wc, ranges, offsets, n_scans, angle_min, angle_increment, range_min,
+                           scan_stamp, &c));
+  return assemble_keyframes_on_device(h, opt, n_poses, c.stamp, c.q, c.t, c.ranges, c.off, n_scans, c.n_rays, c.am, c.ai, c.rm, c.sstamp, nullptr,
+                                      scan_pose, info);
 }
 
 int clc_stored_observations(clc_handle* h, int* n_poses, double* tag_q_wxyz, double* tag_t, int64_t* pts_off, double* pts,
@@ -835,10 +849,8 @@ int clc_assemble_stations_device(clc_handle* h, const clc_station_options* opt_i
                                  const double* q_wc_wxyz_dev, const double* t_wc_dev, const float* ranges_dev, const int64_t* offsets_dev,
                                  size_t n_scans, size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
                                  const float* range_min_dev, const double* scan_stamp_dev, int32_t* scan_station_dev, clc_station_info* info) {
-  if (!h || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
-      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
-      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_stations_device: bad argument");
+  CLC_TRY(scan_call_check("clc_assemble_stations_device", h != nullptr, n_poses, pose_stamp_dev && q_wc_wxyz_dev && t_wc_dev, n_scans,
+                          offsets_dev && angle_min_dev && angle_increment_dev && range_min_dev && scan_stamp_dev, n_rays, ranges_dev));
   clc_station_options opt;
   CLC_TRY(check_station_options("clc_assemble_stations_device: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
@@ -850,37 +862,17 @@ int clc_assemble_stations(clc_handle* h, const clc_station_options* opt_in, size
                           const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
                           const float* angle_increment, const float* range_min, const double* scan_stamp, int32_t* scan_station,
                           clc_station_info* info) {
-  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
-      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
-      n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_stations: bad argument");
+  const char* who = "clc_assemble_stations";
+  CLC_TRY(scan_call_check(who, h != nullptr, n_poses, pose_stamp && q_wc_wxyz && t_wc, n_scans,
+                          offsets && angle_min && angle_increment && range_min && scan_stamp, 0, nullptr));
   clc_station_options opt;
   CLC_TRY(check_station_options("clc_assemble_stations: bad options", opt_in, &opt));
-  std::vector<long long> rel;
-  size_t n_rays;
-  CLC_TRY(host_offsets("clc_assemble_stations", offsets, n_scans, true, "rays", &rel, &n_rays));
-  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_stations: NULL ranges");
-  CLC_HIP(hipSetDevice(h->device));
-  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
-  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
-  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
-  CLC_HIP(boff.alloc(n_scans + 1));
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
-  };
-  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
-  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
-  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
-  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
-  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
-  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
-  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
-  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
-  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
-  return assemble_stations_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p,
-                                     bai.p, brm.p, bss.p, nullptr, scan_station, info);
+  Staging st(h);
+  ScanCall c;
+  CLC_TRY(upload_scan_call(h, st, who, n_poses, pose_stamp, q_wc_wxyz, t_wc, ranges, offsets, n_scans, angle_min, angle_increment, range_min,
+                           scan_stamp, &c));
+  return assemble_stations_on_device(h, opt, n_poses, c.stamp, c.q, c.t, c.ranges, c.off, n_scans, c.n_rays, c.am, c.ai, c.rm, c.sstamp, nullptr,
+                                     scan_station, info);
 }
 
 // ---- interpolated tag poses (K15) ---------------------------------------------------------------------------------------------------
@@ -931,10 +923,8 @@ int clc_assemble_interpolated_device(clc_handle* h, const clc_interp_options* op
                                      size_t n_scans, size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
                                      const float* range_min_dev, const double* scan_stamp_dev, int32_t* scan_bracket_dev, double* scan_u_dev,
                                      clc_assemble_info* info) {
-  if (!h || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
-      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
-      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_interpolated_device: bad argument");
+  CLC_TRY(scan_call_check("clc_assemble_interpolated_device", h != nullptr, n_poses, pose_stamp_dev && q_wc_wxyz_dev && t_wc_dev, n_scans,
+                          offsets_dev && angle_min_dev && angle_increment_dev && range_min_dev && scan_stamp_dev, n_rays, ranges_dev));
   clc_interp_options opt;
   CLC_TRY(check_interp_options("clc_assemble_interpolated_device: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
@@ -947,37 +937,17 @@ int clc_assemble_interpolated(clc_handle* h, const clc_interp_options* opt_in, s
                               const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
                               const float* angle_increment, const float* range_min, const double* scan_stamp, int32_t* scan_bracket,
                               double* scan_u, clc_assemble_info* info) {
-  if (!h || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
-      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
-      n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_assemble_interpolated: bad argument");
+  const char* who = "clc_assemble_interpolated";
+  CLC_TRY(scan_call_check(who, h != nullptr, n_poses, pose_stamp && q_wc_wxyz && t_wc, n_scans,
+                          offsets && angle_min && angle_increment && range_min && scan_stamp, 0, nullptr));
   clc_interp_options opt;
   CLC_TRY(check_interp_options("clc_assemble_interpolated: bad options", opt_in, &opt));
-  std::vector<long long> rel;
-  size_t n_rays;
-  CLC_TRY(host_offsets("clc_assemble_interpolated", offsets, n_scans, true, "rays", &rel, &n_rays));
-  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_assemble_interpolated: NULL ranges");
-  CLC_HIP(hipSetDevice(h->device));
-  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
-  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
-  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
-  CLC_HIP(boff.alloc(n_scans + 1));
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
-  };
-  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
-  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
-  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
-  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
-  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
-  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
-  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
-  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
-  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
-  return assemble_interpolated_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays,
-                                         bam.p, bai.p, brm.p, bss.p, nullptr, nullptr, scan_bracket, scan_u, info);
+  Staging st(h);
+  ScanCall c;
+  CLC_TRY(upload_scan_call(h, st, who, n_poses, pose_stamp, q_wc_wxyz, t_wc, ranges, offsets, n_scans, angle_min, angle_increment, range_min,
+                           scan_stamp, &c));
+  return assemble_interpolated_on_device(h, opt, n_poses, c.stamp, c.q, c.t, c.ranges, c.off, n_scans, c.n_rays, c.am, c.ai, c.rm, c.sstamp,
+                                         nullptr, nullptr, scan_bracket, scan_u, info);
 }
 
 // ---- the clock sweep (K15) ------------------------------------------------------------------------------------------------------------
@@ -1021,10 +991,8 @@ int clc_clock_offset_sweep_device(clc_handle* h, const clc_clock_offset_options*
                                  size_t n_scans, size_t n_rays, const float* angle_min_dev, const float* angle_increment_dev,
                                  const float* range_min_dev, const double* scan_stamp_dev, const double pose7[7], double* offsets_out,
                                  double* final_cost, double* poses, clc_summary* summaries, clc_clock_offset_result* result) {
-  if (!h || !pose7 || !result || (n_poses > 0 && (!pose_stamp_dev || !q_wc_wxyz_dev || !t_wc_dev)) ||
-      (n_scans > 0 && (!offsets_dev || !angle_min_dev || !angle_increment_dev || !range_min_dev || !scan_stamp_dev)) ||
-      (n_rays > 0 && (!ranges_dev || n_scans == 0)) || n_poses > 0x7FFFFFF0ull || n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_sweep_device: bad argument");
+  CLC_TRY(scan_call_check("clc_clock_offset_sweep_device", h && pose7 && result, n_poses, pose_stamp_dev && q_wc_wxyz_dev && t_wc_dev, n_scans,
+                          offsets_dev && angle_min_dev && angle_increment_dev && range_min_dev && scan_stamp_dev, n_rays, ranges_dev));
   clc_clock_offset_options opt;
   CLC_TRY(check_sweep_options("clc_clock_offset_sweep_device: bad options", opt_in, &opt));
   CLC_HIP(hipSetDevice(h->device));
@@ -1036,37 +1004,17 @@ int clc_clock_offset_sweep(clc_handle* h, const clc_clock_offset_options* opt_in
                           const double* t_wc, const float* ranges, const int64_t* offsets, size_t n_scans, const float* angle_min,
                           const float* angle_increment, const float* range_min, const double* scan_stamp, const double pose7[7],
                           double* offsets_out, double* final_cost, double* poses, clc_summary* summaries, clc_clock_offset_result* result) {
-  if (!h || !pose7 || !result || (n_poses > 0 && (!pose_stamp || !q_wc_wxyz || !t_wc)) ||
-      (n_scans > 0 && (!offsets || !angle_min || !angle_increment || !range_min || !scan_stamp)) || n_poses > 0x7FFFFFF0ull ||
-      n_scans > 0x7FFFFFF0ull)
-    return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_sweep: bad argument");
+  const char* who = "clc_clock_offset_sweep";
+  CLC_TRY(scan_call_check(who, h && pose7 && result, n_poses, pose_stamp && q_wc_wxyz && t_wc, n_scans,
+                          offsets && angle_min && angle_increment && range_min && scan_stamp, 0, nullptr));
   clc_clock_offset_options opt;
   CLC_TRY(check_sweep_options("clc_clock_offset_sweep: bad options", opt_in, &opt));
-  std::vector<long long> rel;
-  size_t n_rays;
-  CLC_TRY(host_offsets("clc_clock_offset_sweep", offsets, n_scans, true, "rays", &rel, &n_rays));
-  if (n_rays > 0 && !ranges) return fail(CLC_ERR_INVALID_ARG, "clc_clock_offset_sweep: NULL ranges");
-  CLC_HIP(hipSetDevice(h->device));
-  DevBuf<double> bstamp(&h->pool), bq(&h->pool), bt(&h->pool), bss(&h->pool);
-  DevBuf<float> br(&h->pool), bam(&h->pool), bai(&h->pool), brm(&h->pool);
-  DevBuf<long long> boff(&h->pool);
-  CLC_HIP(bstamp.alloc(n_poses)); CLC_HIP(bq.alloc(4 * n_poses)); CLC_HIP(bt.alloc(3 * n_poses)); CLC_HIP(bss.alloc(n_scans));
-  CLC_HIP(br.alloc(n_rays)); CLC_HIP(bam.alloc(n_scans)); CLC_HIP(bai.alloc(n_scans)); CLC_HIP(brm.alloc(n_scans));
-  CLC_HIP(boff.alloc(n_scans + 1));
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
-  };
-  CLC_HIP(up(bstamp.p, pose_stamp, n_poses * sizeof(double)));
-  CLC_HIP(up(bq.p, q_wc_wxyz, 4 * n_poses * sizeof(double)));
-  CLC_HIP(up(bt.p, t_wc, 3 * n_poses * sizeof(double)));
-  CLC_HIP(up(bss.p, scan_stamp, n_scans * sizeof(double)));
-  CLC_HIP(up(br.p, n_rays ? ranges + offsets[0] : nullptr, n_rays * sizeof(float)));
-  CLC_HIP(up(bam.p, angle_min, n_scans * sizeof(float)));
-  CLC_HIP(up(bai.p, angle_increment, n_scans * sizeof(float)));
-  CLC_HIP(up(brm.p, range_min, n_scans * sizeof(float)));
-  CLC_HIP(up(boff.p, rel.data(), (n_scans + 1) * sizeof(long long)));
-  return sweep_on_device(h, opt, n_poses, bstamp.p, bq.p, bt.p, br.p, reinterpret_cast<const int64_t*>(boff.p), n_scans, n_rays, bam.p, bai.p, brm.p,
-                         bss.p, pose7, offsets_out, final_cost, poses, summaries, result);
+  Staging st(h);
+  ScanCall c;
+  CLC_TRY(upload_scan_call(h, st, who, n_poses, pose_stamp, q_wc_wxyz, t_wc, ranges, offsets, n_scans, angle_min, angle_increment, range_min,
+                           scan_stamp, &c));
+  return sweep_on_device(h, opt, n_poses, c.stamp, c.q, c.t, c.ranges, c.off, n_scans, c.n_rays, c.am, c.ai, c.rm, c.sstamp, pose7, offsets_out,
+                         final_cost, poses, summaries, result);
 }
 
 }  // extern "C"

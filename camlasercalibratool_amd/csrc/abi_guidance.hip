@@ -2,6 +2,7 @@
 // (K20 in clc_guidance.hpp).  A unit of its own, held to its own register figures (tests/test_guidance_resources.py).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
+#include "abi_staging.hpp"
 #include "clc_guidance.hpp"
 
 using namespace clc_abi;
@@ -42,94 +43,93 @@ int guidance_model(const clc_guidance_options* in, const double* pose_cl, const 
 }
 
 // The direction table and the cast of every candidate, on the handle's stream.
-hipError_t enqueue_cast(clc_handle* h, const gd::GuideModel& g, double* dirs, const double* q, const double* t, size_t n, int32_t* n_hits,
-                        double* H_add) {
+void enqueue_cast(Staging& st, const gd::GuideModel& g, const double* q, const double* t, size_t n, int32_t* n_hits, double* H_add) {
+  double* dirs = st.scratch<double>(2 * (size_t)g.n_rays);
   gd::CastArgs a{};
   a.g = g; a.dirs = dirs; a.q = q; a.t = t; a.n_cand = (long long)n; a.n_hits = n_hits; a.H_add = H_add;
+  if (!st.ok()) return;
   const unsigned blocks = (unsigned)((n + gd::CAST_WAVES - 1) / gd::CAST_WAVES);
 #ifdef CLC_TEST_HOOKS
   if (!g_dir_table.load(std::memory_order_relaxed)) {
-    hipLaunchKernelGGL(gd::guidance_cast_kernel<false>, dim3(blocks), dim3(gd::CAST_THREADS), 0, h->stream, a);
-    return hipGetLastError();
+    hipLaunchKernelGGL(gd::guidance_cast_kernel<false>, dim3(blocks), dim3(gd::CAST_THREADS), 0, st.stream(), a);
+    st.launched();
+    return;
   }
 #endif
-  hipLaunchKernelGGL(gd::guidance_dirs_kernel, dim3((unsigned)((g.n_rays + 255) / 256)), dim3(256), 0, h->stream, g, dirs);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(gd::guidance_cast_kernel<true>, dim3(blocks), dim3(gd::CAST_THREADS), 0, h->stream, a);
-  return hipGetLastError();
+  hipLaunchKernelGGL(gd::guidance_dirs_kernel, dim3((unsigned)((g.n_rays + 255) / 256)), dim3(256), 0, st.stream(), g, dirs);
+  st.launched();
+  if (!st.ok()) return;
+  hipLaunchKernelGGL(gd::guidance_cast_kernel<true>, dim3(blocks), dim3(gd::CAST_THREADS), 0, st.stream(), a);
+  st.launched();
 }
 
 unsigned score_blocks(size_t n) { return (unsigned)((n + gd::SCORE_THREADS - 1) / gd::SCORE_THREADS); }
 
-// Cast and score with the candidates and the outputs (every one nullable) in device memory; no synchronisation.  The buffers of the
-// outputs the caller does not take live until the caller's synchronisation: ws owns them.
-struct ScoreScratch {
-  DevBuf<double> dirs, M, H_add;
-  DevBuf<int32_t> n_hits;
-  explicit ScoreScratch(DevPool* p) : dirs(p), M(p), H_add(p), n_hits(p) {}
-};
-int enqueue_score(clc_handle* h, const gd::GuideModel& g, const double* M0, size_t n, const double* q, const double* t, int32_t* n_hits,
-                  double* H_add, double* sv, double* score, ScoreScratch& ws) {
-  CLC_HIP(ws.dirs.alloc(2 * (size_t)g.n_rays));
-  if (!n_hits) { CLC_HIP(ws.n_hits.alloc(n)); n_hits = ws.n_hits.p; }
-  if (!H_add) { CLC_HIP(ws.H_add.alloc(36 * n)); H_add = ws.H_add.p; }
-  CLC_HIP(enqueue_cast(h, g, ws.dirs.p, q, t, n, n_hits, H_add));
-  if (!sv && !score) return CLC_OK;
-  CLC_HIP(ws.M.alloc(36));
-  CLC_HIP(hipMemcpyAsync(ws.M.p, M0, 36 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+// What the score kernels read and write, every array on the device (the fields of the greedy rounds left NULL).
+gd::ScoreArgs score_args(const gd::GuideModel& g, const double* M, const double* H_add, const int32_t* n_hits, size_t n, double* sv,
+                         double* score) {
   gd::ScoreArgs s{};
   s.criterion = g.criterion; s.min_points = g.min_points; s.eig_floor = g.eig_floor;
-  s.M = ws.M.p; s.H_add = H_add; s.n_hits = n_hits; s.n_cand = (long long)n; s.sv = sv; s.score = score;
+  s.M = M; s.H_add = H_add; s.n_hits = n_hits; s.n_cand = (long long)n; s.sv = sv; s.score = score;
+  return s;
+}
+
+// Cast and score with the candidates and the outputs (every one nullable) in device memory, under both forms of
+// clc_score_board_poses.  The cast's outputs are needed whether or not the caller takes them: NULL -> scratch.
+void enqueue_score(Staging& st, const gd::GuideModel& g, const double* M0, size_t n, const double* q, const double* t, int32_t* n_hits,
+                   double* H_add, double* sv, double* score) {
+  if (!n_hits) n_hits = st.scratch<int32_t>(n);
+  if (!H_add) H_add = st.scratch<double>(36 * n);
+  enqueue_cast(st, g, q, t, n, n_hits, H_add);
+  if (!sv && !score) return;
+  const gd::ScoreArgs s = score_args(g, st.in(M0, 36), H_add, n_hits, n, sv, score);
+  if (!st.ok()) return;
 #ifdef CLC_TEST_HOOKS
   if (g_score_rows.load(std::memory_order_relaxed)) {
     hipLaunchKernelGGL(gd::guidance_score_rows_kernel, dim3((unsigned)((n + gd::CAST_WAVES - 1) / gd::CAST_WAVES)), dim3(gd::CAST_THREADS), 0,
-                       h->stream, s);
-    CLC_HIP(hipGetLastError());
-    return CLC_OK;
+                       st.stream(), s);
+    st.launched();
+    return;
   }
 #endif
-  hipLaunchKernelGGL(gd::guidance_score_kernel<false>, dim3(score_blocks(n)), dim3(gd::SCORE_THREADS), 0, h->stream, s);
-  CLC_HIP(hipGetLastError());
-  return CLC_OK;
+  hipLaunchKernelGGL(gd::guidance_score_kernel<false>, dim3(score_blocks(n)), dim3(gd::SCORE_THREADS), 0, st.stream(), s);
+  st.launched();
 }
 
-// The greedy choice with the candidates in device memory: the cast once, `rounds` rounds back to back, the small results to the host
-// arrays, one synchronisation.
-int select_device(clc_handle* h, const gd::GuideModel& g, const double* M0, size_t n, const double* q, const double* t, size_t k,
-                  int64_t* chosen, double* sv_after, double* score_after, double* H_after, int32_t* n_chosen) {
+// The greedy choice with the candidates in device memory, under both forms of clc_select_board_poses: the cast once, `rounds` rounds
+// back to back, the small results to the host arrays, one synchronisation.
+int select_on_device(Staging& st, const char* who, const gd::GuideModel& g, const double* M0, size_t n, const double* q, const double* t,
+                     size_t k, int64_t* chosen, double* sv_after, double* score_after, double* H_after, int32_t* n_chosen) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "index type");
   const size_t rounds = std::min(k, n);
   const unsigned blocks = score_blocks(n);
-  DevBuf<double> dirs(&h->pool), M(&h->pool), H_add(&h->pool), sv(&h->pool), score(&h->pool), best_s(&h->pool), sva(&h->pool), sca(&h->pool);
-  DevBuf<int32_t> n_hits(&h->pool);
-  DevBuf<unsigned char> taken(&h->pool);
-  DevBuf<long long> best_i(&h->pool), ch(&h->pool);
-  CLC_HIP(dirs.alloc(2 * (size_t)g.n_rays)); CLC_HIP(M.alloc(36)); CLC_HIP(H_add.alloc(36 * n)); CLC_HIP(sv.alloc(6 * n));
-  CLC_HIP(score.alloc(n)); CLC_HIP(best_s.alloc(blocks)); CLC_HIP(best_i.alloc(blocks)); CLC_HIP(n_hits.alloc(n)); CLC_HIP(taken.alloc(n));
-  CLC_HIP(ch.alloc(rounds)); CLC_HIP(sva.alloc(6 * rounds)); CLC_HIP(sca.alloc(rounds));
-  CLC_HIP(hipMemcpyAsync(M.p, M0, 36 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(hipMemsetAsync(taken.p, 0, n, h->stream));
-  CLC_HIP(enqueue_cast(h, g, dirs.p, q, t, n, n_hits.p, H_add.p));
-  gd::ScoreArgs s{};
-  s.criterion = g.criterion; s.min_points = g.min_points; s.eig_floor = g.eig_floor;
-  s.M = M.p; s.H_add = H_add.p; s.n_hits = n_hits.p; s.n_cand = (long long)n; s.sv = sv.p; s.score = score.p;
-  s.taken = taken.p; s.best_score = best_s.p; s.best_index = best_i.p;
+  double* M = H_after ? st.inout(H_after, 36, M0) : st.in(M0, 36);  // the running information matrix
+  double* H_add = st.scratch<double>(36 * n);
+  double* sv = st.scratch<double>(6 * n);
+  double* score = st.scratch<double>(n);
+  double* best_s = st.scratch<double>(blocks);
+  long long* best_i = st.scratch<long long>(blocks);
+  int32_t* n_hits = st.scratch<int32_t>(n);
+  unsigned char* taken = st.scratch<unsigned char>(n);
+  long long* ch = st.out(reinterpret_cast<long long*>(chosen), rounds);
+  double* sva = sv_after ? st.out(sv_after, 6 * rounds) : st.scratch<double>(6 * rounds);
+  double* sca = score_after ? st.out(score_after, rounds) : st.scratch<double>(rounds);
+  if (st.ok()) st.check(hipMemsetAsync(taken, 0, n, st.stream()));
+  enqueue_cast(st, g, q, t, n, n_hits, H_add);
+  gd::ScoreArgs s = score_args(g, M, H_add, n_hits, n, sv, score);
+  s.taken = taken; s.best_score = best_s; s.best_index = best_i;
   gd::PickArgs p{};
-  p.n_blocks = (long long)blocks; p.best_score = best_s.p; p.best_index = best_i.p; p.H_add = H_add.p; p.sv = sv.p; p.score = score.p;
-  p.M = M.p; p.taken = taken.p; p.chosen = ch.p; p.sv_after = sva.p; p.score_after = sca.p;
-  for (size_t r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(gd::guidance_score_kernel<true>, dim3(blocks), dim3(gd::SCORE_THREADS), 0, h->stream, s);
-    CLC_HIP(hipGetLastError());
+  p.n_blocks = (long long)blocks; p.best_score = best_s; p.best_index = best_i; p.H_add = H_add; p.sv = sv; p.score = score;
+  p.M = M; p.taken = taken; p.chosen = ch; p.sv_after = sva; p.score_after = sca;
+  for (size_t r = 0; r < rounds && st.ok(); ++r) {
+    hipLaunchKernelGGL(gd::guidance_score_kernel<true>, dim3(blocks), dim3(gd::SCORE_THREADS), 0, st.stream(), s);
+    st.launched();
+    if (!st.ok()) break;
     p.round = (int)r;
-    hipLaunchKernelGGL(gd::guidance_pick_kernel, dim3(1), dim3(gd::PICK_THREADS), 0, h->stream, p);
-    CLC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(gd::guidance_pick_kernel, dim3(1), dim3(gd::PICK_THREADS), 0, st.stream(), p);
+    st.launched();
   }
-  static_assert(sizeof(long long) == sizeof(int64_t), "index type");
-  CLC_HIP(hipMemcpyAsync(chosen, ch.p, rounds * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-  if (sv_after) CLC_HIP(hipMemcpyAsync(sv_after, sva.p, 6 * rounds * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (score_after) CLC_HIP(hipMemcpyAsync(score_after, sca.p, rounds * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (H_after) CLC_HIP(hipMemcpyAsync(H_after, M.p, 36 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
+  CLC_TRY(st.finish(who));
   const double nan = std::nan("");
   int32_t nc = 0;
   for (size_t r = 0; r < k; ++r) {
@@ -181,10 +181,9 @@ int clc_score_board_poses_device(clc_handle* h, const clc_guidance_options* gopt
   CLC_TRY(count_check(who, n_cand, q_ca_wxyz_dev, t_ca_dev));
   if (n_cand == 0 || (!n_hits_dev && !H_add_dev && !sv_dev && !score_dev)) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
-  ScoreScratch ws(&h->pool);
-  CLC_TRY(enqueue_score(h, g, M0, n_cand, q_ca_wxyz_dev, t_ca_dev, n_hits_dev, H_add_dev, sv_dev, score_dev, ws));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  Staging st(h);
+  enqueue_score(st, g, M0, n_cand, q_ca_wxyz_dev, t_ca_dev, n_hits_dev, H_add_dev, sv_dev, score_dev);
+  return st.finish(who);
 }
 
 int clc_score_board_poses(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0, size_t n_cand,
@@ -198,24 +197,14 @@ int clc_score_board_poses(clc_handle* h, const clc_guidance_options* gopt, const
   if (n_cand == 0 || (!n_hits && !H_add && !sv && !score)) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
   const size_t n = n_cand;
-  DevBuf<double> bq(&h->pool), bt(&h->pool), bH(&h->pool), bsv(&h->pool), bsc(&h->pool);
-  DevBuf<int32_t> bn(&h->pool);
-  CLC_HIP(bq.alloc(4 * n)); CLC_HIP(bt.alloc(3 * n));
-  if (n_hits) CLC_HIP(bn.alloc(n));
-  if (H_add) CLC_HIP(bH.alloc(36 * n));
-  if (sv) CLC_HIP(bsv.alloc(6 * n));
-  if (score) CLC_HIP(bsc.alloc(n));
-  CLC_HIP(hipMemcpyAsync(bq.p, q_ca_wxyz, 4 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(hipMemcpyAsync(bt.p, t_ca, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  ScoreScratch ws(&h->pool);
-  CLC_TRY(enqueue_score(h, g, M0, n, bq.p, bt.p, n_hits ? bn.p : nullptr, H_add ? bH.p : nullptr, sv ? bsv.p : nullptr,
-                        score ? bsc.p : nullptr, ws));
-  if (n_hits) CLC_HIP(hipMemcpyAsync(n_hits, bn.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (H_add) CLC_HIP(hipMemcpyAsync(H_add, bH.p, 36 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (sv) CLC_HIP(hipMemcpyAsync(sv, bsv.p, 6 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (score) CLC_HIP(hipMemcpyAsync(score, bsc.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  return CLC_OK;
+  Staging st(h);
+  const double* q_dev = st.in(q_ca_wxyz, 4 * n);
+  const double* t_dev = st.in(t_ca, 3 * n);
+  int32_t* n_hits_dev = st.out_opt(n_hits, n);
+  double* H_add_dev = st.out_opt(H_add, 36 * n);
+  double* sv_dev = st.out_opt(sv, 6 * n);
+  enqueue_score(st, g, M0, n, q_dev, t_dev, n_hits_dev, H_add_dev, sv_dev, st.out_opt(score, n));
+  return st.finish(who);
 }
 
 int clc_select_board_poses_device(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0,
@@ -230,7 +219,8 @@ int clc_select_board_poses_device(clc_handle* h, const clc_guidance_options* gop
   CLC_TRY(count_check(who, n_cand, q_ca_wxyz_dev, t_ca_dev));
   if (n_cand == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
-  return select_device(h, g, M0, n_cand, q_ca_wxyz_dev, t_ca_dev, k, chosen, sv_after, score_after, H_after, n_chosen);
+  Staging st(h);
+  return select_on_device(st, who, g, M0, n_cand, q_ca_wxyz_dev, t_ca_dev, k, chosen, sv_after, score_after, H_after, n_chosen);
 }
 
 int clc_select_board_poses(clc_handle* h, const clc_guidance_options* gopt, const double pose_cl[7], const double* H0, size_t n_cand,
@@ -245,11 +235,10 @@ int clc_select_board_poses(clc_handle* h, const clc_guidance_options* gopt, cons
   CLC_TRY(count_check(who, n_cand, q_ca_wxyz, t_ca));
   if (n_cand == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
-  DevBuf<double> bq(&h->pool), bt(&h->pool);
-  CLC_HIP(bq.alloc(4 * n_cand)); CLC_HIP(bt.alloc(3 * n_cand));
-  CLC_HIP(hipMemcpyAsync(bq.p, q_ca_wxyz, 4 * n_cand * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  CLC_HIP(hipMemcpyAsync(bt.p, t_ca, 3 * n_cand * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  return select_device(h, g, M0, n_cand, bq.p, bt.p, k, chosen, sv_after, score_after, H_after, n_chosen);
+  Staging st(h);
+  const double* q_dev = st.in(q_ca_wxyz, 4 * n_cand);
+  const double* t_dev = st.in(t_ca, 3 * n_cand);
+  return select_on_device(st, who, g, M0, n_cand, q_dev, t_dev, k, chosen, sv_after, score_after, H_after, n_chosen);
 }
 
 }  // extern "C"
