@@ -42,6 +42,7 @@ EXPORTED = [
     "clc_camcal_options_default", "clc_camera_guess", "clc_camera_guess_device", "clc_camera_calibrate", "clc_camera_calibrate_device",
     "clc_guidance_options_default", "clc_score_board_poses", "clc_score_board_poses_device", "clc_select_board_poses",
     "clc_select_board_poses_device",
+    "clc_range_options_default", "clc_joint_refine_range", "clc_joint_refine_range_device", "clc_range_correct", "clc_range_correct_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -181,6 +182,12 @@ class AltPoseOptions(C.Structure):
 class JointOptions(C.Structure):
     """clc_joint_options (include/clc.h): sigma_corner in normalized image units (pixels / focal), sigma_laser in metres."""
     _fields_ = [("sigma_corner", C.c_double), ("sigma_laser", C.c_double), ("hold_board_poses", C.c_int32), ("hold_extrinsic", C.c_int32)]
+
+
+class RangeOptions(C.Structure):
+    """clc_range_options (include/clc.h): clc_joint_options and hold_range_mask (bit 0: the range offset is held, bit 1: the scale)."""
+    _fields_ = [("sigma_corner", C.c_double), ("sigma_laser", C.c_double), ("hold_board_poses", C.c_int32), ("hold_extrinsic", C.c_int32),
+                ("hold_range_mask", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CamcalOptions(C.Structure):
@@ -328,6 +335,13 @@ def load(path: str):
             L.clc_joint_options_default.restype = None
             L.clc_joint_refine.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 7
             L.clc_joint_refine_device.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 7
+        if hasattr(L, "clc_joint_refine_range"):
+            L.clc_range_options_default.argtypes = [V, V]
+            L.clc_range_options_default.restype = None
+            L.clc_joint_refine_range.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 8
+            L.clc_joint_refine_range_device.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 8
+            L.clc_range_correct.argtypes = [V, V, V, C.c_size_t, V]
+            L.clc_range_correct_device.argtypes = [V, V, V, C.c_size_t, V]
         if hasattr(L, "clc_camera_calibrate"):
             L.clc_camcal_options_default.argtypes = [V, C.c_int32]
             L.clc_camcal_options_default.restype = None
@@ -417,6 +431,14 @@ def default_joint_options(camera) -> JointOptions:
     o = JointOptions()
     c = camera.to_c()
     lib().clc_joint_options_default(C.byref(o), C.byref(c))
+    return o
+
+
+def default_range_options(camera=None) -> RangeOptions:
+    """clc_range_options_default: clc_joint_options_default's sigmas, nothing held; camera None: sigma_corner 0 (for hold_board_poses)."""
+    o = RangeOptions()
+    c = camera.to_c() if camera is not None else None
+    lib().clc_range_options_default(C.byref(o), C.byref(c) if c is not None else None)
     return o
 
 

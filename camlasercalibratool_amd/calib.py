@@ -613,6 +613,102 @@ def CamLaserCalibrationJoint(camera, corners_px: Sequence[np.ndarray], board_xy:
                                          use_linefitting_data, sigma_px, sigma_laser, solver, options)[0]
 
 
+def _range_hold_mask(hold) -> int:
+    """hold: None, a mask 0..3, or names out of ("offset", "scale")."""
+    if hold is None:
+        return 0
+    if isinstance(hold, (int, np.integer)):
+        return int(hold)
+    names = {"offset": 1, "scale": 2}
+    return sum(names[str(h)] for h in set(hold))
+
+
+def CamLaserCalibrationRangeBatch(camera, problems: Sequence[dict], use_linefitting_data: bool = False, hold=None,
+                                  hold_board_poses: bool = False, hold_extrinsic: bool = False, sigma_px: float = 0.3,
+                                  sigma_laser: float = 0.01, solver: Optional[Solver] = None, options: Optional[Options] = None):
+    """CamLaserCalibrationRange for a list of problems in one call (one workgroup each): every problem a dict(corners_px, board_xy —
+    one array per image; None with hold_board_poses —, obs, Tcl [4, 4], range0 (optional, (offset, scale)), keep (optional)).
+    -> list of (Tcl, ObservationSet, report)."""
+    sv = solver or _shared_solver()
+    sets = [_as_set(p["obs"]) for p in problems]
+    with_corners = not (hold_board_poses and all(p.get("corners_px") is None for p in problems))
+    if with_corners:
+        cp, bx, co, pts, po, pr, q0, t0 = _joint_arrays([p["corners_px"] for p in problems], [p["board_xy"] for p in problems], sets,
+                                                        use_linefitting_data)
+    else:
+        empty = [[np.zeros((0, 2), np.float32)] * s.n_poses for s in sets]
+        _, _, _, pts, po, pr, q0, t0 = _joint_arrays(empty, empty, sets, use_linefitting_data)
+        cp = bx = co = None
+    keep = None
+    if any(p.get("keep") is not None for p in problems):
+        keep = np.concatenate([np.ones(s.n_poses, bool) if p.get("keep") is None else np.asarray(p["keep"], bool) for p, s in zip(problems, sets)])
+    ro = _capi.default_range_options(camera)
+    if camera is not None:
+        ro.sigma_corner = sigma_px / float(np.sqrt(abs(camera.proj[0] * camera.proj[1])))
+    ro.sigma_laser = sigma_laser
+    ro.hold_board_poses, ro.hold_extrinsic, ro.hold_range_mask = int(bool(hold_board_poses)), int(bool(hold_extrinsic)), _range_hold_mask(hold)
+    cl0 = np.stack([simdata.pose7_from_T(np.asarray(p["Tcl"], np.float64)) for p in problems]) if problems else np.zeros((0, 7))
+    r0 = np.array([(0.0, 0.0) if p.get("range0") is None else p["range0"] for p in problems], np.float64).reshape(len(problems), 2)
+    r = sv.joint_refine_range(camera, cp, bx, co, pts, po, q0, t0, cl0, range0=r0, problem_offsets=pr, keep=keep, options=options,
+                              range_options=ro)
+    free = np.array([not hold_extrinsic] * 6 + [not (ro.hold_range_mask >> j) & 1 for j in range(2)])
+    out = []
+    for k, s in enumerate(sets):
+        sl = slice(pr[k], pr[k + 1])
+        H = r["H_cr"][k]
+        sigma, corr = np.full(8, np.nan), np.full(3, np.nan)
+        fi = np.flatnonzero(free)
+        if np.all(np.isfinite(H)) and len(fi):
+            try:
+                cov = np.linalg.inv(H[np.ix_(fi, fi)])
+                if np.all(np.diag(cov) > 0):
+                    sigma[fi] = np.sqrt(np.diag(cov))
+                    if free[6] and not hold_extrinsic:
+                        full = np.zeros((8, 8))
+                        full[np.ix_(fi, fi)] = cov
+                        corr = full[6, :3] / (sigma[6] * sigma[:3])
+            except np.linalg.LinAlgError:
+                pass
+        report = dict(summary=r["summaries"][k], termination=_capi.TERMINATION.get(r["summaries"][k].termination, "?"),
+                      range_offset=float(r["range"][k, 0]), range_scale=float(r["range"][k, 1]), H_cr=H,
+                      singular_values=np.linalg.svd(H, compute_uv=False) if np.all(np.isfinite(H)) else np.full(8, np.nan),
+                      sigma=sigma, corr_offset_tcl=corr, cost_corner=float(r["cost_parts"][k, 0]), cost_laser=float(r["cost_parts"][k, 1]),
+                      status=r["status"][sl].copy())
+        refined = ObservationSet(r["q"][sl].copy(), r["t"][sl].copy(), s.pts_off, s.pts, s.ptl_off, s.ptl)
+        out.append((simdata.T_from_pose7(r["poses_cl"][k]), refined, report))
+    return out
+
+
+def CamLaserCalibrationRange(camera, corners_px, board_xy, obs: ObsLike, Tcl: np.ndarray, range0=(0.0, 0.0), hold=None,
+                             hold_board_poses: bool = False, hold_extrinsic: bool = False, use_linefitting_data: bool = False, keep=None,
+                             sigma_px: float = 0.3, sigma_laser: float = 0.01, solver: Optional[Solver] = None,
+                             options: Optional[Options] = None):
+    """CamLaserCalibrationJoint with the scanner's range offset b (metres) and range scale kappa (K21): the laser points enter the
+    cost corrected along their rays, p' = (1 + kappa + b / |p|) p, i.e. true range = (1 + kappa) measured + b.  range0: the start;
+    hold: None, or out of ("offset", "scale") (or the mask: bit 0 offset, bit 1 scale) — a held parameter keeps range0's value and
+    is still applied.  With hold_board_poses the tag poses of `obs` stay and camera, corners_px and board_xy may be None: T_cl and
+    the range parameters from tag poses and points alone.
+    -> (Tcl [4, 4], the observation set with the refined tag poses (the points as measured: ApplyRangeCorrection corrects them),
+    report: summary, termination, range_offset, range_scale, H_cr — the information on [T_cl tangent, b, kappa] with the board poses
+    marginalised —, its singular_values, sigma (1 sigma of the 8 parameters from the inverse of H_cr over the free ones, NaN for a
+    held one), corr_offset_tcl (the correlation of b with t_cl), cost_corner, cost_laser, status per image).
+    Observability: b and kappa separate only through a spread of ranges, b separates from t_cl only through a spread of plane
+    normals and ray directions.  singular_values and sigma show when to hold one of them; a recording at a single range cannot have
+    both free (the damping keeps the solve finite there, and sigma comes back NaN or huge)."""
+    return CamLaserCalibrationRangeBatch(camera, [dict(corners_px=corners_px, board_xy=board_xy, obs=obs, Tcl=Tcl, range0=range0, keep=keep)],
+                                         use_linefitting_data, hold, hold_board_poses, hold_extrinsic, sigma_px, sigma_laser, solver,
+                                         options)[0]
+
+
+def ApplyRangeCorrection(obs: ObsLike, offset: float, scale: float, solver: Optional[Solver] = None) -> ObservationSet:
+    """The observation set with `points` and `points_on_line` corrected for the scanner's range offset and scale (clc_range_correct):
+    upload, closed form, CamLaserCalibration, K18 and the pose guidance then run on corrected data."""
+    sv = solver or _shared_solver()
+    s = _as_set(obs)
+    return ObservationSet(s.tag_q.copy(), s.tag_t.copy(), s.pts_off.copy(), sv.range_correct(s.pts, offset, scale), s.ptl_off.copy(),
+                          sv.range_correct(s.ptl, offset, scale))
+
+
 @dataclass
 class GuidanceReport:
     """What SuggestBoardPoses returns; indices in the caller's numbering of the candidates."""

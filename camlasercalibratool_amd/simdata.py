@@ -234,15 +234,36 @@ def points_from_tag_poses(Rca: np.ndarray, tca: np.ndarray, n_rays: int = 180, n
     return ObservationSet(tag_q, np.array(tca, dtype=np.float64).copy(), off, pts, off.copy(), pts.copy())
 
 
+def apply_range_error(pts: np.ndarray, offset: float, scale: float) -> np.ndarray:
+    """What a scanner with range offset `offset` (metres) and range scale `scale` measures for the true points pts [N, 3] (laser frame):
+    the point moved along its ray to the range (true - offset) / (1 + scale) — the inverse of K21's correction
+    p' = (1 + scale + offset / |p|) p, true = (1 + scale) measured + offset.  A point at the origin stays there."""
+    p = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    rho = np.linalg.norm(p, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(rho > 0, (rho - offset) / (1.0 + scale) / rho, 1.0)
+    return np.ascontiguousarray(p * f[:, None])
+
+
+def with_range_error(S: ObservationSet, offset: float, scale: float) -> ObservationSet:
+    """An observation set as a scanner with the given range offset and scale would have recorded it (points and points_on_line)."""
+    if offset == 0.0 and scale == 0.0:
+        return S
+    return ObservationSet(S.tag_q, S.tag_t, S.pts_off, apply_range_error(S.pts, offset, scale), S.ptl_off,
+                          apply_range_error(S.ptl, offset, scale))
+
+
 def GenerateSimData(seed: int, n_poses: int = 50, n_rays: int = 180, noise_sigma: float = 0.0,
-                    Rlc: np.ndarray = GT_RLC, tlc: np.ndarray = GT_TLC) -> ObservationSet:
+                    Rlc: np.ndarray = GT_RLC, tlc: np.ndarray = GT_TLC, range_offset: float = 0.0,
+                    range_scale: float = 0.0) -> ObservationSet:
     """C1 — restatement of GenerateSimData, main/calibr_simulation.cpp:10-108: tag poses drawn from the reference's
     distributions (with numpy's generator — the reference seeds its engine from std::random_device, so there is no
     stream to reproduce), then `points_from_tag_poses`, which tests/test_ref_pin.py checks against the reference's own
-    function on the reference's own poses.  noise_sigma adds N(0,sigma) range noise (the reference is noise-free)."""
+    function on the reference's own poses.  noise_sigma adds N(0,sigma) range noise (the reference is noise-free);
+    range_offset / range_scale: the scanner's range error (apply_range_error), none by default."""
     rng = np.random.default_rng(seed)
     Rca, tca = _draw_tag_poses(rng, n_poses)
-    return points_from_tag_poses(Rca, tca, n_rays, noise_sigma, rng, Rlc, tlc)
+    return with_range_error(points_from_tag_poses(Rca, tca, n_rays, noise_sigma, rng, Rlc, tlc), range_offset, range_scale)
 
 
 def _valid_interval(n, d):

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, GuidanceOptions, Iteration, JointOptions, Options, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, GuidanceOptions, Iteration, JointOptions, Options, RangeOptions, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -678,6 +678,83 @@ class Solver:
                                               V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
                                               V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
                                               V(summaries_ptr), V(H_cl_ptr), V(cost_parts_ptr), V(status_ptr)), "clc_joint_refine_device")
+
+    # ---- joint refinement with the scanner's range offset and scale (K21) ----
+    def joint_refine_range(self, camera, corners_px, board_xy, corner_offsets, pts: np.ndarray, pts_offsets: np.ndarray,
+                           q_ca_wxyz: np.ndarray, t_ca: np.ndarray, poses_cl: np.ndarray, range0: Optional[np.ndarray] = None,
+                           problem_offsets: Optional[np.ndarray] = None, keep: Optional[np.ndarray] = None,
+                           options: Optional[Options] = None, range_options: Optional[RangeOptions] = None) -> dict:
+        """clc_joint_refine_range (K21): joint_refine's cost with the laser points corrected along their rays,
+        p' = (1 + kappa + b / |p|) p, and b (range offset, metres) and kappa (range scale) in the shared block beside T_cl.
+        range0 [n_problems, 2]: the start (None: zeros; a held parameter keeps its value and is still applied).  With
+        range_options.hold_board_poses the camera and the three corner arrays may be None.
+        -> dict(q, t, poses_cl, range [n_problems, 2], summaries, H_cr [n_problems, 8, 8] (the information on [T_cl tangent, b,
+        kappa], board poses marginalised), cost_parts, status)."""
+        P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        po = np.ascontiguousarray(pts_offsets, dtype=np.int64)
+        n = len(po) - 1
+        cp = bx = co = None
+        if corner_offsets is not None:
+            cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+            bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+            co = np.ascontiguousarray(corner_offsets, dtype=np.int64)
+            if len(co) != n + 1:
+                raise ValueError("joint_refine_range: corner_offsets and pts_offsets need one entry per image plus one")
+            if n > 0 and (co[-1] > len(cp) or co[-1] > len(bx) or co[0] < 0):
+                raise ValueError("joint_refine_range: offsets run past corners_px or board_xy")
+        if n < 0 or (n > 0 and (po[-1] > len(P) or po[0] < 0)):
+            raise ValueError("joint_refine_range: offsets run past pts")
+        pr = None if problem_offsets is None else np.ascontiguousarray(problem_offsets, dtype=np.int64)
+        npb = 1 if pr is None else len(pr) - 1
+        q = np.array(q_ca_wxyz, dtype=np.float64, order="C").reshape(n, 4)
+        t = np.array(t_ca, dtype=np.float64, order="C").reshape(n, 3)
+        cl = np.array(poses_cl, dtype=np.float64, order="C").reshape(npb, 7)
+        rg = np.zeros((npb, 2)) if range0 is None else np.array(range0, dtype=np.float64, order="C").reshape(npb, 2)
+        kp = None if keep is None else np.ascontiguousarray(np.asarray(keep).astype(np.uint8))
+        if kp is not None and kp.shape != (n,):
+            raise ValueError("joint_refine_range: keep needs one entry per image")
+        if pr is not None and (len(pr) < 1 or (len(pr) > 1 and pr[-1] > n)):
+            raise ValueError("joint_refine_range: problem_offsets run past the images")
+        sm = (Summary * max(npb, 1))()
+        H = np.empty((npb, 8, 8)); parts = np.empty((npb, 2)); st = np.empty(n, dtype=np.int32)
+        c = camera.to_c() if camera is not None else None
+        V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_joint_refine_range(self._h, C.byref(c) if c is not None else None, C.byref(options) if options is not None else None,
+                                             C.byref(range_options) if range_options is not None else None, V(cp), V(bx), V(co), V(P), V(po),
+                                             V(kp), C.c_size_t(n), V(pr), C.c_size_t(npb), V(q), V(t), V(cl), V(rg), sm, V(H), V(parts), V(st)),
+              "clc_joint_refine_range")
+        return dict(q=q, t=t, poses_cl=cl, range=rg, summaries=sm, H_cr=H, cost_parts=parts, status=st)
+
+    def joint_refine_range_device(self, camera, corners_ptr: int, board_ptr: int, corner_offsets_ptr: int, pts_ptr: int, pts_offsets_ptr: int,
+                                  n_images: int, n_problems: int, q_ptr: int, t_ptr: int, poses_cl_ptr: int, range_ptr: int,
+                                  summaries_ptr: int, status_ptr: int, problem_offsets_ptr: int = 0, keep_ptr: int = 0, H_cr_ptr: int = 0,
+                                  cost_parts_ptr: int = 0, options: Optional[Options] = None, range_options: Optional[RangeOptions] = None):
+        """clc_joint_refine_range_device on device-resident arrays (data_ptr()s; ready on the solver's stream): the conventions of
+        joint_refine_device; q, t, poses_cl and range in / out."""
+        c = camera.to_c() if camera is not None else None
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_joint_refine_range_device(self._h, C.byref(c) if c is not None else None,
+                                                    C.byref(options) if options is not None else None,
+                                                    C.byref(range_options) if range_options is not None else None, V(corners_ptr),
+                                                    V(board_ptr), V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr),
+                                                    C.c_size_t(n_images), V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr),
+                                                    V(poses_cl_ptr), V(range_ptr), V(summaries_ptr), V(H_cr_ptr), V(cost_parts_ptr),
+                                                    V(status_ptr)), "clc_joint_refine_range_device")
+
+    def range_correct(self, pts: np.ndarray, offset: float, scale: float) -> np.ndarray:
+        """clc_range_correct: p' = (1 + scale + offset / |p|) p of pts [N, 3]; NaN for a point that is non-finite or at the origin."""
+        P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        out = np.empty_like(P)
+        rg = np.array([offset, scale], dtype=np.float64)
+        V = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_range_correct(self._h, V(rg), V(P), C.c_size_t(len(P)), V(out)), "clc_range_correct")
+        return out
+
+    def range_correct_device(self, pts_ptr: int, n: int, out_ptr: int, offset: float, scale: float):
+        """clc_range_correct_device on device-resident arrays (data_ptr()s; out may be pts)."""
+        rg = np.array([offset, scale], dtype=np.float64)
+        check(self._L.clc_range_correct_device(self._h, rg.ctypes.data_as(C.c_void_p), C.c_void_p(pts_ptr or 0), C.c_size_t(n),
+                                               C.c_void_p(out_ptr or 0)), "clc_range_correct_device")
 
     # ---- pose guidance (K20) ----
     @staticmethod

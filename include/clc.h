@@ -1143,6 +1143,58 @@ int clc_select_board_poses_device(clc_handle* h, const clc_guidance_options* gop
                                   size_t n_cand, const double* q_ca_wxyz_dev, const double* t_ca_dev, size_t k, int64_t* chosen,
                                   double* sv_after, double* score_after, double* H_after, int32_t* n_chosen);
 
+/* ---- laser range offset and scale in the joint refinement (K21) ----------------------------------------------------------
+ * clc_joint_refine's cost with the scanner's own two parameters: the measured point p (laser frame) is corrected along its ray,
+ *   p' = (1 + kappa + b / |p|) p        true range = (1 + kappa) measured + b;  b: range offset (metres), kappa: range scale
+ * and takes p's place in the laser term.  The shared block of the solve has 8 parameters [dt_cl, dtheta_cl, b, kappa]; b and kappa
+ * move additively.  One kernel launch per call (one workgroup per problem), clc_options as in clc_joint_refine, deterministic.
+ * b and kappa separate only through a spread of ranges, and b separates from t_cl only through a spread of plane normals and ray
+ * directions: a recording at a single range cannot have both free (the damping keeps the solve finite; H_cr shows it) — hold one
+ * of them there. */
+typedef struct clc_range_options {
+  double sigma_corner;      /* as clc_joint_options; not looked at with hold_board_poses */
+  double sigma_laser;       /* metres, finite, > 0 */
+  int32_t hold_board_poses; /* 1: the board poses stay; the corner terms are constant and left out, no corner is read */
+  int32_t hold_extrinsic;   /* 1: T_cl stays */
+  int32_t hold_range_mask;  /* bit 0: the offset is held, bit 1: the scale is held; a held parameter is still applied */
+  int32_t reserved;         /* 0 */
+} clc_range_options;        /* 32 bytes */
+
+/* clc_joint_options_default's sigmas, nothing held; cam NULL: sigma_corner 0 (refused unless hold_board_poses is set). */
+void clc_range_options_default(clc_range_options* ropt, const clc_camera* cam);
+
+/* The arguments of clc_joint_refine, and range[2 n_problems] in / out: b, kappa of every problem (the start, e.g. zeros; a held
+ * one keeps its bits).  image_status: the CLC_JOINT_* values; a laser point that is non-finite or has |p| = 0 (the scanner's "no
+ * return") makes its image CLC_JOINT_NONFINITE.  With hold_board_poses an image needs no corners: it takes part if it is kept and
+ * its points and start pose are finite; corners_px, board_xy and corner_offsets may then be NULL (they are not read), cam may be
+ * NULL, and the corner share of the cost is 0.  Without it fewer than 4 corners give CLC_JOINT_TOO_FEW.  With no laser point in a
+ * problem T_cl and range come back bit for bit; hold_extrinsic leaves T_cl bit for bit while the free range parameters move.  A
+ * problem with no participating image, a non-finite T_cl or range, or a failed solve ends CLC_FAILURE with everything untouched.
+ * H_cr[64 n_problems] (nullable): the information on [T_cl tangent, b, kappa] with the board poses marginalised, at the returned
+ * point, undamped (C itself with hold_board_poses; NaN where an A_i is not positive definite; rows and columns of held parameters,
+ * T_cl's with hold_extrinsic, zero).  summaries, cost_parts: as clc_joint_refine.  ropt NULL: the defaults.
+ * CLC_ERR_INVALID_ARG before any device work: NULL required pointers, a sigma that is not finite and positive (sigma_corner only
+ * without hold_board_poses), both hold flags, a mask outside 0..3, reserved != 0, offsets that decrease, corner arrays NULL without
+ * hold_board_poses.  One enqueue (lift, then the solve) and one synchronisation. */
+int clc_joint_refine_range(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_range_options* ropt,
+                           const float* corners_px, const float* board_xy, const int64_t* corner_offsets, const double* pts,
+                           const int64_t* pts_offsets, const uint8_t* keep, size_t n_images, const int64_t* problem_offsets,
+                           size_t n_problems, double* q_ca_wxyz, double* t_ca, double* poses_cl, double* range, clc_summary* summaries,
+                           double* H_cr, double* cost_parts, int32_t* image_status);
+/* The same with every array in DEVICE memory; the conventions of clc_joint_refine_device. */
+int clc_joint_refine_range_device(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_range_options* ropt,
+                                  const float* corners_px_dev, const float* board_xy_dev, const int64_t* corner_offsets_dev,
+                                  const double* pts_dev, const int64_t* pts_offsets_dev, const uint8_t* keep_dev, size_t n_images,
+                                  const int64_t* problem_offsets_dev, size_t n_problems, double* q_ca_wxyz_dev, double* t_ca_dev,
+                                  double* poses_cl_dev, double* range_dev, clc_summary* summaries_dev, double* H_cr_dev,
+                                  double* cost_parts_dev, int32_t* image_status_dev);
+
+/* out[3 n] = p' of pts[3 n] for range = {b, kappa}; a point that is non-finite or has |p| = 0 becomes NaN.  out may be pts.
+ * CLC_ERR_INVALID_ARG: NULL h, range, or (n > 0) pts / out; CLC_ERR_NONFINITE: a non-finite b or kappa.  n = 0: CLC_OK. */
+int clc_range_correct(clc_handle* h, const double range[2], const double* pts, size_t n, double* out);
+/* The same with pts and out in DEVICE memory (ready on the handle's stream); range on the host.  The same bits. */
+int clc_range_correct_device(clc_handle* h, const double range[2], const double* pts_dev, size_t n, double* out_dev);
+
 #ifdef __cplusplus
 }
 #endif
