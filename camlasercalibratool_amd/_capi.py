@@ -43,6 +43,7 @@ EXPORTED = [
     "clc_guidance_options_default", "clc_score_board_poses", "clc_score_board_poses_device", "clc_select_board_poses",
     "clc_select_board_poses_device",
     "clc_range_options_default", "clc_joint_refine_range", "clc_joint_refine_range_device", "clc_range_correct", "clc_range_correct_device",
+    "clc_joint_loss_options_default", "clc_joint_refine_robust", "clc_joint_refine_robust_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -188,6 +189,11 @@ class RangeOptions(C.Structure):
     """clc_range_options (include/clc.h): clc_joint_options and hold_range_mask (bit 0: the range offset is held, bit 1: the scale)."""
     _fields_ = [("sigma_corner", C.c_double), ("sigma_laser", C.c_double), ("hold_board_poses", C.c_int32), ("hold_extrinsic", C.c_int32),
                 ("hold_range_mask", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JointLossOptions(C.Structure):
+    """clc_joint_loss_options (include/clc.h): the Cauchy scales of K22 in units of sigma_corner / sigma_laser; 0: no loss."""
+    _fields_ = [("loss_corner", C.c_double), ("loss_laser", C.c_double)]
 
 
 class CamcalOptions(C.Structure):
@@ -342,6 +348,11 @@ def load(path: str):
             L.clc_joint_refine_range_device.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 8
             L.clc_range_correct.argtypes = [V, V, V, C.c_size_t, V]
             L.clc_range_correct_device.argtypes = [V, V, V, C.c_size_t, V]
+        if hasattr(L, "clc_joint_refine_robust"):
+            L.clc_joint_loss_options_default.argtypes = [V, V]
+            L.clc_joint_loss_options_default.restype = None
+            L.clc_joint_refine_robust.argtypes = [V] * 11 + [C.c_size_t, V, C.c_size_t] + [V] * 9
+            L.clc_joint_refine_robust_device.argtypes = [V] * 11 + [C.c_size_t, V, C.c_size_t] + [V] * 9
         if hasattr(L, "clc_camera_calibrate"):
             L.clc_camcal_options_default.argtypes = [V, C.c_int32]
             L.clc_camcal_options_default.restype = None
@@ -439,6 +450,14 @@ def default_range_options(camera=None) -> RangeOptions:
     o = RangeOptions()
     c = camera.to_c() if camera is not None else None
     lib().clc_range_options_default(C.byref(o), C.byref(c) if c is not None else None)
+    return o
+
+
+def default_joint_loss_options(joint=None) -> JointLossOptions:
+    """clc_joint_loss_options_default: loss_laser = 0.05 m over the sigma_laser of `joint` (5 without it), loss_corner = 3 (a design
+    value: 0.9 px at 0.3 px)."""
+    o = JointLossOptions()
+    lib().clc_joint_loss_options_default(C.byref(o), C.byref(joint) if joint is not None else None)
     return o
 
 

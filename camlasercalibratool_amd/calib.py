@@ -613,6 +613,56 @@ def CamLaserCalibrationJoint(camera, corners_px: Sequence[np.ndarray], board_xy:
                                          use_linefitting_data, sigma_px, sigma_laser, solver, options)[0]
 
 
+def CamLaserCalibrationJointRobustBatch(camera, problems: Sequence[dict], use_linefitting_data: bool = False, sigma_px: float = 0.3,
+                                        sigma_laser: float = 0.01, solver: Optional[Solver] = None, options: Optional[Options] = None,
+                                        loss_px_sigmas: float = 3.0, loss_laser_m: float = 0.05):
+    """CamLaserCalibrationJointRobust for a list of problems in one call (one workgroup each): the problems of
+    CamLaserCalibrationJointBatch.  -> list of (Tcl, ObservationSet, report)."""
+    sv = solver or _shared_solver()
+    sets = [_as_set(p["obs"]) for p in problems]
+    cp, bx, co, pts, po, pr, q0, t0 = _joint_arrays([p["corners_px"] for p in problems], [p["board_xy"] for p in problems], sets,
+                                                    use_linefitting_data)
+    keep = None
+    if any(p.get("keep") is not None for p in problems):
+        keep = np.concatenate([np.ones(s.n_poses, bool) if p.get("keep") is None else np.asarray(p["keep"], bool) for p, s in zip(problems, sets)])
+    jo = _capi.default_joint_options(camera)
+    jo.sigma_corner = sigma_px / float(np.sqrt(abs(camera.proj[0] * camera.proj[1])))
+    jo.sigma_laser = sigma_laser
+    lo = _capi.JointLossOptions(float(loss_px_sigmas), float(loss_laser_m) / float(sigma_laser))
+    cl0 = np.stack([simdata.pose7_from_T(np.asarray(p["Tcl"], np.float64)) for p in problems]) if problems else np.zeros((0, 7))
+    r = sv.joint_refine_robust(camera, cp, bx, co, pts, po, q0, t0, cl0, problem_offsets=pr, keep=keep, options=options, joint=jo, loss=lo)
+    out = []
+    for k, s in enumerate(sets):
+        sl = slice(pr[k], pr[k + 1])
+        H = r["H_cl"][k]
+        w_corner = [r["w_corner"][co[i]:co[i + 1]].copy() for i in range(pr[k], pr[k + 1])]
+        w_laser = [r["w_laser"][po[i]:po[i + 1]].copy() for i in range(pr[k], pr[k + 1])]
+        report = dict(summary=r["summaries"][k], termination=_capi.TERMINATION.get(r["summaries"][k].termination, "?"), H_cl=H,
+                      singular_values=np.linalg.svd(H, compute_uv=False) if np.all(np.isfinite(H)) else np.full(6, np.nan),
+                      cost_corner=float(r["cost_parts"][k, 0]), cost_laser=float(r["cost_parts"][k, 1]), status=r["status"][sl].copy(),
+                      w_corner=w_corner, w_laser=w_laser, inlier_corner=[w >= 0.5 for w in w_corner], inlier_laser=[w >= 0.5 for w in w_laser])
+        refined = ObservationSet(r["q"][sl].copy(), r["t"][sl].copy(), s.pts_off, s.pts, s.ptl_off, s.ptl)
+        out.append((simdata.T_from_pose7(r["poses_cl"][k]), refined, report))
+    return out
+
+
+def CamLaserCalibrationJointRobust(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], obs: ObsLike, Tcl: np.ndarray,
+                                   use_linefitting_data: bool = False, keep=None, sigma_px: float = 0.3, sigma_laser: float = 0.01,
+                                   solver: Optional[Solver] = None, options: Optional[Options] = None, loss_px_sigmas: float = 3.0,
+                                   loss_laser_m: float = 0.05):
+    """CamLaserCalibrationJoint under a Cauchy loss per corner and per laser point (K22): a single bad laser point inside a board
+    segment (a leg or a cable in front of the board, the mixed pixel at a board edge) or a single mis-refined corner is
+    down-weighted instead of biasing T_cl.  loss_laser_m: the Cauchy scale of a laser residual in metres (0.05: the reference's
+    CauchyLoss(0.05)); loss_px_sigmas: the scale of a corner's residual vector in units of sigma_px (3: a design value of this
+    library, 0.9 px at 0.3 px); 0: no loss on that term.
+    -> (Tcl [4, 4], the observation set with the refined tag poses, report: CamLaserCalibrationJoint's — cost_corner, cost_laser and
+    the summary's costs are the robust ones — and per image w_corner, w_laser (rho' of every observation at the returned poses; NaN
+    for an image that takes no part) and the masks inlier_corner, inlier_laser (w >= 0.5: |residual| within the loss scale))."""
+    return CamLaserCalibrationJointRobustBatch(camera, [dict(corners_px=corners_px, board_xy=board_xy, obs=obs, Tcl=Tcl, keep=keep)],
+                                               use_linefitting_data, sigma_px, sigma_laser, solver, options, loss_px_sigmas,
+                                               loss_laser_m)[0]
+
+
 def _range_hold_mask(hold) -> int:
     """hold: None, a mask 0..3, or names out of ("offset", "scale")."""
     if hold is None:

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, GuidanceOptions, Iteration, JointOptions, Options, RangeOptions, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -678,6 +678,66 @@ class Solver:
                                               V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
                                               V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
                                               V(summaries_ptr), V(H_cl_ptr), V(cost_parts_ptr), V(status_ptr)), "clc_joint_refine_device")
+
+    # ---- robust joint refinement: a Cauchy loss per corner and per laser point (K22) ----
+    def joint_refine_robust(self, camera, corners_px: np.ndarray, board_xy: np.ndarray, corner_offsets: np.ndarray, pts: np.ndarray,
+                            pts_offsets: np.ndarray, q_ca_wxyz: np.ndarray, t_ca: np.ndarray, poses_cl: np.ndarray,
+                            problem_offsets: Optional[np.ndarray] = None, keep: Optional[np.ndarray] = None,
+                            options: Optional[Options] = None, joint: Optional[JointOptions] = None,
+                            loss: Optional[JointLossOptions] = None) -> dict:
+        """clc_joint_refine_robust (K22): joint_refine's arguments and cost with a Cauchy loss on every corner (scale loss.loss_corner,
+        in units of sigma_corner) and on every laser point (loss.loss_laser, in units of sigma_laser); loss None: the defaults, a
+        scale 0: no loss on that term.
+        -> joint_refine's dict (final_cost and cost_parts are the robust cost and its shares) and w_corner [len(corners_px)],
+        w_laser [len(pts)]: rho' of every observation at the returned poses (1 where the term has no loss, NaN for an image that
+        takes no part or a problem that ended CLC_FAILURE; w >= 0.5: |residual| <= scale * sigma)."""
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+        co = np.ascontiguousarray(corner_offsets, dtype=np.int64)
+        P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        po = np.ascontiguousarray(pts_offsets, dtype=np.int64)
+        n = len(co) - 1
+        if n < 0 or len(po) != n + 1:
+            raise ValueError("joint_refine_robust: corner_offsets and pts_offsets need one entry per image plus one")
+        if n > 0 and (co[-1] > len(cp) or co[-1] > len(bx) or po[-1] > len(P) or co[0] < 0 or po[0] < 0):
+            raise ValueError("joint_refine_robust: offsets run past corners_px, board_xy or pts")
+        pr = None if problem_offsets is None else np.ascontiguousarray(problem_offsets, dtype=np.int64)
+        npb = 1 if pr is None else len(pr) - 1
+        q = np.array(q_ca_wxyz, dtype=np.float64, order="C").reshape(n, 4)
+        t = np.array(t_ca, dtype=np.float64, order="C").reshape(n, 3)
+        cl = np.array(poses_cl, dtype=np.float64, order="C").reshape(npb, 7)
+        kp = None if keep is None else np.ascontiguousarray(np.asarray(keep).astype(np.uint8))
+        if kp is not None and kp.shape != (n,):
+            raise ValueError("joint_refine_robust: keep needs one entry per image")
+        if pr is not None and (len(pr) < 1 or (len(pr) > 1 and pr[-1] > n)):
+            raise ValueError("joint_refine_robust: problem_offsets run past the images")
+        sm = (Summary * max(npb, 1))()
+        H = np.empty((npb, 6, 6)); parts = np.empty((npb, 2)); st = np.empty(n, dtype=np.int32)
+        wc, wl = np.full(len(cp), np.nan), np.full(len(P), np.nan)
+        c = camera.to_c()
+        V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_joint_refine_robust(self._h, C.byref(c), C.byref(options) if options is not None else None,
+                                              C.byref(joint) if joint is not None else None, C.byref(loss) if loss is not None else None,
+                                              V(cp), V(bx), V(co), V(P), V(po), V(kp), C.c_size_t(n), V(pr), C.c_size_t(npb), V(q), V(t), V(cl),
+                                              sm, V(H), V(parts), V(st), V(wc), V(wl)), "clc_joint_refine_robust")
+        return dict(q=q, t=t, poses_cl=cl, summaries=sm, H_cl=H, cost_parts=parts, status=st, w_corner=wc, w_laser=wl)
+
+    def joint_refine_robust_device(self, camera, corners_ptr: int, board_ptr: int, corner_offsets_ptr: int, pts_ptr: int,
+                                   pts_offsets_ptr: int, n_images: int, n_problems: int, q_ptr: int, t_ptr: int, poses_cl_ptr: int,
+                                   summaries_ptr: int, status_ptr: int, problem_offsets_ptr: int = 0, keep_ptr: int = 0, H_cl_ptr: int = 0,
+                                   cost_parts_ptr: int = 0, w_corner_ptr: int = 0, w_laser_ptr: int = 0, options: Optional[Options] = None,
+                                   joint: Optional[JointOptions] = None, loss: Optional[JointLossOptions] = None):
+        """clc_joint_refine_robust_device on device-resident arrays (data_ptr()s; ready on the solver's stream): joint_refine_device's
+        conventions; w_corner, w_laser (float64) are indexed by the absolute corner / point offsets."""
+        c = camera.to_c()
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_joint_refine_robust_device(self._h, C.byref(c), C.byref(options) if options is not None else None,
+                                                     C.byref(joint) if joint is not None else None,
+                                                     C.byref(loss) if loss is not None else None, V(corners_ptr), V(board_ptr),
+                                                     V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
+                                                     V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
+                                                     V(summaries_ptr), V(H_cl_ptr), V(cost_parts_ptr), V(status_ptr), V(w_corner_ptr),
+                                                     V(w_laser_ptr)), "clc_joint_refine_robust_device")
 
     # ---- joint refinement with the scanner's range offset and scale (K21) ----
     def joint_refine_range(self, camera, corners_px, board_xy, corner_offsets, pts: np.ndarray, pts_offsets: np.ndarray,

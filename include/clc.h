@@ -1195,6 +1195,50 @@ int clc_range_correct(clc_handle* h, const double range[2], const double* pts, s
 /* The same with pts and out in DEVICE memory (ready on the handle's stream); range on the host.  The same bits. */
 int clc_range_correct_device(clc_handle* h, const double range[2], const double* pts_dev, size_t n, double* out_dev);
 
+/* ---- robust joint refinement: a Cauchy loss per corner and per laser point (K22) -------------------------------------------
+ * clc_joint_refine's model, tangent, sigmas, hold flags, image status, keep, offsets and clc_options, under the cost
+ *   1/2 sum rho_ac(|e_j|^2) + 1/2 sum rho_al(r_k^2),   rho_a(z) = a^2 log1p(z / a^2),  rho_a'(z) = 1 / (1 + z / a^2)
+ * with e_j the corner's residual 2-vector over sigma_corner (one loss on its squared norm, a 2-D residual block under a Ceres
+ * LossFunction) and r_k the laser residual over sigma_laser.  The scales a are in units of sigma; a = 0: no loss on that term.
+ * The Gauss-Newton blocks follow Ceres' corrector for rho'' <= 0: the rows and the residual of an observation are scaled by
+ * sqrt(rho'), so the blocks take w J^T J and the gradients w J^T r, w = rho'(z).  keep drops whole images, K16 whole tags and K12
+ * whole poses; this cost is the way out for a single bad laser point inside a board segment or a single bad corner.
+ * One workgroup per problem and the whole solve in one launch, as clc_joint_refine; deterministic. */
+typedef struct clc_joint_loss_options {
+  double loss_corner;  /* Cauchy scale of a corner's residual vector in units of sigma_corner; 0: no loss */
+  double loss_laser;   /* Cauchy scale of a laser residual in units of sigma_laser; 0: no loss */
+} clc_joint_loss_options;   /* 16 bytes */
+
+/* loss_laser = 0.05 / jopt->sigma_laser: the reference's CauchyLoss(0.05) in metres (5 at the default 0.01 m; 5 with jopt NULL).
+ * loss_corner = 3: a design value of this library (0.9 px at the default 0.3 px); the reference puts no loss on corners. */
+void clc_joint_loss_options_default(clc_joint_loss_options* lopt, const clc_joint_options* jopt);
+
+/* The arguments of clc_joint_refine in its order, lopt after jopt (NULL: the defaults for the call's jopt), and two outputs:
+ * w_corner (nullable; indexed as corners_px: one value per corner) and w_laser (nullable; indexed as pts: one per point) =
+ * rho'(z) of every observation at the returned poses — 1 where that term has no loss, NaN for an image that takes no part (any
+ * status but CLC_JOINT_OK, or outside every problem) and for a problem that ended CLC_FAILURE.  w >= 0.5 is the same statement
+ * as |residual| <= a sigma.  summaries[k].final_cost is the robust cost at the returned point, cost_parts its corner and laser
+ * shares, H_cl the Schur complement of the weighted blocks there.  An evaluation with a corner at depth <= 0 is invalid, as in
+ * clc_joint_refine.  With both scales 0 the call returns clc_joint_refine's bits (and weights 1).
+ * CLC_ERR_INVALID_ARG before any device work: everything clc_joint_refine refuses, with its messages behind this function's
+ * name, and a loss scale that is negative or not finite ("loss_corner must be finite and >= 0", "loss_laser ...").
+ * One enqueue (lift, solve, weights) and one synchronisation. */
+int clc_joint_refine_robust(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_joint_options* jopt,
+                            const clc_joint_loss_options* lopt, const float* corners_px, const float* board_xy,
+                            const int64_t* corner_offsets, const double* pts, const int64_t* pts_offsets, const uint8_t* keep,
+                            size_t n_images, const int64_t* problem_offsets, size_t n_problems, double* q_ca_wxyz, double* t_ca,
+                            double* poses_cl, clc_summary* summaries, double* H_cl, double* cost_parts, int32_t* image_status,
+                            double* w_corner, double* w_laser);
+/* The same with every array in DEVICE memory; the conventions of clc_joint_refine_device.  w_corner_dev and w_laser_dev are
+ * indexed by the absolute corner / point offsets; the entries of images outside every problem are left as they are. */
+int clc_joint_refine_robust_device(clc_handle* h, const clc_camera* cam, const clc_options* opt, const clc_joint_options* jopt,
+                                   const clc_joint_loss_options* lopt, const float* corners_px_dev, const float* board_xy_dev,
+                                   const int64_t* corner_offsets_dev, const double* pts_dev, const int64_t* pts_offsets_dev,
+                                   const uint8_t* keep_dev, size_t n_images, const int64_t* problem_offsets_dev, size_t n_problems,
+                                   double* q_ca_wxyz_dev, double* t_ca_dev, double* poses_cl_dev, clc_summary* summaries_dev,
+                                   double* H_cl_dev, double* cost_parts_dev, int32_t* image_status_dev, double* w_corner_dev,
+                                   double* w_laser_dev);
+
 #ifdef __cplusplus
 }
 #endif
