@@ -10,13 +10,14 @@ from .solver import Solver, SolveResult, flatten_observations  # noqa: F401
 from .calib import (CamLaserCalibration, CamLaserCalClosedSolution, CamLaserCalibrationFromStarts, CamLaserCalibrationResample, CamLaserCalibrationConsensus, CamLaserCalibrationBatch, CalibrationReport,  # noqa: F401
                     AutoGetLinePts, LineFittingCeres, CalcCamPoses, CalcCamPosesRobust, BoardPosesChecked, CamLaserCalibrationJoint, CamLaserCalibrationJointBatch, CalibrateCamera, SuggestBoardPoses, GuidanceReport, Session, points_on_fitted_lines, CalibrateOffline, CalibrateOfflineStations, CalibrateOfflineInterpolated, GetStaticPose,
                     CamLaserCalibrationRange, CamLaserCalibrationRangeBatch, ApplyRangeCorrection,
-                    CamLaserCalibrationJointRobust, CamLaserCalibrationJointRobustBatch)
+                    CamLaserCalibrationJointRobust, CamLaserCalibrationJointRobustBatch, CalibrateFull, CalibrateFullBatch)
 from ._capi import RangeOptions, default_range_options  # noqa: F401
 from ._capi import JointLossOptions, default_joint_loss_options  # noqa: F401
+from ._capi import FullOptions, default_full_options  # noqa: F401
 from .camera import Camera  # noqa: F401
 from . import resample  # noqa: F401
 
 __all__ = [
-    "CamLaserCalibration", "CamLaserCalClosedSolution", "CamLaserCalibrationFromStarts", "CamLaserCalibrationResample", "CamLaserCalibrationConsensus", "CamLaserCalibrationBatch", "CamLaserCalibrationJoint", "CamLaserCalibrationJointBatch", "CamLaserCalibrationRange", "CamLaserCalibrationRangeBatch", "ApplyRangeCorrection", "RangeOptions", "default_range_options", "CamLaserCalibrationJointRobust", "CamLaserCalibrationJointRobustBatch", "JointLossOptions", "default_joint_loss_options", "CalibrateCamera", "SuggestBoardPoses", "GuidanceReport", "GuidanceOptions", "default_guidance_options", "CalcCamPoses", "CalcCamPosesRobust", "BoardPosesChecked", "Camera", "AutoGetLinePts", "LineFittingCeres", "Oberserve", "ObservationSet", "GenerateSimData",
+    "CamLaserCalibration", "CamLaserCalClosedSolution", "CamLaserCalibrationFromStarts", "CamLaserCalibrationResample", "CamLaserCalibrationConsensus", "CamLaserCalibrationBatch", "CamLaserCalibrationJoint", "CamLaserCalibrationJointBatch", "CamLaserCalibrationRange", "CamLaserCalibrationRangeBatch", "ApplyRangeCorrection", "RangeOptions", "default_range_options", "CamLaserCalibrationJointRobust", "CamLaserCalibrationJointRobustBatch", "JointLossOptions", "default_joint_loss_options", "CalibrateFull", "CalibrateFullBatch", "FullOptions", "default_full_options", "CalibrateCamera", "SuggestBoardPoses", "GuidanceReport", "GuidanceOptions", "default_guidance_options", "CalcCamPoses", "CalcCamPosesRobust", "BoardPosesChecked", "Camera", "AutoGetLinePts", "LineFittingCeres", "Oberserve", "ObservationSet", "GenerateSimData",
     "Session", "CalibrateOffline", "CalibrateOfflineStations", "CalibrateOfflineInterpolated", "GetStaticPose", "InterpOptions", "default_interp_options", "TimeOffsetOptions", "default_time_offset_options", "StationOptions", "StationInfo", "default_station_options", "AssembleOptions", "AssembleInfo", "default_assemble_options", "Solver", "SolveResult", "Options", "default_options", "flatten_observations", "ClcError",
 ]

@@ -44,6 +44,7 @@ EXPORTED = [
     "clc_select_board_poses_device",
     "clc_range_options_default", "clc_joint_refine_range", "clc_joint_refine_range_device", "clc_range_correct", "clc_range_correct_device",
     "clc_joint_loss_options_default", "clc_joint_refine_robust", "clc_joint_refine_robust_device",
+    "clc_full_options_default", "clc_calibrate_full", "clc_calibrate_full_device",
     "clc_solve_subsets", "clc_score_blocks",
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
@@ -194,6 +195,15 @@ class RangeOptions(C.Structure):
 class JointLossOptions(C.Structure):
     """clc_joint_loss_options (include/clc.h): the Cauchy scales of K22 in units of sigma_corner / sigma_laser; 0: no loss."""
     _fields_ = [("loss_corner", C.c_double), ("loss_laser", C.c_double)]
+
+
+class FullOptions(C.Structure):
+    """clc_full_options (include/clc.h): the options of K23.  sigma_px in pixels, sigma_laser in metres; the Cauchy scales in units of
+    sigma (0: no loss); bit j of hold_intrinsics_mask holds intrinsic j (proj[0..3], dist[0..3]); hold_range_mask bit 0: b, bit 1:
+    kappa."""
+    _fields_ = [("sigma_px", C.c_double), ("sigma_laser", C.c_double), ("loss_corner", C.c_double), ("loss_laser", C.c_double),
+                ("hold_intrinsics_mask", C.c_uint32), ("hold_range_mask", C.c_int32), ("hold_board_poses", C.c_int32),
+                ("hold_extrinsic", C.c_int32)]
 
 
 class CamcalOptions(C.Structure):
@@ -353,6 +363,11 @@ def load(path: str):
             L.clc_joint_loss_options_default.restype = None
             L.clc_joint_refine_robust.argtypes = [V] * 11 + [C.c_size_t, V, C.c_size_t] + [V] * 9
             L.clc_joint_refine_robust_device.argtypes = [V] * 11 + [C.c_size_t, V, C.c_size_t] + [V] * 9
+        if hasattr(L, "clc_calibrate_full"):
+            L.clc_full_options_default.argtypes = [V, C.c_int32]
+            L.clc_full_options_default.restype = None
+            L.clc_calibrate_full.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 11
+            L.clc_calibrate_full_device.argtypes = [V] * 10 + [C.c_size_t, V, C.c_size_t] + [V] * 11
         if hasattr(L, "clc_camera_calibrate"):
             L.clc_camcal_options_default.argtypes = [V, C.c_int32]
             L.clc_camcal_options_default.restype = None
@@ -458,6 +473,13 @@ def default_joint_loss_options(joint=None) -> JointLossOptions:
     value: 0.9 px at 0.3 px)."""
     o = JointLossOptions()
     lib().clc_joint_loss_options_default(C.byref(o), C.byref(joint) if joint is not None else None)
+    return o
+
+
+def default_full_options(model: int) -> FullOptions:
+    """clc_full_options_default: 0.3 px, 0.01 m, loss scales 3 and 5; k4 and k5 (bits 6, 7) held for KANNALA_BRANDT, nothing else."""
+    o = FullOptions()
+    lib().clc_full_options_default(C.byref(o), C.c_int32(model))
     return o
 
 

@@ -861,6 +861,109 @@ def CalibrateCamera(model: int, width: int, height: int, corners_px: Sequence[np
     return res["cameras"][0], res["q"], res["t"], report
 
 
+FULL_NAMES = ("t_cl_x", "t_cl_y", "t_cl_z", "theta_cl_x", "theta_cl_y", "theta_cl_z", "offset", "scale", "proj0", "proj1", "proj2", "proj3",
+              "dist0", "dist1", "dist2", "dist3")  # the order of H_full
+
+
+def _full_hold(hold, model: int):
+    """hold: None (the model's default: Kannala-Brandt's k4, k5), a dict(intrinsics=mask or indices, range=mask or names out of
+    ("offset", "scale"), extrinsic=bool, board_poses=bool) or a sequence of names out of FULL_NAMES[6:] -> (intrinsics mask, range
+    mask, hold_extrinsic, hold_board_poses)."""
+    intr = int(_capi.default_full_options(model).hold_intrinsics_mask)
+    if hold is None:
+        return intr, 0, 0, 0
+    if not isinstance(hold, dict):
+        names = set(str(h) for h in hold)
+        return (sum(1 << j for j in range(8) if FULL_NAMES[8 + j] in names), _range_hold_mask([h for h in names if h in ("offset", "scale")]),
+                0, 0)
+    if hold.get("intrinsics") is not None:
+        h = hold["intrinsics"]
+        intr = int(h) if np.isscalar(h) else int(sum(1 << int(j) for j in set(h)))
+    return intr, _range_hold_mask(hold.get("range")), int(bool(hold.get("extrinsic"))), int(bool(hold.get("board_poses")))
+
+
+def CalibrateFullBatch(problems: Sequence[dict], hold=None, use_linefitting_data: bool = False, sigma_px: float = 0.3,
+                       sigma_laser: float = 0.01, loss_px_sigmas: float = 3.0, loss_laser_m: float = 0.05, solver: Optional[Solver] = None,
+                       options: Optional[Options] = None):
+    """CalibrateFull for a list of problems in one call (one workgroup each): every problem a dict(camera0, corners_px, board_xy — one
+    array per image —, obs, Tcl [4, 4], range0 (optional, (offset, scale)), keep (optional)).  The problems share `hold` and the
+    options, so their cameras share a model.  -> list of (Camera, Tcl, offset, scale, ObservationSet, report)."""
+    sv = solver or _shared_solver()
+    sets = [_as_set(p["obs"]) for p in problems]
+    cp, bx, co, pts, po, pr, q0, t0 = _joint_arrays([p["corners_px"] for p in problems], [p["board_xy"] for p in problems], sets,
+                                                    use_linefitting_data)
+    cams0 = [p["camera0"] for p in problems]
+    if len(set(c.model for c in cams0)) > 1:
+        raise ValueError("CalibrateFullBatch: the problems of one call share a camera model")
+    model = cams0[0].model if cams0 else 1
+    fo = _capi.default_full_options(model)
+    fo.sigma_px, fo.sigma_laser = float(sigma_px), float(sigma_laser)
+    fo.loss_corner, fo.loss_laser = float(loss_px_sigmas), float(loss_laser_m) / float(sigma_laser)
+    fo.hold_intrinsics_mask, fo.hold_range_mask, fo.hold_extrinsic, fo.hold_board_poses = _full_hold(hold, model)
+    keep = None
+    if any(p.get("keep") is not None for p in problems):
+        keep = np.concatenate([np.ones(s.n_poses, bool) if p.get("keep") is None else np.asarray(p["keep"], bool) for p, s in zip(problems, sets)])
+    cl0 = np.stack([simdata.pose7_from_T(np.asarray(p["Tcl"], np.float64)) for p in problems]) if problems else np.zeros((0, 7))
+    r0 = np.array([(0.0, 0.0) if p.get("range0") is None else p["range0"] for p in problems], np.float64).reshape(len(problems), 2)
+    r = sv.calibrate_full(cams0, cp, bx, co, pts, po, q0, t0, cl0, range0=r0, problem_offsets=pr, keep=keep, options=options, full=fo)
+    held = np.array([bool(fo.hold_extrinsic)] * 6 + [bool((fo.hold_range_mask >> j) & 1) for j in range(2)] +
+                    [bool((fo.hold_intrinsics_mask >> j) & 1) for j in range(8)])
+    out = []
+    for k, s in enumerate(sets):
+        sl = slice(pr[k], pr[k + 1])
+        H = r["H_full"][k]
+        free = ~held
+        if po[pr[k + 1]] == po[pr[k]]:  # no laser point: the problem holds T_cl, b and kappa by itself
+            free[:8] = False
+        fi = np.flatnonzero(free)
+        sigma = np.full(16, np.nan)
+        if np.all(np.isfinite(H)) and len(fi):
+            try:
+                cov = np.linalg.inv(H[np.ix_(fi, fi)])
+                if np.all(np.diag(cov) > 0):
+                    sigma[fi] = np.sqrt(np.diag(cov))
+            except np.linalg.LinAlgError:
+                pass
+        w_corner = [r["w_corner"][co[i]:co[i + 1]].copy() for i in range(pr[k], pr[k + 1])]
+        w_laser = [r["w_laser"][po[i]:po[i + 1]].copy() for i in range(pr[k], pr[k + 1])]
+        sm = r["summaries"][k]
+        report = dict(summary=sm, termination=_capi.TERMINATION.get(sm.termination, "?"), cost=sm.final_cost,
+                      cost_corner=float(r["cost_parts"][k, 0]), cost_laser=float(r["cost_parts"][k, 1]), rms_px=float(r["rms_px"][k]),
+                      iterations=sm.num_iterations, H_full=H, names=FULL_NAMES, sigma=sigma, free=free, status=r["status"][sl].copy(),
+                      w_corner=w_corner, w_laser=w_laser, inlier_corner=[w >= 0.5 for w in w_corner],
+                      inlier_laser=[w >= 0.5 for w in w_laser], camera0=cams0[k])
+        refined = ObservationSet(r["q"][sl].copy(), r["t"][sl].copy(), s.pts_off, s.pts, s.ptl_off, s.ptl)
+        out.append((r["cameras"][k], simdata.T_from_pose7(r["poses_cl"][k]), float(r["range"][k, 0]), float(r["range"][k, 1]), refined, report))
+    return out
+
+
+def CalibrateFull(camera0, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], obs: ObsLike, Tcl: np.ndarray,
+                  range0=(0.0, 0.0), hold=None, use_linefitting_data: bool = False, keep=None, sigma_px: float = 0.3,
+                  sigma_laser: float = 0.01, loss_px_sigmas: float = 3.0, loss_laser_m: float = 0.05, model: Optional[int] = None,
+                  width: int = 0, height: int = 0, solver: Optional[Solver] = None, options: Optional[Options] = None):
+    """The call at the end of the flow (K23): the camera's intrinsics, every board pose, T_cl and the scanner's range offset and scale
+    refined under one robust cost — pixel reprojection of the corners (CalibrateCamera's residual), point-to-plane of the laser
+    points corrected along their rays (CamLaserCalibrationRange's), a Cauchy loss per corner and per point
+    (CamLaserCalibrationJointRobust's).  camera0: the start camera; None: CalibrateCamera's answer on these corners (model, width and
+    height are then needed).  The tag poses of `obs` are the start poses.  hold: see _full_hold — None holds only what the model's
+    default holds (Kannala-Brandt: k4, k5).
+    -> (Camera, Tcl [4, 4], offset, scale, the observation set with the refined tag poses, report: summary, termination, cost,
+    cost_corner, cost_laser, rms_px, iterations, H_full [16, 16] — the information on `names` = [T_cl tangent, offset, scale,
+    proj[0..3], dist[0..3]] with the board poses marginalised —, sigma (1 sigma of the free shared parameters from the inverse of
+    H_full over the free set, NaN for a held one: T_cl's now carries the intrinsics' uncertainty), free, status per image, and per
+    image w_corner, w_laser, inlier_corner, inlier_laser (w >= 0.5)).
+    Observability: the focal length, the boards' depth, the range scale and t_cl trade against each other along one weakly held
+    direction; one-sided laser outliers (objects in front of the board) pull along it through the loss's tail.  Where `sigma` of the
+    scale is large or the recording has little spread of ranges, hold "scale" (DESIGN.md K23)."""
+    sv = solver or _shared_solver()
+    if camera0 is None:
+        if model is None:
+            raise ValueError("CalibrateFull: camera0 None needs model, width and height for CalibrateCamera")
+        camera0 = CalibrateCamera(model, width, height, corners_px, board_xy, sigma_px=sigma_px, solver=sv, options=options)[0]
+    return CalibrateFullBatch([dict(camera0=camera0, corners_px=corners_px, board_xy=board_xy, obs=obs, Tcl=Tcl, range0=range0, keep=keep)],
+                              hold, use_linefitting_data, sigma_px, sigma_laser, loss_px_sigmas, loss_laser_m, sv, options)[0]
+
+
 def AutoGetLinePts(points: np.ndarray, debug: bool = True, solver: Optional[Solver] = None) -> np.ndarray:
     """The calibration board's segment in one scan — mirror of AutoGetLinePts(points, debug), src/selectScanPoints.cpp:17-190:
     points [n,3] -> the chosen segment's points [k,3] (empty when there is none).  Raises IndexError where the reference's

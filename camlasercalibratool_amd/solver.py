@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -959,6 +959,79 @@ class Solver:
                                                   V(corner_offsets_ptr), V(keep_ptr), C.c_size_t(n_images), V(problem_offsets_ptr),
                                                   C.c_size_t(n_problems), V(cameras_ptr), V(q_ptr), V(t_ptr), V(summaries_ptr), V(H_cam_ptr),
                                                   V(rms_ptr), V(status_ptr)), "clc_camera_calibrate_device")
+
+    # ---- one robust cost over intrinsics, board poses, T_cl and range (K23) ----
+    def calibrate_full(self, cameras, corners_px, board_xy, corner_offsets, pts: np.ndarray, pts_offsets: np.ndarray,
+                       q_ca_wxyz: np.ndarray, t_ca: np.ndarray, poses_cl: np.ndarray, range0: Optional[np.ndarray] = None,
+                       problem_offsets: Optional[np.ndarray] = None, keep: Optional[np.ndarray] = None,
+                       options: Optional[Options] = None, full: Optional[FullOptions] = None) -> dict:
+        """clc_calibrate_full (K23): per problem the pixel reprojection error of the corners and the point-to-plane error of the
+        range-corrected laser points under one Cauchy cost, minimised over the free members of [T_cl, b, kappa, the 8 intrinsics] and
+        every board pose.  cameras: one Camera (one problem) or one per problem: the starts.  The other arguments are
+        joint_refine_range's; corners_px, board_xy and corner_offsets may be None where full holds the board poses and all 8
+        intrinsics.  full None: clc_full_options_default of the first camera's model.
+        -> dict(cameras [list of Camera], q [n, 4], t [n, 3], poses_cl [n_problems, 7], range [n_problems, 2], summaries, H_full
+        [n_problems, 16, 16] (order: dt_cl, dtheta_cl, b, kappa, proj[0..3], dist[0..3]), cost_parts [n_problems, 2], rms_px
+        [n_problems], status [n] int32 (CLC_JOINT_*), w_corner [len(corners_px)], w_laser [len(pts)]: rho' of every observation at
+        the returned point, NaN for an image that takes no part)."""
+        from .camera import Camera, ClcCamera
+        cams_in = [cameras] if isinstance(cameras, Camera) else list(cameras)
+        P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        po = np.ascontiguousarray(pts_offsets, dtype=np.int64)
+        n = len(po) - 1
+        cp = bx = co = None
+        if corner_offsets is not None:
+            cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+            bx = np.ascontiguousarray(board_xy, dtype=np.float32).reshape(-1, 2)
+            co = np.ascontiguousarray(corner_offsets, dtype=np.int64)
+            if len(co) != n + 1:
+                raise ValueError("calibrate_full: corner_offsets and pts_offsets need one entry per image plus one")
+            if n > 0 and (co[-1] > len(cp) or co[-1] > len(bx) or co[0] < 0):
+                raise ValueError("calibrate_full: offsets run past corners_px or board_xy")
+        if n < 0 or (n > 0 and (po[-1] > len(P) or po[0] < 0)):
+            raise ValueError("calibrate_full: offsets run past pts")
+        pr = None if problem_offsets is None else np.ascontiguousarray(problem_offsets, dtype=np.int64)
+        npb = 1 if pr is None else len(pr) - 1
+        if len(cams_in) != npb:
+            raise ValueError("calibrate_full: one camera per problem")
+        if pr is not None and (len(pr) < 1 or (len(pr) > 1 and pr[-1] > n)):
+            raise ValueError("calibrate_full: problem_offsets run past the images")
+        q = np.array(q_ca_wxyz, dtype=np.float64, order="C").reshape(n, 4)
+        t = np.array(t_ca, dtype=np.float64, order="C").reshape(n, 3)
+        cl = np.array(poses_cl, dtype=np.float64, order="C").reshape(npb, 7)
+        rg = np.zeros((npb, 2)) if range0 is None else np.array(range0, dtype=np.float64, order="C").reshape(npb, 2)
+        kp = None if keep is None else np.ascontiguousarray(np.asarray(keep).astype(np.uint8))
+        if kp is not None and kp.shape != (n,):
+            raise ValueError("calibrate_full: keep needs one entry per image")
+        cams = (ClcCamera * max(npb, 1))(*[c.to_c() for c in cams_in])
+        sm = (Summary * max(npb, 1))()
+        H = np.empty((npb, 16, 16)); parts = np.empty((npb, 2)); rms = np.empty(npb); st = np.empty(n, dtype=np.int32)
+        wc = None if cp is None else np.full(len(cp), np.nan)
+        wl = np.full(len(P), np.nan)
+        V = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_calibrate_full(self._h, cams, C.byref(options) if options is not None else None,
+                                         C.byref(full) if full is not None else None, V(cp), V(bx), V(co), V(P), V(po), V(kp), C.c_size_t(n),
+                                         V(pr), C.c_size_t(npb), V(q), V(t), V(cl), V(rg), sm, V(H), V(parts), V(rms), V(st), V(wc), V(wl)),
+              "clc_calibrate_full")
+        out = [Camera(cams[k].model, tuple(cams[k].proj), tuple(cams[k].dist), cams_in[k].width, cams_in[k].height) for k in range(npb)]
+        return dict(cameras=out, q=q, t=t, poses_cl=cl, range=rg, summaries=sm, H_full=H, cost_parts=parts, rms_px=rms, status=st,
+                    w_corner=wc, w_laser=wl)
+
+    def calibrate_full_device(self, cameras_ptr: int, corners_ptr: int, board_ptr: int, corner_offsets_ptr: int, pts_ptr: int,
+                              pts_offsets_ptr: int, n_images: int, n_problems: int, q_ptr: int, t_ptr: int, poses_cl_ptr: int,
+                              range_ptr: int, summaries_ptr: int, status_ptr: int, problem_offsets_ptr: int = 0, keep_ptr: int = 0,
+                              H_full_ptr: int = 0, cost_parts_ptr: int = 0, rms_ptr: int = 0, w_corner_ptr: int = 0, w_laser_ptr: int = 0,
+                              options: Optional[Options] = None, full: Optional[FullOptions] = None):
+        """clc_calibrate_full_device on device-resident arrays (data_ptr()s; ready on the solver's stream): joint_refine_device's
+        conventions, cameras as clc_camera records (72 bytes each) in / out as in camera_calibrate_device; w_corner, w_laser
+        (float64) are indexed by the absolute corner / point offsets.  Nothing is read back ahead of the enqueue."""
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_calibrate_full_device(self._h, V(cameras_ptr), C.byref(options) if options is not None else None,
+                                                C.byref(full) if full is not None else None, V(corners_ptr), V(board_ptr),
+                                                V(corner_offsets_ptr), V(pts_ptr), V(pts_offsets_ptr), V(keep_ptr), C.c_size_t(n_images),
+                                                V(problem_offsets_ptr), C.c_size_t(n_problems), V(q_ptr), V(t_ptr), V(poses_cl_ptr),
+                                                V(range_ptr), V(summaries_ptr), V(H_full_ptr), V(cost_parts_ptr), V(rms_ptr), V(status_ptr),
+                                                V(w_corner_ptr), V(w_laser_ptr)), "clc_calibrate_full_device")
 
     # ---- board-segment detection ----
     def board_segments(self, points: np.ndarray, offsets: np.ndarray):

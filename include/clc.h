@@ -1239,6 +1239,69 @@ int clc_joint_refine_robust_device(clc_handle* h, const clc_camera* cam, const c
                                    double* H_cl_dev, double* cost_parts_dev, int32_t* image_status_dev, double* w_corner_dev,
                                    double* w_laser_dev);
 
+/* ---- one robust cost over intrinsics, board poses, T_cl and range (K23) ------------------------------------------------------
+ * The call at the end of the flow: one problem is one camera, one scanner and P images, and everything is refined under one cost,
+ *   corner j of image i   e_j = (project(cam, R_i X_j + t_i) - u_j) / sigma_px                  clc_camera_calibrate's residual, pixels
+ *   laser point k         r_k = e3^T R_i^T (R_cl p'_k + t_cl - t_i) / sigma_laser,  p' = (1 + kappa + b / |p|) p   clc_joint_refine_range's
+ *   cost = 1/2 sum rho_ac(|e_j|^2) + 1/2 sum rho_al(r_k^2)                                      clc_joint_refine_robust's loss and corrector
+ * over the tangent [dt, dtheta] of every board pose and a shared block of 16 in this order:
+ *   [dt_cl(3), dtheta_cl(3), b, kappa, proj[0..3], dist[0..3]]
+ * (the leading 8 laid out as H_cr, the trailing 8 in clc_camera order; b, kappa and the intrinsics move additively).  The laser rows
+ * do not depend on the intrinsics and the corner rows not on T_cl, b, kappa: the two groups couple only through the board poses.
+ * One workgroup per problem and the whole Levenberg-Marquardt solve in one launch, clc_options as in the other solves (opt NULL =
+ * clc_pose_options_default()); deterministic: the same bits on every run, for a problem alone or in a batch, and through both forms. */
+typedef struct clc_full_options {
+  double sigma_px;               /* pixels, finite, > 0 (only looked at while the corners take part) */
+  double sigma_laser;            /* metres, finite, > 0 */
+  double loss_corner;            /* Cauchy scale of a corner's residual vector in units of sigma_px; 0: no loss; finite, >= 0 */
+  double loss_laser;             /* Cauchy scale of a laser residual in units of sigma_laser; 0: no loss; finite, >= 0 */
+  uint32_t hold_intrinsics_mask; /* bit j: intrinsic j (proj[0..3], dist[0..3]) is held */
+  int32_t hold_range_mask;       /* bit 0: b is held, bit 1: kappa is held; a held one is still applied */
+  int32_t hold_board_poses;      /* 1: the board poses stay */
+  int32_t hold_extrinsic;        /* 1: T_cl stays */
+} clc_full_options;              /* 48 bytes */
+
+/* 0.3 px, 0.01 m, loss scales 3 and 5 (clc_joint_loss_options_default's at those sigmas); for CLC_CAMERA_KANNALA_BRANDT k4 and k5
+ * are held (clc_camcal_options_default); nothing else is held. */
+void clc_full_options_default(clc_full_options* fopt, int32_t model);
+
+/* The arguments of clc_joint_refine_range in its order, with cams[n_problems] in / out (one start camera per problem, as
+ * clc_camera_calibrate; a held intrinsic keeps its bits) in place of cam, and the outputs summaries, H_full[256 n_problems],
+ * cost_parts[2 n_problems], rms_px[n_problems], image_status, w_corner (one per corner, indexed as corners_px) and w_laser (one per
+ * point, indexed as pts); all of them nullable except summaries and image_status.  image_status: the CLC_JOINT_* values, a corner at
+ * a non-finite pixel or a point that is non-finite or has |p| = 0 makes its image CLC_JOINT_NONFINITE; an evaluation with a corner
+ * at P_z <= 0 is invalid.  H_full: the information on the 16 shared parameters with the board poses marginalised,
+ * C - sum B_i^T A_i^-1 B_i of the weighted blocks at the returned point, undamped and unscaled; rows and columns of held parameters
+ * zero; C itself with hold_board_poses; NaN where an A_i is not positive definite.  rms_px: sigma_px sqrt(2 cost_corner / corners)
+ * over the participating images — clc_camera_calibrate's RMS where loss_corner is 0.  w_corner, w_laser: rho' of every observation
+ * at the returned point, clc_joint_refine_robust's conventions (1 without a loss, NaN for an image that takes no part or a failed
+ * problem).  A held parameter keeps its bits: the intrinsics and b, kappa bit by bit, T_cl with hold_extrinsic, the board poses
+ * with hold_board_poses; a problem without a laser point holds T_cl, b and kappa by itself.  With hold_board_poses and all 8
+ * intrinsics held the corner terms are constant: they are left out, no corner is read (the corner arrays may be NULL), an image
+ * needs no corners, the corner share of the cost is 0 and no w_corner is written.  Both hold flags together are allowed as long as
+ * something else moves.  A problem with no participating image, a non-finite start or a failed solve ends CLC_FAILURE with
+ * everything of the problem untouched.  fopt NULL: clc_full_options_default of cams[0].model.
+ * CLC_ERR_INVALID_ARG before any device work: NULL required pointers, a sigma that is not finite and positive, a loss scale that is
+ * negative or not finite, mask bits out of range, all 16 shared parameters held together with hold_board_poses, offsets that
+ * decrease, a camera whose model is neither of the two.  One enqueue (solve, weights) and one synchronisation. */
+int clc_calibrate_full(clc_handle* h, clc_camera* cams, const clc_options* opt, const clc_full_options* fopt, const float* corners_px,
+                       const float* board_xy, const int64_t* corner_offsets, const double* pts, const int64_t* pts_offsets,
+                       const uint8_t* keep, size_t n_images, const int64_t* problem_offsets, size_t n_problems, double* q_ca_wxyz,
+                       double* t_ca, double* poses_cl, double* range, clc_summary* summaries, double* H_full, double* cost_parts,
+                       double* rms_px, int32_t* image_status, double* w_corner, double* w_laser);
+/* The same with every array, cams included, in DEVICE memory; the indexing conventions of clc_joint_refine_device.  Nothing is
+ * read back ahead of the enqueue (the workspace is sized from n_images alone, as clc_camera_calibrate_device): offsets are not
+ * validated, and a camera with an unknown model ends its problem CLC_FAILURE.  fopt NULL: the defaults of CLC_CAMERA_PINHOLE (the
+ * models are not known to the host).  The entries of w_corner_dev / w_laser_dev of images outside every problem are left as they
+ * are. */
+int clc_calibrate_full_device(clc_handle* h, clc_camera* cams_dev, const clc_options* opt, const clc_full_options* fopt,
+                              const float* corners_px_dev, const float* board_xy_dev, const int64_t* corner_offsets_dev,
+                              const double* pts_dev, const int64_t* pts_offsets_dev, const uint8_t* keep_dev, size_t n_images,
+                              const int64_t* problem_offsets_dev, size_t n_problems, double* q_ca_wxyz_dev, double* t_ca_dev,
+                              double* poses_cl_dev, double* range_dev, clc_summary* summaries_dev, double* H_full_dev,
+                              double* cost_parts_dev, double* rms_px_dev, int32_t* image_status_dev, double* w_corner_dev,
+                              double* w_laser_dev);
+
 #ifdef __cplusplus
 }
 #endif
