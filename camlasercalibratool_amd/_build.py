@@ -18,19 +18,20 @@ UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip",
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
            "clc_batchflow.hpp", "clc_campose.hpp"]
-HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
+HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp", "abi_jointcall.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
 # kernels of their own that include HEADERS and are included by none of them: the kernels whose measured constants csrc_sha16 guards
 # (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
 # abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md), those of abi_frontend.hip by clc_stations.hpp
 # (profiles/offline_stations.md), those of abi_campose.hip by clc_robustpose.hpp (tests/test_robustpose_resources.py holds
-# board_pose_kernel's figures) or by clc_altpose.hpp (tests/test_altpose_resources.py); clc_arrow.hpp (the arrow solve) is included by clc_joint.hpp,
-# which abi_joint.hip alone includes (tests/test_joint_resources.py), and by clc_camcal.hpp, which abi_camcal.hip alone includes
-# (tests/test_camcal_resources.py), and by clc_laserrange.hpp, which abi_laserrange.hip alone includes
-# (tests/test_laserrange_resources.py), and by clc_jointrobust.hpp, which abi_jointrobust.hip alone includes
-# (tests/test_jointrobust_resources.py), and — with clc_camcal.hpp — by clc_fullcal.hpp, which abi_fullcal.hip alone includes
-# (tests/test_fullcal_resources.py); clc_guidance.hpp (pose guidance) by abi_guidance.hip alone (tests/test_guidance_resources.py).
-# They rebuild the libraries and are not part of csrc_sha16.
-SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp"]
+# board_pose_kernel's figures) or by clc_altpose.hpp (tests/test_altpose_resources.py); the arrow problems live one kernel header per unit, each unit held to
+# its own register figures: clc_joint.hpp in abi_joint.hip alone (tests/test_joint_resources.py), clc_camcal.hpp in abi_camcal.hip
+# (tests/test_camcal_resources.py), clc_laserrange.hpp in abi_laserrange.hip (tests/test_laserrange_resources.py), clc_jointrobust.hpp in
+# abi_jointrobust.hip (tests/test_jointrobust_resources.py), clc_fullcal.hpp — over clc_camcal.hpp — in abi_fullcal.hip
+# (tests/test_fullcal_resources.py).  What they share is inline code in two leaf headers that hold no solve kernel: clc_arrow.hpp (the
+# arrow solve and the shared blocks' bookkeeping, under all five) and clc_jointterms.hpp (the laser term, the loss, the accumulations
+# and the image rule of the four joint problems, included by their four kernel headers).  clc_guidance.hpp (pose guidance) is in
+# abi_guidance.hip alone (tests/test_guidance_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
+SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the

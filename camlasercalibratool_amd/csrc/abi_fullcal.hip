@@ -5,8 +5,7 @@
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include <limits>
 
-#include "abi_drive.hpp"
-#include "abi_staging.hpp"
+#include "abi_jointcall.hpp"
 #include "clc_fullcal.hpp"
 
 using namespace clc_abi;
@@ -23,12 +22,10 @@ int full_options(const clc_full_options* in, int32_t model, clc_full_options* o,
   if (in) *o = *in; else clc_full_options_default(o, model);
   const std::string w(who);
   if (o->hold_intrinsics_mask > 0xFFu) return fail(CLC_ERR_INVALID_ARG, (w + ": hold_intrinsics_mask has bits beyond the 8 intrinsics").c_str());
-  if (o->hold_range_mask < 0 || o->hold_range_mask > 3) return fail(CLC_ERR_INVALID_ARG, (w + ": hold_range_mask outside 0..3").c_str());
-  if (corners_take_part(*o) && !(std::isfinite(o->sigma_px) && o->sigma_px > 0.0))
-    return fail(CLC_ERR_INVALID_ARG, (w + ": sigma_px must be finite and > 0").c_str());
-  if (!(std::isfinite(o->sigma_laser) && o->sigma_laser > 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": sigma_laser must be finite and > 0").c_str());
-  if (!(std::isfinite(o->loss_corner) && o->loss_corner >= 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": loss_corner must be finite and >= 0").c_str());
-  if (!(std::isfinite(o->loss_laser) && o->loss_laser >= 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": loss_laser must be finite and >= 0").c_str());
+  CLC_TRY(check_range_mask(who, o->hold_range_mask));
+  if (corners_take_part(*o)) CLC_TRY(check_sigma(who, "sigma_px", o->sigma_px));  // (unchecked where the corners take no part)
+  CLC_TRY(check_sigma(who, "sigma_laser", o->sigma_laser));
+  CLC_TRY(check_loss_scales(who, o->loss_corner, o->loss_laser));
   if (o->hold_board_poses && o->hold_extrinsic && o->hold_range_mask == 3 && o->hold_intrinsics_mask == 0xFFu)
     return fail(CLC_ERR_INVALID_ARG, (w + ": everything is held").c_str());
   return CLC_OK;

@@ -2,7 +2,7 @@
 // extrinsic (K18 in clc_joint.hpp).  A unit of its own: the kernels of abi_campose.hip are held to their register figures, and this
 // one is held to its own (tests/test_joint_resources.py).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "abi_drive.hpp"
+#include "abi_jointcall.hpp"
 #include "abi_lift.hpp"
 #include "clc_joint.hpp"
 
@@ -12,22 +12,14 @@ namespace {
 
 namespace jt = clc::jt;
 
-// The joint call's options: the caller's or the defaults; checked.
-int joint_options(const clc_joint_options* in, const clc_camera* cam, clc_joint_options* o, const char* who) {
-  if (in) *o = *in; else clc_joint_options_default(o, cam);
-  const std::string w(who);
-  if (!(std::isfinite(o->sigma_corner) && o->sigma_corner > 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": sigma_corner must be finite and > 0").c_str());
-  if (!(std::isfinite(o->sigma_laser) && o->sigma_laser > 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": sigma_laser must be finite and > 0").c_str());
-  if (o->hold_board_poses && o->hold_extrinsic) return fail(CLC_ERR_INVALID_ARG, (w + ": both hold flags set").c_str());
-  return CLC_OK;
-}
-
-// The refusals both forms make first, in the same order: the camera and the options.
+// The refusals both forms make first, in the same order: the camera, the solve options, then the joint call's options (the caller's or
+// the defaults).
 int joint_checks(const char* who, const clc_camera* cam, const clc_options* opt_in, const clc_joint_options* jopt_in, clc_options* opt,
                  clc_joint_options* jo) {
   CLC_TRY(camera_check(cam, who));
   CLC_TRY(pose_options(opt_in, opt, who));
-  return joint_options(jopt_in, cam, jo, who);
+  if (jopt_in) *jo = *jopt_in; else clc_joint_options_default(jo, cam);
+  return check_sigmas_and_holds(who, true, jo->sigma_corner, jo->sigma_laser, jo->hold_board_poses, jo->hold_extrinsic);
 }
 
 // K18 on device arrays, the one function under both forms.  `a` arrives with the call's arrays and ranges named by the form (the
@@ -72,43 +64,21 @@ int clc_joint_refine(clc_handle* h, const clc_camera* cam, const clc_options* op
   clc_options opt;
   clc_joint_options jo;
   CLC_TRY(joint_checks(who, cam, opt_in, jopt_in, &opt, &jo));
-  if ((n_images > 0 && (!corner_offsets || !pts_offsets || !q_ca_wxyz || !t_ca || !image_status)) ||
-      (n_problems > 0 && (!poses_cl || !summaries)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine: bad argument");
-  CLC_TRY(problem_count_checks(who, n_images, problem_offsets != nullptr, n_problems));
+  const JointArrays c{corners_px, board_xy, corner_offsets, pts, pts_offsets, keep, n_images, problem_offsets, n_problems, q_ca_wxyz, t_ca,
+                      poses_cl, summaries, H_cl, cost_parts, image_status};
   std::vector<long long> crel, prel;
   size_t M = 0, N = 0;
-  CLC_TRY(host_offsets(who, corner_offsets, n_images, true, nullptr, &crel, &M));
-  CLC_TRY(host_offsets(who, pts_offsets, n_images, true, nullptr, &prel, &N));
-  CLC_TRY(host_problem_offsets(who, problem_offsets, n_problems, n_images));
-  if (!h || (M > 0 && (!corners_px || !board_xy)) || (N > 0 && !pts)) return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine: bad argument");
+  CLC_TRY(joint_host_checks(who, h, c, &crel, &prel, &M, &N));
   if (n_problems == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
   const auto t0 = Clock::now();
-  const size_t n = n_images, np = n_problems;
-  const size_t n_off = n > 0 ? n + 1 : 0;  // a call without images sends no offsets
-  const std::vector<int32_t> not_kept(n, CLC_JOINT_NOT_KEPT);  // the status of the images outside every problem
+  const std::vector<int32_t> not_kept(n_images, CLC_JOINT_NOT_KEPT);  // the status of the images outside every problem
   Staging st(h);
-  const float* corners_dev = st.in(M > 0 ? corners_px + 2 * corner_offsets[0] : nullptr, 2 * M);
-  jt::JointArgs a{};  // the host arrays start at image 0 and, rebased, at corner 0 and point 0
-  a.board = st.in(M > 0 ? board_xy + 2 * corner_offsets[0] : nullptr, 2 * M);
-  a.coff = st.in(crel.data(), n_off);
-  a.n_corners = (long long)M;
-  a.pts = st.in(N > 0 ? pts + 3 * pts_offsets[0] : nullptr, 3 * N);
-  a.poff = st.in(prel.data(), n_off);
-  a.keep = st.in_opt(keep, n);
-  a.prob_off = st.in_opt(reinterpret_cast<const long long*>(problem_offsets), np + 1);
-  a.n_images = (long long)n;
-  a.q = st.inout(q_ca_wxyz, 4 * n);
-  a.t = st.inout(t_ca, 3 * n);
-  a.status = st.inout(image_status, n, not_kept.data());
-  a.poses_cl = st.inout(poses_cl, 7 * np);
-  a.summaries = st.out(summaries, np);
-  a.H_cl = st.out_opt(H_cl, 36 * np);
-  a.cost_parts = st.out_opt(cost_parts, 2 * np);
-  enqueue_joint(st, *cam, opt, jo, corners_dev, a, np);
+  jt::JointArgs a{};
+  const float* corners_dev = stage_joint_arrays(st, c, crel, prel, M, N, not_kept.data(), a);
+  enqueue_joint(st, *cam, opt, jo, corners_dev, a, n_problems);
   CLC_TRY(st.finish(who));
-  stamp_solve_ms(summaries, np, t0);
+  stamp_solve_ms(summaries, n_problems, t0);
   return CLC_OK;
 }
 
@@ -122,45 +92,15 @@ int clc_joint_refine_device(clc_handle* h, const clc_camera* cam, const clc_opti
   clc_options opt;
   clc_joint_options jo;
   CLC_TRY(joint_checks(who, cam, opt_in, jopt_in, &opt, &jo));
-  if (!h || (n_images > 0 && (!corner_offsets_dev || !pts_offsets_dev || !q_ca_wxyz_dev || !t_ca_dev || !image_status_dev)) ||
-      (n_problems > 0 && (!poses_cl_dev || !summaries_dev)))
-    return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine_device: bad argument");
-  CLC_TRY(problem_count_checks(who, n_images, problem_offsets_dev != nullptr, n_problems));
+  const JointArrays c{corners_px_dev, board_xy_dev, corner_offsets_dev, pts_dev, pts_offsets_dev, keep_dev, n_images, problem_offsets_dev,
+                      n_problems, q_ca_wxyz_dev, t_ca_dev, poses_cl_dev, summaries_dev, H_cl_dev, cost_parts_dev, image_status_dev};
+  CLC_TRY(joint_device_checks(who, h, c));
   if (n_problems == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
-  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
   jt::JointArgs a{};
-  a.board = board_xy_dev;
-  a.coff = reinterpret_cast<const long long*>(corner_offsets_dev);
-  a.pts = pts_dev;
-  a.poff = reinterpret_cast<const long long*>(pts_offsets_dev);
-  a.keep = keep_dev;
-  a.prob_off = reinterpret_cast<const long long*>(problem_offsets_dev);
-  a.n_images = (long long)n_images;
-  a.q = q_ca_wxyz_dev;
-  a.t = t_ca_dev;
-  a.status = image_status_dev;
-  a.poses_cl = poses_cl_dev;
-  a.summaries = summaries_dev;
-  a.H_cl = H_cl_dev;
-  a.cost_parts = cost_parts_dev;
-  // the image and corner ranges, to size the lifted corners and the workspace: one small read ahead of the enqueue (as
-  // clc_board_poses_device reads the ends of its offsets)
-  long long ends[3] = {0, 0, 0};
-  if (n_images > 0) {
-    Staging read(h);
-    long long* ends_dev = read.out(ends, 3);
-    if (read.ok()) {
-      hipLaunchKernelGGL(jt::joint_ends_kernel, dim3(1), dim3(64), 0, read.stream(), a.prob_off, a.coff, (long long)n_images, ends_dev);
-      read.launched();
-    }
-    CLC_TRY(read.finish(who));
-  }
-  if (ends[0] < 0 || ends[1] < 0 || ends[2] < ends[1]) return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine_device: offsets not monotone");
-  a.first_image = ends[0];
-  a.first_corner = ends[1];
-  a.n_corners = ends[2] - ends[1];
-  if (a.n_corners > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine_device: bad argument");
+  name_joint_arrays(c, a);
+  // the image and corner ranges, to size the lifted corners and the workspace
+  CLC_TRY(read_joint_ends(h, who, jt::joint_ends_kernel<>, n_images > 0, n_images, corners_px_dev, a));
   Staging st(h);
   enqueue_joint(st, *cam, opt, jo, corners_px_dev, a, n_problems);
   return st.finish(who);

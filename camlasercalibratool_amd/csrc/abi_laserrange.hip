@@ -2,7 +2,7 @@
 // with the scanner's range offset and scale (K21 in clc_laserrange.hpp).  A unit of its own: range_refine_kernel is held to its own
 // register figures (tests/test_laserrange_resources.py).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
-#include "abi_drive.hpp"
+#include "abi_jointcall.hpp"
 #include "abi_lift.hpp"
 #include "clc_laserrange.hpp"
 
@@ -15,13 +15,10 @@ namespace lr = clc::lr;
 // The call's options: the caller's or the defaults; checked.
 int range_options(const clc_range_options* in, const clc_camera* cam, clc_range_options* o, const char* who) {
   if (in) *o = *in; else clc_range_options_default(o, cam);
-  const std::string w(who);
-  if (!o->hold_board_poses && !(std::isfinite(o->sigma_corner) && o->sigma_corner > 0.0))
-    return fail(CLC_ERR_INVALID_ARG, (w + ": sigma_corner must be finite and > 0").c_str());
-  if (!(std::isfinite(o->sigma_laser) && o->sigma_laser > 0.0)) return fail(CLC_ERR_INVALID_ARG, (w + ": sigma_laser must be finite and > 0").c_str());
-  if (o->hold_board_poses && o->hold_extrinsic) return fail(CLC_ERR_INVALID_ARG, (w + ": both hold flags set").c_str());
-  if (o->hold_range_mask < 0 || o->hold_range_mask > 3) return fail(CLC_ERR_INVALID_ARG, (w + ": hold_range_mask outside 0..3").c_str());
-  if (o->reserved != 0) return fail(CLC_ERR_INVALID_ARG, (w + ": reserved must be 0").c_str());
+  // (with the board poses held the corners take no part and their sigma goes unchecked)
+  CLC_TRY(check_sigmas_and_holds(who, !o->hold_board_poses, o->sigma_corner, o->sigma_laser, o->hold_board_poses, o->hold_extrinsic));
+  CLC_TRY(check_range_mask(who, o->hold_range_mask));
+  if (o->reserved != 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": reserved must be 0").c_str());
   return CLC_OK;
 }
 
@@ -178,22 +175,8 @@ int clc_joint_refine_range_device(clc_handle* h, const clc_camera* cam, const cl
   a.summaries = summaries_dev;
   a.H_cr = H_cr_dev;
   a.cost_parts = cost_parts_dev;
-  // the image and corner ranges, to size the lifted corners and the workspace: one small read ahead of the enqueue
-  long long ends[3] = {0, 0, 0};
-  if (n_images > 0 && (corners || a.prob_off)) {
-    Staging read(h);
-    long long* ends_dev = read.out(ends, 3);
-    if (read.ok()) {
-      hipLaunchKernelGGL(lr::range_ends_kernel, dim3(1), dim3(64), 0, read.stream(), a.prob_off, a.coff, (long long)n_images, ends_dev);
-      read.launched();
-    }
-    CLC_TRY(read.finish(who));
-  }
-  if (ends[0] < 0 || ends[1] < 0 || ends[2] < ends[1]) return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine_range_device: offsets not monotone");
-  a.first_image = ends[0];
-  a.first_corner = ends[1];
-  a.n_corners = ends[2] - ends[1];
-  if (a.n_corners > 0 && (!corners_px_dev || !board_xy_dev)) return fail(CLC_ERR_INVALID_ARG, "clc_joint_refine_range_device: bad argument");
+  // the image and corner ranges, to size the lifted corners and the workspace (nothing to read without corners and problem offsets)
+  CLC_TRY(read_joint_ends(h, who, lr::joint_ends_kernel<>, n_images > 0 && (corners || a.prob_off), n_images, corners_px_dev, a));
   Staging st(h);
   enqueue_range(st, cam, opt, ro, corners_px_dev, a, n_problems);
   return st.finish(who);

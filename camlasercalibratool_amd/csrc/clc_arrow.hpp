@@ -1,4 +1,7 @@
-// clc_arrow.hpp — the Levenberg-Marquardt solve of one "arrow" problem, written once for K18 (clc_joint.hpp) and K19 (clc_camcal.hpp).
+// clc_arrow.hpp — the Levenberg-Marquardt solve of one "arrow" problem, written once for the five problems K18 (clc_joint.hpp), K19
+// (clc_camcal.hpp), K21 (clc_laserrange.hpp), K22 and K23, and the bookkeeping of a shared block that their traits have in common.
+// A leaf: it holds no kernel.  The kernels live one per unit, each held to its own register figures; what they share is inline code
+// here and, for the terms of the four joint problems, in clc_jointterms.hpp.
 //
 // The unknowns are the tangent [dt, dtheta] of every board pose (Se3Manifold: t += dt, R <- R Exp(dtheta)) and one shared block of NC
 // parameters.  The normal matrix is an arrow: a 6x6 block A_i per image, coupled through B_i (6 x NC) only to the NC x NC block C of
@@ -35,9 +38,13 @@
 //   accept_block(sh)                  the candidate becomes the accepted block
 //   information(a)                    where the marginal information of the shared blocks goes, [NC x NC] per problem (nullable)
 //   write_outputs(a, pb, sh, failed)  the problem's own outputs (thread 0)
+// What several traits do the same way stands below block_candidate, once: problem_range (the clamp of a problem's images), T_cl as
+// the leading six of a shared block (tcl_*), the cost in two parts and its cost_parts, the shares of an additive parameter's
+// candidate, the list of free parameters, and the reduced system compacted to them, solved (chol_solve<N> by the caller's switch, or
+// chol_solve_n at run-time n) and scattered into step_c.
 //
-// Everything numeric is CLC_HD: tests/shim/joint_shim.cpp and tests/shim/camcal_shim.cpp compile this header for the host with g++
-// and run the same code with the threads as loops, in the same summation order.
+// Everything numeric is CLC_HD: the shims of tests/shim (joint, camcal and the three later problems') compile this header for the
+// host with g++ and run the same code with the threads as loops, in the same summation order.
 #pragma once
 #include "clc_campose.hpp"
 
@@ -178,6 +185,34 @@ CLC_HD void chol_apply6(const double* L, const double* b, int bs, double* y, int
   }
 }
 
+// Solve A y = b for the symmetric positive definite n x n A (row-major, n at run time): chol_solve of clc_math.hpp, rolled.
+// L (n * n), z (n) scratch; false if a pivot is not positive.
+CLC_HD bool chol_solve_n(int n, const double* A, const double* b, double* y, double* L, double* z) {
+  CLC_AW_ROLLED for (int j = 0; j < n; ++j) {
+    double d = A[n * j + j];
+    CLC_AW_ROLLED for (int k = 0; k < j; ++k) d -= L[n * j + k] * L[n * j + k];
+    if (!(d > 0.0)) return false;
+    const double inv = rsqrt_pos(d);
+    L[n * j + j] = inv;
+    CLC_AW_ROLLED for (int i = j + 1; i < n; ++i) {
+      double s = A[n * i + j];
+      CLC_AW_ROLLED for (int k = 0; k < j; ++k) s -= L[n * i + k] * L[n * j + k];
+      L[n * i + j] = s * inv;
+    }
+  }
+  CLC_AW_ROLLED for (int i = 0; i < n; ++i) {
+    double s = b[i];
+    CLC_AW_ROLLED for (int k = 0; k < i; ++k) s -= L[n * i + k] * z[k];
+    z[i] = s * L[n * i + i];
+  }
+  CLC_AW_ROLLED for (int i = n - 1; i >= 0; --i) {
+    double s = z[i];
+    CLC_AW_ROLLED for (int k = i + 1; k < n; ++k) s -= L[n * k + i] * y[k];
+    y[i] = s * L[n * i + i];
+  }
+  return true;
+}
+
 // ||x - Plus(x, -g)||_inf of one pose block.
 CLC_HD double block_gradient_norm(const double* x, const double* g) {
   double xx[7], ng[6], pr[7];
@@ -209,6 +244,126 @@ CLC_HD double block_candidate(const double* x, const double* step, const double*
   }
   *n2 = nn;
   return s;
+}
+
+// ---- what the problems' traits have in common -----------------------------------------------------------------------------
+// [first image, images) of problem pb and its workspace, clamped to the call's images [first, first + n_images); ws: image `first`
+// first.
+template <class Image>
+CLC_HD Problem<Image> problem_range(const long long* prob_off, long long pb, long long first, long long n_images, Image* ws) {
+  long long i0 = prob_off ? prob_off[pb] : first, i1 = prob_off ? prob_off[pb + 1] : first + n_images;
+  if (i0 < first) i0 = first;
+  if (i1 > first + n_images) i1 = first + n_images;
+  return {i0, i1 > i0 ? i1 - i0 : 0, ws + (i0 - first)};
+}
+
+// A cost in two parts (corners, laser) behind the record of ArrowRecord<NC>: the cost of a row of totals, and the problem's
+// cost_parts[2] (nullable; NaN without an evaluation or after a failure).
+template <int NC>
+CLC_HD double cost_of_parts(const double* tot) {
+  using R = ArrowRecord<NC>;
+  return tot[R::E_COST - R::E_C] + tot[R::E_COST + 1 - R::E_C];
+}
+template <int NC, class Sh>
+CLC_HD void write_cost_parts(double* cost_parts, long long pb, const Sh& sh, bool failed) {
+  using R = ArrowRecord<NC>;
+  if (!cost_parts) return;
+  const bool have = sh.n_evals > 0 && !failed;
+  cost_parts[2 * pb] = have ? sh.tot[sh.cur][R::E_COST - R::E_C] : __builtin_nan("");
+  cost_parts[2 * pb + 1] = have ? sh.tot[sh.cur][R::E_COST + 1 - R::E_C] : __builtin_nan("");
+}
+
+// T_cl as the leading six of a shared block; Sh holds it as xc[7] (accepted) and xce[7] (to evaluate), Ctx as Rcl[9], tcl[3].
+template <class Sh>
+CLC_HD bool tcl_init(const double* pose_cl, Sh& sh) {  // false: not finite
+  bool ok = true;
+  CLC_AW_ROLLED for (int i = 0; i < 7; ++i) {
+    const double v = pose_cl[i];
+    sh.xc[i] = sh.xce[i] = v;
+    ok = ok && finite_d(v);
+  }
+  return ok;
+}
+template <class Sh, class Ctx>
+CLC_HD void tcl_context(const Sh& sh, Ctx& c) {
+  double q[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = sh.xce[3 + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) c.tcl[i] = sh.xce[i];
+  quat_to_rot(q, c.Rcl);
+}
+template <class Sh>
+CLC_HD void tcl_candidate(Sh& sh, bool hold, double& sn, double& xn) {
+  double n2 = 0.0;
+  if (!hold) {
+    sn += block_candidate(sh.xc, sh.step_c, sh.scale_c, sh.xce, &n2);
+  } else {  // a held T_cl keeps its bits
+    CLC_AW_ROLLED for (int i = 0; i < 7; ++i) {
+      sh.xce[i] = sh.xc[i];
+      n2 += sh.xc[i] * sh.xc[i];
+    }
+  }
+  xn += n2;
+}
+template <class Sh>
+CLC_HD void tcl_accept(Sh& sh) {
+  CLC_AW_ROLLED for (int i = 0; i < 7; ++i) sh.xc[i] = sh.xce[i];
+}
+template <int NC, class Sh>
+CLC_HD double tcl_gradient(const Sh& sh, double m) {
+  return fmax(m, block_gradient_norm(sh.xc, sh.tot[sh.cur] + (ArrowRecord<NC>::E_GC - ArrowRecord<NC>::E_C)));
+}
+
+// An additive parameter of a shared block moved from x to its candidate v (a held one keeps its bits: v = x): its shares of
+// |x - xe|^2 and |xe|^2.  Returns v.
+CLC_HD double additive_candidate(double x, double v, double& sn, double& xn) {
+  sn += (x - v) * (x - v);
+  xn += v * v;
+  return v;
+}
+
+// The free parameters of a shared block, Sh holds them as free_idx[NC] (ascending, the rest 0): returns how many.
+template <int NC, class F>
+CLC_HD int free_parameters(int32_t* free_idx, F is_free) {
+  int nf = 0;
+  CLC_AW_ROLLED for (int i = 0; i < NC; ++i) {
+    free_idx[i] = 0;
+    if (is_free(i)) free_idx[nf++] = i;
+  }
+  return nf;
+}
+
+// max(m, the gradient max norm over the free additive parameters from index `from` on)
+template <int NC, class Sh>
+CLC_HD double free_gradient(const Sh& sh, int from, double m) {
+  CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f)
+    if (sh.free_idx[f] >= from) m = fmax(m, fabs(sh.tot[sh.cur][(ArrowRecord<NC>::E_GC - ArrowRecord<NC>::E_C) + sh.free_idx[f]]));
+  return m;
+}
+
+// The reduced system sh.A / sh.rhs without the rows and columns of the held parameters: sh.Af (n x n), sh.rf.
+template <int NC, class Sh>
+CLC_HD void compact_free(Sh& sh, int n) {
+  CLC_AW_ROLLED for (int p = 0; p < n; ++p) {
+    CLC_AW_ROLLED for (int q = 0; q < n; ++q) sh.Af[n * p + q] = sh.A[NC * sh.free_idx[p] + sh.free_idx[q]];
+    sh.rf[p] = sh.rhs[sh.free_idx[p]];
+  }
+}
+// ... solved with chol_solve at N free parameters: sh.yf[0..N)
+template <int NC, int N, class Sh>
+CLC_HD bool solve_free(Sh& sh) {
+  compact_free<NC>(sh, N);
+  return chol_solve<N>(sh.Af, sh.rf, sh.yf, sh.L, sh.z);
+}
+// ... and -sh.yf scattered into sh.step_c; false if `ok` is or a component is not finite.
+template <class Sh>
+CLC_HD bool scatter_free(Sh& sh, bool ok) {
+  CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) {
+    sh.step_c[sh.free_idx[f]] = -sh.yf[f];
+    if (!finite_d(sh.yf[f])) ok = false;
+  }
+  return ok;
 }
 
 // Y = M^-1 B (6 x NC) and S = B^T Y (tri<NC> order) of one image, from im.L.

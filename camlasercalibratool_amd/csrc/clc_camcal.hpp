@@ -275,16 +275,6 @@ CLC_HD void camera_of(const CalShared& sh, const double* k, clc_camera& c) {
   for (int i = 0; i < 4; ++i) { c.proj[i] = k[i]; c.dist[i] = k[4 + i]; }
 }
 
-// The reduced system sh.A / sh.rhs without the rows and columns of the held intrinsics, solved: sh.yf[0..N).
-template <int N>
-CLC_HD bool solve_free(CalShared& sh) {
-  CLC_AW_ROLLED for (int p = 0; p < N; ++p) {
-    CLC_AW_ROLLED for (int q = 0; q < N; ++q) sh.Af[N * p + q] = sh.A[NK * sh.free_idx[p] + sh.free_idx[q]];
-    sh.rf[p] = sh.rhs[sh.free_idx[p]];
-  }
-  return chol_solve<N>(sh.Af, sh.rf, sh.yf, sh.L, sh.z);
-}
-
 // Why an image takes no part (wave-uniform; every lane of the image's wave calls it).
 CLC_HD int image_status(const CalArgs& a, long long img) {
   if (a.keep && !a.keep[img]) return CLC_CAMCAL_NOT_KEPT;
@@ -316,11 +306,7 @@ struct CalTraits {
 
   // clamped to the call's images: n_images from prob_off[0] on
   static CLC_HD aw::Problem<Image> problem(const Args& a, long long pb) {
-    const long long first = a.prob_off ? a.prob_off[0] : 0;
-    long long i0 = a.prob_off ? a.prob_off[pb] : 0, i1 = a.prob_off ? a.prob_off[pb + 1] : a.n_images;
-    if (i0 < first) i0 = first;
-    if (i1 > first + a.n_images) i1 = first + a.n_images;
-    return {i0, i1 > i0 ? i1 - i0 : 0, a.ws + (i0 - first)};
+    return aw::problem_range(a.prob_off, pb, a.prob_off ? a.prob_off[0] : 0, a.n_images, a.ws);
   }
   static CLC_HD int image_status(const Args& a, long long img) { return cc::image_status(a, img); }
   static CLC_HD long long observations(const Args& a, long long img) { return a.coff[img + 1] - a.coff[img]; }
@@ -337,50 +323,35 @@ struct CalTraits {
       ok = ok && finite_d(cam.proj[i]) && finite_d(cam.dist[i]);
     }
     sh.model = cam.model;
-    int nf = 0;
-    CLC_AW_ROLLED for (int i = 0; i < NK; ++i) {
-      sh.free_idx[i] = 0;
-      if (!held(a, i)) sh.free_idx[nf++] = i;
-    }
-    sh.n_free = nf;
+    sh.n_free = aw::free_parameters<NK>(sh.free_idx, [&](int i) { return !held(a, i); });
     sh.n_corners = n_corners;
-    sh.move_c = nf > 0 ? 1 : 0;
+    sh.move_c = sh.n_free > 0 ? 1 : 0;
     if (sh.move_c) CLC_AW_ROLLED for (int i = 0; i < NK; ++i) xn += sh.kc[i] * sh.kc[i];
     return ok;
   }
   static CLC_HD bool held(const Args& a, int p) { return (a.hold_mask >> p) & 1u; }
   static CLC_HD double cost(const double* tot) { return tot[E_COST - E_C]; }
-  static CLC_HD double block_gradient(const Shared& sh, double m) {
-    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) m = fmax(m, fabs(sh.tot[sh.cur][(E_GC - E_C) + sh.free_idx[f]]));
-    return m;
-  }
+  static CLC_HD double block_gradient(const Shared& sh, double m) { return aw::free_gradient<NK>(sh, 0, m); }
   // held intrinsics lose their rows and columns: chol_solve at the number of free ones
   static CLC_HD bool solve_block(Shared& sh) {
     bool ok;
     switch (sh.n_free) {
-      case 1: ok = solve_free<1>(sh); break;
-      case 2: ok = solve_free<2>(sh); break;
-      case 3: ok = solve_free<3>(sh); break;
-      case 4: ok = solve_free<4>(sh); break;
-      case 5: ok = solve_free<5>(sh); break;
-      case 6: ok = solve_free<6>(sh); break;
-      case 7: ok = solve_free<7>(sh); break;
-      default: ok = solve_free<8>(sh); break;
+      case 1: ok = aw::solve_free<NK, 1>(sh); break;
+      case 2: ok = aw::solve_free<NK, 2>(sh); break;
+      case 3: ok = aw::solve_free<NK, 3>(sh); break;
+      case 4: ok = aw::solve_free<NK, 4>(sh); break;
+      case 5: ok = aw::solve_free<NK, 5>(sh); break;
+      case 6: ok = aw::solve_free<NK, 6>(sh); break;
+      case 7: ok = aw::solve_free<NK, 7>(sh); break;
+      default: ok = aw::solve_free<NK, 8>(sh); break;
     }
-    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) {
-      sh.step_c[sh.free_idx[f]] = -sh.yf[f];
-      if (!finite_d(sh.yf[f])) ok = false;
-    }
-    return ok;
+    return aw::scatter_free(sh, ok);
   }
   static CLC_HD void block_candidate(Shared& sh, double& sn, double& xn) {
     CLC_AW_ROLLED for (int p = 0; p < NK; ++p) {
       // a held intrinsic (scale 0, step 0) keeps its bits
       const double d = sh.step_c[p] * sh.scale_c[p];
-      const double v = sh.scale_c[p] != 0.0 ? sh.kc[p] + d : sh.kc[p];
-      sh.kce[p] = v;
-      sn += (sh.kc[p] - v) * (sh.kc[p] - v);
-      xn += v * v;
+      sh.kce[p] = aw::additive_candidate(sh.kc[p], sh.scale_c[p] != 0.0 ? sh.kc[p] + d : sh.kc[p], sn, xn);
     }
   }
   static CLC_HD void accept_block(Shared& sh) {

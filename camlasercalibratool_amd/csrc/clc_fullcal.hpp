@@ -5,15 +5,17 @@
 //   cost = 1/2 sum rho_ac(|e_j|^2) + 1/2 sum rho_al(r_k^2)        rho_a(z) = a^2 log1p(z / a^2), rho_a'(z) = 1 / (1 + z / a^2); a = 0: z
 //
 // The loss is K22's: one loss on a corner's residual 2-vector, Ceres' corrector for rho'' <= 0 (rows and residual scaled by
-// sqrt(rho')), so the Gauss-Newton blocks take w J^T J and w J^T r with w = rho'(z).  The fifth arrow problem of clc_arrow.hpp, with
+// sqrt(rho')), so the Gauss-Newton blocks take w J^T J and w J^T r with w = rho'(z).  An arrow problem of clc_arrow.hpp, with
 // a 16-wide shared block
 //
 //   [dt_cl(3), dtheta_cl(3), b, kappa, proj[0..3], dist[0..3]]       the leading 8 as K21's H_cr, the trailing 8 in clc_camera order
 //
 // T_cl moves on its tangent, b, kappa and the intrinsics additively.  The laser rows do not depend on the intrinsics and the corner
 // rows not on T_cl, b, kappa: the [T_cl, range] x intrinsics block of C is exactly zero, it is written as zeros and never summed; the
-// two groups couple only through the board poses in the Schur complement.  The range correction (clc_laserrange.hpp) and the Cauchy
-// weight (clc_jointrobust.hpp) are restated here in their few lines: those headers belong to their own units.
+// two groups couple only through the board poses in the Schur complement.  The laser row under the range correction, the point rules, the
+// Cauchy loss and the skeleton of the weights are clc_jointterms.hpp's, the same that K21 and K22 take, and the corner rows
+// clc_camcal.hpp's; this file holds K23's arguments, its evaluation with the eight passes written out, and what is its shared block's
+// own.
 //
 //   fullcal_kernel   one 256-thread workgroup (4 waves) per problem, the whole Levenberg-Marquardt solve in one launch.
 //     evaluation   per image a wave all-reduces K19's four corner passes with each corner's rows weighted by rho' — {A_i, g_i, sum rho}
@@ -31,13 +33,13 @@
 // the threads as loops, in the same summation order (log1p is the platform's: the device and the host build agree to rounding where
 // a loss is on).
 #pragma once
-#include "clc_arrow.hpp"
+#include "clc_jointterms.hpp"
 #include "clc_camcal.hpp"
 
 namespace clc {
 namespace fc {
 
-using aw::finite_d;
+using namespace jtm;
 
 constexpr int FULL_THREADS = aw::ARROW_THREADS;
 constexpr int NF = 16;  // the shared block
@@ -87,84 +89,22 @@ struct FullArgs {
   FullImage* ws;                   // [n_images], the call's first image first
 };
 
-// rho_a and rho_a' at z, with a2 = a^2 and inv_a2 = 1 / a^2 (K22's definitions).
-CLC_HD double cauchy_weight(double z, double inv_a2) { return 1.0 / (1.0 + z * inv_a2); }
-CLC_HD double cauchy_rho(double z, double a2, double inv_a2) { return a2 * log1p(z * inv_a2); }
-
-// |p|, and a point the model takes: finite with a range that is finite and > 0 (K21's rule).
-CLC_HD double point_range(const double* p) {
-  CLC_BF_NO_CONTRACT
-  return sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
-}
-CLC_HD bool point_usable(const double* p) {
-  const double rho = point_range(p);
-  return finite_d(p[0]) && finite_d(p[1]) && finite_d(p[2]) && finite_d(rho) && rho > 0.0;
-}
-
-// The laser residual of the measured point p and its Jacobians (K21's range_point): p' = (1 + kappa + b / |p|) p,
-// r = e3^T R^T (R_cl p' + t_cl - t) / sigma; Ji over [dt_i, dtheta_i], Jc over [dt_cl, dtheta_cl, b, kappa].
-CLC_HD void range_point(const double* R, const double* t, const double* Rcl, const double* tcl, double b, double kappa, const double* p,
-                        double inv_s, double* Ji, double* Jc, double* r) {
-  CLC_BF_NO_CONTRACT
-  const double rho = point_range(p), inv = 1.0 / rho;
-  const double s = (1.0 + kappa) + b / rho;
-  double pc[3], uh[3], d[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    uh[i] = p[i] * inv;
-    pc[i] = s * p[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) d[i] = (((Rcl[3 * i] * pc[0] + Rcl[3 * i + 1] * pc[1]) + Rcl[3 * i + 2] * pc[2]) + tcl[i]) - t[i];
-  const double m0 = (R[0] * d[0] + R[3] * d[1]) + R[6] * d[2];
-  const double m1 = (R[1] * d[0] + R[4] * d[1]) + R[7] * d[2];
-  const double m2 = (R[2] * d[0] + R[5] * d[1]) + R[8] * d[2];
-  const double n0 = R[2], n1 = R[5], n2 = R[8];
-  *r = m2 * inv_s;
-  Ji[0] = -n0 * inv_s; Ji[1] = -n1 * inv_s; Ji[2] = -n2 * inv_s;
-  Ji[3] = -m1 * inv_s; Ji[4] = m0 * inv_s; Ji[5] = 0.0;
-  // u = R_cl^T n; d r / d theta_cl = (p' x u) / sigma
-  const double u0 = (Rcl[0] * n0 + Rcl[3] * n1) + Rcl[6] * n2;
-  const double u1 = (Rcl[1] * n0 + Rcl[4] * n1) + Rcl[7] * n2;
-  const double u2 = (Rcl[2] * n0 + Rcl[5] * n1) + Rcl[8] * n2;
-  Jc[0] = n0 * inv_s; Jc[1] = n1 * inv_s; Jc[2] = n2 * inv_s;
-  Jc[3] = (pc[1] * u2 - pc[2] * u1) * inv_s;
-  Jc[4] = (pc[2] * u0 - pc[0] * u2) * inv_s;
-  Jc[5] = (pc[0] * u1 - pc[1] * u0) * inv_s;
-  Jc[6] = ((u0 * uh[0] + u1 * uh[1]) + u2 * uh[2]) * inv_s;
-  Jc[7] = ((u0 * p[0] + u1 * p[1]) + u2 * p[2]) * inv_s;
-}
-
 // What an evaluation sees of the shared block at its candidate.
 struct FullCtx {
   clc_camera cam;
   double Rcl[9], tcl[3], b, kappa;
 };
 
-// The loss scales of a call, prepared once per evaluation.
-struct Loss {
-  bool corner, laser;
-  double ac2, inv_ac2, al2, inv_al2;
-};
-CLC_HD Loss loss_of(const FullArgs& a) {
-  Loss l;
-  l.corner = a.loss_corner != 0.0;
-  l.laser = a.loss_laser != 0.0;
-  l.ac2 = a.loss_corner * a.loss_corner;
-  l.al2 = a.loss_laser * a.loss_laser;
-  l.inv_ac2 = l.corner ? 1.0 / l.ac2 : 0.0;
-  l.inv_al2 = l.laser ? 1.0 / l.al2 : 0.0;
-  return l;
-}
-
-// One image's evaluation record at pose7 / ctx: every lane of the image's wave calls it (host: once); the lead lane stores.
+// One image's evaluation record at pose7 / ctx: every lane of the image's wave calls it (host: once); the lead lane stores.  The
+// eight passes are written out: grouped from the shared accumulate helpers fullcal_kernel computed the same sums in another
+// instruction order and its batch measured 0.3 % slower (profiles/joint_terms_refactor.md).
 CLC_HD void eval_image(const FullArgs& a, const FullCtx& c, long long img, const double* pose7, double* E) {
   CLC_BF_NO_CONTRACT
   double xe[7], R[9];
 #pragma unroll
   for (int i = 0; i < 7; ++i) xe[i] = pose7[i];
   quat_to_rot(xe + 3, R);
-  const Loss ls = loss_of(a);
+  const Loss ls = loss_of(a.loss_corner, a.loss_laser);
   // the cross block of C: the laser rows carry no intrinsics, the corner rows nothing of [T_cl, b, kappa]
   if (bf::lead_lane())
     CLC_AW_ROLLED for (int p = 0; p < NX; ++p)
@@ -431,8 +371,15 @@ CLC_HD void eval_image(const FullArgs& a, const FullCtx& c, long long img, const
   }
 }
 
+// What the weights read of a call: the corners (where they take part) are pixels indexed by the absolute offsets, no end named.
+CLC_HD ImageView view_of(const FullArgs& a) {
+  return {a.corners, a.board, a.use_corners ? a.coff : nullptr, 0, 0, NO_CORNER_END, a.pts, a.poff, a.keep, a.q, a.t, a.status,
+          a.w_corner, a.w_laser};
+}
+
 // Why an image takes no part (wave-uniform; every lane of the image's wave calls it): K19's rule for the corners (where they take
-// part), K21's for the points.
+// part), K21's for the points.  The rule of jtm::image_status, written out: through jtm's view fullcal_kernel's batch measured
+// 1.3 % slower (profiles/joint_terms_refactor.md).  A change to the rule has to be made in both places.
 CLC_HD int image_status(const FullArgs& a, long long img) {
   if (a.keep && !a.keep[img]) return CLC_JOINT_NOT_KEPT;
   const long long pb = a.poff[img], np = a.poff[img + 1] - pb;
@@ -463,46 +410,6 @@ CLC_HD int image_status(const FullArgs& a, long long img) {
   return CLC_JOINT_OK;
 }
 
-// Solve A y = b for the symmetric positive definite n x n A (row-major, n at run time): chol_solve of clc_math.hpp, rolled.
-// L (n * n), z (n) scratch; false if a pivot is not positive.
-CLC_HD bool chol_solve_n(int n, const double* A, const double* b, double* y, double* L, double* z) {
-  CLC_AW_ROLLED for (int j = 0; j < n; ++j) {
-    double d = A[n * j + j];
-    CLC_AW_ROLLED for (int k = 0; k < j; ++k) d -= L[n * j + k] * L[n * j + k];
-    if (!(d > 0.0)) return false;
-    const double inv = rsqrt_pos(d);
-    L[n * j + j] = inv;
-    CLC_AW_ROLLED for (int i = j + 1; i < n; ++i) {
-      double s = A[n * i + j];
-      CLC_AW_ROLLED for (int k = 0; k < j; ++k) s -= L[n * i + k] * L[n * j + k];
-      L[n * i + j] = s * inv;
-    }
-  }
-  CLC_AW_ROLLED for (int i = 0; i < n; ++i) {
-    double s = b[i];
-    CLC_AW_ROLLED for (int k = 0; k < i; ++k) s -= L[n * i + k] * z[k];
-    z[i] = s * L[n * i + i];
-  }
-  CLC_AW_ROLLED for (int i = n - 1; i >= 0; --i) {
-    double s = z[i];
-    CLC_AW_ROLLED for (int k = i + 1; k < n; ++k) s -= L[n * k + i] * y[k];
-    y[i] = s * L[n * i + i];
-  }
-  return true;
-}
-
-// [first image, images) of problem pb and its first image's place in the workspace, clamped to the call's images: n_images from
-// prob_off[0] on (K19's convention: nothing is read back to size the workspace).
-CLC_HD void problem_range(const FullArgs& a, long long pb, long long* i0, long long* P, long long* w0) {
-  const long long first = a.prob_off ? a.prob_off[0] : 0;
-  long long b = a.prob_off ? a.prob_off[pb] : 0, e = a.prob_off ? a.prob_off[pb + 1] : a.n_images;
-  if (b < first) b = first;
-  if (e > first + a.n_images) e = first + a.n_images;
-  *i0 = b;
-  *P = e > b ? e - b : 0;
-  *w0 = b - first;
-}
-
 // What K23 gives the arrow solve (clc_arrow.hpp): the 16-wide shared block.
 struct FullTraits {
   static constexpr int NC = NF, EVAL_DOUBLES = fc::EVAL_DOUBLES;
@@ -511,20 +418,16 @@ struct FullTraits {
   using Shared = FullShared;
   using Ctx = FullCtx;
 
+  // the call's images: n_images from prob_off[0] on (K19's convention: nothing is read back to size the workspace)
   static CLC_HD aw::Problem<Image> problem(const Args& a, long long pb) {
-    long long i0, P, w0;
-    problem_range(a, pb, &i0, &P, &w0);
-    return {i0, P, a.ws + w0};
+    return aw::problem_range(a.prob_off, pb, a.prob_off ? a.prob_off[0] : 0, a.n_images, a.ws);
   }
-  static CLC_HD int image_status(const Args& a, long long img) { return fc::image_status(a, img); }
+  static CLC_HD int image_status(const Args& a, long long img) {
+    return fc::image_status(a, img);
+  }
   static CLC_HD long long observations(const Args& a, long long img) { return a.poff[img + 1] - a.poff[img]; }
   static CLC_HD void context(const Shared& sh, Ctx& c) {
-    double q[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) q[i] = sh.xce[3 + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c.tcl[i] = sh.xce[i];
-    quat_to_rot(q, c.Rcl);
+    aw::tcl_context(sh, c);
     c.b = sh.rge[0];
     c.kappa = sh.rge[1];
     c.cam.model = sh.model;
@@ -544,11 +447,7 @@ struct FullTraits {
   static CLC_HD bool init_block(const Args& a, long long pb, long long n_laser, Shared& sh, double& xn) {
     const clc_camera& cam = a.cams[pb];
     bool ok = cam.model == CLC_CAMERA_PINHOLE || cam.model == CLC_CAMERA_KANNALA_BRANDT;
-    CLC_AW_ROLLED for (int i = 0; i < 7; ++i) {
-      const double v = a.poses_cl[7 * pb + i];
-      sh.xc[i] = sh.xce[i] = v;
-      ok = ok && finite_d(v);
-    }
+    ok = aw::tcl_init(a.poses_cl + 7 * pb, sh) && ok;
     CLC_AW_ROLLED for (int i = 0; i < 2; ++i) {
       const double v = a.range[2 * pb + i];
       sh.rg[i] = sh.rge[i] = v;
@@ -561,17 +460,14 @@ struct FullTraits {
     }
     sh.model = cam.model;
     // without a laser point nothing constrains T_cl, b, kappa: the problem holds them by itself
-    int nf = 0;
-    CLC_AW_ROLLED for (int i = 0; i < NF; ++i) {
-      sh.free_idx[i] = 0;
+    sh.n_free = aw::free_parameters<NF>(sh.free_idx, [&](int i) {  // (the predicate also records sh.is_free[i])
       const bool fr = !held(a, i) && !(i < NX && n_laser == 0);
       sh.is_free[i] = fr ? 1 : 0;
-      if (fr) sh.free_idx[nf++] = i;
-    }
-    sh.n_free = nf;
+      return fr;
+    });
     sh.hold_pose = (a.hold_extrinsic || n_laser == 0) ? 1 : 0;
     sh.n_laser = n_laser;
-    sh.move_c = nf > 0 ? 1 : 0;
+    sh.move_c = sh.n_free > 0 ? 1 : 0;
     if (sh.move_c) {
       CLC_AW_ROLLED for (int i = 0; i < 7; ++i) xn += sh.xc[i] * sh.xc[i];
       CLC_AW_ROLLED for (int i = 0; i < 2; ++i) xn += sh.rg[i] * sh.rg[i];
@@ -579,50 +475,28 @@ struct FullTraits {
     }
     return ok;
   }
-  static CLC_HD double cost(const double* tot) { return tot[E_COST_CORNER - E_C] + tot[E_COST_LASER - E_C]; }
+  static CLC_HD double cost(const double* tot) { return aw::cost_of_parts<NF>(tot); }
   static CLC_HD double block_gradient(const Shared& sh, double m) {
     if (!sh.move_c) return m;
-    if (!sh.hold_pose) m = fmax(m, aw::block_gradient_norm(sh.xc, sh.tot[sh.cur] + (E_GC - E_C)));
-    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f)
-      if (sh.free_idx[f] >= 6) m = fmax(m, fabs(sh.tot[sh.cur][(E_GC - E_C) + sh.free_idx[f]]));
-    return m;
+    if (!sh.hold_pose) m = aw::tcl_gradient<NF>(sh, m);
+    return aw::free_gradient<NF>(sh, 6, m);
   }
-  // held parameters lose their rows and columns: the Cholesky runs at the number of free ones
+  // held parameters lose their rows and columns: the rolled Cholesky runs at the number of free ones
   static CLC_HD bool solve_block(Shared& sh) {
-    const int n = sh.n_free;
-    CLC_AW_ROLLED for (int p = 0; p < n; ++p) {
-      CLC_AW_ROLLED for (int q = 0; q < n; ++q) sh.Af[n * p + q] = sh.A[NF * sh.free_idx[p] + sh.free_idx[q]];
-      sh.rf[p] = sh.rhs[sh.free_idx[p]];
-    }
-    bool ok = chol_solve_n(n, sh.Af, sh.rf, sh.yf, sh.L, sh.z);
-    CLC_AW_ROLLED for (int f = 0; f < n; ++f) {
-      sh.step_c[sh.free_idx[f]] = -sh.yf[f];
-      if (!finite_d(sh.yf[f])) ok = false;
-    }
-    return ok;
+    aw::compact_free<NF>(sh, sh.n_free);
+    return aw::scatter_free(sh, aw::chol_solve_n(sh.n_free, sh.Af, sh.rf, sh.yf, sh.L, sh.z));
   }
   static CLC_HD void block_candidate(Shared& sh, double& sn, double& xn) {
-    double n2 = 0.0;
-    if (!sh.hold_pose) {
-      sn += aw::block_candidate(sh.xc, sh.step_c, sh.scale_c, sh.xce, &n2);
-    } else {  // a held T_cl keeps its bits
-      CLC_AW_ROLLED for (int i = 0; i < 7; ++i) {
-        sh.xce[i] = sh.xc[i];
-        n2 += sh.xc[i] * sh.xc[i];
-      }
-    }
-    xn += n2;
+    aw::tcl_candidate(sh, sh.hold_pose != 0, sn, xn);
     CLC_AW_ROLLED for (int p = 6; p < NF; ++p) {
       // a held parameter keeps its bits
       const double x0 = p < NX ? sh.rg[p - 6] : sh.kc[p - NX];
-      const double v = sh.is_free[p] ? x0 + sh.step_c[p] * sh.scale_c[p] : x0;
+      const double v = aw::additive_candidate(x0, sh.is_free[p] ? x0 + sh.step_c[p] * sh.scale_c[p] : x0, sn, xn);
       if (p < NX) sh.rge[p - 6] = v; else sh.kce[p - NX] = v;
-      sn += (x0 - v) * (x0 - v);
-      xn += v * v;
     }
   }
   static CLC_HD void accept_block(Shared& sh) {
-    CLC_AW_ROLLED for (int i = 0; i < 7; ++i) sh.xc[i] = sh.xce[i];
+    aw::tcl_accept(sh);
     CLC_AW_ROLLED for (int i = 0; i < 2; ++i) sh.rg[i] = sh.rge[i];
     CLC_AW_ROLLED for (int i = 0; i < NK; ++i) sh.kc[i] = sh.kce[i];
   }
@@ -637,13 +511,10 @@ struct FullTraits {
           if (i < 4) a.cams[pb].proj[i] = sh.kc[i]; else a.cams[pb].dist[i - 4] = sh.kc[i];
         }
     }
-    const bool have = sh.n_evals > 0 && !failed;
-    if (a.cost_parts) {
-      a.cost_parts[2 * pb] = have ? sh.tot[sh.cur][E_COST_CORNER - E_C] : __builtin_nan("");
-      a.cost_parts[2 * pb + 1] = have ? sh.tot[sh.cur][E_COST_LASER - E_C] : __builtin_nan("");
-    }
+    aw::write_cost_parts<NF>(a.cost_parts, pb, sh, failed);
     if (a.rms) {
       // sigma_px sqrt(2 cost_corner / corners) over the participating images: K19's RMS where the corners carry no loss
+      const bool have = sh.n_evals > 0 && !failed;
       long long n_corners = 0;
       if (a.use_corners) {
         const aw::Problem<Image> pr = problem(a, pb);
@@ -658,87 +529,35 @@ struct FullTraits {
 // One problem: every thread of its workgroup calls it (host: once).
 CLC_HD void full_problem(const FullArgs& a, long long pb, FullShared& sh) { aw::arrow_problem<FullTraits>(a, pb, sh); }
 
-// f(lane) on the 64 lanes of a wave (host: a loop).
-template <class F>
-CLC_HD void each_wave_lane(F f) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  f((int)(threadIdx.x & 63));
-#else
-  for (int l = 0; l < cp::POSE_LANES; ++l) f(l);
-#endif
-}
-
-// The weights of one image at the returned point, after the solve: every lane of the image's wave calls it (host: once).  `failed`:
-// the image's problem ended CLC_FAILURE.  An image that takes no part gets NaN over the ranges its offsets name (K22's convention);
-// without use_corners no corner weight is written.
-CLC_HD void weights_image(const FullArgs& a, long long img, bool failed, const clc_camera& cam, const double* pose_cl, double b, double kappa) {
-  CLC_BF_NO_CONTRACT
-  const long long pb = a.poff[img], np = a.poff[img + 1] - pb;
-  long long cb = 0, n = 0;
-  if (a.use_corners) {
-    cb = a.coff[img];
-    n = a.coff[img + 1] - cb;
-  }
-  const bool corners_in = a.use_corners && cb >= 0 && n >= 0, points_in = pb >= 0 && np >= 0;
-  const bool part = a.status[img] == CLC_JOINT_OK && !failed;
-  if (!part) {
-    each_wave_lane([&](int lane) {
-      if (a.w_corner && corners_in)
-        for (long long k = lane; k < n; k += cp::POSE_LANES) a.w_corner[cb + k] = __builtin_nan("");
-      if (a.w_laser && points_in)
-        for (long long k = lane; k < np; k += cp::POSE_LANES) a.w_laser[pb + k] = __builtin_nan("");
-    });
-    return;
-  }
-  // the pose as the solve reads it: [t, q(xyzw)] normalised
-  const double qw = a.q[4 * img], qx = a.q[4 * img + 1], qy = a.q[4 * img + 2], qz = a.q[4 * img + 3];
-  const double inv = 1.0 / sqrt((qw * qw + qx * qx) + (qy * qy + qz * qz));
-  const double xe[7] = {a.t[3 * img], a.t[3 * img + 1], a.t[3 * img + 2], qx * inv, qy * inv, qz * inv, qw * inv};
-  double R[9], Rcl[9], qcl[4];
-  quat_to_rot(xe + 3, R);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) qcl[i] = pose_cl[3 + i];
-  quat_to_rot(qcl, Rcl);
-  const Loss ls = loss_of(a);
-  const double inv_px = 1.0 / a.sigma_px, inv_s = 1.0 / a.sigma_laser;
-  const float* __restrict__ px = a.use_corners ? a.corners + 2 * cb : nullptr;
-  const float* __restrict__ board = a.use_corners ? a.board + 2 * cb : nullptr;
-  const double* __restrict__ pts = a.pts + 3 * pb;
-  each_wave_lane([&](int lane) {
-    if (a.w_corner)
-      for (long long k = lane; k < n; k += cp::POSE_LANES) {
-        double w = 1.0;
-        if (ls.corner) {
-          double r[2], J[12], JK[16];
-          cc::corner_terms(cam, R, xe, board[2 * k], board[2 * k + 1], px[2 * k], px[2 * k + 1], inv_px, r, J, JK);
-          w = cauchy_weight(r[0] * r[0] + r[1] * r[1], ls.inv_ac2);
-        }
-        a.w_corner[cb + k] = w;
-      }
-    if (a.w_laser)
-      for (long long k = lane; k < np; k += cp::POSE_LANES) {
-        double w = 1.0;
-        if (ls.laser) {
-          double Ji[6], Jc[NX], r;
-          range_point(R, xe, Rcl, pose_cl, b, kappa, pts + 3 * k, inv_s, Ji, Jc, &r);
-          w = cauchy_weight(r * r, ls.inv_al2);
-        }
-        a.w_laser[pb + k] = w;
-      }
-  });
-}
-
-// The weights of one problem: the waves take its images round-robin (host: a loop).
+// The weights of one problem at the returned point: the waves take its images round-robin (host: a loop).  Without use_corners no
+// corner weight is written.
 CLC_HD void weights_problem(const FullArgs& a, long long pb) {
-  long long i0, P, w0;
-  problem_range(a, pb, &i0, &P, &w0);
+  CLC_BF_NO_CONTRACT
+  const aw::Problem<FullImage> pr = FullTraits::problem(a, pb);
   const bool failed = a.summaries[pb].termination == CLC_FAILURE;
   const clc_camera cam = a.cams[pb];
   double pose_cl[7];
 #pragma unroll
   for (int i = 0; i < 7; ++i) pose_cl[i] = a.poses_cl[7 * pb + i];
   const double b = a.range[2 * pb], kappa = a.range[2 * pb + 1];
-  aw::each_image_wave(P, [&](long long j) { weights_image(a, i0 + j, failed, cam, pose_cl, b, kappa); });
+  const ImageView v = view_of(a);
+  const Loss ls = loss_of(a.loss_corner, a.loss_laser);
+  const double inv_px = 1.0 / a.sigma_px, inv_s = 1.0 / a.sigma_laser;
+  aw::each_image_wave(pr.P, [&](long long j) {
+    double Rcl[9];
+    quat_to_rot(pose_cl + 3, Rcl);
+    weights_image(v, ls, pr.i0 + j, failed,
+                  [&](const double* R, const double* xe, const float* px, const float* board, long long k) {
+                    double r[2], J[12], JK[16];
+                    cc::corner_terms(cam, R, xe, board[2 * k], board[2 * k + 1], px[2 * k], px[2 * k + 1], inv_px, r, J, JK);
+                    return cauchy_weight(r[0] * r[0] + r[1] * r[1], ls.inv_ac2);
+                  },
+                  [&](const double* R, const double* xe, const double* pts, long long k) {
+                    double Ji[6], Jc[NX], r;
+                    range_point(R, xe, Rcl, pose_cl, b, kappa, pts + 3 * k, inv_s, Ji, Jc, &r);
+                    return cauchy_weight(r * r, ls.inv_al2);
+                  });
+  });
 }
 
 #if defined(__HIPCC__)

@@ -9,8 +9,9 @@
 //
 // The arrow of clc_arrow.hpp with an 8-wide shared block [dt_cl, dtheta_cl, b, kappa]: T_cl moves on its tangent as in K18, b and
 // kappa additively.  With u = R_cl^T n, n = R_i e3:  d r / d b = (u . p / |p|) / sigma,  d r / d kappa = (u . p) / sigma; the Jacobians
-// over the board pose and T_cl are K18's at p'.  The solve (step, controller, outputs) is aw::arrow_problem; this file holds the
-// cost and what is the shared block's own.
+// over the board pose and T_cl are K18's at p' (range_point of clc_jointterms.hpp, where the terms of the cost are).  The solve
+// (step, controller, outputs) is aw::arrow_problem; this file holds K21's arguments, its evaluation with the passes written out, and
+// what is its shared block's own.
 //
 //   range_refine_kernel    one 256-thread workgroup (4 waves) per problem, the whole Levenberg-Marquardt solve in one launch.
 //     evaluation   per image a wave all-reduces (wave_sum of clc_campose.hpp) the corners' {H, g, sum r^2} (reproj_accumulate; left
@@ -28,12 +29,12 @@
 // Everything numeric is CLC_HD: tests/shim/laserrange_shim.cpp compiles this header for the host with g++ and runs the same code
 // with the threads as loops, in the same summation order.
 #pragma once
-#include "clc_arrow.hpp"
+#include "clc_jointterms.hpp"
 
 namespace clc {
 namespace lr {
 
-using aw::finite_d;
+using namespace jtm;
 
 constexpr int RANGE_THREADS = aw::ARROW_THREADS;
 constexpr int NR = 8;  // the shared block: T_cl's tangent (6), b, kappa
@@ -75,61 +76,11 @@ struct RangeArgs {
   RangeImage* ws;                 // [n_images], image first_image first
 };
 
-// |p|, summed as everywhere in this file.
-CLC_HD double point_range(const double* p) {
-  CLC_BF_NO_CONTRACT
-  return sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
-}
-
-// A point the model takes: finite with a range that is finite and > 0 (a zero range is the scanner's "no return").
-CLC_HD bool point_usable(const double* p) {
-  const double rho = point_range(p);
-  return finite_d(p[0]) && finite_d(p[1]) && finite_d(p[2]) && finite_d(rho) && rho > 0.0;
-}
-
-// p' = (1 + kappa + b / |p|) p; uh = p / |p|.  (b, kappa) = (0, 0) gives p itself, bit for bit.
-CLC_HD void correct_point(const double* p, double b, double kappa, double* pc, double* uh) {
-  CLC_BF_NO_CONTRACT
-  const double rho = point_range(p), inv = 1.0 / rho;
-  const double s = (1.0 + kappa) + b / rho;  // (the model's own expression, not b * inv: one rounding fewer)
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    uh[i] = p[i] * inv;
-    pc[i] = s * p[i];
-  }
-}
-
-// The laser residual of the measured point p and its Jacobians: r = e3^T R^T (R_cl p' + t_cl - t) / sigma; Ji over [dt_i, dtheta_i],
-// Jc over [dt_cl, dtheta_cl, b, kappa].  The first six of Jc, Ji and r are K18's laser_point at p'.
-CLC_HD void range_point(const double* R, const double* t, const double* Rcl, const double* tcl, double b, double kappa, const double* p,
-                        double inv_s, double* Ji, double* Jc, double* r) {
-  CLC_BF_NO_CONTRACT
-  double pc[3], uh[3], d[3];
-  correct_point(p, b, kappa, pc, uh);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) d[i] = (((Rcl[3 * i] * pc[0] + Rcl[3 * i + 1] * pc[1]) + Rcl[3 * i + 2] * pc[2]) + tcl[i]) - t[i];
-  const double m0 = (R[0] * d[0] + R[3] * d[1]) + R[6] * d[2];
-  const double m1 = (R[1] * d[0] + R[4] * d[1]) + R[7] * d[2];
-  const double m2 = (R[2] * d[0] + R[5] * d[1]) + R[8] * d[2];
-  const double n0 = R[2], n1 = R[5], n2 = R[8];
-  *r = m2 * inv_s;
-  Ji[0] = -n0 * inv_s; Ji[1] = -n1 * inv_s; Ji[2] = -n2 * inv_s;
-  Ji[3] = -m1 * inv_s; Ji[4] = m0 * inv_s; Ji[5] = 0.0;
-  // u = R_cl^T n; d r / d theta_cl = (p' x u) / sigma
-  const double u0 = (Rcl[0] * n0 + Rcl[3] * n1) + Rcl[6] * n2;
-  const double u1 = (Rcl[1] * n0 + Rcl[4] * n1) + Rcl[7] * n2;
-  const double u2 = (Rcl[2] * n0 + Rcl[5] * n1) + Rcl[8] * n2;
-  Jc[0] = n0 * inv_s; Jc[1] = n1 * inv_s; Jc[2] = n2 * inv_s;
-  Jc[3] = (pc[1] * u2 - pc[2] * u1) * inv_s;
-  Jc[4] = (pc[2] * u0 - pc[0] * u2) * inv_s;
-  Jc[5] = (pc[0] * u1 - pc[1] * u0) * inv_s;
-  Jc[6] = ((u0 * uh[0] + u1 * uh[1]) + u2 * uh[2]) * inv_s;
-  Jc[7] = ((u0 * p[0] + u1 * p[1]) + u2 * p[2]) * inv_s;
-}
-
 struct RangeCtx { double Rcl[9], tcl[3], b, kappa; };
 
-// One image's evaluation record at pose7 / ctx: every lane of the image's wave calls it (host: once); the lead lane stores.
+// One image's evaluation record at pose7 / ctx: every lane of the image's wave calls it (host: once); the lead lane stores.  The
+// passes are K18's (jtm::lifted_corner_pass, jtm::laser_passes) written out: through the shared bodies range_refine_kernel computed
+// the same sums in another instruction order and measured up to 1 % slower (profiles/joint_terms_refactor.md).
 CLC_HD void eval_image(const RangeArgs& a, const RangeCtx& c, long long img, const double* pose7, double* E) {
   CLC_BF_NO_CONTRACT
   double xe[7], R[9];
@@ -232,46 +183,11 @@ CLC_HD void eval_image(const RangeArgs& a, const RangeCtx& c, long long img, con
   }
 }
 
-// Why an image takes no part (wave-uniform; every lane of the image's wave calls it).  With the board poses held an image needs no
-// corners: it takes part if it is kept, its points are usable and its start pose is finite.
-CLC_HD int image_status(const RangeArgs& a, long long img) {
-  if (a.keep && !a.keep[img]) return CLC_JOINT_NOT_KEPT;
-  const long long pb = a.poff[img], np = a.poff[img + 1] - pb;
-  long long n = 0;
-  const float *lifted = nullptr, *board = nullptr;
-  if (!a.hold_board_poses) {
-    const long long cb = a.coff[img];
-    n = a.coff[img + 1] - cb;
-    if (n < 4) return CLC_JOINT_TOO_FEW;
-    if (cb < a.first_corner || cb + n > a.first_corner + a.n_corners) return CLC_JOINT_NONFINITE;
-    lifted = a.lifted + 2 * (cb - a.first_corner);
-    board = a.board + 2 * cb;
-  }
-  if (np < 0 || pb < 0) return CLC_JOINT_NONFINITE;
-  const double* pts = a.pts + 3 * pb;
-  double bad[1];
-  cp::wave_sum<1>([&](int lane, double* acc) {
-    for (long long k = lane; k < n; k += cp::POSE_LANES)
-      if (!(isfinite(lifted[2 * k]) && isfinite(lifted[2 * k + 1]) && isfinite(board[2 * k]) && isfinite(board[2 * k + 1]))) acc[0] += 1.0;
-    for (long long k = lane; k < np; k += cp::POSE_LANES)
-      if (!point_usable(pts + 3 * k)) acc[0] += 1.0;
-    if (lane < 4 && !finite_d(a.q[4 * img + lane])) acc[0] += 1.0;
-    if (lane < 3 && !finite_d(a.t[3 * img + lane])) acc[0] += 1.0;
-  }, bad);
-  if (bad[0] != 0.0) return CLC_JOINT_NONFINITE;
-  const double w = a.q[4 * img], x = a.q[4 * img + 1], y = a.q[4 * img + 2], z = a.q[4 * img + 3];
-  if (!((w * w + x * x) + (y * y + z * z) > 0.0)) return CLC_JOINT_NONFINITE;
-  return CLC_JOINT_OK;
-}
-
-// The reduced system sh.A / sh.rhs without the rows and columns of the held parameters, solved: sh.yf[0..N).
-template <int N>
-CLC_HD bool solve_free(RangeShared& sh) {
-  CLC_AW_ROLLED for (int p = 0; p < N; ++p) {
-    CLC_AW_ROLLED for (int q = 0; q < N; ++q) sh.Af[N * p + q] = sh.A[NR * sh.free_idx[p] + sh.free_idx[q]];
-    sh.rf[p] = sh.rhs[sh.free_idx[p]];
-  }
-  return chol_solve<N>(sh.Af, sh.rf, sh.yf, sh.L, sh.z);
+// With the board poses held an image needs no corners: it takes part if it is kept, its points are usable and its start pose is
+// finite.
+CLC_HD ImageView view_of(const RangeArgs& a) {
+  return {a.lifted, a.board, a.hold_board_poses ? nullptr : a.coff, a.first_corner, a.first_corner, a.first_corner + a.n_corners, a.pts,
+          a.poff, a.keep, a.q, a.t, a.status, nullptr, nullptr};
 }
 
 // What K21 gives the arrow solve (clc_arrow.hpp): the shared block is T_cl's tangent and the two range parameters.
@@ -282,22 +198,15 @@ struct RangeTraits {
   using Shared = RangeShared;
   using Ctx = RangeCtx;
 
-  // clamped to [first_image, first_image + n_images)
   static CLC_HD aw::Problem<Image> problem(const Args& a, long long pb) {
-    long long i0 = a.prob_off ? a.prob_off[pb] : a.first_image, i1 = a.prob_off ? a.prob_off[pb + 1] : a.first_image + a.n_images;
-    if (i0 < a.first_image) i0 = a.first_image;
-    if (i1 > a.first_image + a.n_images) i1 = a.first_image + a.n_images;
-    return {i0, i1 > i0 ? i1 - i0 : 0, a.ws + (i0 - a.first_image)};
+    return aw::problem_range(a.prob_off, pb, a.first_image, a.n_images, a.ws);
   }
-  static CLC_HD int image_status(const Args& a, long long img) { return lr::image_status(a, img); }
+  static CLC_HD int image_status(const Args& a, long long img) {
+    return jtm::image_status(view_of(a), img, [](const double* p) { return point_usable(p); });
+  }
   static CLC_HD long long observations(const Args& a, long long img) { return a.poff[img + 1] - a.poff[img]; }
   static CLC_HD void context(const Shared& sh, Ctx& c) {
-    double q[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) q[i] = sh.xce[3 + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c.tcl[i] = sh.xce[i];
-    quat_to_rot(q, c.Rcl);
+    aw::tcl_context(sh, c);
     c.b = sh.rge[0];
     c.kappa = sh.rge[1];
   }
@@ -306,78 +215,50 @@ struct RangeTraits {
   }
   static CLC_HD bool held(const Args& a, int p) { return p < 6 ? a.hold_extrinsic != 0 : ((a.hold_range_mask >> (p - 6)) & 1) != 0; }
   static CLC_HD bool init_block(const Args& a, long long pb, long long n_laser, Shared& sh, double& xn) {
-    bool ok = true;
-    CLC_AW_ROLLED for (int i = 0; i < 7; ++i) {
-      const double v = a.poses_cl[7 * pb + i];
-      sh.xc[i] = sh.xce[i] = v;
-      ok = ok && finite_d(v);
-    }
+    bool ok = aw::tcl_init(a.poses_cl + 7 * pb, sh);
     CLC_AW_ROLLED for (int i = 0; i < 2; ++i) {
       const double v = a.range[2 * pb + i];
       sh.rg[i] = sh.rge[i] = v;
       ok = ok && finite_d(v);
     }
-    int nf = 0;
-    CLC_AW_ROLLED for (int i = 0; i < NR; ++i) {
-      sh.free_idx[i] = 0;
-      if (!held(a, i)) sh.free_idx[nf++] = i;
-    }
-    sh.n_free = nf;
+    sh.n_free = aw::free_parameters<NR>(sh.free_idx, [&](int i) { return !held(a, i); });
     sh.hold_pose = a.hold_extrinsic ? 1 : 0;
     sh.n_laser = n_laser;
-    sh.move_c = (nf == 0 || n_laser == 0) ? 0 : 1;
+    sh.move_c = (sh.n_free == 0 || n_laser == 0) ? 0 : 1;
     if (sh.move_c) {
       CLC_AW_ROLLED for (int i = 0; i < 7; ++i) xn += sh.xc[i] * sh.xc[i];
       CLC_AW_ROLLED for (int i = 0; i < 2; ++i) xn += sh.rg[i] * sh.rg[i];
     }
     return ok;
   }
-  static CLC_HD double cost(const double* tot) { return tot[E_COST_CORNER - E_C] + tot[E_COST_LASER - E_C]; }
+  static CLC_HD double cost(const double* tot) { return aw::cost_of_parts<NR>(tot); }
   static CLC_HD double block_gradient(const Shared& sh, double m) {
     if (!sh.move_c) return m;
-    if (!sh.hold_pose) m = fmax(m, aw::block_gradient_norm(sh.xc, sh.tot[sh.cur] + (E_GC - E_C)));
-    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f)
-      if (sh.free_idx[f] >= 6) m = fmax(m, fabs(sh.tot[sh.cur][(E_GC - E_C) + sh.free_idx[f]]));
-    return m;
+    if (!sh.hold_pose) m = aw::tcl_gradient<NR>(sh, m);
+    return aw::free_gradient<NR>(sh, 6, m);
   }
   // held parameters lose their rows and columns: chol_solve at the number of free ones
   static CLC_HD bool solve_block(Shared& sh) {
     bool ok;
     switch (sh.n_free) {
-      case 1: ok = solve_free<1>(sh); break;
-      case 2: ok = solve_free<2>(sh); break;
-      case 6: ok = solve_free<6>(sh); break;
-      case 7: ok = solve_free<7>(sh); break;
-      default: ok = solve_free<8>(sh); break;
+      case 1: ok = aw::solve_free<NR, 1>(sh); break;
+      case 2: ok = aw::solve_free<NR, 2>(sh); break;
+      case 6: ok = aw::solve_free<NR, 6>(sh); break;
+      case 7: ok = aw::solve_free<NR, 7>(sh); break;
+      default: ok = aw::solve_free<NR, 8>(sh); break;
     }
-    CLC_AW_ROLLED for (int f = 0; f < sh.n_free; ++f) {
-      sh.step_c[sh.free_idx[f]] = -sh.yf[f];
-      if (!finite_d(sh.yf[f])) ok = false;
-    }
-    return ok;
+    return aw::scatter_free(sh, ok);
   }
   static CLC_HD void block_candidate(Shared& sh, double& sn, double& xn) {
-    double n2 = 0.0;
-    if (!sh.hold_pose) {
-      sn += aw::block_candidate(sh.xc, sh.step_c, sh.scale_c, sh.xce, &n2);
-    } else {  // a held T_cl keeps its bits
-      CLC_AW_ROLLED for (int i = 0; i < 7; ++i) {
-        sh.xce[i] = sh.xc[i];
-        n2 += sh.xc[i] * sh.xc[i];
-      }
-    }
-    xn += n2;
+    aw::tcl_candidate(sh, sh.hold_pose != 0, sn, xn);
     CLC_AW_ROLLED for (int p = 0; p < 2; ++p) {
       // a held parameter (scale 0, step 0) keeps its bits
       const double d = sh.step_c[6 + p] * sh.scale_c[6 + p];
-      const double v = sh.scale_c[6 + p] != 0.0 ? sh.rg[p] + d : sh.rg[p];
-      sh.rge[p] = v;
-      sn += (sh.rg[p] - v) * (sh.rg[p] - v);
-      xn += v * v;
+      sh.rge[p] = aw::additive_candidate(sh.rg[p], sh.scale_c[6 + p] != 0.0 ? sh.rg[p] + d : sh.rg[p], sn, xn);
     }
   }
   static CLC_HD void accept_block(Shared& sh) {
-    CLC_AW_ROLLED for (int i = 0; i < 7; ++i) sh.xc[i] = sh.xce[i];
+    aw::tcl_accept(sh);
     CLC_AW_ROLLED for (int i = 0; i < 2; ++i) sh.rg[i] = sh.rge[i];
   }
   static CLC_HD double* information(const Args& a) { return a.H_cr; }
@@ -387,11 +268,7 @@ struct RangeTraits {
       CLC_AW_ROLLED for (int i = 0; i < 2; ++i)
         if (!held(a, 6 + i)) a.range[2 * pb + i] = sh.rg[i];
     }
-    if (a.cost_parts) {
-      const bool have = sh.n_evals > 0 && !failed;
-      a.cost_parts[2 * pb] = have ? sh.tot[sh.cur][E_COST_CORNER - E_C] : __builtin_nan("");
-      a.cost_parts[2 * pb + 1] = have ? sh.tot[sh.cur][E_COST_LASER - E_C] : __builtin_nan("");
-    }
+    aw::write_cost_parts<NR>(a.cost_parts, pb, sh, failed);
   }
 };
 
@@ -427,18 +304,6 @@ static __global__ __launch_bounds__(CORRECT_THREADS) void range_correct_kernel(c
     out[3 * k + 1] = o[1];
     out[3 * k + 2] = o[2];
   }
-}
-
-// The ranges a device-array call needs on the host to size its scratch: {first image, first corner, end of the corners}; coff NULL
-// (the board poses held): no corners.
-static __global__ void range_ends_kernel(const long long* __restrict__ prob_off, const long long* __restrict__ coff, const long long n_images,
-                                         long long* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const long long first = prob_off ? prob_off[0] : 0;
-  out[0] = first;
-  const bool ok = first >= 0 && coff != nullptr;
-  out[1] = ok ? coff[first] : 0;
-  out[2] = ok ? coff[first + n_images] : (first >= 0 ? 0 : -1);
 }
 
 #endif  // __HIPCC__

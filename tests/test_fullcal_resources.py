@@ -1,4 +1,4 @@
-"""Build-time guard of the kernels of K23 (csrc/clc_fullcal.hpp on clc_arrow.hpp and clc_camcal.hpp), without a GPU: the build wiring,
+"""Build-time guard of the kernels of K23 (csrc/clc_fullcal.hpp on clc_jointterms.hpp, clc_arrow.hpp and clc_camcal.hpp), without a GPU: the build wiring,
 and hipcc's kernel-resource-usage remarks for gfx950 over abi_fullcal.hip only.  fullcal_kernel — the evaluation waves with the four
 weighted corner passes and the four weighted laser passes, the per-lane Schur step over a 6 x 16 coupling block and the controller
 with its run-time-n Cholesky in one kernel — uses no scratch memory, spills no VGPR and stays within the figures it was built with;
@@ -21,8 +21,9 @@ def test_build_wiring():
     assert "abi_fullcal.hip" in _build.UNITS
     assert "clc_fullcal.hpp" in _build.SIDE_HEADERS and "clc_fullcal.hpp" not in _build.HEADERS
     src = open(os.path.join(CSRC, "clc_fullcal.hpp")).read()
-    # the arrow and K19's corner terms; neither K21's nor K22's header (their own units alone include them)
-    assert re.findall(r'#include\s+["<]([^">]+)[">]', src) == ["clc_arrow.hpp", "clc_camcal.hpp"]
+    # the leaf of the joint problems (over clc_arrow.hpp) and K19's corner terms; neither K21's nor K22's header (their own units alone
+    # include them)
+    assert re.findall(r'#include\s+["<]([^">]+)[">]', src) == ["clc_jointterms.hpp", "clc_camcal.hpp"]
     others = [u for u in _build.UNITS + _build.HEADERS + _build.HOST_HEADERS + _build.SIDE_HEADERS if u not in ("abi_fullcal.hip", "clc_fullcal.hpp")]
     for u in others:  # the unit alone includes the header
         assert "clc_fullcal.hpp" not in re.findall(r'#include\s+"([^"]+)"', open(os.path.join(CSRC, u)).read()), u
@@ -93,8 +94,8 @@ def test_no_kernel_reads_ranges_back(usage):
 
 
 def test_other_units_do_not_name_the_new_kernels():
-    """clc_arrow.hpp, clc_camcal.hpp, clc_laserrange.hpp, clc_jointrobust.hpp and their units are as they were: none of them mentions
-    K23."""
+    """The headers and units of K19, K21 and K22 and the headers under them know nothing of K23: what they share they take from
+    clc_arrow.hpp, clc_jointterms.hpp and abi_jointcall.hpp (the last two may name every unit), never from one another."""
     for u in ("clc_arrow.hpp", "clc_camcal.hpp", "abi_camcal.hip", "clc_laserrange.hpp", "abi_laserrange.hip", "clc_jointrobust.hpp",
               "abi_jointrobust.hip", "clc_campose.hpp", "clc_math.hpp"):
         assert "fullcal" not in open(os.path.join(CSRC, u)).read(), u

@@ -1,4 +1,4 @@
-"""Build-time guard of the kernels of K22 (csrc/clc_jointrobust.hpp on clc_arrow.hpp), without a GPU: the build wiring, and hipcc's
+"""Build-time guard of the kernels of K22 (csrc/clc_jointrobust.hpp on clc_jointterms.hpp and clc_arrow.hpp), without a GPU: the build wiring, and hipcc's
 kernel-resource-usage remarks for gfx950 over abi_jointrobust.hip only.  joint_robust_kernel — the evaluation waves with the
 per-corner row and its weight, the three weighted laser passes, the per-lane Schur step and the controller in one kernel — uses no
 scratch memory, spills no VGPR and stays within the figures it was built with; the weights kernel and the kernel that reads the
@@ -20,7 +20,7 @@ def test_build_wiring():
     assert "abi_jointrobust.hip" in _build.UNITS
     assert "clc_jointrobust.hpp" in _build.SIDE_HEADERS and "clc_jointrobust.hpp" not in _build.HEADERS
     src = open(os.path.join(CSRC, "clc_jointrobust.hpp")).read()
-    assert re.findall(r'#include\s+["<]([^">]+)[">]', src) == ["clc_arrow.hpp"]
+    assert re.findall(r'#include\s+["<]([^">]+)[">]', src) == ["clc_jointterms.hpp"]  # the leaf of the joint problems (over clc_arrow.hpp)
     others = [u for u in _build.UNITS + _build.HEADERS + _build.HOST_HEADERS + _build.SIDE_HEADERS if u not in ("abi_jointrobust.hip", "clc_jointrobust.hpp")]
     for u in others:  # the unit alone includes the header
         assert "clc_jointrobust.hpp" not in re.findall(r'#include\s+"([^"]+)"', open(os.path.join(CSRC, u)).read()), u
@@ -78,12 +78,13 @@ def test_weights_kernel_is_small(usage):
 
 
 def test_ends_kernel_is_small(usage):
-    r = one(usage, "robust_ends_kernel")
+    r = one(usage, "joint_ends_kernelILi0E")  # clc_jointterms.hpp's (a template), the one under K18, K21 and K22
     assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["LDS Size"] == 0, r
     assert r["VGPRs"] + r["AGPRs"] <= 16, r
 
 
 def test_other_units_do_not_name_the_new_kernels():
-    """clc_arrow.hpp, clc_joint.hpp and abi_joint.hip are as they were: none of them mentions K22."""
+    """K18's header and unit and the headers under them know nothing of K22: what the two share they take from clc_jointterms.hpp and
+    abi_jointcall.hpp (which may name every unit), never from one another."""
     for u in ("clc_arrow.hpp", "clc_joint.hpp", "abi_joint.hip", "clc_campose.hpp", "clc_math.hpp"):
         assert "jointrobust" not in open(os.path.join(CSRC, u)).read() and "joint_robust" not in open(os.path.join(CSRC, u)).read(), u

@@ -1,4 +1,4 @@
-"""Build-time guard of the kernels of K21 (csrc/clc_laserrange.hpp on clc_arrow.hpp), without a GPU: the build wiring, and hipcc's
+"""Build-time guard of the kernels of K21 (csrc/clc_laserrange.hpp on clc_jointterms.hpp and clc_arrow.hpp), without a GPU: the build wiring, and hipcc's
 kernel-resource-usage remarks for gfx950 over abi_laserrange.hip only.  range_refine_kernel — the evaluation waves with the 48-wide
 and 44-wide passes, the per-lane Schur step and the controller in one kernel — uses no scratch memory, spills no VGPR and stays within
 the figures it was built with; the point correction and the kernel that reads the ranges of a device-array call stay small."""
@@ -18,7 +18,7 @@ def test_build_wiring():
     assert "abi_laserrange.hip" in _build.UNITS
     assert "clc_laserrange.hpp" in _build.SIDE_HEADERS and "clc_laserrange.hpp" not in _build.HEADERS
     src = open(os.path.join(CSRC, "clc_laserrange.hpp")).read()
-    assert re.findall(r'#include\s+["<]([^">]+)[">]', src) == ["clc_arrow.hpp"]
+    assert re.findall(r'#include\s+["<]([^">]+)[">]', src) == ["clc_jointterms.hpp"]  # the leaf of the joint problems (over clc_arrow.hpp)
     others = [u for u in _build.UNITS + _build.HEADERS + _build.HOST_HEADERS + _build.SIDE_HEADERS if u not in ("abi_laserrange.hip", "clc_laserrange.hpp")]
     for u in others:  # the unit alone includes the header
         assert "clc_laserrange.hpp" not in re.findall(r'#include\s+"([^"]+)"', open(os.path.join(CSRC, u)).read()), u
@@ -74,6 +74,6 @@ def test_correct_kernel_is_small(usage):
 
 
 def test_ends_kernel_is_small(usage):
-    r = one(usage, "range_ends_kernel")
+    r = one(usage, "joint_ends_kernelILi0E")  # clc_jointterms.hpp's (a template), the one under K18, K21 and K22
     assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["LDS Size"] == 0, r
     assert r["VGPRs"] + r["AGPRs"] <= 16, r
