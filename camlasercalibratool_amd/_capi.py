@@ -49,6 +49,7 @@ EXPORTED = [
     "clc_assemble_options_default", "clc_keyframes", "clc_assemble_observations", "clc_assemble_observations_device",
     "clc_stored_observations",
     "clc_station_options_default", "clc_static_poses", "clc_assemble_stations", "clc_assemble_stations_device",
+    "clc_subpix_options_default", "clc_corner_subpix", "clc_corner_subpix_device",
     "clc_interp_options_default", "clc_interpolate_poses", "clc_assemble_interpolated", "clc_assemble_interpolated_device",
     "clc_clock_offset_options_default", "clc_clock_offset_best", "clc_clock_offset_sweep", "clc_clock_offset_sweep_device",
 ]
@@ -218,6 +219,14 @@ class GuidanceOptions(C.Structure):
                 ("eig_floor", C.c_double), ("criterion", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SubpixOptions(C.Structure):
+    """clc_subpix_options (include/clc.h): the half-window, the zero zone (-1: none) and the stopping rule of K24."""
+    _fields_ = [("win_x", C.c_int32), ("win_y", C.c_int32), ("zero_x", C.c_int32), ("zero_y", C.c_int32), ("max_iter", C.c_int32),
+                ("reserved", C.c_int32), ("eps", C.c_double)]
+
+
+SUBPIX_MAX_WIN = 15  # CLC_SUBPIX_MAX_WIN
+SUBPIX_CONVERGED, SUBPIX_MAX_ITER, SUBPIX_SINGULAR, SUBPIX_LEFT_IMAGE, SUBPIX_REVERTED, SUBPIX_NONFINITE = 1, 0, -1, -2, -3, -4  # CLC_SUBPIX_*
 GUIDE_LOGDET, GUIDE_MIN_EIG = 0, 1  # CLC_GUIDE_*
 JOINT_OK, JOINT_TOO_FEW, JOINT_NOT_KEPT, JOINT_NONFINITE = 1, 0, -1, -2  # CLC_JOINT_*
 CAMCAL_OK, CAMCAL_TOO_FEW, CAMCAL_NOT_KEPT, CAMCAL_NONFINITE = 1, 0, -1, -2  # CLC_CAMCAL_*
@@ -382,6 +391,11 @@ def load(path: str):
             L.clc_score_board_poses_device.argtypes = [V, V, V, V, C.c_size_t] + [V] * 6
             L.clc_select_board_poses.argtypes = [V, V, V, V, C.c_size_t, V, V, C.c_size_t] + [V] * 5
             L.clc_select_board_poses_device.argtypes = [V, V, V, V, C.c_size_t, V, V, C.c_size_t] + [V] * 5
+        if hasattr(L, "clc_corner_subpix"):
+            L.clc_subpix_options_default.argtypes = [V, C.c_int32]
+            L.clc_subpix_options_default.restype = None
+            L.clc_corner_subpix.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 6
+            L.clc_corner_subpix_device.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 6
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -488,6 +502,14 @@ def default_guidance_options() -> GuidanceOptions:
     the floored log-determinant."""
     o = GuidanceOptions()
     lib().clc_guidance_options_default(C.byref(o))
+    return o
+
+
+def default_subpix_options(win: int = 3) -> SubpixOptions:
+    """clc_subpix_options_default: the half-window `win` on both axes (<= 0: 3, the reference's Kalibr call; its chessboard call uses
+    11), no zero zone, 30 iterations, eps 0.1."""
+    o = SubpixOptions()
+    lib().clc_subpix_options_default(C.byref(o), C.c_int32(win))
     return o
 
 

@@ -503,6 +503,25 @@ def CalcCamPoses(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np
     return q, t, st, rms
 
 
+def CornerSubPix(images, corners_px: Sequence[np.ndarray], win: int = 3, zero_zone: int = -1, max_iter: int = 30, eps: float = 0.1,
+                 solver: Optional[Solver] = None):
+    """cv::cornerSubPix as the reference calls it on every detection (src/calcCamPose.cpp:20-22: win 11 on the chessboard; :86-89: win 3
+    on the Kalibr tag grid; TermCriteria(EPS + MAX_ITER, 30, 0.1)), for many images at once (clc_corner_subpix, K24): images uint8
+    [n, H, W] grey, corners_px[k] [m_k, 2] the coarse corners of image k, e.g. the integer corners of a tag decoder.  Returns (refined,
+    status, strength), one array per image: the refined float32 corners as CalcCamPoses takes them, the CLC_SUBPIX_* codes (1 converged,
+    0 max_iter; < 0: -1 singular window, -2 left the image, -3 moved farther than the window and was put back, -4 non-finite start)
+    and the smaller eigenvalue of the window's gradient matrix, to drop weak corners by."""
+    counts = [len(np.asarray(c).reshape(-1, 2)) for c in corners_px]
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cat = (np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a in corners_px]) if len(corners_px)
+           else np.zeros((0, 2), np.float32))
+    o = _capi.SubpixOptions(win, win, zero_zone, zero_zone, max_iter, 0, eps)
+    sv = solver or _shared_solver()
+    r = sv.corner_subpix(images, cat, off, o)
+    cut = lambda a: [a[off[k]:off[k + 1]] for k in range(len(counts))]
+    return cut(r["corners"]), cut(r["status"]), cut(r["strength"])
+
+
 def CalcCamPosesRobust(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], solver: Optional[Solver] = None,
                        options: Optional[Options] = None, robust=None):
     """CalcCamPoses with a consensus over the tags of every image ahead of the fit (clc_board_poses_robust, K16): a tag decoded with a

@@ -30,16 +30,7 @@ Corners upload_corners(Staging& st, const float* corners_px, const float* board_
   return {px, board, st.in(rel.data(), rel.size()), 0, n_corners, rel.size() - 1};
 }
 
-// The corner range of a _device call: the two ends of its offsets (a small read and a synchronise ahead of the call's enqueue; the
-// lifted corners go to a scratch array of that size).  The offsets in between are not validated.
-int device_offset_ends(clc_handle* h, const char* who, const int64_t* offsets_dev, size_t n, long long ends[2]) {
-  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
-  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  CLC_HIP(hipStreamSynchronize(h->stream));
-  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": offsets not monotone").c_str());
-  return CLC_OK;
-}
+// (the corner range of a _device call: device_offset_ends of abi_drive.hpp; the lifted corners go to a scratch array of that size)
 Corners device_corners(const float* corners_px_dev, const float* board_xy_dev, const int64_t* offsets_dev, const long long ends[2], size_t n_images) {
   return {corners_px_dev, board_xy_dev, reinterpret_cast<const long long*>(offsets_dev), ends[0], (size_t)(ends[1] - ends[0]), n_images};
 }

@@ -145,6 +145,17 @@ inline int host_offsets(const char* who, const int64_t* offsets, size_t n, bool 
   return CLC_OK;
 }
 
+// The corner range of a _device call (abi_campose.hip, abi_subpix.hip): the two ends of its offsets [n + 1] in device memory (a small
+// read and a synchronise ahead of the call's enqueue).  The offsets in between are not validated.
+inline int device_offset_ends(clc_handle* h, const char* who, const int64_t* offsets_dev, size_t n, long long ends[2]) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
+  CLC_HIP(hipMemcpyAsync(&ends[0], offsets_dev, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipMemcpyAsync(&ends[1], offsets_dev + n, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  CLC_HIP(hipStreamSynchronize(h->stream));
+  if (ends[1] < ends[0] || ends[0] < 0) return fail(CLC_ERR_INVALID_ARG, (std::string(who) + ": offsets not monotone").c_str());
+  return CLC_OK;
+}
+
 // The counts and the problem offsets of the calls over problems of images (abi_joint.hip, abi_camcal.hip): what both forms of a
 // pair refuse alike, then (host form) the offsets [n_problems + 1] themselves, NULL being one problem over every image.
 inline int problem_count_checks(const char* who, size_t n_images, bool has_problem_offsets, size_t n_problems) {

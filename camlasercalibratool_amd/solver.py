@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, SubpixOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -882,6 +882,40 @@ class Solver:
         come back to the host as select_board_poses' do."""
         return self._select_board_poses("clc_select_board_poses_device", pose_cl, H0, options, n_cand, C.c_void_p(q_ptr or 0),
                                         C.c_void_p(t_ptr or 0), k)
+
+    # ---- sub-pixel corner refinement (K24) ----
+    def corner_subpix(self, images: np.ndarray, corners_px: np.ndarray, offsets: np.ndarray, options: Optional[SubpixOptions] = None,
+                      width: Optional[int] = None) -> dict:
+        """clc_corner_subpix (K24, cv::cornerSubPix restated): images uint8 [n, H, W], or [n, H, pitch] with width= given; corners_px
+        [M, 2] float32 start pixels grouped per image by the CSR offsets [n + 1] (absolute rows of corners_px).
+        -> dict(corners [M, 2] float32, status [M] int32 (CLC_SUBPIX_*), iterations [M] int32, strength [M]); rows outside
+        [offsets[0], offsets[n]) come back as they went in, with status -99, iterations 0 and strength NaN."""
+        img = np.ascontiguousarray(images, dtype=np.uint8)
+        if img.ndim != 3:
+            raise ValueError("corner_subpix: images must be [n, height, pitch]")
+        cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(off) - 1
+        if n != img.shape[0] or (n > 0 and (off[0] < 0 or off[-1] > len(cp))):
+            raise ValueError("corner_subpix: offsets need one entry per image and one more, inside corners_px")
+        out = cp.copy()
+        st = np.full(len(cp), -99, dtype=np.int32); it = np.zeros(len(cp), dtype=np.int32); lam = np.full(len(cp), np.nan)
+        V = lambda a: a.ctypes.data_as(C.c_void_p)
+        o = C.byref(options) if options is not None else None
+        check(self._L.clc_corner_subpix(self._h, o, V(img), C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]),
+                                        C.c_int64(img.shape[2]), C.c_size_t(n), V(cp), V(off), V(out), V(st), V(it), V(lam)),
+              "clc_corner_subpix")
+        return dict(corners=out, status=st, iterations=it, strength=lam)
+
+    def corner_subpix_device(self, images_ptr: int, width: int, height: int, pitch: int, n_images: int, corners_ptr: int, offsets_ptr: int,
+                             out_ptr: int, status_ptr: int = 0, iterations_ptr: int = 0, strength_ptr: int = 0,
+                             options: Optional[SubpixOptions] = None):
+        """clc_corner_subpix_device on device-resident arrays (data_ptr()s; ready on the solver's stream); out_ptr may be corners_ptr."""
+        V = lambda p: C.c_void_p(p or 0)
+        o = C.byref(options) if options is not None else None
+        check(self._L.clc_corner_subpix_device(self._h, o, V(images_ptr), C.c_int32(width), C.c_int32(height), C.c_int64(pitch),
+                                               C.c_size_t(n_images), V(corners_ptr), V(offsets_ptr), V(out_ptr), V(status_ptr),
+                                               V(iterations_ptr), V(strength_ptr)), "clc_corner_subpix_device")
 
     # ---- camera intrinsics from the board images (K19) ----
     def camera_guess(self, model: int, width: int, height: int, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray):

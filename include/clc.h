@@ -1302,6 +1302,55 @@ int clc_calibrate_full_device(clc_handle* h, clc_camera* cams_dev, const clc_opt
                               double* cost_parts_dev, double* rms_px_dev, int32_t* image_status_dev, double* w_corner_dev,
                               double* w_laser_dev);
 
+/* ---- sub-pixel corner refinement: batched cornerSubPix (K24) -----------------------------------------------------------------
+ * What the reference runs on every detection ahead of its pose estimate (cv::cornerSubPix, src/calcCamPose.cpp:20-22 with
+ * half-window 11 on the chessboard, :86-89 with half-window 3 on the Kalibr tag grid; 30 iterations, eps 0.1), restated from
+ * the published algorithm (DESIGN.md K24 holds every rounding step; the gap to OpenCV's own bits is NOT measured: OpenCV does not
+ * exist where this library is built).  Per corner, from cI = the start, in float32:
+ *   the (2 win_x + 3) x (2 win_y + 3) patch about cI, bilinear with ONE fractional pair for the whole patch and the border
+ *   replicated (getRectSubPix);  central differences tgx, tgy on the (2 win_x + 1) x (2 win_y + 1) window;  with the mask
+ *   m = exp(-(i / win_y)^2) exp(-(j / win_x)^2), 0 inside the zero zone:  a = sum m tgx^2, b = sum m tgx tgy, c = sum m tgy^2,
+ *   bb1 = sum m (tgx^2 px + tgx tgy py), bb2 = sum m (tgx tgy px + tgy^2 py) in double;  cI += [[a, b], [b, c]]^-1 [bb1, bb2];
+ *   until the squared shift is <= eps^2, max_iter iterations are done, the matrix is singular (|det| <= DBL_EPSILON^2) or cI has
+ *   left the image;  a result farther than the half-window from the start in x or y is given up: the start comes back.
+ * Two additions over OpenCV, both per corner and never an error of the call: a non-finite start comes back unchanged
+ * (CLC_SUBPIX_NONFINITE), and so does a start outside [0, width) x [0, height) (CLC_SUBPIX_LEFT_IMAGE, 0 iterations). */
+#define CLC_SUBPIX_MAX_WIN 15
+#define CLC_SUBPIX_CONVERGED 1   /* the last shift was <= eps */
+#define CLC_SUBPIX_MAX_ITER 0    /* max_iter iterations, the result kept */
+#define CLC_SUBPIX_SINGULAR -1   /* a flat or edge-only window: the iterate before it is returned */
+#define CLC_SUBPIX_LEFT_IMAGE -2 /* the iterate (or the start) is outside the image; the iterate is returned as it is */
+#define CLC_SUBPIX_REVERTED -3   /* farther than the half-window from the start: the start is returned; over every other status */
+#define CLC_SUBPIX_NONFINITE -4  /* a non-finite start, returned unchanged */
+typedef struct clc_subpix_options {
+  int32_t win_x, win_y;   /* half sizes of the window, 1 .. CLC_SUBPIX_MAX_WIN */
+  int32_t zero_x, zero_y; /* half sizes of the zero zone; off when either is negative or it is not smaller than the window */
+  int32_t max_iter;       /* 1 .. 100 */
+  int32_t reserved;       /* 0 */
+  double eps;             /* pixels, finite, >= 0 */
+} clc_subpix_options;     /* 32 bytes */
+
+/* win_x = win_y = win (win <= 0: 3, the reference's Kalibr call), no zero zone, 30 iterations, eps 0.1. */
+void clc_subpix_options_default(clc_subpix_options* sopt, int32_t win);
+
+/* images[n_images][height][pitch] uint8 grey (pitch >= width bytes per row), corners_in[2 M] float32 (x, y) pixels grouped per
+ * image by offsets[n_images + 1] (absolute indices into the corner arrays; offsets[0] may be > 0).  corners_out[2 M] (required;
+ * may be corners_in), and, every one nullable, status[M] (CLC_SUBPIX_*), iterations[M], strength[M]: the smaller eigenvalue of
+ * [[a, b], [b, c]] / sum m at the last evaluated iterate (NaN where none was evaluated) — a measure to drop weak corners by.
+ * All of them indexed as corners_in.  sopt NULL: the defaults of win 3.  CLC_ERR_INVALID_ARG before any device work: NULL h,
+ * images, corners_in, offsets or corners_out, width or height < 1, pitch < width, a half-window outside 1 .. 15, max_iter outside
+ * 1 .. 100, eps negative or not finite, reserved != 0, offsets that decrease.  n_images = 0 or no corner: CLC_OK, nothing
+ * written.  One wave per corner; deterministic: the same bits on every run, for a corner alone or in a batch, and through both
+ * forms.  One enqueue, one synchronisation. */
+int clc_corner_subpix(clc_handle* h, const clc_subpix_options* sopt, const uint8_t* images, int32_t width, int32_t height,
+                      int64_t pitch, size_t n_images, const float* corners_in, const int64_t* offsets, float* corners_out,
+                      int32_t* status, int32_t* iterations, double* strength);
+/* The same with every array in DEVICE memory (ready on the handle's stream); complete on return.  The two ends of offsets_dev
+ * are read ahead of the enqueue; the offsets in between are not validated. */
+int clc_corner_subpix_device(clc_handle* h, const clc_subpix_options* sopt, const uint8_t* images_dev, int32_t width, int32_t height,
+                             int64_t pitch, size_t n_images, const float* corners_in_dev, const int64_t* offsets_dev,
+                             float* corners_out_dev, int32_t* status_dev, int32_t* iterations_dev, double* strength_dev);
+
 #ifdef __cplusplus
 }
 #endif
