@@ -10,9 +10,11 @@
 //   pass        every lane: m = R^T n, c0 from the published rotation + translation (12 LDS reads), moments of its points,
 //               expansion (rows_flush), the first two levels of the wave butterfly (28 -> 7 registers per lane)  -> LDS
 //   row         wave w finishes accumulators 7 w .. 7 w + 6 over the 4 x 16 partial lanes and publishes them -> board A
-//   exchange    (wave 0) the first workgroup of each group of 32 (blockIdx % 8: the workgroups the dispatcher places on one
-//               XCD) sums its group's rows -> board B;  everybody reads the 8 rows of board B
-//   controller  wave 0 of EVERY workgroup advances the LM state it keeps in its registers (clc_lmuni.hpp) on the same 28 totals —
+//   exchange    the first workgroup of each group of 32 (blockIdx % 8: the workgroups the dispatcher places on one XCD) sums its
+//               group's rows -> board B, on a wave of its own (the gather wave, wave 5: it has nothing else to do, so the group
+//               row never waits for that workgroup's controller, nor the controller for the gather);  everybody reads the 8 rows
+//               of board B
+//   controller  wave 4 of EVERY workgroup advances the LM state it keeps in its registers (clc_lmuni.hpp) on the same 28 totals —
 //               the same arithmetic in the same order everywhere, so all 256 copies stay bit-identical (what the step chain
 //               already relies on) — and publishes the next rotation + translation + status for its workgroup
 //
@@ -63,7 +65,9 @@ constexpr int COOP_A_STRIDE = CLC_COOP_A_STRIDE, COOP_B_STRIDE = CLC_COOP_B_STRI
 // lanes with twice the points each issue ~30 % fewer instructions per SIMD than two waves per SIMD; the LDS part (98 KB) also
 // keeps a second workgroup off the CU.  Points per lane in registers + in LDS.
 constexpr int COOP_NW = 4, COOP_NL = 64 * COOP_NW;  // the point waves / lanes of a workgroup ...
-constexpr int COOP_THREADS = COOP_NL + 64;           // ... + the controller wave
+// ... + the controller wave (wave 4) + the gather wave (wave 5: it lives on the 8 group leaders of the two-hop form and ends at kernel
+// entry everywhere else).  Six waves are still at most two per SIMD: the 256-VGPR cap per wave stands.
+constexpr int COOP_THREADS = COOP_NL + 128;
 constexpr int COOP_STATUS_ABORT = -1;                // published instead of an LM status when the launch gives up
 constexpr int COOP_PR = 16, COOP_PL = 24;
 // points that carry z (p.z != 0 in some record: 24 bytes per slot instead of 16): the same registers and the same 98 KB of LDS hold
@@ -77,11 +81,14 @@ constexpr int COOP_DONE_OK = 1, COOP_DONE_ABORT = 2;
 #endif
 // (round 5, after the pose / totals reads became ds_read again and lmu_pre ~400 cycles shorter: C2 kernel flat within noise, 76.0-77.7 us,
 // for D1 600-1100 x D2 1200-2800; D2 3500 +1 us, D1 300 +10 us — scripts/r05_coop_sweep.sh)
+// (round 11, with the gather wave: D1 matters again — a gather wave that looks at 900 usually looks twice —, D2 hardly: C2 kernel
+// 76.3-77.4 us at D1 600, 76.4-76.8 at 900, 73.5-75.4 at 1 200, 74.9-76.2 at 1 500, 76.7-78.0 at 1 800, 78.0-79.0 at 2 100; at D1 1 200
+// D2 1 400 was 0.1-0.7 us below D2 2 200 in three sweeps out of three — the table is in profiles/r11_coop.md)
 #ifndef CLC_COOP_D1
-#define CLC_COOP_D1 900         // shader cycles after barrier A at which a leader first looks at its group's rows
+#define CLC_COOP_D1 1200        // shader cycles after barrier A at which a gather wave first looks at its group's rows
 #endif
 #ifndef CLC_COOP_D2
-#define CLC_COOP_D2 2200        // ... at which everybody first looks at the 8 group rows
+#define CLC_COOP_D2 1400        // ... at which every controller wave first looks at the 8 group rows (behind its lmu_pre, ~1 200 cycles)
 #endif
 
 #ifndef CLC_COOP_GRP
@@ -133,8 +140,8 @@ __device__ __forceinline__ void coop_wait_until(const long long t) {
 }
 
 #ifdef CLC_STAMPS
-// Debug build only (scripts/stamps_coop.py): shader-clock stamps of point wave 0 and the controller wave (row 0: they stamp disjoint
-// slots; point wave 3 in row 1) of workgroups 0, 7 (leaders), 8 and 255, per pass p < COOP_STAMP_PASSES at 12 p: 0 pass start, 1 pass done (partials in LDS), 2 row published, 3 (leaders) group rows
+// Debug build only (scripts/stamps_coop.py): shader-clock stamps of point wave 0, the controller wave and the gather wave (row 0: they stamp disjoint
+// slots; point wave 3 in row 1) of workgroups 0, 7 (leaders), 8 and 255, per pass p < COOP_STAMP_PASSES at 12 p: 0 pass start, 1 pass done (partials in LDS), 2 row published, 3 (leaders' gather wave) group rows
 // gathered, 4 group row published, 5 the 8 group rows arrived, 6 totals in LDS, 7 controller done (behind its barrier); inside the pass:
 // 8 pose + plane set up, 9 points done, 10 expansion done; 11 lmu_pre done.  Slot 12 * COOP_STAMP_PASSES: kernel entry, + 1: points in.
 constexpr int COOP_STAMP_PASSES = 16, COOP_STAMP_PER_PASS = 12, COOP_STAMP_SLOTS = COOP_STAMP_PER_PASS * COOP_STAMP_PASSES + 2;
@@ -166,6 +173,50 @@ __device__ __forceinline__ void wave_reduce_to_rows(double (&acc)[NACC], double 
   }
 }
 
+// Poll NR elements `step` bytes apart until every one of them carries `tag`.  One look in flight at a time, s_sleep between looks.
+// Measured and dropped: 2-3 looks in flight 256 cycles apart (6.8-7.1 us per pass against 6.2: the extra requests slow the rows they
+// look for), copies of the group-row board (8 or 32: the leaders' extra stores cost more than the shorter queues save).  Bounded by
+// `limit` ticks of the wall clock; after 20 us the launch's abort word is read as well.  false: the wait ran out, or the abort word is up.
+template <int NR>
+__device__ __forceinline__ bool coop_poll(const __amdgpu_buffer_rsrc_t rs, const unsigned int base, const unsigned int step, const unsigned int tag,
+                                          const unsigned int tag0, const unsigned long long limit, v4u (&w)[NR]) {
+  const unsigned long long t0 = wall_clock64();
+  for (;;) {
+    bool ok = true;
+    unsigned int bo = base;
+    asm volatile("" : "+v"(bo));  // (a fresh sample every iteration)
+#pragma unroll
+    for (int i = 0; i < NR; ++i) w[i] = coop_get(rs, bo + (unsigned int)i * step);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) ok = ok && coop_valid(w[i], tag);
+    if (__all(ok)) return true;
+    const unsigned long long waited = wall_clock64() - t0;
+    if (waited > COOP_ABORT_CHECK_TICKS) {  // (the abort word is ONE line for 256 readers: nobody looks at it while things are well)
+      unsigned int co = (unsigned int)offsetof(CoopBoard, ctl);
+      asm volatile("" : "+v"(co));
+      if (waited > limit || coop_get(rs, co)[0] == tag0) return false;
+    }
+    __builtin_amdgcn_s_sleep(CLC_COOP_POLL_SLEEP);
+  }
+}
+
+// Hop 1: the rows of group `grp` (workgroups grp + groups m; lane (h = lane >> 5, e = lane & 31) takes element e of members
+// 16 h .. 16 h + 15) summed in the fixed order members 0-15 + 16-31: lanes < NACC return element `lane` of the group row.
+template <int GROUPS>
+__device__ __forceinline__ bool coop_gather_group(const __amdgpu_buffer_rsrc_t rs, const int par, const int grp, const int lane, const unsigned int tag,
+                                                  const unsigned int tag0, const unsigned long long limit, double& row) {
+  const int h = lane >> 5, e = (lane & 31) < NACC ? (lane & 31) : NACC - 1;
+  v4u w[16];
+  const bool fine = coop_poll<16>(rs, coop_row_a(par, grp + GROUPS * 16 * h) + 16u * (unsigned int)e, (unsigned int)(GROUPS * COOP_A_STRIDE * 8), tag, tag0, limit, w);
+  double s = coop_value(w[0]);
+#pragma unroll
+  for (int i = 1; i < 16; ++i) s += coop_value(w[i]);
+  double s_lo = s, s_hi = s;
+  swap_halves(s_lo, s_hi);  // lanes < 32: own half (members 0-15) + the other half's (16-31)
+  row = s_lo + s_hi;
+  return fine;
+}
+
 template <bool WITH_LOSS, bool NT, bool WITH_Z = false, bool ONE_HOP = false>
 __global__ __launch_bounds__(COOP_THREADS) void coop_solve_kernel(
     const double* __restrict__ xyl, const double* __restrict__ zl, const unsigned int* __restrict__ res_row, const ResLane* __restrict__ lane_desc,
@@ -189,19 +240,54 @@ __global__ __launch_bounds__(COOP_THREADS) void coop_solve_kernel(
   COOP_STAMP(COOP_STAMP_PER_PASS * COOP_STAMP_PASSES);
 #endif
 
+  if (wave == NW + 1) {
+    // =====================================================================================================================
+    // The gather wave: hop 1 of the two-hop form, on the 8 group leaders only — everywhere else it ends HERE, before barrier 0 (a wave
+    // that has ended is not counted by the workgroup's barriers).  Per pass: [barrier A] -> sleep until D1 -> the group's 32 rows ->
+    // their sum -> the group row on board B -> [barrier B] -> the status word the controller wave has published.  It shares nothing
+    // with the controller wave but the barriers: the controller of a leader is a follower like any other.
+    // =====================================================================================================================
+    if (ONE_HOP || wg >= COOP_GROUPS) return;
+    const __amdgpu_buffer_rsrc_t rs = coop_rsrc(board);
+    const long long d1 = board->ctl[1] ? (long long)board->ctl[1] : CLC_COOP_D1;
+    const int grp = wg;  // (wg < COOP_GROUPS: wg % COOP_GROUPS)
+    __syncthreads();  // barrier 0
+    for (int k = 0;; ++k) {
+      __syncthreads();  // barrier A
+      const long long t_a = clock64();
+      const unsigned int tag = tag0 + (unsigned int)k;
+      const int par = k & 1;
+      coop_wait_until(t_a + d1);
+      double row;
+      const bool fine = coop_gather_group<COOP_GROUPS>(rs, par, grp, lane, tag, tag0, k == 0 ? COOP_CENSUS_TICKS : COOP_TIMEOUT_TICKS, row);
+      COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 3);
+      if (fine) {
+        if (lane < NACC) {
+#pragma unroll
+          for (int r = 0; r < COOP_REPLICAS; ++r) coop_put(rs, coop_row_b(par, (r + grp) % COOP_REPLICAS, grp), lane, row, tag);
+        }
+      } else if (lane == 0) {
+        // the poll timed out, or somebody else's did: the launch's abort word goes up (every poll loop reads it); nothing is published
+        __hip_atomic_store(reinterpret_cast<unsigned int*>(&board->ctl[0]), tag0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 4);
+      __syncthreads();  // barrier B: the controller wave has published the next pose, or the end
+      if (reinterpret_cast<const volatile int*>(sh_pub + 12)[0] != CLC_RUNNING) return;  // (wave-uniform: terminated, or the launch aborted)
+#ifdef CLC_STAMPS
+      ++stamp_pass;
+#endif
+    }
+  }
+
   if (wave == NW) {
     // =====================================================================================================================
     // The controller wave: no scan points, the LM state in its registers (clc_lmuni.hpp).  Per pass: [barrier A: the point waves'
-    // partials are in LDS] -> (leaders: gather the group's rows, publish the group row) -> lmu_pre while the rows travel -> the 8
-    // group rows -> totals -> lmu_post -> [barrier B: pose + status published].
+    // partials are in LDS] -> lmu_pre while the rows travel -> the 8 group rows (one-hop form: all 32 rows) -> totals -> lmu_post ->
+    // [barrier B: pose + status published].
     // =====================================================================================================================
-    // ONE_HOP = false: COOP_WGS workgroups, two hops (8 groups of 32).  ONE_HOP = true: COOP_SMALL_WGS (32) workgroups — the problem is
-    // small enough for them —, every one of them gathers all 32 rows itself (what a group leader does) and nobody publishes a group
-    // row.  (A compile-time switch: as a run-time one it cost the 256-workgroup form 4 % at C2.)
-    constexpr bool one_hop = ONE_HOP;
-    constexpr int groups = ONE_HOP ? 1 : COOP_GROUPS;
-    const int grp = ONE_HOP ? 0 : wg % COOP_GROUPS;  // (the XCD the dispatcher places this workgroup on: round-robin)
-    const bool leader = ONE_HOP || wg < COOP_GROUPS;
+    // ONE_HOP = false: COOP_WGS workgroups, two hops (8 groups of 32; hop 1 is the gather wave's, above).  ONE_HOP = true:
+    // COOP_SMALL_WGS (32) workgroups — the problem is small enough for them —, every one of them gathers all 32 rows itself and
+    // nobody publishes a group row.  (A compile-time switch: as a run-time one it cost the 256-workgroup form 4 % at C2.)
     clc_iteration* const tr = wg == 0 ? trace : nullptr;
     const int tr_cap = wg == 0 ? trace_cap : 0;
     LmState& st = *reinterpret_cast<LmState*>(sh_state);
@@ -225,108 +311,33 @@ __global__ __launch_bounds__(COOP_THREADS) void coop_solve_kernel(
     // have gone).
     // (one-hop form: lmu_pre runs first, ~1 100 cycles; the rows are published ~950 cycles after barrier A and take a hop to become
     // visible — first look at 1 900, measured 800...2 200: 4.6-4.9 us per pass, the minimum here)
-    const long long d1 = board->ctl[1] ? (long long)board->ctl[1] : (ONE_HOP ? 1900 : CLC_COOP_D1), d2 = board->ctl[2] ? (long long)board->ctl[2] : CLC_COOP_D2;
+    const long long d = ONE_HOP ? (board->ctl[1] ? (long long)board->ctl[1] : 1900) : (board->ctl[2] ? (long long)board->ctl[2] : CLC_COOP_D2);
     for (int k = 0;; ++k) {
       __syncthreads();  // barrier A
       // ---- the 28 totals of pass `k` over all workgroups -> sh_tot[1 - S.hx]; fixed order: group members 0-15 + 16-31, groups
       // 0-3 + 4-7.  Lane (h = lane >> 5, e = lane & 31) polls element e of half h of the rows. ----
       const unsigned int tag = tag0 + (unsigned int)k;
       const int par = k & 1;
-      const int h = lane >> 5, e = (lane & 31) < NACC ? (lane & 31) : NACC - 1;
       const bool mine = lane < NACC;
       const unsigned long long limit = k == 0 ? COOP_CENSUS_TICKS : COOP_TIMEOUT_TICKS;
-      bool fine = true;
+      bool fine;
       const long long t_a = clock64();
-      // What does not need the totals (lmu_pre), while the rows travel: a follower has the whole of hop 1 for it (and looks at the group
-      // rows afterwards); in the one-hop form it takes the place of the wait for the rows' publication.  (The leaders of the two-hop
-      // form: behind their first look at the group rows, below.)
-      if (ONE_HOP) {
-        if (k > 0) lmu_pre(S, st, opt, sh_tot, tr, tr_cap, lane);
-        COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 11);
-      }
-      if (leader) {
-        coop_wait_until(t_a + d1);
-        // rows of this group: workgroups grp + 8 m, m = 16 h .. 16 h + 15
-        v4u w[16];
-        const unsigned int base = coop_row_a(par, grp + groups * 16 * h) + 16u * (unsigned int)e;
-        constexpr unsigned int row_step = (unsigned int)(groups * COOP_A_STRIDE * 8);
-        const unsigned long long t0 = wall_clock64();
-        for (;;) {
-          bool ok = true;
-          unsigned int bo = base;
-          asm volatile("" : "+v"(bo));  // (a fresh sample every iteration)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) w[i] = coop_get(rs, bo + (unsigned int)i * row_step);
-#pragma unroll
-          for (int i = 0; i < 16; ++i) ok = ok && coop_valid(w[i], tag);
-          if (__all(ok)) break;
-          const unsigned long long waited = wall_clock64() - t0;
-          if (waited > COOP_ABORT_CHECK_TICKS) {  // (the abort word is ONE line for 256 readers: nobody looks at it while things are well)
-            unsigned int co = (unsigned int)offsetof(CoopBoard, ctl);
-            asm volatile("" : "+v"(co));
-            if (waited > limit || coop_get(rs, co)[0] == tag0) { fine = false; break; }
-          }
-          __builtin_amdgcn_s_sleep(CLC_COOP_POLL_SLEEP);
-        }
+      // What does not need the totals (lmu_pre), while the rows travel: it has the whole of hop 1 (one-hop form: the wait for the rows'
+      // publication) for it.
+      if (k > 0) lmu_pre(S, st, opt, sh_tot, tr, tr_cap, lane);
+      COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 11);
+      coop_wait_until(t_a + d);
+      if (ONE_HOP) {  // all 32 rows: the group IS the problem, its row the totals
+        double row;
+        fine = coop_gather_group<1>(rs, par, 0, lane, tag, tag0, limit, row);
         COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 3);
-        double s = coop_value(w[0]);
-#pragma unroll
-        for (int i = 1; i < 16; ++i) s += coop_value(w[i]);
-        double s_lo = s, s_hi = s;
-        swap_halves(s_lo, s_hi);  // lanes < 32: own half (members 0-15) + the other half's (16-31)
-        if (one_hop) {  // the group IS the problem: these are the totals
-          if (mine) sh_tot[32 * (1 - S.hx) + lane] = s_lo + s_hi;
-        } else if (mine && fine) {
-          int so = lane;
-          asm volatile("" : "+v"(so));  // (the store's lane offset computed HERE: hoisted out of the pass loop it was spilled, and its reload sat in front of the store)
-#pragma unroll
-          for (int r = 0; r < COOP_REPLICAS; ++r) coop_put(rs, coop_row_b(par, (r + grp) % COOP_REPLICAS, grp), so, s_lo + s_hi, tag);
-        }
+        if (mine) sh_tot[32 * (1 - S.hx) + lane] = row;
         COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 4);
-      }
-      // A leader of the two-hop form has just published its group row: its first look at the 8 group rows goes out BEFORE its lmu_pre
-      // and is evaluated behind it (lmu_pre is about as long as the hop: issued after it, that poll cost the leaders, and with them
-      // every workgroup's next pass, ~700 cycles).
-      if (!ONE_HOP) {
-        if (k > 0 && !leader) lmu_pre(S, st, opt, sh_tot, tr, tr_cap, lane);
-        if (!leader) COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 11);
-      }
-      if (fine && !one_hop) {
+      } else {
         // the 8 group rows: groups 4 h .. 4 h + 3
-        coop_wait_until(t_a + d2);
-        const unsigned int base = coop_row_b(par, wg % COOP_REPLICAS, 4 * h) + 16u * (unsigned int)e;
-        const unsigned long long t0 = wall_clock64();
-        bool pre_due = k > 0 && leader;
-        // One look in flight at a time.  Measured and dropped: 2-3 looks in flight 256 cycles apart (6.8-7.1 us per pass against
-        // 6.2: the extra requests slow the rows they look for), copies of the group-row board (8 or 32: the leaders' extra stores
-        // cost more than the shorter queues save), a leader taking its own group row from registers with its first look issued
-        // before its store (+0.15 us: that look goes out too early, see d2).
+        const int h = lane >> 5, e = (lane & 31) < NACC ? (lane & 31) : NACC - 1;
         v4u w[4];
-        for (;;) {
-          bool ok = true;
-          unsigned int bo = base;
-          asm volatile("" : "+v"(bo));  // (a fresh sample every iteration)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) w[i] = coop_get(rs, bo + (unsigned int)(i * COOP_B_STRIDE * 8));
-          if (pre_due) {  // (wave-uniform; the loads above stay in flight: nothing below touches their registers)
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            lmu_pre(S, st, opt, sh_tot, tr, tr_cap, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 11);
-            pre_due = false;
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ok = ok && coop_valid(w[i], tag);
-          if (__all(ok)) break;
-          const unsigned long long waited = wall_clock64() - t0;
-          if (waited > COOP_ABORT_CHECK_TICKS) {
-            unsigned int co = (unsigned int)offsetof(CoopBoard, ctl);
-            asm volatile("" : "+v"(co));
-            if (waited > limit || coop_get(rs, co)[0] == tag0) { fine = false; break; }
-          }
-          __builtin_amdgcn_s_sleep(CLC_COOP_POLL_SLEEP);
-        }
+        fine = coop_poll<4>(rs, coop_row_b(par, wg % COOP_REPLICAS, 4 * h) + 16u * (unsigned int)e, (unsigned int)(COOP_B_STRIDE * 8), tag, tag0, limit, w);
         COOP_STAMP(COOP_STAMP_PER_PASS * stamp_pass + 5);
         double s = coop_value(w[0]);
 #pragma unroll

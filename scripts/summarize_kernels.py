@@ -58,8 +58,8 @@ if inf:
     passes = inf.get("passes", 0)
     L = [f"# rocprofv3 evidence for the cooperative solve, {TAG} (MI355X) — `scripts/profile_kernels.sh`", "",
          f"Target: `scripts/prof_probe.py coop 1000000` — {len(d)} (trace run; 5 in the counter runs) default `clc_solve` of the C2 problem (1e6 observations, {inf.get('points_per_lane')} points per lane, "
-         f"{passes} evaluation passes per solve), each ONE launch of `coop_solve_kernel` (5 waves per workgroup: 4 point waves + the controller wave of "
-         f"`csrc/clc_lmuni.hpp`); launches that timed out: {inf.get('aborts')}.", "",
+         f"{passes} evaluation passes per solve), each ONE launch of `coop_solve_kernel` (6 waves per workgroup: 4 point waves + the controller wave of "
+         f"`csrc/clc_lmuni.hpp` + the gather wave, which lives on the 8 group leaders only); launches that timed out: {inf.get('aborts')}.", "",
          f"| | {TAG} | round 3 (`profiles/r03_coop.md`; rounds 4, 5: `profiles/r04_coop.md`, `profiles/r05_coop.md`) |", "|---|---|---|",
          f"| `coop_solve_kernel` dispatches in the trace | {len(d)} | 5 |",
          f"| duration per launch, rocprofv3 kernel trace (us) | median {statistics.median(d):.1f}, min {min(d):.1f}, max {max(d):.1f} | median 88.5, min 88.1, max 91.4 |",
