@@ -114,9 +114,12 @@ int finish_solve(clc_handle* h, const clc_summary& out, const double* out_pose, 
                  clc_iteration* trace, int trace_cap, double kernel_ms, int64_t kernel_launches,
                  std::chrono::steady_clock::time_point t0) {
   *summary = out;
+  // A solve whose first evaluation is not finite ends CLC_FAILURE before iteration zero is recorded, and the kernels' epilogue
+  // (lm_fill_summary: recorded iterations - 1) says -1 then.  clc_solve reports 0 iterations, as the oracle's restatement of Ceres does.
+  if (summary->num_iterations < 0) summary->num_iterations = 0;
   for (int i = 0; i < 7; ++i) pose[i] = out_pose[i];
   if (trace != nullptr && trace_cap > 0) {
-    const int n = std::min(std::min(summary->num_iterations + 1, trace_cap), (int)h->d_trace.size());
+    const int n = std::min(std::min(out.num_iterations + 1, trace_cap), (int)h->d_trace.size());  // (the rows recorded: none for such a solve)
     if (n > 0) CLC_HIP(hipMemcpy(trace, h->d_trace, sizeof(clc_iteration) * (size_t)n, hipMemcpyDeviceToHost));
   }
   summary->eval_kernel_ms = kernel_ms;

@@ -107,7 +107,7 @@ typedef struct clc_iteration {
 
 typedef struct clc_summary {
   int32_t termination;            /* CLC_CONVERGENCE_* / CLC_NO_CONVERGENCE / CLC_FAILURE    */
-  int32_t num_iterations;         /* recorded iterations - 1                                 */
+  int32_t num_iterations;         /* recorded iterations - 1 (clc_solve: 0 when none was)    */
   int32_t num_successful_steps;
   int32_t num_unsuccessful_steps;
   int64_t num_evaluations;        /* fused residual+Jacobian passes over the observations    */

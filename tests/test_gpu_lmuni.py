@@ -73,9 +73,11 @@ def test_register_controller_is_bit_identical_to_the_lds_controller(sv):
 
 def test_register_controller_rejected_steps(sv):
     """Rejected steps — HandleUnsuccessfulStep shrinks the radius and the step is recomputed from the Gauss-Newton system kept at x (the
-    totals buffer the state points to).  This cost is so benign that Ceres' default acceptance threshold never rejects (54 far starts x
-    first radii tried: not one rejected step), so the threshold is raised: above 1 no step is ever good enough and the solve ends on
-    the minimum trust-region radius after a run of rejections; just below 1 rejections and acceptances alternate."""
+    totals buffer the state points to).  With the Cauchy loss this cost is so benign that Ceres' default acceptance threshold never
+    rejects (54 far starts x first radii tried: not one rejected step); without the loss it does (use_loss = 0 from a far start: case
+    R2 of tests/coop_controller_cases.py, five rejections in a row under the default thresholds).  Here the loss stays on and the
+    threshold is raised: above 1 no step is ever good enough and the solve ends on the minimum trust-region radius after a run of
+    rejections; just below 1 rejections and acceptances alternate."""
     rec = clc.flatten_observations(sd.GenerateSimData(5, noise_sigma=0.02), False)
     n = 0
     for angles, t, mrd, min_radius in (((0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.5, 1e-3), ((2.0, -1.0, 2.5), (3.0, -2.0, 1.0), 0.9999, 1e-32),

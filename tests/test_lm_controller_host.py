@@ -122,6 +122,36 @@ def test_controller_no_loss_and_no_scaling(shim, oracle_mod):
     assert abs(sm.final_cost - ref.summary.final_cost) < 1e-12
 
 
+def test_controller_invalid_steps_and_a_non_finite_start_against_the_closed_form(shim, oracle_mod):
+    """The serial controller on the exact cases of tests/coop_controller_cases.py: the t_x and t_y rows of the system are exact zeros and
+    the damping is clamped to 0, so every step is invalid — the trace is known in closed form (radius 1e4 * 2**-(k (k + 1) / 2)) and
+    equals the oracle's; the passes are not counted (one evaluation).  And a NaN record: FAILURE before iteration zero is recorded — no
+    step counted, one evaluation, the start pose returned."""
+    import coop_controller_cases as K
+
+    for case in (c for c in K.CASES if c.exact):
+        rec = K.records(case)
+        opt = K.options(case, _capi.default_options)
+        pose, sm, tr, calls = _solve_with_controller(shim, oracle_mod, rec, opt, K.start(case))
+        ref = oracle_mod.solve(rec, K.start(case), options=_mirror_opts(oracle_mod, opt), linear_solver="qr")
+        want = K.exact_invalid_expectation(case)
+        assert [(t.iteration, t.step_is_valid, t.step_is_successful, t.trust_region_radius) for t in tr] == want, case.name
+        assert [(t.iteration, t.step_is_valid, t.step_is_successful, t.trust_region_radius) for t in ref.trace] == want, case.name
+        assert all(t.cost == sm.initial_cost and t.cost_change == 0.0 and t.step_norm == 0.0 and t.relative_decrease == 0.0 for t in tr)
+        assert (sm.termination, sm.num_iterations) == (ref.summary.termination, ref.summary.num_iterations) == (case.termination, case.iterations)
+        assert sm.num_evaluations == len(calls) == 1 and sm.num_successful_steps == 1 and sm.num_unsuccessful_steps == len(want) - 1
+        assert pose.tobytes() == K.start(case).tobytes() and sm.final_cost == sm.initial_cost
+    case = K.BY_NAME["NAN"]
+    rec = K.records(case)
+    opt = _capi.default_options()
+    pose, sm, tr, calls = _solve_with_controller(shim, oracle_mod, rec, opt, K.start(case))
+    ref = oracle_mod.solve(rec, K.start(case), linear_solver="qr")
+    assert sm.termination == ref.summary.termination == 6 and ref.summary.num_iterations == 0
+    # (no iteration recorded: the controller's own summary says "recorded - 1"; clc_solve reports 0, tests/test_gpu_coop_controller.py)
+    assert (sm.num_successful_steps, sm.num_unsuccessful_steps, sm.num_evaluations, len(calls)) == (0, 0, 1, 1)
+    assert pose.tobytes() == K.start(case).tobytes() and ref.pose.tobytes() == K.start(case).tobytes()
+
+
 def test_shared_math_matches_oracle(shim, oracle_mod):
     rng = np.random.default_rng(0)
     dp = C.POINTER(C.c_double)
