@@ -14,11 +14,11 @@ CSRC = os.path.join(_HERE, "csrc")
 PRODUCT_LIB_PATH = os.path.join(CSRC, "libclc_hip.so")
 HOOKS_LIB_PATH = os.path.join(CSRC, "libclc_hip_hooks.so")
 LIB_PATH = os.environ.get("CLC_LIBRARY") or PRODUCT_LIB_PATH  # CLC_LIBRARY: run the package on a different build
-UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_batchflow.hip", "abi_campose.hip", "abi_joint.hip", "abi_camcal.hip", "abi_guidance.hip", "abi_laserrange.hip", "abi_jointrobust.hip", "abi_fullcal.hip", "abi_subpix.hip", "abi_comm.hip", "abi_debug.hip"]
+UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_batchflow.hip", "abi_campose.hip", "abi_joint.hip", "abi_camcal.hip", "abi_guidance.hip", "abi_laserrange.hip", "abi_jointrobust.hip", "abi_fullcal.hip", "abi_subpix.hip", "abi_chess.hip", "abi_comm.hip", "abi_debug.hip"]
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
            "clc_batchflow.hpp", "clc_campose.hpp"]
-HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp", "abi_jointcall.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
+HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp", "abi_jointcall.hpp", "clc_chessorder.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
 # kernels of their own that include HEADERS and are included by none of them: the kernels whose measured constants csrc_sha16 guards
 # (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
 # abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md), those of abi_frontend.hip by clc_stations.hpp
@@ -31,8 +31,10 @@ HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assembl
 # arrow solve and the shared blocks' bookkeeping, under all five) and clc_jointterms.hpp (the laser term, the loss, the accumulations
 # and the image rule of the four joint problems, included by their four kernel headers).  clc_guidance.hpp (pose guidance) is in
 # abi_guidance.hip alone (tests/test_guidance_resources.py), clc_subpix.hpp (corner refinement) in abi_subpix.hip alone
-# (tests/test_subpix_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
-SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp"]
+# (tests/test_subpix_resources.py), clc_chess.hpp (chessboard-corner detection) in abi_chess.hip alone (tests/test_chess_resources.py;
+# its host-side ordering, clc_chessorder.hpp, is plain C++ among the HOST_HEADERS).  They rebuild the libraries and are not part of
+# csrc_sha16.
+SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp", "clc_chess.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the

@@ -50,6 +50,8 @@ EXPORTED = [
     "clc_stored_observations",
     "clc_station_options_default", "clc_static_poses", "clc_assemble_stations", "clc_assemble_stations_device",
     "clc_subpix_options_default", "clc_corner_subpix", "clc_corner_subpix_device",
+    "clc_chess_options_default", "clc_chessorder_options_default", "clc_chess_corners", "clc_chess_corners_device",
+    "clc_chessboard_order", "clc_find_chessboard",
     "clc_interp_options_default", "clc_interpolate_poses", "clc_assemble_interpolated", "clc_assemble_interpolated_device",
     "clc_clock_offset_options_default", "clc_clock_offset_best", "clc_clock_offset_sweep", "clc_clock_offset_sweep_device",
 ]
@@ -225,7 +227,20 @@ class SubpixOptions(C.Structure):
                 ("reserved", C.c_int32), ("eps", C.c_double)]
 
 
+class ChessOptions(C.Structure):
+    """clc_chess_options (include/clc.h): the threshold on R5, the suppression radius, the relative gate and the stride of K25."""
+    _fields_ = [("threshold", C.c_int32), ("nms_radius", C.c_int32), ("rel_permille", C.c_int32), ("max_per_image", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ChessOrderOptions(C.Structure):
+    """clc_chessorder_options (include/clc.h): the match gate of the grid ordering of K25."""
+    _fields_ = [("tol", C.c_double), ("reserved", C.c_int32), ("reserved2", C.c_int32)]
+
+
 SUBPIX_MAX_WIN = 15  # CLC_SUBPIX_MAX_WIN
+CHESS_MAX_CANDIDATES, CHESS_RAW_CAP = 1024, 4096  # CLC_CHESS_*
+CHESS_OK, CHESS_FOUND, CHESS_TOO_FEW, CHESS_NO_GRID, CHESS_OVERFLOW = 1, 1, 0, -1, -2
 SUBPIX_CONVERGED, SUBPIX_MAX_ITER, SUBPIX_SINGULAR, SUBPIX_LEFT_IMAGE, SUBPIX_REVERTED, SUBPIX_NONFINITE = 1, 0, -1, -2, -3, -4  # CLC_SUBPIX_*
 GUIDE_LOGDET, GUIDE_MIN_EIG = 0, 1  # CLC_GUIDE_*
 JOINT_OK, JOINT_TOO_FEW, JOINT_NOT_KEPT, JOINT_NONFINITE = 1, 0, -1, -2  # CLC_JOINT_*
@@ -396,6 +411,15 @@ def load(path: str):
             L.clc_subpix_options_default.restype = None
             L.clc_corner_subpix.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 6
             L.clc_corner_subpix_device.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 6
+        if hasattr(L, "clc_chess_corners"):
+            L.clc_chess_options_default.argtypes = [V]
+            L.clc_chess_options_default.restype = None
+            L.clc_chessorder_options_default.argtypes = [V]
+            L.clc_chessorder_options_default.restype = None
+            L.clc_chess_corners.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 5
+            L.clc_chess_corners_device.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 5
+            L.clc_chessboard_order.argtypes = [V, V, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 5
+            L.clc_find_chessboard.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 3
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L
@@ -502,6 +526,20 @@ def default_guidance_options() -> GuidanceOptions:
     the floored log-determinant."""
     o = GuidanceOptions()
     lib().clc_guidance_options_default(C.byref(o))
+    return o
+
+
+def default_chess_options() -> ChessOptions:
+    """clc_chess_options_default: threshold 500 on R5, suppression radius 3, relative gate 250 permille, 256 candidates per image."""
+    o = ChessOptions()
+    lib().clc_chess_options_default(C.byref(o))
+    return o
+
+
+def default_chessorder_options() -> ChessOrderOptions:
+    """clc_chessorder_options_default: tol 0.3."""
+    o = ChessOrderOptions()
+    lib().clc_chessorder_options_default(C.byref(o))
     return o
 
 

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, SubpixOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, ChessOptions, ChessOrderOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, SubpixOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -42,6 +42,28 @@ def flatten_observations(obs_set, use_linefitting_data: bool = True, use_boundar
 
 RESULT_RECORD = 12  # doubles per clc_result_record: pose[7], final_cost, initial_cost, iterations, termination, global index
 COMM_ID_BYTES = 128
+
+
+def chessboard_order(cand_xy: np.ndarray, count: np.ndarray, cols: int, rows: int, status: Optional[np.ndarray] = None,
+                     options: Optional[ChessOrderOptions] = None) -> dict:
+    """clc_chessboard_order (K25; host code: no Solver, no device): cand_xy [n, stride, 2] and count [n] as Solver.chess_corners returns
+    them (status: its status, -2 passes through) -> dict(index [n, rows, cols] int32: the candidate slot of node (j, i) at [i, j], -1
+    where no grid was found; status [n]: 1 found, 0 too few candidates, -1 no grid, -2 overflow; n_labelings [n]; worst [n])."""
+    xy = np.ascontiguousarray(cand_xy, dtype=np.float32)
+    if xy.ndim != 3 or xy.shape[2] != 2:
+        raise ValueError("chessboard_order: cand_xy must be [n, stride, 2]")
+    n, stride = xy.shape[0], xy.shape[1]
+    cnt = np.ascontiguousarray(count, dtype=np.int32)
+    if cnt.shape != (n,):
+        raise ValueError("chessboard_order: count needs one entry per image")
+    st = np.ones(n, np.int32) if status is None else np.array(status, dtype=np.int32).reshape(n)
+    per = max(int(cols) * int(rows), 1)
+    index = np.full((n, per), -1, np.int32); lab = np.zeros(n, np.int32); worst = np.full(n, np.nan)
+    V = lambda a: a.ctypes.data_as(C.c_void_p)
+    o = C.byref(options) if options is not None else None
+    check(_capi.lib().clc_chessboard_order(V(xy), V(cnt), C.c_int64(stride), C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), o, V(index), V(st),
+                                           V(lab), V(worst)), "clc_chessboard_order")
+    return dict(index=index.reshape(n, rows, cols) if per == cols * rows else index, status=st, n_labelings=lab, worst=worst)
 
 
 def comm_unique_id() -> bytes:
@@ -916,6 +938,50 @@ class Solver:
         check(self._L.clc_corner_subpix_device(self._h, o, V(images_ptr), C.c_int32(width), C.c_int32(height), C.c_int64(pitch),
                                                C.c_size_t(n_images), V(corners_ptr), V(offsets_ptr), V(out_ptr), V(status_ptr),
                                                V(iterations_ptr), V(strength_ptr)), "clc_corner_subpix_device")
+
+    # ---- chessboard corners from images (K25) ----
+    def chess_corners(self, images: np.ndarray, options: Optional[ChessOptions] = None, width: Optional[int] = None) -> dict:
+        """clc_chess_corners (K25): images uint8 [n, H, W], or [n, H, pitch] with width= given -> dict(xy [n, stride, 2] float32 integer
+        pixels ordered by (-R5, y, x), NaN in the unused slots; r5 [n, stride] int32; count [n]; count_raw [n]; status [n]: 1, or -2
+        where the image has more than 4096 raw candidates), stride = options.max_per_image."""
+        img = np.ascontiguousarray(images, dtype=np.uint8)
+        if img.ndim != 3:
+            raise ValueError("chess_corners: images must be [n, height, pitch]")
+        o = options if options is not None else _capi.default_chess_options()
+        n, stride = img.shape[0], max(int(o.max_per_image), 1)
+        xy = np.full((n, stride, 2), -7.0, np.float32); r5 = np.full((n, stride), -7, np.int32)
+        cnt = np.full(n, -7, np.int32); raw = np.full(n, -7, np.int32); st = np.full(n, -99, np.int32)
+        V = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._L.clc_chess_corners(self._h, C.byref(o), V(img), C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]),
+                                        C.c_int64(img.shape[2]), C.c_size_t(n), V(xy), V(r5), V(cnt), V(raw), V(st)), "clc_chess_corners")
+        return dict(xy=xy, r5=r5, count=cnt, count_raw=raw, status=st)
+
+    def chess_corners_device(self, images_ptr: int, width: int, height: int, pitch: int, n_images: int, xy_ptr: int, count_ptr: int,
+                             status_ptr: int, r5_ptr: int = 0, count_raw_ptr: int = 0, options: Optional[ChessOptions] = None):
+        """clc_chess_corners_device on device-resident arrays (data_ptr()s; ready on the solver's stream)."""
+        V = lambda p: C.c_void_p(p or 0)
+        o = C.byref(options) if options is not None else None
+        check(self._L.clc_chess_corners_device(self._h, o, V(images_ptr), C.c_int32(width), C.c_int32(height), C.c_int64(pitch),
+                                               C.c_size_t(n_images), V(xy_ptr), V(r5_ptr), V(count_ptr), V(count_raw_ptr), V(status_ptr)),
+              "clc_chess_corners_device")
+
+    def find_chessboard(self, images: np.ndarray, cols: int, rows: int, chess_options: Optional[ChessOptions] = None,
+                        order_options: Optional[ChessOrderOptions] = None, subpix_options: Optional[SubpixOptions] = None,
+                        width: Optional[int] = None) -> dict:
+        """clc_find_chessboard (K25): detection on the device, ordering into the cols x rows grid on the host, and with subpix_options
+        the refinement (K24) -> dict(corners [n, cols rows, 2] float32, row i cols + j = node (j, i), NaN where no board was found;
+        found [n] bool; strength [n, cols rows])."""
+        img = np.ascontiguousarray(images, dtype=np.uint8)
+        if img.ndim != 3:
+            raise ValueError("find_chessboard: images must be [n, height, pitch]")
+        n, per = img.shape[0], max(int(cols) * int(rows), 1)
+        corners = np.full((n, per, 2), np.nan, np.float32); found = np.zeros(n, np.int32); lam = np.full((n, per), np.nan)
+        V = lambda a: a.ctypes.data_as(C.c_void_p)
+        ref = lambda o: C.byref(o) if o is not None else None
+        check(self._L.clc_find_chessboard(self._h, ref(chess_options), ref(order_options), ref(subpix_options), V(img),
+                                          C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]), C.c_int64(img.shape[2]),
+                                          C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), V(corners), V(found), V(lam)), "clc_find_chessboard")
+        return dict(corners=corners, found=found.astype(bool), strength=lam)
 
     # ---- camera intrinsics from the board images (K19) ----
     def camera_guess(self, model: int, width: int, height: int, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray):

@@ -1351,6 +1351,84 @@ int clc_corner_subpix_device(clc_handle* h, const clc_subpix_options* sopt, cons
                              int64_t pitch, size_t n_images, const float* corners_in_dev, const int64_t* offsets_dev,
                              float* corners_out_dev, int32_t* status_dev, int32_t* iterations_dev, double* strength_dev);
 
+/* ---- chessboard corners from images: detect, order, refine (K25) ----------------------------------------------------------------
+ * The step the reference takes from OpenCV ahead of cornerSubPix on its chessboard (cv::findChessboardCorners,
+ * src/calcCamPose.cpp:10-47), by an algorithm of this library's own (nothing of OpenCV's implementation is used or
+ * matched).  Detection on the device: the ChESS response (Bennett & Lasenby) scaled by 5, exact int32 arithmetic on the uint8 image.
+ * Integer pixel coordinates are pixel centres.  With I the image, the ring (dx, dy), n = 0 .. 15:
+ *   (0,-5) (2,-5) (3,-3) (5,-2) (5,0) (5,2) (3,3) (2,5) (0,5) (-2,5) (-3,3) (-5,2) (-5,0) (-5,-2) (-3,-3) (-2,-5)
+ * and the cross (0,0) (1,0) (-1,0) (0,1) (0,-1):  SR = sum_{n<4} |(s_n + s_{n+8}) - (s_{n+4} + s_{n+12})|,
+ * DR = sum_{n<8} |s_n - s_{n+8}|, ring = sum s_n, loc = sum cross, R5 = 5 SR - 5 DR - |5 ring - 16 loc| on the domain
+ * 5 <= x < width - 5, 5 <= y < height - 5 (empty where width < 11 or height < 11: CLC_OK, no candidate).
+ * A domain pixel p is a raw candidate iff R5(p) >= threshold and every other domain pixel q within nms_radius in x and in y has
+ * R5(q) < R5(p), or R5(q) == R5(p) and comes after p in raster order (y, then x).  Of the raw candidates those with
+ * 1000 R5 >= rel_permille x the image's largest R5 are kept, ordered by (-R5, y, x), and the first max_per_image are returned.
+ * An image with more than CLC_CHESS_RAW_CAP raw candidates has status CLC_CHESS_OVERFLOW and no candidate. */
+#define CLC_CHESS_MAX_CANDIDATES 1024
+#define CLC_CHESS_RAW_CAP 4096
+#define CLC_CHESS_OK 1        /* detection: the image's candidates are complete */
+#define CLC_CHESS_FOUND 1     /* ordering: index holds the board's grid */
+#define CLC_CHESS_TOO_FEW 0   /* ordering: fewer than cols x rows candidates */
+#define CLC_CHESS_NO_GRID -1  /* ordering: no valid labeling */
+#define CLC_CHESS_OVERFLOW -2 /* detection: more than CLC_CHESS_RAW_CAP raw candidates; passed through by the ordering */
+typedef struct clc_chess_options {
+  int32_t threshold;     /* on R5, >= 1 */
+  int32_t nms_radius;    /* 1 .. 7 */
+  int32_t rel_permille;  /* 0 .. 1000 */
+  int32_t max_per_image; /* 1 .. CLC_CHESS_MAX_CANDIDATES: the stride of the candidate arrays */
+  int32_t reserved;      /* 0 */
+} clc_chess_options;     /* 20 bytes */
+typedef struct clc_chessorder_options {
+  double tol;            /* the largest match distance over the smallest predicted spacing, in (0, 0.5] */
+  int32_t reserved, reserved2; /* 0 */
+} clc_chessorder_options; /* 16 bytes */
+
+/* threshold 500, nms_radius 3, rel_permille 250, max_per_image 256. */
+void clc_chess_options_default(clc_chess_options* copt);
+/* tol 0.3. */
+void clc_chessorder_options_default(clc_chessorder_options* oopt);
+
+/* images[n_images][height][pitch] uint8 grey, as clc_corner_subpix takes them.  With stride = max_per_image:
+ * cand_xy[n_images stride 2] float32 the integer pixels (x, y) in the order above, NaN in the unused slots (the whole array can go
+ * to clc_corner_subpix_device with offsets k stride: a non-finite start comes back unchanged); cand_r5[n_images stride] (nullable;
+ * 0 in the unused slots); count[n_images]; count_raw[n_images] (nullable; the raw candidates, also beyond the cap);
+ * status[n_images] (CLC_CHESS_OK / CLC_CHESS_OVERFLOW).  copt NULL: the defaults.  CLC_ERR_INVALID_ARG before any device work: an
+ * option outside its range, width or height < 1, pitch < width, more than 2^31 - 1 images or tiles of 64 x 16 pixels, NULL images,
+ * cand_xy, count or status, NULL h.  n_images = 0: CLC_OK, nothing written.  Deterministic: the same bits on every run, for an image
+ * alone or in a batch, and through both forms.  One enqueue (in chunks of 170 images on the handle's stream), one synchronisation. */
+int clc_chess_corners(clc_handle* h, const clc_chess_options* copt, const uint8_t* images, int32_t width, int32_t height, int64_t pitch,
+                      size_t n_images, float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status);
+/* The same with every array in DEVICE memory (ready on the handle's stream); complete on return. */
+int clc_chess_corners_device(clc_handle* h, const clc_chess_options* copt, const uint8_t* images_dev, int32_t width, int32_t height,
+                             int64_t pitch, size_t n_images, float* cand_xy_dev, int32_t* cand_r5_dev, int32_t* count_dev,
+                             int32_t* count_raw_dev, int32_t* status_dev);
+
+/* Host code, no handle and no device: the first cols x rows candidates of every image (cand_xy[n_images stride 2], count[n_images]
+ * as clc_chess_corners wrote them) ordered into the board's grid of cols x rows inner corners.  Per image: the convex hull of the
+ * integer pixels; the 4 hull vertices of the largest quadrilateral; for each of its 4 rotations as the images of the grid nodes
+ * (0, 0), (cols - 1, 0), (cols - 1, rows - 1), (0, rows - 1) the 4-point homography, every node's nearest candidate, valid iff a
+ * bijection with every distance <= tol x the smallest predicted spacing, then the least-squares homography of all matches and the
+ * matching once more.  The board is taken to be seen from its front, so 2 labelings are valid on a rectangular grid and up to 4 on a
+ * square one: the one whose node (0, 0) comes first in raster order (y, then x) is returned; the colour of the squares is not
+ * consulted (cv::findChessboardCorners leaves the same half turn open).  index[n_images cols rows]: index[i cols + j] = the candidate
+ * slot of node (j, i), -1 where status != CLC_CHESS_FOUND, the order of the reference's board points (j square, i square, 0),
+ * src/calcCamPose.cpp:26-36.  status[n_images] is read and written: CLC_CHESS_OVERFLOW on entry stays; otherwise CLC_CHESS_FOUND,
+ * CLC_CHESS_TOO_FEW (count < cols rows) or CLC_CHESS_NO_GRID.  n_labelings[n_images], worst[n_images] (the largest distance /
+ * spacing ratio of the last pass; NaN where no grid was found): nullable.  oopt NULL: tol 0.3.  CLC_ERR_INVALID_ARG: tol outside
+ * (0, 0.5], reserved != 0, cols or rows < 2, cols rows > CLC_CHESS_MAX_CANDIDATES, stride < cols rows, a NULL required array.
+ * A board under strong fisheye distortion is beyond one homography: CLC_CHESS_NO_GRID. */
+int clc_chessboard_order(const float* cand_xy, const int32_t* count, int64_t stride, size_t n_images, int32_t cols, int32_t rows,
+                         const clc_chessorder_options* oopt, int32_t* index, int32_t* status, int32_t* n_labelings, double* worst);
+
+/* Images in, ordered corners out (host arrays): the detection on the device, the ordering on the host, and with sopt != NULL the
+ * refinement of the ordered pixels by clc_corner_subpix_device on the images already uploaded (the reference's chessboard call:
+ * clc_subpix_options_default(&s, 11)); sopt NULL: the integer pixels.  corners[n_images cols rows 2], found[n_images] (1 / 0),
+ * strength[n_images cols rows] (nullable; clc_corner_subpix's).  An image without a board has NaN corners and found = 0 and never
+ * fails the call.  copt->max_per_image must be >= cols rows.  Every CLC_ERR_INVALID_ARG of the three calls, before any device work. */
+int clc_find_chessboard(clc_handle* h, const clc_chess_options* copt, const clc_chessorder_options* oopt, const clc_subpix_options* sopt,
+                        const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
+                        float* corners, int32_t* found, double* strength);
+
 #ifdef __cplusplus
 }
 #endif

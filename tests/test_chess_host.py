@@ -1,0 +1,328 @@
+"""K25 (csrc/clc_chess.hpp, csrc/clc_chessorder.hpp) on the host: the detection compiled with g++ (tests/shim/chess_shim.cpp, the threads
+a loop) against the numpy restatement tests/chess_ref.py, bit for bit on x, y, R5, count, count_raw and status — every value is an
+integer, so there is no tolerance; what the cases are built to show (the ties, the tile edges, the overflow, the gates) asserted on the
+restatement; the ordering through the product library's clc_chessboard_order (host code: no device) against the restatement and the
+rendered truth; the refusals of every call (they need no device), the structs, the symbols; two stand-alone AddressSanitizer / UBSan
+programs."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+import chess_cases as cases  # noqa: E402
+import chess_ref as ref  # noqa: E402
+import subpix_cases as sp  # noqa: E402
+from camlasercalibratool_amd import _capi  # noqa: E402
+
+TOL = 0.3
+
+
+def V(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return cases.build_shim(str(tmp_path_factory.mktemp("ch") / "libchess_shim.so"))
+
+
+def candidates(r, k=0):
+    return [(int(x), int(y), int(v)) for (x, y), v in zip(r["xy"][k, :r["count"][k]], r["r5"][k, :r["count"][k]])]
+
+
+def test_structs_defaults_symbols(shim):
+    assert shim.shim_chess_options_size() == C.sizeof(_capi.ChessOptions) == 20 and C.sizeof(_capi.ChessOrderOptions) == 16
+    d = _capi.default_chess_options()  # the library's own, no device needed
+    assert (d.threshold, d.nms_radius, d.rel_permille, d.max_per_image, d.reserved) == (500, 3, 250, 256, 0)
+    assert ref.Options() == ref.Options(500, 3, 250, 256)
+    o = _capi.default_chessorder_options()
+    assert (o.tol, o.reserved, o.reserved2) == (TOL, 0, 0)
+    names = ["clc_chess_options_default", "clc_chessorder_options_default", "clc_chess_corners", "clc_chess_corners_device",
+             "clc_chessboard_order", "clc_find_chessboard"]
+    header = open(os.path.join(ROOT, "include", "clc.h")).read()
+    L = _capi.lib()
+    for n in names:
+        assert re.search(r"\b%s\(" % n, header) and n in _capi.EXPORTED and hasattr(L, n), n
+    for n, v in (("CLC_CHESS_MAX_CANDIDATES", 1024), ("CLC_CHESS_RAW_CAP", 4096), ("CLC_CHESS_OK", 1), ("CLC_CHESS_FOUND", 1), ("CLC_CHESS_TOO_FEW", 0),
+                 ("CLC_CHESS_NO_GRID", -1), ("CLC_CHESS_OVERFLOW", -2)):
+        assert re.search(r"#define %s +%d\b" % (n, v), header), n
+    assert (_capi.CHESS_MAX_CANDIDATES, _capi.CHESS_RAW_CAP) == (ref.MAX_CANDIDATES, ref.RAW_CAP) == (1024, 4096)
+    assert (_capi.CHESS_OK, _capi.CHESS_FOUND, _capi.CHESS_TOO_FEW, _capi.CHESS_NO_GRID, _capi.CHESS_OVERFLOW) == (ref.OK, ref.FOUND, ref.TOO_FEW,
+                                                                                                                  ref.NO_GRID, ref.OVERFLOW)
+    assert L.clc_version() == 210
+    import camlasercalibratool_amd as pkg
+    assert pkg.FindChessboardCorners and pkg.chessboard_order and pkg.ChessOptions is _capi.ChessOptions
+    assert all(hasattr(pkg.Solver, m) for m in ("chess_corners", "chess_corners_device", "find_chessboard"))
+
+
+def test_response_against_the_formula_written_out():
+    """The restatement's array arithmetic against R5 written out sample by sample at a few pixels, and its bound |R5| <= 30 600."""
+    img = cases.scenes()[3]
+    R = ref.response(img)
+    I = img.astype(int)
+    rng = np.random.default_rng(2510)
+    for _ in range(50):
+        x, y = int(rng.integers(5, 155)), int(rng.integers(5, 115))
+        s = [I[y + dy, x + dx] for dx, dy in ref.RING]
+        sr = sum(abs((s[n] + s[n + 8]) - (s[n + 4] + s[n + 12])) for n in range(4))
+        dr = sum(abs(s[n] - s[n + 8]) for n in range(8))
+        loc = sum(I[y + dy, x + dx] for dx, dy in ref.CROSS)
+        assert R[y - 5, x - 5] == 5 * sr - 5 * dr - abs(5 * sum(s) - 16 * loc)
+    extreme = np.zeros((11, 11), np.uint8)
+    for n, (dx, dy) in enumerate(ref.RING):
+        extreme[5 + dy, 5 + dx] = 255 if (n // 4) % 2 == 0 else 0
+    for dx, dy in ref.CROSS:
+        extreme[5 + dy, 5 + dx] = 128
+    assert abs(int(ref.response(extreme)[0, 0])) <= 30600 and abs(int(ref.response(255 - extreme)[0, 0])) <= 30600
+    assert np.abs(R).max() <= 30600
+
+
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_shim_is_the_restatement_bit_for_bit(shim, name):
+    c = cases.cases()[name]
+    want = cases.reference(name)
+    got = cases.shim_detect(shim, c["images"], c["width"], c["options"])
+    print(name, "count", want["count"][:12], "raw", want["count_raw"][:12], "status", want["status"][:12])
+    cases.assert_same_bits(got, want, name)
+    # the launch's chunk of images and the padding bytes behind each row change nothing
+    cases.assert_same_bits(cases.shim_detect(shim, c["images"], c["width"], c["options"], chunk=1), want, name + " (one image per launch)")
+    pitch = c["images"].shape[2] + 3
+    cases.assert_same_bits(cases.shim_detect(shim, sp.padded(c["images"][..., :c["width"]], pitch, fill=201), c["width"], c["options"]), want,
+                           name + " (another pitch)")
+    # each image alone gives its rows of the batch
+    for k in range(min(len(c["images"]), 3)):
+        one = cases.shim_detect(shim, c["images"][k:k + 1], c["width"], c["options"])
+        for key in cases.KEYS:
+            assert np.array_equal(one[key][0], want[key][k], equal_nan=True), (name, k, key)
+
+
+def test_what_the_cases_are_built_to_show():
+    """On the restatement alone, so that a change of the renderer cannot hide what a case is there for."""
+    r = cases.reference
+    assert sum(r("junctions0")["count"]) >= 2 and sum(r("junctions1")["count"]) >= 2  # the saddles; an L-corner is no chess corner
+    assert r("one_pixel")["count_raw"][0] == 1 and candidates(r("one_pixel"))[0][:2] == (5, 5)
+    assert r("empty_domain")["count_raw"][0] == 0 and r("empty_domain")["status"][0] == ref.OK
+    assert np.isnan(r("empty_domain")["xy"]).all() and (r("empty_domain")["r5"] == 0).all()
+    # the ties: four equal maxima; at radius 1 all are kept, at 3 the two of the first row, at 7 the raster-first alone
+    four = candidates(r("tie_far"))
+    assert [c[:2] for c in four] == [(28, 22), (32, 22), (28, 24), (32, 24)] and len({c[2] for c in four}) == 1
+    assert candidates(r("tie_mid")) == four[:2] and candidates(r("tie_near")) == four[:1]
+    # corners on both sides of every tile edge
+    e = r("tile_edges")
+    xs = {candidates(e, k)[0][0] for k in range(len(e["count"]))}
+    ys = {candidates(e, k)[0][1] for k in range(len(e["count"]))}
+    assert (e["count"] == 1).all() and {cases.TILE_W - 1, cases.TILE_W} <= xs
+    assert {cases.TILE_H - 1, cases.TILE_H, 2 * cases.TILE_H - 1, 2 * cases.TILE_H} <= ys
+    assert (r("tile_edges_r7")["count_raw"] > r("tile_edges")["count_raw"]).any()
+    o = r("overflow")
+    assert o["count_raw"][0] > ref.RAW_CAP and o["status"][0] == ref.OVERFLOW and o["count"][0] == 0 and np.isnan(o["xy"]).all()
+    assert (r("rel_0")["count"] == r("rel_0")["count_raw"]).all() and (r("rel_0")["count"] > 100).all()
+    assert (r("rel_1000")["count"] == 1).all() and (r("max_1")["count"] == 1).all() and (r("max_1")["count_raw"] == 20).all()
+    assert np.array_equal(r("rel_1000")["xy"][:, 0], r("scenes")["xy"][:3, 0]) and np.array_equal(r("max_1")["xy"][:, 0], r("scenes")["xy"][:3, 0])
+    assert (r("max_1024")["count"] > 256).all()
+
+
+def test_the_scenes_give_their_twenty_corners():
+    """A required property of the inputs, on the restatement alone: on the 12 scenes with default options exactly 20 candidates pass the
+    relative gate, each within 1 px of a true corner, every true corner once.  As measured: the farthest 0.70 px; the weakest true
+    corner R5 = 4 067."""
+    r = cases.reference("scenes")
+    for k, seed in enumerate(cases.SCENE_SEEDS):
+        truth = sp.board_scene(seed)["truth"]
+        assert r["count"][k] == 20 and r["status"][k] == ref.OK
+        d = np.linalg.norm(r["xy"][k, :20, None].astype(float) - truth[None], axis=2)
+        print("seed", seed, "farthest", d.min(axis=1).max(), "weakest R5", r["r5"][k, :20].min(), "raw", r["count_raw"][k])
+        assert d.min(axis=1).max() <= 1.0 and sorted(d.argmin(axis=1)) == list(range(20))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The ordering (clc_chessboard_order of the product library: host code)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def boards_of(inner):
+    return [b for b in cases.tilted_boards() if b["inner"] == inner]
+
+
+@pytest.mark.parametrize("which", ["scenes", "tilted 9 x 6", "tilted 6 x 6"])
+def test_ordering_is_the_restatement_and_the_truth(which):
+    """index, status and n_labelings equal the restatement's; the ordered pixels within 1.5 px of the truth relabelled by the rule (node
+    (0, 0) first in raster order); no pass of the restatement with its worst ratio within 10 % of tol, so that rounding cannot flip a
+    decision.  As measured: 2 labelings on the rectangular grids and 4 on the square one, the worst ratio of a valid pass 0.12, the
+    farthest ordered pixel 1.06 px from the truth."""
+    import camlasercalibratool_amd as clc
+    if which == "scenes":
+        images, width, (cols, rows) = cases.scenes(), sp.BOARD_W, sp.INNER
+        truths = [sp.board_scene(s)["truth"] for s in cases.SCENE_SEEDS]
+    else:
+        inner = (9, 6) if "9" in which else (6, 6)
+        bs = boards_of(inner)
+        images, width, (cols, rows), truths = np.stack([b["image"] for b in bs]), cases.TILTED_W, inner, [b["truth"] for b in bs]
+    det = ref.detect(images, width)
+    assert (det["count"] == cols * rows).all()
+    del ref.RATIOS[:]
+    want = ref.order(det["xy"], det["count"], cols, rows, det["status"], TOL)
+    near = [x for x in ref.RATIOS if 0.9 * TOL <= x <= 1.1 * TOL]
+    print(which, "labelings", want["n_labelings"], "worst", want["worst"].round(3), "largest valid ratio", max(x for x in ref.RATIOS if x <= TOL))
+    assert not near, near
+    got = clc.chessboard_order(det["xy"], det["count"], cols, rows, det["status"])
+    assert (want["status"] == ref.FOUND).all() and (want["n_labelings"] == (4 if cols == rows else 2)).all()
+    assert np.array_equal(got["index"], want["index"]) and np.array_equal(got["status"], want["status"])
+    assert np.array_equal(got["n_labelings"], want["n_labelings"])
+    assert np.abs(got["worst"] - want["worst"]).max() <= 1e-9
+    for k in range(len(images)):
+        px = det["xy"][k, got["index"][k].ravel()].astype(float)
+        truth = cases.relabel_truth(truths[k], cols, rows, det["xy"][k, :cols * rows].astype(float))
+        err = np.linalg.norm(px - truth, axis=1).max()
+        print(which, k, "farthest from the truth", err)
+        assert err <= 1.5
+
+
+def test_ordering_refusals():
+    import camlasercalibratool_amd as clc
+    det = ref.detect(cases.scenes()[:4], sp.BOARD_W)
+    xy, count, status = det["xy"].copy(), det["count"].copy(), det["status"].copy()
+    count[0] = 19                                            # one short
+    status[1] = ref.OVERFLOW                                 # passes through
+    good = ref.order(xy[2:3], count[2:3], 5, 4)["index"][0]
+    corner, inward = good[3, 4], good[3, 3]
+    xy[2, corner] += xy[2, corner] - xy[2, inward]           # a corner moved by a full spacing
+    xy[3, :20] = np.stack([10 + 3 * np.arange(20), 20 + 2 * np.arange(20)], 1)  # collinear
+    want = ref.order(xy, count, 5, 4, status)
+    got = clc.chessboard_order(xy, count, 5, 4, status)
+    assert list(want["status"]) == [ref.TOO_FEW, ref.OVERFLOW, ref.NO_GRID, ref.NO_GRID] == list(got["status"])
+    assert (got["index"] == -1).all() and (got["n_labelings"] == 0).all() and np.isnan(got["worst"]).all()
+    # the unused slots of a short image are NaN, and more candidates than the grid has are ignored beyond the strongest cols x rows
+    more = ref.detect(cases.scenes()[:1], sp.BOARD_W, ref.Options(threshold=20, rel_permille=0))
+    assert more["count"][0] > 20
+    a, b = clc.chessboard_order(more["xy"], more["count"], 5, 4), clc.chessboard_order(det["xy"][:1], det["count"][:1], 5, 4)
+    assert a["status"][0] == ref.FOUND and np.array_equal(a["index"], b["index"])
+
+
+@pytest.mark.parametrize("seed", sp.BOARD_SEEDS)
+def test_end_to_end_on_the_restatements(seed):
+    """What tests/test_gpu_chess.py asserts of calib.FindChessboardCorners, first on the numpy restatements: detection, ordering and
+    the K24 refinement (eps 0.01, half-windows 3 and 5) from the detector's pixels against the same refinement from the truth's rounded
+    corners.  Gate: RMS to the truth <= 1.25 x the existing route's.  As measured (seeds 1, 5, 7, 8): the ratio 0.998-1.001 (e.g. seed 1:
+    0.05365 against 0.05365 px at half-window 3, 0.03457 against 0.03464 px at 5)."""
+    import subpix_ref
+    s = sp.board_scene(seed)
+    cols, rows = sp.INNER
+    det = ref.detect(s["image"][None], sp.BOARD_W)
+    o = ref.order(det["xy"], det["count"], cols, rows)
+    assert o["status"][0] == ref.FOUND
+    start = det["xy"][0, o["index"][0].ravel()]
+    truth = cases.relabel_truth(s["truth"], cols, rows, det["xy"][0, :cols * rows].astype(float))
+    rounded = np.rint(truth).astype(np.float32)
+    for w in (3, 5):
+        opt = subpix_ref.Options(w, w, eps=0.01)
+        a = subpix_ref.refine(s["image"][None], sp.BOARD_W, start, [0, len(start)], opt)
+        b = subpix_ref.refine(s["image"][None], sp.BOARD_W, rounded, [0, len(start)], opt)
+        ra, rb = sp.rms(a["corners"], truth), sp.rms(b["corners"], truth)
+        print("seed", seed, "half-window", w, "from the detector", ra, "from the rounded truth", rb, "ratio", ra / rb)
+        assert ra <= 1.25 * rb
+
+
+def order_call(L, xy, count, stride, n, cols, rows, o, index, status, lab=None, worst=None):
+    code = L.clc_chessboard_order(V(xy), V(count), stride, n, cols, rows, None if o is None else C.byref(o), V(index), V(status), V(lab), V(worst))
+    return code, L.clc_last_error().decode()
+
+
+def test_ordering_argument_checks():
+    L = _capi.lib()
+    xy = np.zeros((1, 20, 2), np.float32); count = np.array([20], np.int32); index = np.zeros(20, np.int32); status = np.ones(1, np.int32)
+    bad = lambda **kw: _capi.ChessOrderOptions(**{**dict(tol=0.3, reserved=0, reserved2=0), **kw})
+    for args, text in [((xy, count, 20, 1, 5, 4, bad(tol=0.0), index, status), "tol"), ((xy, count, 20, 1, 5, 4, bad(tol=0.51), index, status), "tol"),
+                       ((xy, count, 20, 1, 5, 4, bad(tol=float("nan")), index, status), "tol"), ((xy, count, 20, 1, 5, 4, bad(tol=-0.3), index, status), "tol"),
+                       ((xy, count, 20, 1, 5, 4, bad(reserved=1), index, status), "reserved"), ((xy, count, 20, 1, 5, 4, bad(reserved2=1), index, status), "reserved"),
+                       ((xy, count, 20, 1, 1, 20, None, index, status), "cols and rows"), ((xy, count, 20, 1, 20, 1, None, index, status), "cols and rows"),
+                       ((xy, count, 20, 1, 0, 4, None, index, status), "cols and rows"), ((xy, count, 20, 1, 33, 32, None, index, status), "cols and rows"),
+                       ((xy, count, 19, 1, 5, 4, None, index, status), "stride"), ((None, count, 20, 1, 5, 4, None, index, status), "bad argument"),
+                       ((xy, None, 20, 1, 5, 4, None, index, status), "bad argument"), ((xy, count, 20, 1, 5, 4, None, None, status), "bad argument"),
+                       ((xy, count, 20, 1, 5, 4, None, index, None), "bad argument")]:
+        code, msg = order_call(L, *args)
+        assert code == -1 and msg.startswith("clc_chessboard_order:") and text in msg, (code, msg, text)
+    assert order_call(L, None, None, 20, 0, 5, 4, None, None, None)[0] == 0  # no image: nothing to do
+    assert order_call(L, xy, count, 20, 1, 5, 4, None, index, status)[0] == 0 and status[0] == ref.NO_GRID  # (20 coincident candidates)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The refusals of the device calls: all before a handle is needed
+# ---------------------------------------------------------------------------------------------------------------------------------
+def detect_both(L, o, img, width, height, pitch, n, xy, count, status):
+    res = []
+    for name in ("clc_chess_corners", "clc_chess_corners_device"):
+        code = getattr(L, name)(None, None if o is None else C.byref(o), V(img), width, height, pitch, n, V(xy), None, V(count), None, V(status))
+        res.append((name, code, L.clc_last_error().decode()))
+    return res
+
+
+REFUSED = [(dict(threshold=0), "threshold"), (dict(threshold=-5), "threshold"), (dict(nms_radius=0), "nms_radius"), (dict(nms_radius=8), "nms_radius"),
+           (dict(rel_permille=-1), "rel_permille"), (dict(rel_permille=1001), "rel_permille"), (dict(max_per_image=0), "max_per_image"),
+           (dict(max_per_image=1025), "max_per_image"), (dict(reserved=1), "reserved")]
+
+
+@pytest.mark.parametrize("change,text", REFUSED)
+def test_every_refused_option(change, text):
+    L = _capi.lib()
+    o = _capi.default_chess_options()
+    for k, v in change.items():
+        setattr(o, k, v)
+    img = np.zeros((1, 16, 16), np.uint8); xy = np.zeros((1, 1024, 2), np.float32); count = np.zeros(1, np.int32); status = np.zeros(1, np.int32)
+    for name, code, msg in detect_both(L, o, img, 16, 16, 16, 1, xy, count, status):
+        assert code == -1 and msg.startswith(name + ":") and text in msg, (name, code, msg)
+    found = np.zeros(1, np.int32); corners = np.zeros((20, 2), np.float32)
+    code = L.clc_find_chessboard(None, C.byref(o), None, None, V(img), 16, 16, 16, 1, 5, 4, V(corners), V(found), None)
+    msg = L.clc_last_error().decode()
+    assert code == -1 and msg.startswith("clc_find_chessboard:") and text in msg, (code, msg)
+
+
+def test_refusals_of_arguments():
+    L = _capi.lib()
+    img = np.zeros((1, 16, 16), np.uint8); xy = np.zeros((1, 256, 2), np.float32); count = np.zeros(1, np.int32); status = np.zeros(1, np.int32)
+    for args, text in [((img, 0, 16, 16, 1, xy, count, status), "width and height"), ((img, 16, 0, 16, 1, xy, count, status), "width and height"),
+                       ((img, 16, -2, 16, 1, xy, count, status), "width and height"), ((img, 16, 16, 15, 1, xy, count, status), "pitch"),
+                       ((img, 16, 16, 16, 2 ** 31, xy, count, status), "too many images"), ((img, 16, 16, 2 ** 62, 3, xy, count, status), "too many images"),
+                       ((None, 16, 16, 16, 1, xy, count, status), "bad argument"), ((img, 16, 16, 16, 1, None, count, status), "bad argument"),
+                       ((img, 16, 16, 16, 1, xy, None, status), "bad argument"), ((img, 16, 16, 16, 1, xy, count, None), "bad argument"),
+                       ((img, 16, 16, 16, 1, xy, count, status), "bad argument")]:  # the last: nothing wrong but the NULL handle
+        for name, code, msg in detect_both(L, None, *args):
+            assert code == -1 and msg.startswith(name + ":") and text in msg, (name, code, msg, text)
+    # an image of more than 2^31 - 1 tiles
+    for name, code, msg in detect_both(L, None, img, 2 ** 31 - 1, 2 ** 20, 2 ** 31 - 1, 1, xy, count, status):
+        assert code == -1 and "too large" in msg, (name, msg)
+    # clc_find_chessboard: the three calls' refusals, then the NULL handle
+    found = np.zeros(1, np.int32); corners = np.zeros((20, 2), np.float32)
+    small = _capi.default_chess_options(); small.max_per_image = 19
+    bad_order = _capi.ChessOrderOptions(0.7, 0, 0)
+    bad_subpix = _capi.default_subpix_options(11); bad_subpix.win_x = 16
+    call = lambda co, oo, so, im, w, cols, rows, cr, fd: (
+        L.clc_find_chessboard(None, None if co is None else C.byref(co), None if oo is None else C.byref(oo), None if so is None else C.byref(so), V(im), w,
+                              16, 16, 1, cols, rows, V(cr), V(fd), None), L.clc_last_error().decode())
+    for args, text in [((small, None, None, img, 16, 5, 4, corners, found), "max_per_image must be >= cols x rows"),
+                       ((None, bad_order, None, img, 16, 5, 4, corners, found), "tol"), ((None, None, bad_subpix, img, 16, 5, 4, corners, found), "refinement"),
+                       ((None, None, None, img, 16, 1, 4, corners, found), "cols and rows"), ((None, None, None, img, 0, 5, 4, corners, found), "width and height"),
+                       ((None, None, None, None, 16, 5, 4, corners, found), "bad argument"), ((None, None, None, img, 16, 5, 4, None, found), "bad argument"),
+                       ((None, None, None, img, 16, 5, 4, corners, None), "bad argument"), ((None, None, None, img, 16, 5, 4, corners, found), "bad argument")]:
+        code, msg = call(*args)
+        assert code == -1 and msg.startswith("clc_find_chessboard:") and text in msg, (code, msg, text)
+
+
+@pytest.mark.parametrize("program,needle", [("chessorder_main.cpp", "boards found 30"), ("chess_sanitize_main.cpp", "candidates ")])
+def test_sanitized_standalone_programs(tmp_path, program, needle):
+    """tests/shim/chessorder_main.cpp (the ordering on boards under a homography and on the refusals) and
+    tests/shim/chess_sanitize_main.cpp (the detection on the edge shapes, the image allocation exact and at every offset from a word
+    boundary), built with -fsanitize=address,undefined and run as ordinary processes."""
+    exe = str(tmp_path / program.replace(".cpp", ""))
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(HERE, "shim", program), "-o", exe])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "shapes ok" in p.stdout and needle in p.stdout, p.stdout
+    print(p.stdout)
