@@ -32,9 +32,9 @@ HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assembl
 # and the image rule of the four joint problems, included by their four kernel headers).  clc_guidance.hpp (pose guidance) is in
 # abi_guidance.hip alone (tests/test_guidance_resources.py), clc_subpix.hpp (corner refinement) in abi_subpix.hip alone
 # (tests/test_subpix_resources.py), clc_chess.hpp (chessboard-corner detection) in abi_chess.hip alone (tests/test_chess_resources.py;
-# its host-side ordering, clc_chessorder.hpp, is plain C++ among the HOST_HEADERS).  They rebuild the libraries and are not part of
-# csrc_sha16.
-SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp", "clc_chess.hpp"]
+# its host-side ordering, clc_chessorder.hpp, is plain C++ among the HOST_HEADERS; the same ordering on the device, clc_boardorder.hpp, is
+# in abi_chess.hip too: tests/test_boardorder_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
+SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp", "clc_chess.hpp", "clc_boardorder.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the

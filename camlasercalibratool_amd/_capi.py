@@ -52,6 +52,7 @@ EXPORTED = [
     "clc_subpix_options_default", "clc_corner_subpix", "clc_corner_subpix_device",
     "clc_chess_options_default", "clc_chessorder_options_default", "clc_chess_corners", "clc_chess_corners_device",
     "clc_chessboard_order", "clc_find_chessboard",
+    "clc_chessboard_order_device", "clc_find_chessboard_device", "clc_find_chessboard_gpu",
     "clc_interp_options_default", "clc_interpolate_poses", "clc_assemble_interpolated", "clc_assemble_interpolated_device",
     "clc_clock_offset_options_default", "clc_clock_offset_best", "clc_clock_offset_sweep", "clc_clock_offset_sweep_device",
 ]
@@ -420,6 +421,10 @@ def load(path: str):
             L.clc_chess_corners_device.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 5
             L.clc_chessboard_order.argtypes = [V, V, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 5
             L.clc_find_chessboard.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 3
+        if hasattr(L, "clc_chessboard_order_device"):
+            L.clc_chessboard_order_device.argtypes = [V, V, V, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 5
+            L.clc_find_chessboard_device.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 3
+            L.clc_find_chessboard_gpu.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 3
         L.has_hooks = hasattr(L, "clc_debug_build_features")
         _libs[path] = L
     return L

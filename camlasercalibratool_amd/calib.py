@@ -523,18 +523,20 @@ def CornerSubPix(images, corners_px: Sequence[np.ndarray], win: int = 3, zero_zo
 
 
 def FindChessboardCorners(images, pattern_size, square_size: float, refine_win: int = 11, max_iter: int = 30, eps: float = 0.1,
-                          chess_options=None, order_options=None, solver: Optional[Solver] = None):
+                          chess_options=None, order_options=None, solver: Optional[Solver] = None, ordering: str = "host"):
     """The front of CamPoseEst::chessBoardPose (src/calcCamPose.cpp:10-47: cv::findChessboardCorners, cornerSubPix at half-window 11,
     p3ds = (j square, i square, 0) row by row) for many images at once (clc_find_chessboard, K25 + K24): images uint8 [n, H, W] grey,
     pattern_size = (cols, rows) inner corners.  Returns (corners_px, board_xy, found): per image the refined float32 corners
     [cols rows, 2] (NaN where no board was found; refine_win 0: the detector's integer pixels), the board points (j square, i square)
     in the same order, and found [n] bool — corners_px[found] and board_xy[found] are ready for CalcCamPoses, CalibrateCamera and
     CalibrateFull.  The board is taken to be seen from its front; which of the two (square pattern: four) labelings a half turn apart
-    is returned is decided by position (node (0, 0) first in raster order), not by the squares' colour, as with OpenCV."""
+    is returned is decided by position (node (0, 0) first in raster order), not by the squares' colour, as with OpenCV.
+    ordering="device" runs the ordering on the device as well (clc_find_chessboard_gpu, K26): the same arrays, without the read-back
+    and the host core between detection and refinement."""
     cols, rows = int(pattern_size[0]), int(pattern_size[1])
     sv = solver or _shared_solver()
     so = _capi.SubpixOptions(refine_win, refine_win, -1, -1, max_iter, 0, eps) if refine_win > 0 else None
-    r = sv.find_chessboard(images, cols, rows, chess_options, order_options, so)
+    r = sv.find_chessboard(images, cols, rows, chess_options, order_options, so, ordering=ordering)
     gx, gy = np.meshgrid(np.arange(cols), np.arange(rows))
     board = np.stack([gx.ravel() * square_size, gy.ravel() * square_size], 1).astype(np.float32)
     n = len(r["found"])

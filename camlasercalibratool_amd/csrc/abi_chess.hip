@@ -1,11 +1,13 @@
 // abi_chess.hip — clc_chess_options_default, clc_chess_corners(_device), clc_chessorder_options_default, clc_chessboard_order,
-// clc_find_chessboard: chessboard corners from images (K25: the kernels in clc_chess.hpp, the host ordering in clc_chessorder.hpp).
+// clc_find_chessboard: chessboard corners from images (K25: the kernels in clc_chess.hpp, the host ordering in clc_chessorder.hpp);
+// clc_chessboard_order_device, clc_find_chessboard_device, clc_find_chessboard_gpu: the ordering on the device (K26: clc_boardorder.hpp).
 // A unit of its own, held to its own register figures (tests/test_chess_resources.py).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
 #include "abi_staging.hpp"
 #include "clc_chess.hpp"
 #include "clc_chessorder.hpp"
+#include "clc_boardorder.hpp"
 
 using namespace clc_abi;
 
@@ -80,6 +82,76 @@ int order_checks(const char* who, bool required, const clc_chessorder_options* i
   if (!required) return fail(CLC_ERR_INVALID_ARG, (w + ": bad argument").c_str());
   *tol = o.tol;
   return CLC_OK;
+}
+
+namespace bo = clc::boardorder;
+
+// Images per launch of the K26 kernels (the grid of one launch stays far below 2^32 threads).
+constexpr size_t kOrderLaunchImages = (size_t)1 << 20;
+
+// K26 on device arrays: one wave per image.
+void enqueue_order(Staging& st, const float* cand_xy, const int32_t* count, int64_t stride, size_t n_images, int32_t cols, int32_t rows, double tol,
+                   int32_t* index, int32_t* status, int32_t* n_labelings, double* worst) {
+  bo::OrderArgs a{};
+  a.cand_xy = cand_xy; a.count = count; a.stride = (long long)stride; a.cols = cols; a.rows = rows; a.tol = tol;
+  a.index = index; a.status = status; a.n_labelings = n_labelings; a.worst = worst;
+  const size_t lds = bo::lds_bytes(cols * rows);
+  for (size_t first = 0; first < n_images && st.ok(); first += kOrderLaunchImages) {
+    a.first = (long long)first;
+    hipLaunchKernelGGL(bo::board_order_kernel, dim3((unsigned)std::min(kOrderLaunchImages, n_images - first)), dim3(bo::LANES), lds, st.stream(), a);
+    st.launched();
+  }
+}
+
+// The ordered candidate pixels as the refinement's starts (NaN where no board was found), found, and where asked the offsets and a
+// NaN strength.
+void enqueue_gather(Staging& st, const float* cand_xy, const int32_t* index, const int32_t* status, int64_t stride, size_t n_images, int32_t n,
+                    float* starts, int32_t* found, int64_t* offsets, double* strength) {
+  bo::GatherArgs g{};
+  g.cand_xy = cand_xy; g.index = index; g.status = status; g.stride = (long long)stride; g.n_images = (long long)n_images; g.n = n;
+  g.starts = starts; g.found = found; g.offsets = offsets; g.strength = strength;
+  for (size_t first = 0; first < n_images && st.ok(); first += kOrderLaunchImages) {
+    hipLaunchKernelGGL(bo::board_gather_kernel, dim3((unsigned)std::min(kOrderLaunchImages, n_images - first)), dim3(bo::LANES), 0, st.stream(), g,
+                       (long long)first);
+    st.launched();
+  }
+}
+
+// What clc_find_chessboard refuses, in its order, under the caller's name; then the options.
+int find_checks(const char* who, bool required, const clc_chess_options* copt, const clc_chessorder_options* oopt, const clc_subpix_options* sopt,
+                int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows, clc_chess_options* o, double* tol) {
+  const std::string w(who);
+  CLC_TRY(chess_checks(who, required, copt, width, height, pitch, n_images, o));
+  CLC_TRY(order_checks(who, required, oopt, cols, rows, n_images, tol));
+  if ((size_t)o->max_per_image < (size_t)cols * (size_t)rows) return fail(CLC_ERR_INVALID_ARG, (w + ": max_per_image must be >= cols x rows").c_str());
+  if (sopt && (sopt->win_x < 1 || sopt->win_x > CLC_SUBPIX_MAX_WIN || sopt->win_y < 1 || sopt->win_y > CLC_SUBPIX_MAX_WIN || sopt->max_iter < 1 ||
+               sopt->max_iter > 100 || !(std::isfinite(sopt->eps) && sopt->eps >= 0.0) || sopt->reserved != 0))
+    return fail(CLC_ERR_INVALID_ARG, (w + ": the refinement options are not valid (clc_corner_subpix)").c_str());
+  return CLC_OK;
+}
+
+// Detection, ordering, gather and refinement on device arrays, nothing read back in between.  With sopt the call ends in
+// clc_corner_subpix_device's synchronise; without it nothing has been waited for yet.
+int find_on_device(const char* who, clc_handle* h, Staging& st, const clc_chess_options& o, double tol, const clc_subpix_options* sopt,
+                   const uint8_t* img_dev, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
+                   float* corners_dev, int32_t* found_dev, double* strength_dev) {
+  const size_t stride = (size_t)o.max_per_image, per = (size_t)cols * (size_t)rows, M = n_images * per;
+  float* xy_dev = st.scratch<float>(2 * n_images * stride);
+  int32_t* count_dev = st.scratch<int32_t>(n_images);
+  int32_t* status_dev = st.scratch<int32_t>(n_images);
+  int32_t* index_dev = st.scratch<int32_t>(M);
+  float* starts_dev = sopt ? st.scratch<float>(2 * M) : corners_dev;
+  int64_t* off_dev = sopt ? st.scratch<int64_t>(n_images + 1) : nullptr;
+  CLC_TRY(st.status(who));
+  enqueue_chess(st, o, img_dev, width, height, pitch, n_images, xy_dev, nullptr, count_dev, nullptr, status_dev);
+  if (st.ok()) enqueue_order(st, xy_dev, count_dev, (int64_t)stride, n_images, cols, rows, tol, index_dev, status_dev, nullptr, nullptr);
+  if (st.ok())
+    enqueue_gather(st, xy_dev, index_dev, status_dev, (int64_t)stride, n_images, (int32_t)per, starts_dev, found_dev, off_dev,
+                   sopt ? nullptr : strength_dev);
+  CLC_TRY(st.status(who));
+  if (!sopt) return CLC_OK;
+  // (a NaN start comes back as it is: an image without a board keeps its NaN corners)
+  return clc_corner_subpix_device(h, sopt, img_dev, width, height, pitch, n_images, starts_dev, off_dev, corners_dev, nullptr, nullptr, strength_dev);
 }
 
 }  // namespace
@@ -202,6 +274,58 @@ int clc_find_chessboard(clc_handle* h, const clc_chess_options* copt, const clc_
   CLC_TRY(st.status(who));
   // (a NaN start comes back as it is: an image without a board keeps its NaN corners)
   CLC_TRY(clc_corner_subpix_device(h, sopt, img_dev, width, height, pitch, n_images, starts_dev, off_dev, out_dev, nullptr, nullptr, strength_dev));
+  return st.finish(who);
+}
+
+int clc_chessboard_order_device(clc_handle* h, const float* cand_xy_dev, const int32_t* count_dev, int64_t stride, size_t n_images, int32_t cols,
+                                int32_t rows, const clc_chessorder_options* oopt, int32_t* index_dev, int32_t* status_dev,
+                                int32_t* n_labelings_dev, double* worst_dev) {
+  const char* who = "clc_chessboard_order_device";
+  double tol = 0.0;
+  CLC_TRY(order_checks(who, n_images == 0 || (cand_xy_dev && count_dev && index_dev && status_dev), oopt, cols, rows, n_images, &tol));
+  if (n_images > 0 && stride < (int64_t)cols * rows) return fail(CLC_ERR_INVALID_ARG, "clc_chessboard_order_device: stride must be >= cols x rows");
+  if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_chessboard_order_device: bad argument");
+  if (n_images == 0) return CLC_OK;
+  CLC_HIP(hipSetDevice(h->device));
+  Staging st(h);
+  enqueue_order(st, cand_xy_dev, count_dev, stride, n_images, cols, rows, tol, index_dev, status_dev, n_labelings_dev, worst_dev);
+  return st.finish(who);
+}
+
+int clc_find_chessboard_device(clc_handle* h, const clc_chess_options* copt, const clc_chessorder_options* oopt, const clc_subpix_options* sopt,
+                               const uint8_t* images_dev, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols,
+                               int32_t rows, float* corners_dev, int32_t* found_dev, double* strength_dev) {
+  const char* who = "clc_find_chessboard_device";
+  clc_chess_options o;
+  double tol = 0.0;
+  CLC_TRY(find_checks(who, n_images == 0 || (images_dev && corners_dev && found_dev), copt, oopt, sopt, width, height, pitch, n_images, cols, rows,
+                      &o, &tol));
+  if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_find_chessboard_device: bad argument");
+  if (n_images == 0) return CLC_OK;
+  CLC_HIP(hipSetDevice(h->device));
+  Staging st(h);
+  CLC_TRY(find_on_device(who, h, st, o, tol, sopt, images_dev, width, height, pitch, n_images, cols, rows, corners_dev, found_dev, strength_dev));
+  return st.finish(who);
+}
+
+int clc_find_chessboard_gpu(clc_handle* h, const clc_chess_options* copt, const clc_chessorder_options* oopt, const clc_subpix_options* sopt,
+                            const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
+                            float* corners, int32_t* found, double* strength) {
+  const char* who = "clc_find_chessboard_gpu";
+  clc_chess_options o;
+  double tol = 0.0;
+  CLC_TRY(find_checks(who, n_images == 0 || (images && corners && found), copt, oopt, sopt, width, height, pitch, n_images, cols, rows, &o, &tol));
+  if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_find_chessboard_gpu: bad argument");
+  if (n_images == 0) return CLC_OK;
+  CLC_HIP(hipSetDevice(h->device));
+  const size_t M = n_images * (size_t)cols * (size_t)rows;
+  Staging st(h);  // the images go up once
+  const uint8_t* img_dev = st.in(images, n_images * (size_t)height * (size_t)pitch);
+  float* corners_dev = st.out(corners, 2 * M);
+  int32_t* found_dev = st.out(found, n_images);
+  double* strength_dev = st.out_opt(strength, M);
+  CLC_TRY(st.status(who));
+  CLC_TRY(find_on_device(who, h, st, o, tol, sopt, img_dev, width, height, pitch, n_images, cols, rows, corners_dev, found_dev, strength_dev));
   return st.finish(who);
 }
 

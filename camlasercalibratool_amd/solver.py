@@ -967,10 +967,13 @@ class Solver:
 
     def find_chessboard(self, images: np.ndarray, cols: int, rows: int, chess_options: Optional[ChessOptions] = None,
                         order_options: Optional[ChessOrderOptions] = None, subpix_options: Optional[SubpixOptions] = None,
-                        width: Optional[int] = None) -> dict:
+                        width: Optional[int] = None, ordering: str = "host") -> dict:
         """clc_find_chessboard (K25): detection on the device, ordering into the cols x rows grid on the host, and with subpix_options
         the refinement (K24) -> dict(corners [n, cols rows, 2] float32, row i cols + j = node (j, i), NaN where no board was found;
-        found [n] bool; strength [n, cols rows])."""
+        found [n] bool; strength [n, cols rows]).  ordering="device": clc_find_chessboard_gpu (K26), the ordering on the device too
+        and nothing read back between the stages; the same results."""
+        if ordering not in ("host", "device"):
+            raise ValueError("find_chessboard: ordering must be 'host' or 'device'")
         img = np.ascontiguousarray(images, dtype=np.uint8)
         if img.ndim != 3:
             raise ValueError("find_chessboard: images must be [n, height, pitch]")
@@ -978,10 +981,34 @@ class Solver:
         corners = np.full((n, per, 2), np.nan, np.float32); found = np.zeros(n, np.int32); lam = np.full((n, per), np.nan)
         V = lambda a: a.ctypes.data_as(C.c_void_p)
         ref = lambda o: C.byref(o) if o is not None else None
-        check(self._L.clc_find_chessboard(self._h, ref(chess_options), ref(order_options), ref(subpix_options), V(img),
-                                          C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]), C.c_int64(img.shape[2]),
-                                          C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), V(corners), V(found), V(lam)), "clc_find_chessboard")
+        name = "clc_find_chessboard" if ordering == "host" else "clc_find_chessboard_gpu"
+        check(getattr(self._L, name)(self._h, ref(chess_options), ref(order_options), ref(subpix_options), V(img),
+                                     C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]), C.c_int64(img.shape[2]),
+                                     C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), V(corners), V(found), V(lam)), name)
         return dict(corners=corners, found=found.astype(bool), strength=lam)
+
+    # ---- the ordering on the device (K26) ----
+    def chessboard_order_device(self, cand_xy_ptr: int, count_ptr: int, stride: int, n_images: int, cols: int, rows: int, index_ptr: int,
+                                status_ptr: int, n_labelings_ptr: int = 0, worst_ptr: int = 0, options: Optional[ChessOrderOptions] = None):
+        """clc_chessboard_order_device on device-resident arrays (data_ptr()s; ready on the solver's stream): cand_xy [n, stride, 2]
+        float32 and count [n] int32 as chess_corners_device wrote them, status [n] int32 read and written, index [n, cols rows] int32;
+        n_labelings [n] int32 and worst [n] float64 may be left out."""
+        V = lambda p: C.c_void_p(p or 0)
+        o = C.byref(options) if options is not None else None
+        check(self._L.clc_chessboard_order_device(self._h, V(cand_xy_ptr), V(count_ptr), C.c_int64(stride), C.c_size_t(n_images), C.c_int32(cols),
+                                                  C.c_int32(rows), o, V(index_ptr), V(status_ptr), V(n_labelings_ptr), V(worst_ptr)),
+              "clc_chessboard_order_device")
+
+    def find_chessboard_device(self, images_ptr: int, width: int, height: int, pitch: int, n_images: int, cols: int, rows: int, corners_ptr: int,
+                               found_ptr: int, strength_ptr: int = 0, chess_options: Optional[ChessOptions] = None,
+                               order_options: Optional[ChessOrderOptions] = None, subpix_options: Optional[SubpixOptions] = None):
+        """clc_find_chessboard_device on device-resident arrays (data_ptr()s; ready on the solver's stream): images uint8, corners
+        [n, cols rows, 2] float32, found [n] int32, strength [n, cols rows] float64 (may be left out)."""
+        V = lambda p: C.c_void_p(p or 0)
+        ref = lambda o: C.byref(o) if o is not None else None
+        check(self._L.clc_find_chessboard_device(self._h, ref(chess_options), ref(order_options), ref(subpix_options), V(images_ptr),
+                                                 C.c_int32(width), C.c_int32(height), C.c_int64(pitch), C.c_size_t(n_images), C.c_int32(cols),
+                                                 C.c_int32(rows), V(corners_ptr), V(found_ptr), V(strength_ptr)), "clc_find_chessboard_device")
 
     # ---- camera intrinsics from the board images (K19) ----
     def camera_guess(self, model: int, width: int, height: int, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray):

@@ -1429,6 +1429,30 @@ int clc_find_chessboard(clc_handle* h, const clc_chess_options* copt, const clc_
                         const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
                         float* corners, int32_t* found, double* strength);
 
+/* ---- the ordering on the device (K26) ------------------------------------------------------------------------------------------
+ * clc_chessboard_order on device arrays, one wave per image, rule for rule the host code: index, status and n_labelings are the
+ * host call's values; worst agrees with it to a few units in the last place (the predicted spacing is sqrt(dx dx + dy dy) where the
+ * host calls hypot) and is the same bits from call to call.  One enqueue on the handle's stream and one synchronisation; the arrays
+ * must be ready on that stream.  n_labelings_dev and worst_dev are nullable.  It refuses what clc_chessboard_order refuses, in the
+ * same order, then a NULL handle; all before any device work. */
+int clc_chessboard_order_device(clc_handle* h, const float* cand_xy_dev, const int32_t* count_dev, int64_t stride, size_t n_images,
+                                int32_t cols, int32_t rows, const clc_chessorder_options* oopt, int32_t* index_dev, int32_t* status_dev,
+                                int32_t* n_labelings_dev, double* worst_dev);
+
+/* clc_find_chessboard on device arrays: detection, ordering, the gather of the ordered pixels and with sopt != NULL the refinement,
+ * all on the device with nothing read back in between.  corners_dev[n_images cols rows 2], found_dev[n_images], strength_dev
+ * [n_images cols rows] (nullable; NaN with sopt NULL).  The results are clc_find_chessboard's.  It refuses what clc_find_chessboard
+ * refuses, in the same order. */
+int clc_find_chessboard_device(clc_handle* h, const clc_chess_options* copt, const clc_chessorder_options* oopt,
+                               const clc_subpix_options* sopt, const uint8_t* images_dev, int32_t width, int32_t height, int64_t pitch,
+                               size_t n_images, int32_t cols, int32_t rows, float* corners_dev, int32_t* found_dev, double* strength_dev);
+
+/* clc_find_chessboard with the ordering on the device (host arrays): the images go up once, clc_find_chessboard_device's stages run,
+ * corners, found and strength come back. */
+int clc_find_chessboard_gpu(clc_handle* h, const clc_chess_options* copt, const clc_chessorder_options* oopt, const clc_subpix_options* sopt,
+                            const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
+                            float* corners, int32_t* found, double* strength);
+
 #ifdef __cplusplus
 }
 #endif
