@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 PRODUCT_LIB_PATH = os.path.join(CSRC, "libclc_hip.so")
 HOOKS_LIB_PATH = os.path.join(CSRC, "libclc_hip_hooks.so")
 LIB_PATH = os.environ.get("CLC_LIBRARY") or PRODUCT_LIB_PATH  # CLC_LIBRARY: run the package on a different build
-UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_batchflow.hip", "abi_campose.hip", "abi_joint.hip", "abi_camcal.hip", "abi_guidance.hip", "abi_laserrange.hip", "abi_jointrobust.hip", "abi_fullcal.hip", "abi_subpix.hip", "abi_chess.hip", "abi_comm.hip", "abi_debug.hip"]
+UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip", "abi_batched.hip", "abi_batchflow.hip", "abi_campose.hip", "abi_joint.hip", "abi_camcal.hip", "abi_guidance.hip", "abi_laserrange.hip", "abi_jointrobust.hip", "abi_fullcal.hip", "abi_subpix.hip", "abi_chess.hip", "abi_tags.hip", "abi_comm.hip", "abi_debug.hip"]
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
            "clc_batchflow.hpp", "clc_campose.hpp"]
@@ -33,8 +33,9 @@ HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assembl
 # abi_guidance.hip alone (tests/test_guidance_resources.py), clc_subpix.hpp (corner refinement) in abi_subpix.hip alone
 # (tests/test_subpix_resources.py), clc_chess.hpp (chessboard-corner detection) in abi_chess.hip alone (tests/test_chess_resources.py;
 # its host-side ordering, clc_chessorder.hpp, is plain C++ among the HOST_HEADERS; the same ordering on the device, clc_boardorder.hpp, is
-# in abi_chess.hip too: tests/test_boardorder_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
-SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp", "clc_chess.hpp", "clc_boardorder.hpp"]
+# in abi_chess.hip too: tests/test_boardorder_resources.py), clc_tags.hpp (tag-grid corners, over clc_boardorder.hpp's 4-point solve) in
+# abi_tags.hip alone (tests/test_tags_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
+SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp", "clc_chess.hpp", "clc_boardorder.hpp", "clc_tags.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default
 # (fast) lets the backend fuse across statements, and it did so differently in different kernels that inline the

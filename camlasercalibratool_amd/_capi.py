@@ -53,6 +53,7 @@ EXPORTED = [
     "clc_chess_options_default", "clc_chessorder_options_default", "clc_chess_corners", "clc_chess_corners_device",
     "clc_chessboard_order", "clc_find_chessboard",
     "clc_chessboard_order_device", "clc_find_chessboard_device", "clc_find_chessboard_gpu",
+    "clc_tag_options_default", "clc_tag_grid", "clc_tag_grid_device", "clc_tag_grid_points_device",
     "clc_interp_options_default", "clc_interpolate_poses", "clc_assemble_interpolated", "clc_assemble_interpolated_device",
     "clc_clock_offset_options_default", "clc_clock_offset_best", "clc_clock_offset_sweep", "clc_clock_offset_sweep_device",
 ]
@@ -239,6 +240,18 @@ class ChessOrderOptions(C.Structure):
     _fields_ = [("tol", C.c_double), ("reserved", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class TagFamilyC(C.Structure):
+    """clc_tag_family (include/clc.h): the payload side d, the border b, the code table (host memory) and the accepted distance of K27."""
+    _fields_ = [("side", C.c_int32), ("border", C.c_int32), ("n_codes", C.c_int32), ("max_hamming", C.c_int32), ("codes", C.c_void_p)]
+
+
+class TagOptions(C.Structure):
+    """clc_tag_options (include/clc.h): the side range of a tag in pixels, the edge contrast, the border errors and the quads decoded (K27)."""
+    _fields_ = [("min_side_px", C.c_int32), ("max_side_px", C.c_int32), ("contrast", C.c_int32), ("max_border_errors", C.c_int32),
+                ("max_quads", C.c_int32), ("reserved", C.c_int32)]
+
+
+TAG_MAX_QUADS, TAG_MAX_OUT, TAG_MAX_TAGS, TAG_MAX_CODES, TAG_OK, TAG_OVERFLOW = 1024, 4, 1024, 4096, 1, -2  # CLC_TAG_*
 SUBPIX_MAX_WIN = 15  # CLC_SUBPIX_MAX_WIN
 CHESS_MAX_CANDIDATES, CHESS_RAW_CAP = 1024, 4096  # CLC_CHESS_*
 CHESS_OK, CHESS_FOUND, CHESS_TOO_FEW, CHESS_NO_GRID, CHESS_OVERFLOW = 1, 1, 0, -1, -2
@@ -421,6 +434,12 @@ def load(path: str):
             L.clc_chess_corners_device.argtypes = [V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t] + [V] * 5
             L.clc_chessboard_order.argtypes = [V, V, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 5
             L.clc_find_chessboard.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 3
+        if hasattr(L, "clc_tag_grid"):
+            L.clc_tag_options_default.argtypes = [V]
+            L.clc_tag_options_default.restype = None
+            L.clc_tag_grid.argtypes = [V] * 6 + [C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 8
+            L.clc_tag_grid_device.argtypes = [V] * 6 + [C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 8
+            L.clc_tag_grid_points_device.argtypes = [V, V, V, C.c_size_t, C.c_int32, C.c_int32, C.c_double, C.c_double, V, V, V]
         if hasattr(L, "clc_chessboard_order_device"):
             L.clc_chessboard_order_device.argtypes = [V, V, V, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 5
             L.clc_find_chessboard_device.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.c_int32, C.c_int32] + [V] * 3
@@ -538,6 +557,13 @@ def default_chess_options() -> ChessOptions:
     """clc_chess_options_default: threshold 500 on R5, suppression radius 3, relative gate 250 permille, 256 candidates per image."""
     o = ChessOptions()
     lib().clc_chess_options_default(C.byref(o))
+    return o
+
+
+def default_tag_options() -> TagOptions:
+    """clc_tag_options_default: sides from 16 px, contrast 40, no white border cell, 256 quads per image."""
+    o = TagOptions()
+    lib().clc_tag_options_default(C.byref(o))
     return o
 
 

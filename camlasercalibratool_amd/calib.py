@@ -543,6 +543,33 @@ def FindChessboardCorners(images, pattern_size, square_size: float, refine_win: 
     return [r["corners"][k] for k in range(n)], [board.copy() for _ in range(n)], r["found"]
 
 
+def FindTagGridCorners(images, grid_size, tag_size: float, tag_spacing: float, family, refine_win: int = 3, max_iter: int = 30,
+                       eps: float = 0.1, tag_options=None, chess_options=None, solver: Optional[Solver] = None):
+    """The front of CamPoseEst's Kalibr branch (src/calcCamPose.cpp:48-139: the tag detector, cornerSubPix at half-window 3, the board
+    points by tag id) for many images at once (clc_tag_grid, K27 + K24): images uint8 [n, H, W] grey, grid_size = (cols, rows) tags,
+    tag id = row cols + col, `family` a solver.TagFamily (the board's code table: this package ships none).  Returns (corners_px,
+    board_xy, tag_ids), one array per image: the corners [4 m_k, 2] float32 of the m_k tags seen, in id order and within a tag in the
+    order of the reference's detector (counter-clockwise on the upright printed tag from its bottom-left corner), refined at half-window
+    refine_win (0: the integer pixels); their board points (X0, Y0), (X0 + a, Y0), (X0 + a, Y0 + a), (X0, Y0 + a) with
+    (X0, Y0) = (col, row) tag_size (1 + tag_spacing); and the ids [m_k].  The lists go straight into CalcCamPoses, CalibrateCamera and
+    CalibrateFull; a board cut by the image border gives the tags fully in view."""
+    cols, rows = int(grid_size[0]), int(grid_size[1])
+    sv = solver or _shared_solver()
+    so = _capi.SubpixOptions(refine_win, refine_win, -1, -1, max_iter, 0, eps) if refine_win > 0 else None
+    r = sv.tag_grid(images, family, cols, rows, tag_options, chess_options, so)
+    period = tag_size * (1.0 + tag_spacing)
+    corners_px, board_xy, tag_ids = [], [], []
+    for k in range(len(r["count"])):
+        ids = np.flatnonzero(r["hamming"][k] >= 0)
+        x0, y0 = (ids % cols) * period, (ids // cols) * period
+        b = np.stack([np.stack([x0, y0], 1), np.stack([x0 + tag_size, y0], 1), np.stack([x0 + tag_size, y0 + tag_size], 1),
+                      np.stack([x0, y0 + tag_size], 1)], 1)
+        corners_px.append(r["corners"][k, ids].reshape(-1, 2))
+        board_xy.append(b.reshape(-1, 2).astype(np.float32))
+        tag_ids.append(ids.astype(np.int32))
+    return corners_px, board_xy, tag_ids
+
+
 def CalcCamPosesRobust(camera, corners_px: Sequence[np.ndarray], board_xy: Sequence[np.ndarray], solver: Optional[Solver] = None,
                        options: Optional[Options] = None, robust=None):
     """CalcCamPoses with a consensus over the tags of every image ahead of the fit (clc_board_poses_robust, K16): a tag decoded with a

@@ -156,6 +156,21 @@ int find_on_device(const char* who, clc_handle* h, Staging& st, const clc_chess_
 
 }  // namespace
 
+// K25's checks and enqueue for the unit that builds on its candidates (abi_tags.hip; declared in abi_staging.hpp).
+namespace clc_abi {
+
+int chess_detection_checks(const char* who, const clc_chess_options* in, int32_t width, int32_t height, int64_t pitch, size_t n_images,
+                           clc_chess_options* o) {
+  return chess_checks(who, true, in, width, height, pitch, n_images, o);
+}
+
+void enqueue_chess_detection(Staging& st, const clc_chess_options& o, const uint8_t* images, int32_t width, int32_t height, int64_t pitch,
+                             size_t n_images, float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status) {
+  enqueue_chess(st, o, images, width, height, pitch, n_images, cand_xy, cand_r5, count, count_raw, status);
+}
+
+}  // namespace clc_abi
+
 extern "C" {
 
 void clc_chess_options_default(clc_chess_options* o) {

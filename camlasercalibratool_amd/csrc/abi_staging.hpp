@@ -96,4 +96,11 @@ inline void stamp_solve_ms(clc_summary* summaries, size_t n, Clock::time_point t
   for (size_t k = 0; k < n; ++k) summaries[k].solve_ms = ms;
 }
 
+// K25's detection on device arrays (abi_chess.hip: its checks with the defaults filled in, and its enqueue: per chunk of 170 images the
+// counters to zero, one workgroup per tile, one wave per image), for the unit that builds on its candidates (abi_tags.hip).
+int chess_detection_checks(const char* who, const clc_chess_options* in, int32_t width, int32_t height, int64_t pitch, size_t n_images,
+                           clc_chess_options* o);
+void enqueue_chess_detection(Staging& st, const clc_chess_options& o, const uint8_t* images, int32_t width, int32_t height, int64_t pitch,
+                             size_t n_images, float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status);
+
 }  // namespace clc_abi

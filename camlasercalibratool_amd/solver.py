@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _capi, resample
-from ._capi import AltPoseOptions, CamcalOptions, ChessOptions, ChessOrderOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, SubpixOptions, Summary, TERMINATION, check, default_line_options, default_options, dptr, iptr
+from ._capi import AltPoseOptions, CamcalOptions, ChessOptions, ChessOrderOptions, FullOptions, GuidanceOptions, Iteration, JointLossOptions, JointOptions, Options, RangeOptions, RobustPoseOptions, SubpixOptions, Summary, TagFamilyC, TagOptions, TERMINATION, check, default_line_options, default_options, dptr, iptr
 
 
 _Pose7 = C.c_double * 7
@@ -42,6 +42,61 @@ def flatten_observations(obs_set, use_linefitting_data: bool = True, use_boundar
 
 RESULT_RECORD = 12  # doubles per clc_result_record: pose[7], final_cost, initial_cost, iterations, termination, global index
 COMM_ID_BYTES = 128
+
+
+class TagFamily:
+    """The code table of a tag family (clc_tag_family, K27): `codes` [n] uint64 words of side x side payload bits, bit side side - 1 the
+    cell (row 0, col 0) of the upright tag, row-major, top row first (the order of the published AprilTag tables); `border` black cells
+    around the payload; a decode is accepted at a Hamming distance <= max_hamming.  This package ships no table: a Kalibr board's
+    36h11 comes from the user's AprilTag install, TagFamily.generate makes seeded families for tests and printed boards of one's own."""
+
+    def __init__(self, codes, side: int, border: int, max_hamming: int = 1):
+        self.codes = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1)
+        self.side, self.border, self.max_hamming = int(side), int(border), int(max_hamming)
+
+    def c_struct(self) -> TagFamilyC:
+        """clc_tag_family over this object's table (which has to outlive the call)."""
+        return TagFamilyC(self.side, self.border, len(self.codes), self.max_hamming, self.codes.ctypes.data)
+
+    @staticmethod
+    def cells(word: int, side: int) -> np.ndarray:
+        """The payload [side, side] of a word: 1 white, row 0 the top row of the upright tag."""
+        n = side * side
+        return np.array([(int(word) >> (n - 1 - k)) & 1 for k in range(n)], dtype=np.uint8).reshape(side, side)
+
+    @staticmethod
+    def word(cells) -> int:
+        w = 0
+        for v in np.asarray(cells).reshape(-1):
+            w = (w << 1) | int(v)
+        return w
+
+    @staticmethod
+    def rotations(word: int, side: int):
+        """The word as read from each of the tag's four corners in turn (quarter turns of the payload)."""
+        m = TagFamily.cells(word, side)
+        return [TagFamily.word(np.rot90(m, k)) for k in range(4)]
+
+    @classmethod
+    def generate(cls, side: int, n: int, min_hamming: int, seed: int, border: int = 2, max_hamming: int = 1) -> "TagFamily":
+        """A seeded greedy search: draw a word, keep it if it is at least min_hamming from every rotation of every kept word and from its
+        own three rotations.  Deterministic in (side, n, min_hamming, seed)."""
+        if not 3 <= side <= 7:
+            raise ValueError("TagFamily.generate: side must be in [3, 7]")
+        rng = np.random.default_rng(seed)
+        ham = lambda a, b: bin(a ^ b).count("1")
+        kept, kept_rot = [], []
+        for _ in range(200000):
+            if len(kept) == n:
+                break
+            w = int(rng.integers(0, 1 << (side * side), dtype=np.uint64))
+            rot = cls.rotations(w, side)
+            if min(ham(w, r) for r in rot[1:]) < min_hamming or any(ham(w, r) < min_hamming for r in kept_rot):
+                continue
+            kept.append(w); kept_rot += rot
+        if len(kept) < n:
+            raise ValueError("TagFamily.generate: no %d codes of %d bits at distance %d" % (n, side * side, min_hamming))
+        return cls(kept, side, border, max_hamming)
 
 
 def chessboard_order(cand_xy: np.ndarray, count: np.ndarray, cols: int, rows: int, status: Optional[np.ndarray] = None,
@@ -1009,6 +1064,53 @@ class Solver:
         check(self._L.clc_find_chessboard_device(self._h, ref(chess_options), ref(order_options), ref(subpix_options), V(images_ptr),
                                                  C.c_int32(width), C.c_int32(height), C.c_int64(pitch), C.c_size_t(n_images), C.c_int32(cols),
                                                  C.c_int32(rows), V(corners_ptr), V(found_ptr), V(strength_ptr)), "clc_find_chessboard_device")
+
+    # ---- tag-grid corners from images (K27) ----
+    def tag_grid(self, images: np.ndarray, family: "TagFamily", cols: int, rows: int, tag_options: Optional[TagOptions] = None,
+                 chess_options: Optional[ChessOptions] = None, subpix_options: Optional[SubpixOptions] = None,
+                 width: Optional[int] = None) -> dict:
+        """clc_tag_grid (K27): images uint8 [n, H, W], or [n, H, pitch] with width= given; a cols x rows grid of tags of `family`, tag
+        id = row cols + col -> dict(corners [n, cols rows, 4, 2] float32, NaN for a tag not seen, integer pixels or with subpix_options
+        refined (K24); hamming [n, cols rows], -1 not seen; count [n]; status [n]: 1, or -2 where the detection overflowed; n_quads,
+        n_foreign, n_edges_dropped [n]; strength [n, cols rows, 4])."""
+        img = np.ascontiguousarray(images, dtype=np.uint8)
+        if img.ndim != 3:
+            raise ValueError("tag_grid: images must be [n, height, pitch]")
+        n, T = img.shape[0], max(int(cols) * int(rows), 1)
+        r = dict(corners=np.full((n, T, 4, 2), -7.0, np.float32), hamming=np.full((n, T), -7, np.int32), count=np.full(n, -7, np.int32),
+                 status=np.full(n, -99, np.int32), n_quads=np.full(n, -7, np.int32), n_foreign=np.full(n, -7, np.int32),
+                 n_edges_dropped=np.full(n, -7, np.int32), strength=np.full((n, T, 4), -7.0))
+        V = lambda a: a.ctypes.data_as(C.c_void_p)
+        ref = lambda o: C.byref(o) if o is not None else None
+        fam = family.c_struct()
+        check(self._L.clc_tag_grid(self._h, C.byref(fam), ref(tag_options), ref(chess_options), ref(subpix_options), V(img),
+                                   C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]), C.c_int64(img.shape[2]),
+                                   C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), V(r["corners"]), V(r["hamming"]), V(r["count"]), V(r["status"]),
+                                   V(r["n_quads"]), V(r["n_foreign"]), V(r["n_edges_dropped"]), V(r["strength"])), "clc_tag_grid")
+        return r
+
+    def tag_grid_device(self, images_ptr: int, width: int, height: int, pitch: int, n_images: int, family: "TagFamily", cols: int, rows: int,
+                        corners_ptr: int, hamming_ptr: int, count_ptr: int, status_ptr: int, n_quads_ptr: int = 0, n_foreign_ptr: int = 0,
+                        n_edges_dropped_ptr: int = 0, strength_ptr: int = 0, tag_options: Optional[TagOptions] = None,
+                        chess_options: Optional[ChessOptions] = None, subpix_options: Optional[SubpixOptions] = None):
+        """clc_tag_grid_device on device-resident arrays (data_ptr()s; ready on the solver's stream): images uint8, corners
+        [n, cols rows, 4, 2] float32, hamming [n, cols rows] int32, count and status [n] int32; the others may be left out."""
+        V = lambda p: C.c_void_p(p or 0)
+        ref = lambda o: C.byref(o) if o is not None else None
+        fam = family.c_struct()
+        check(self._L.clc_tag_grid_device(self._h, C.byref(fam), ref(tag_options), ref(chess_options), ref(subpix_options), V(images_ptr),
+                                          C.c_int32(width), C.c_int32(height), C.c_int64(pitch), C.c_size_t(n_images), C.c_int32(cols),
+                                          C.c_int32(rows), V(corners_ptr), V(hamming_ptr), V(count_ptr), V(status_ptr), V(n_quads_ptr),
+                                          V(n_foreign_ptr), V(n_edges_dropped_ptr), V(strength_ptr)), "clc_tag_grid_device")
+
+    def tag_grid_points_device(self, corners_ptr: int, hamming_ptr: int, n_images: int, cols: int, rows: int, tag_size: float,
+                               tag_spacing: float, corners_px_ptr: int, board_xy_ptr: int, offsets_ptr: int):
+        """clc_tag_grid_points_device: the seen tags of tag_grid_device's result, image by image in id order, as board_poses_device takes
+        them: corners_px and board_xy [n 4 cols rows, 2] float32 (the capacity), offsets [n + 1] int64."""
+        V = lambda p: C.c_void_p(p or 0)
+        check(self._L.clc_tag_grid_points_device(self._h, V(corners_ptr), V(hamming_ptr), C.c_size_t(n_images), C.c_int32(cols), C.c_int32(rows),
+                                                 C.c_double(tag_size), C.c_double(tag_spacing), V(corners_px_ptr), V(board_xy_ptr),
+                                                 V(offsets_ptr)), "clc_tag_grid_points_device")
 
     # ---- camera intrinsics from the board images (K19) ----
     def camera_guess(self, model: int, width: int, height: int, corners_px: np.ndarray, board_xy: np.ndarray, offsets: np.ndarray):

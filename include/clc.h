@@ -1453,6 +1453,73 @@ int clc_find_chessboard_gpu(clc_handle* h, const clc_chess_options* copt, const 
                             const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
                             float* corners, int32_t* found, double* strength);
 
+/* ---- tag-grid corners from images: quads, decode, refine (K27) -------------------------------------------------------------------
+ * The reference's default board (KALIBR_TAG_PATTERN, src/calcCamPose.cpp:48-139): a grid of cols x rows square tags, tag id =
+ * row cols + col, with a black spacer square at every grid intersection, so that every tag corner is an X-junction and K25's response
+ * finds it.  Per image: K25's candidates; the directed edges between candidates that have the tag's black border on their right-hand
+ * side (image coordinates, y down) and white on the other; the directed 4-cycles of such edges (the quads, in lexicographic order of
+ * their slots); per quad one homography from the unit square (K26's 4-point solve), the dd x dd cells sampled at their centres against
+ * the mean of the 48 edge samples, the border ring checked, the payload word compared with every code of the family under its four
+ * rotations, the best under (Hamming, id, rotation) accepted at a distance <= max_hamming.  DESIGN.md K27 holds every rule.  The code
+ * table is the caller's: this library ships none.  A tag cut by the image border is not seen; the others are. */
+#define CLC_TAG_MAX_QUADS 1024
+#define CLC_TAG_MAX_OUT 4     /* kept directed edges per candidate */
+#define CLC_TAG_MAX_TAGS 1024 /* cols x rows */
+#define CLC_TAG_MAX_CODES 4096
+#define CLC_TAG_OK 1
+#define CLC_TAG_OVERFLOW -2   /* the image's detection ended CLC_CHESS_OVERFLOW: no tag */
+typedef struct clc_tag_family {
+  int32_t side;          /* payload cells per side d, 3 .. 7 */
+  int32_t border;        /* black border in cells b, 1 .. 2; dd = d + 2 b */
+  int32_t n_codes;       /* 1 .. CLC_TAG_MAX_CODES */
+  int32_t max_hamming;   /* a decode is accepted at a distance <= this, 0 .. d d / 2 */
+  const uint64_t* codes; /* [n_codes], host memory; bit d d - 1 = payload cell (row 0, col 0) of the upright tag, row-major, top row first */
+} clc_tag_family;
+typedef struct clc_tag_options {
+  int32_t min_side_px;       /* >= 8: shorter candidate pairs are not tested */
+  int32_t max_side_px;       /* 0: min(width, height); otherwise >= min_side_px */
+  int32_t contrast;          /* 1 .. 255: min(outside) - max(inside) of an edge's samples */
+  int32_t max_border_errors; /* 0 .. 8 white cells in the border ring */
+  int32_t max_quads;         /* 1 .. CLC_TAG_MAX_QUADS quads decoded per image */
+  int32_t reserved;          /* 0 */
+} clc_tag_options;           /* 24 bytes */
+
+/* min_side_px 16, max_side_px 0, contrast 40, max_border_errors 0, max_quads 256. */
+void clc_tag_options_default(clc_tag_options* topt);
+
+/* images[n_images][height][pitch] uint8 grey, as clc_chess_corners takes them; T = cols rows tags.  corners[n_images T 4 2]: the
+ * tag's corners 0 .. 3 in the order of the reference's TagDetection::p (counter-clockwise on the upright printed tag from its
+ * bottom-left corner: board points (X0, Y0), (X0 + a, Y0), (X0 + a, Y0 + a), (X0, Y0 + a) with (X0, Y0) = (col, row) a (1 + spacing),
+ * src/calcCamPose.cpp:104-137), integer pixels, or with sopt != NULL refined by clc_corner_subpix_device on the resident images
+ * (the reference's call: clc_subpix_options_default(&s, 3)); NaN for a tag not seen.  hamming[n_images T]: the decode's distance,
+ * -1 for a tag not seen.  count[n_images]: tags seen.  status[n_images]: CLC_TAG_OK / CLC_TAG_OVERFLOW.  Nullable: n_quads[n_images]
+ * (every quad, also those past max_quads), n_foreign[n_images] (decodes of an id >= T), n_edges_dropped[n_images] (passing edges past
+ * CLC_TAG_MAX_OUT of their candidate), strength[n_images T 4] (clc_corner_subpix's; NaN with sopt NULL).  topt NULL: the defaults;
+ * copt NULL: K25's defaults with max_per_image 1024.  CLC_ERR_INVALID_ARG before any device work: an option or a family field out
+ * of range, a code with bits above d d, reserved != 0, cols rows < 1 or > CLC_TAG_MAX_TAGS, what clc_chess_corners refuses, a NULL
+ * required array.  An image without a tag never fails the call; the bits are the same on every run, alone or in a batch. */
+int clc_tag_grid(clc_handle* h, const clc_tag_family* family, const clc_tag_options* topt, const clc_chess_options* copt,
+                 const clc_subpix_options* sopt, const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images,
+                 int32_t cols, int32_t rows, float* corners, int32_t* hamming, int32_t* count, int32_t* status, int32_t* n_quads,
+                 int32_t* n_foreign, int32_t* n_edges_dropped, double* strength);
+
+/* clc_tag_grid on device arrays (the family stays a host struct: the call stages its codes): every stage is enqueued on the handle's
+ * stream with nothing read back in between, and the call returns after one wait at its end (with sopt: clc_corner_subpix_device's). */
+int clc_tag_grid_device(clc_handle* h, const clc_tag_family* family, const clc_tag_options* topt, const clc_chess_options* copt,
+                        const clc_subpix_options* sopt, const uint8_t* images_dev, int32_t width, int32_t height, int64_t pitch,
+                        size_t n_images, int32_t cols, int32_t rows, float* corners_dev, int32_t* hamming_dev, int32_t* count_dev,
+                        int32_t* status_dev, int32_t* n_quads_dev, int32_t* n_foreign_dev, int32_t* n_edges_dropped_dev,
+                        double* strength_dev);
+
+/* The compaction of clc_tag_grid_device's result for clc_board_poses_device: the corners of the tags seen (hamming >= 0), image by
+ * image in id order, corners_px_dev[2 M] float32 and their board points board_xy_dev[2 M] float32 (tag_size a and tag_spacing as in
+ * the reference's board file), offsets_dev[n_images + 1] int64 (rows; offsets[0] = 0, M = offsets[n_images] <= the capacity
+ * n_images 4 cols rows the caller allocates).  CLC_ERR_INVALID_ARG: cols rows out of range, tag_size not finite or <= 0,
+ * tag_spacing not finite or < 0, a NULL array. */
+int clc_tag_grid_points_device(clc_handle* h, const float* corners_dev, const int32_t* hamming_dev, size_t n_images, int32_t cols,
+                               int32_t rows, double tag_size, double tag_spacing, float* corners_px_dev, float* board_xy_dev,
+                               int64_t* offsets_dev);
+
 #ifdef __cplusplus
 }
 #endif
