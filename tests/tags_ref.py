@@ -3,7 +3,8 @@ decode of each quad against the family, the grid by tag id, the compaction), ind
 samples, a set of canonical cycles for the quads, a LAPACK solve for the homography, numpy rotations for the four readings of a word.
 
 Everything before the homography is exact integer arithmetic; the homography only chooses the pixel nearest each cell centre, and
-HALF records how close any sample coordinate came to a half-integer (the tests require a margin, so that rint cannot differ)."""
+HALF records how close any sample coordinate came to a half-integer (the tests require a margin, so that rint cannot differ), and
+AMBIGUOUS, for the scenes whose quads are too many for such a margin, the samples at a half-integer where that could change a cell."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -15,6 +16,8 @@ import chess_ref
 S, MAX_OUT = 8, 4
 OK, OVERFLOW = 1, -2
 HALF = []  # min |frac(coordinate) - 0.5| of every decoded quad since the list was last cleared
+AMBIGUOUS = []  # per decoded quad since the list was last cleared: its samples within TIE of a half-integer that rint could decide either way
+TIE = 1e-9
 
 
 @dataclass(frozen=True)
@@ -114,6 +117,24 @@ def word_of(cells):
     return w
 
 
+def undecidable(img, width, uv, thr):
+    """The samples uv [m, 2] whose pixel is not decidable: a coordinate within TIE of a half-integer (either neighbour may be the nearest
+    pixel) and the two or four pixels it may round to not all inside the image, or inside and not all on one side of 48 I > thr -> their
+    number.  (All of them outside is decidable: the quad is refused either way.)"""
+    n = 0
+    for x, y in uv:
+        xs = [np.floor(x), np.floor(x) + 1] if abs(x - np.floor(x) - 0.5) <= TIE else [np.rint(x)]
+        ys = [np.floor(y), np.floor(y) + 1] if abs(y - np.floor(y) - 0.5) <= TIE else [np.rint(y)]
+        if len(xs) * len(ys) == 1:
+            continue
+        inside = [0 <= i < width and 0 <= j < img.shape[0] for j in ys for i in xs]
+        if not any(inside):
+            continue
+        if not all(inside) or len({48 * int(img[int(j), int(i)]) > thr for j in ys for i in xs}) != 1:
+            n += 1
+    return n
+
+
 def decode(img, width, cand, quad, kept, fam, o):
     """-> None (rejected) or (hamming, id, rotation) of the accepted decode."""
     d, b = fam.side, fam.border
@@ -129,6 +150,7 @@ def decode(img, width, cand, quad, kept, fam, o):
     if not np.isfinite(uv).all():
         return None
     HALF.append(float(np.abs(uv - np.floor(uv) - 0.5).min()))
+    AMBIGUOUS.append(undecidable(img, width, uv, thr))
     ij = np.rint(uv).astype(np.int64)
     if (ij[:, 0] < 0).any() or (ij[:, 0] >= width).any() or (ij[:, 1] < 0).any() or (ij[:, 1] >= img.shape[0]).any():
         return None
@@ -143,11 +165,18 @@ def decode(img, width, cand, quad, kept, fam, o):
     return best if best[0] <= fam.max_hamming else None
 
 
-def image_tags(img, width, cand, fam, o, cols, rows):
-    """One image's candidates [n, 2] -> dict(corners [T, 4, 2], hamming [T], count, n_quads, n_foreign, n_edges_dropped)."""
-    T = cols * rows
+def image_graph(img, width, cand, fam, o):
+    """-> (the kept edges, the number dropped, the quads): what depends on neither the code table nor max_quads."""
     kept, dropped = edges(img, width, cand, fam, o)
-    Q = quads(kept)
+    return kept, dropped, quads(kept)
+
+
+def image_tags(img, width, cand, fam, o, cols, rows, graph=None):
+    """One image's candidates [n, 2] -> dict(corners [T, 4, 2], hamming [T], count, n_quads, n_foreign, n_edges_dropped; and of every id
+    the rank [T] and the rotation [T] of the quad it was accepted from, -1 not seen; quads: the list of all quads).  graph: image_graph's
+    result for the same image, family geometry and edge options."""
+    T = cols * rows
+    kept, dropped, Q = graph if graph is not None else image_graph(img, width, cand, fam, o)
     best, foreign = {}, 0
     for rank, quad in enumerate(Q[:o.max_quads]):
         r = decode(img, width, cand, quad, kept, fam, o)
@@ -159,11 +188,13 @@ def image_tags(img, width, cand, fam, o, cols, rows):
         elif i not in best or (ham, rank) < best[i][:2]:
             best[i] = (ham, rank, rot, quad)
     corners = np.full((T, 4, 2), np.nan, np.float32); hamming = np.full(T, -1, np.int32)
+    ranks = np.full(T, -1, np.int32); rotation = np.full(T, -1, np.int32)
     for i, (ham, rank, rot, quad) in best.items():
-        hamming[i] = ham
+        hamming[i], ranks[i], rotation[i] = ham, rank, rot
         for j in range(4):  # the tag's corner 0 is its bottom-left one: the quad's corner rot + 3
             corners[i, j] = cand[quad[(rot + 3 - j) % 4]]
-    return dict(corners=corners, hamming=hamming, count=len(best), n_quads=len(Q), n_foreign=foreign, n_edges_dropped=dropped)
+    return dict(corners=corners, hamming=hamming, count=len(best), n_quads=len(Q), n_foreign=foreign, n_edges_dropped=dropped, rank=ranks,
+                rotation=rotation, quads=Q)
 
 
 def tag_grid(images, width, fam, cols, rows, o=Options(), chess=CHESS):
