@@ -18,7 +18,7 @@ UNITS = ["abi_core.hip", "abi_layouts.hip", "abi_solve.hip", "abi_frontend.hip",
 HEADERS = ["clc_abi_internal.hpp", "clc_kernels.hpp", "clc_device.hpp", "clc_layouts.hpp", "clc_stream.hpp", "clc_controller.hpp", "clc_frontend.hpp",
            "clc_resident.hpp", "clc_coop.hpp", "clc_lmuni.hpp", "clc_rows.hpp", "clc_lm.hpp", "clc_math.hpp", "clc_host.hpp", "clc_scanseg.hpp",
            "clc_batchflow.hpp", "clc_campose.hpp"]
-HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp", "abi_jointcall.hpp", "clc_chessorder.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
+HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assemble.hpp", "abi_staging.hpp", "abi_lift.hpp", "abi_jointcall.hpp", "abi_imagecall.hpp", "clc_chessorder.hpp"]  # host code shared by the units (no kernels): rebuilds the libraries, not part of csrc_sha16
 # kernels of their own that include HEADERS and are included by none of them: the kernels whose measured constants csrc_sha16 guards
 # (cooperative solve, resident solve) are built from the same bytes whatever these files hold — the symbol sizes of every kernel of
 # abi_batched.hip are unchanged by clc_consensus.hpp (profiles/consensus.md), those of abi_frontend.hip by clc_stations.hpp
@@ -34,7 +34,9 @@ HOST_HEADERS = ["abi_drive.hpp", "abi_memory.hpp", "abi_paths.hpp", "abi_assembl
 # (tests/test_subpix_resources.py), clc_chess.hpp (chessboard-corner detection) in abi_chess.hip alone (tests/test_chess_resources.py;
 # its host-side ordering, clc_chessorder.hpp, is plain C++ among the HOST_HEADERS; the same ordering on the device, clc_boardorder.hpp, is
 # in abi_chess.hip too: tests/test_boardorder_resources.py), clc_tags.hpp (tag-grid corners, over clc_boardorder.hpp's 4-point solve) in
-# abi_tags.hip alone (tests/test_tags_resources.py).  They rebuild the libraries and are not part of csrc_sha16.
+# abi_tags.hip alone (tests/test_tags_resources.py).  What those three units share is host code: abi_imagecall.hpp among the HOST_HEADERS (the
+# rules on the images and the refinement options, and the declarations through which abi_chess.hip and abi_tags.hip enqueue K25's
+# detection and K24's refinement without including clc_chess.hpp or clc_subpix.hpp).  They rebuild the libraries and are not part of csrc_sha16.
 SIDE_HEADERS = ["clc_consensus.hpp", "clc_assemble.hpp", "clc_stations.hpp", "clc_interp.hpp", "clc_robustpose.hpp", "clc_altpose.hpp", "clc_arrow.hpp", "clc_jointterms.hpp", "clc_joint.hpp", "clc_camcal.hpp", "clc_guidance.hpp", "clc_laserrange.hpp", "clc_jointrobust.hpp", "clc_fullcal.hpp", "clc_subpix.hpp", "clc_chess.hpp", "clc_boardorder.hpp", "clc_tags.hpp"]
 SOURCES = UNITS + HEADERS + HOST_HEADERS + SIDE_HEADERS
 # -ffp-contract=on: FMA contraction only where the source spells one expression a*b+c (or fma()).  hipcc's default

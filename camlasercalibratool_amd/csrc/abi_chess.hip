@@ -4,26 +4,19 @@
 // A unit of its own, held to its own register figures (tests/test_chess_resources.py).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
-#include "abi_staging.hpp"
+#include "abi_imagecall.hpp"
 #include "clc_chess.hpp"
 #include "clc_chessorder.hpp"
 #include "clc_boardorder.hpp"
 
 using namespace clc_abi;
 
-namespace {
-
 namespace ch = clc::chess;
 
-// The raw lists of one enqueue: images beyond this many bytes of them go in further chunks on the same stream (48 KiB per image:
-// 170 images per chunk).
-constexpr size_t kRawBudgetBytes = (size_t)8 << 20;
-constexpr size_t kRawBytesPerImage = (size_t)ch::RAW_CAP * 3 * sizeof(int32_t);
-constexpr size_t kChunkImages = kRawBudgetBytes / kRawBytesPerImage;
-
+// K25's checks and enqueue, for this unit and for the unit that builds on its candidates (abi_tags.hip; declared in abi_imagecall.hpp).
 // What both detection forms refuse alike ahead of the handle, in one order; then the options with the defaults filled in.
-int chess_checks(const char* who, bool required, const clc_chess_options* in, int32_t width, int32_t height, int64_t pitch, size_t n_images,
-                 clc_chess_options* o) {
+int clc_abi::chess_checks(const char* who, bool required, const clc_chess_options* in, int32_t width, int32_t height, int64_t pitch,
+                          size_t n_images, clc_chess_options* o) {
   const std::string w(who);
   if (in) *o = *in; else clc_chess_options_default(o);
   if (o->threshold < 1) return fail(CLC_ERR_INVALID_ARG, (w + ": threshold must be >= 1").c_str());
@@ -32,10 +25,7 @@ int chess_checks(const char* who, bool required, const clc_chess_options* in, in
   if (o->max_per_image < 1 || o->max_per_image > CLC_CHESS_MAX_CANDIDATES)
     return fail(CLC_ERR_INVALID_ARG, (w + ": max_per_image must be in [1, 1024]").c_str());
   if (o->reserved != 0) return fail(CLC_ERR_INVALID_ARG, (w + ": reserved must be 0").c_str());
-  if (width < 1 || height < 1) return fail(CLC_ERR_INVALID_ARG, (w + ": width and height must be >= 1").c_str());
-  if (pitch < (int64_t)width) return fail(CLC_ERR_INVALID_ARG, (w + ": pitch must be >= width").c_str());
-  if (n_images > 0x7FFFFFFFull || (n_images > 0 && pitch > (int64_t)(0x7FFFFFFFFFFFFFFFull / n_images / (uint64_t)height)))
-    return fail(CLC_ERR_INVALID_ARG, (w + ": too many images").c_str());
+  CLC_TRY(image_geometry_check(who, width, height, pitch, n_images));
   const uint64_t tiles = (((uint64_t)width + ch::TILE_W - 1) / ch::TILE_W) * (((uint64_t)height + ch::TILE_H - 1) / ch::TILE_H);
   if (tiles > 0x7FFFFFFFull) return fail(CLC_ERR_INVALID_ARG, (w + ": the image is too large").c_str());
   if (!required) return fail(CLC_ERR_INVALID_ARG, (w + ": bad argument").c_str());
@@ -43,9 +33,10 @@ int chess_checks(const char* who, bool required, const clc_chess_options* in, in
 }
 
 // K25 on device arrays: per chunk of images the counters to zero, one workgroup per tile, one wave per image.
-void enqueue_chess(Staging& st, const clc_chess_options& o, const uint8_t* images, int32_t width, int32_t height, int64_t pitch, size_t n_images,
-                   float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status) {
-  const size_t chunk = std::min(n_images, kChunkImages);
+void clc_abi::enqueue_chess(Staging& st, const clc_chess_options& o, const uint8_t* images, int32_t width, int32_t height, int64_t pitch,
+                            size_t n_images, float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status) {
+  static_assert(ch::RAW_CAP == CLC_CHESS_RAW_CAP, "kChessChunkImages is sized by the raw list");
+  const size_t chunk = std::min(n_images, kChessChunkImages);
   ch::ChessArgs a{};
   a.width = width; a.height = height; a.threshold = o.threshold; a.nms_radius = o.nms_radius; a.rel_permille = o.rel_permille;
   a.max_per_image = o.max_per_image; a.pitch = (long long)pitch; a.n_images = (long long)n_images; a.images = images;
@@ -69,6 +60,8 @@ void enqueue_chess(Staging& st, const clc_chess_options& o, const uint8_t* image
     st.launched();
   }
 }
+
+namespace {
 
 int order_checks(const char* who, bool required, const clc_chessorder_options* in, int32_t cols, int32_t rows, size_t n_images, double* tol) {
   const std::string w(who);
@@ -117,59 +110,40 @@ void enqueue_gather(Staging& st, const float* cand_xy, const int32_t* index, con
   }
 }
 
-// What clc_find_chessboard refuses, in its order, under the caller's name; then the options.
+// What the three forms of clc_find_chessboard refuse ahead of the handle, in one order; then the options.
 int find_checks(const char* who, bool required, const clc_chess_options* copt, const clc_chessorder_options* oopt, const clc_subpix_options* sopt,
                 int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows, clc_chess_options* o, double* tol) {
   const std::string w(who);
   CLC_TRY(chess_checks(who, required, copt, width, height, pitch, n_images, o));
   CLC_TRY(order_checks(who, required, oopt, cols, rows, n_images, tol));
   if ((size_t)o->max_per_image < (size_t)cols * (size_t)rows) return fail(CLC_ERR_INVALID_ARG, (w + ": max_per_image must be >= cols x rows").c_str());
-  if (sopt && (sopt->win_x < 1 || sopt->win_x > CLC_SUBPIX_MAX_WIN || sopt->win_y < 1 || sopt->win_y > CLC_SUBPIX_MAX_WIN || sopt->max_iter < 1 ||
-               sopt->max_iter > 100 || !(std::isfinite(sopt->eps) && sopt->eps >= 0.0) || sopt->reserved != 0))
-    return fail(CLC_ERR_INVALID_ARG, (w + ": the refinement options are not valid (clc_corner_subpix)").c_str());
-  return CLC_OK;
+  return refinement_checks(who, sopt, (uint64_t)n_images * (uint64_t)cols * (uint64_t)rows);
 }
 
-// Detection, ordering, gather and refinement on device arrays, nothing read back in between.  With sopt the call ends in
-// clc_corner_subpix_device's synchronise; without it nothing has been waited for yet.
-int find_on_device(const char* who, clc_handle* h, Staging& st, const clc_chess_options& o, double tol, const clc_subpix_options* sopt,
-                   const uint8_t* img_dev, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
-                   float* corners_dev, int32_t* found_dev, double* strength_dev) {
+// Detection, ordering, gather and with sopt the refinement on device arrays, all enqueued on the caller's st: nothing is read back in
+// between and nothing is waited for here.
+void find_on_device(Staging& st, const clc_chess_options& o, double tol, const clc_subpix_options* sopt, const uint8_t* img_dev, int32_t width,
+                    int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows, float* corners_dev, int32_t* found_dev,
+                    double* strength_dev) {
   const size_t stride = (size_t)o.max_per_image, per = (size_t)cols * (size_t)rows, M = n_images * per;
   float* xy_dev = st.scratch<float>(2 * n_images * stride);
   int32_t* count_dev = st.scratch<int32_t>(n_images);
   int32_t* status_dev = st.scratch<int32_t>(n_images);
   int32_t* index_dev = st.scratch<int32_t>(M);
   float* starts_dev = sopt ? st.scratch<float>(2 * M) : corners_dev;
-  int64_t* off_dev = sopt ? st.scratch<int64_t>(n_images + 1) : nullptr;
-  CLC_TRY(st.status(who));
-  enqueue_chess(st, o, img_dev, width, height, pitch, n_images, xy_dev, nullptr, count_dev, nullptr, status_dev);
+  int64_t* off_dev = sopt ? st.scratch<int64_t>(n_images + 1) : nullptr;  // the gather writes them: i per
+  if (st.ok()) enqueue_chess(st, o, img_dev, width, height, pitch, n_images, xy_dev, nullptr, count_dev, nullptr, status_dev);
   if (st.ok()) enqueue_order(st, xy_dev, count_dev, (int64_t)stride, n_images, cols, rows, tol, index_dev, status_dev, nullptr, nullptr);
   if (st.ok())
     enqueue_gather(st, xy_dev, index_dev, status_dev, (int64_t)stride, n_images, (int32_t)per, starts_dev, found_dev, off_dev,
                    sopt ? nullptr : strength_dev);
-  CLC_TRY(st.status(who));
-  if (!sopt) return CLC_OK;
   // (a NaN start comes back as it is: an image without a board keeps its NaN corners)
-  return clc_corner_subpix_device(h, sopt, img_dev, width, height, pitch, n_images, starts_dev, off_dev, corners_dev, nullptr, nullptr, strength_dev);
+  if (sopt && st.ok())
+    enqueue_subpix_refinement(st, *sopt, img_dev, width, height, pitch, n_images, starts_dev, off_dev, 0, M, corners_dev, nullptr, nullptr,
+                              strength_dev);
 }
 
 }  // namespace
-
-// K25's checks and enqueue for the unit that builds on its candidates (abi_tags.hip; declared in abi_staging.hpp).
-namespace clc_abi {
-
-int chess_detection_checks(const char* who, const clc_chess_options* in, int32_t width, int32_t height, int64_t pitch, size_t n_images,
-                           clc_chess_options* o) {
-  return chess_checks(who, true, in, width, height, pitch, n_images, o);
-}
-
-void enqueue_chess_detection(Staging& st, const clc_chess_options& o, const uint8_t* images, int32_t width, int32_t height, int64_t pitch,
-                             size_t n_images, float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status) {
-  enqueue_chess(st, o, images, width, height, pitch, n_images, cand_xy, cand_r5, count, count_raw, status);
-}
-
-}  // namespace clc_abi
 
 extern "C" {
 
@@ -238,18 +212,11 @@ int clc_find_chessboard(clc_handle* h, const clc_chess_options* copt, const clc_
   const char* who = "clc_find_chessboard";
   clc_chess_options o;
   double tol = 0.0;
-  const bool required = n_images == 0 || (images && corners && found);
-  CLC_TRY(chess_checks(who, required, copt, width, height, pitch, n_images, &o));
-  CLC_TRY(order_checks(who, required, oopt, cols, rows, n_images, &tol));
-  const size_t per = (size_t)cols * (size_t)rows;
-  if ((size_t)o.max_per_image < per) return fail(CLC_ERR_INVALID_ARG, "clc_find_chessboard: max_per_image must be >= cols x rows");
-  if (sopt && (sopt->win_x < 1 || sopt->win_x > CLC_SUBPIX_MAX_WIN || sopt->win_y < 1 || sopt->win_y > CLC_SUBPIX_MAX_WIN || sopt->max_iter < 1 ||
-               sopt->max_iter > 100 || !(std::isfinite(sopt->eps) && sopt->eps >= 0.0) || sopt->reserved != 0))
-    return fail(CLC_ERR_INVALID_ARG, "clc_find_chessboard: the refinement options are not valid (clc_corner_subpix)");
+  CLC_TRY(find_checks(who, n_images == 0 || (images && corners && found), copt, oopt, sopt, width, height, pitch, n_images, cols, rows, &o, &tol));
   if (!h) return fail(CLC_ERR_INVALID_ARG, "clc_find_chessboard: bad argument");
   if (n_images == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
-  const size_t stride = (size_t)o.max_per_image, M = n_images * per;
+  const size_t stride = (size_t)o.max_per_image, per = (size_t)cols * (size_t)rows, M = n_images * per;
   std::vector<float> cand(2 * n_images * stride), starts(2 * M, std::nanf(""));
   std::vector<int32_t> count(n_images), status(n_images), index(M);
   Staging st(h);  // the images stay on the device for both stages
@@ -257,8 +224,8 @@ int clc_find_chessboard(clc_handle* h, const clc_chess_options* copt, const clc_
   float* xy_dev = st.scratch<float>(cand.size());
   int32_t* count_dev = st.scratch<int32_t>(n_images);
   int32_t* status_dev = st.scratch<int32_t>(n_images);
+  if (st.ok()) enqueue_chess(st, o, img_dev, width, height, pitch, n_images, xy_dev, nullptr, count_dev, nullptr, status_dev);
   CLC_TRY(st.status(who));
-  CLC_TRY(clc_chess_corners_device(h, &o, img_dev, width, height, pitch, n_images, xy_dev, nullptr, count_dev, nullptr, status_dev));
   st.check(hipMemcpyAsync(cand.data(), xy_dev, cand.size() * sizeof(float), hipMemcpyDeviceToHost, st.stream()));
   st.check(hipMemcpyAsync(count.data(), count_dev, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, st.stream()));
   st.check(hipMemcpyAsync(status.data(), status_dev, n_images * sizeof(int32_t), hipMemcpyDeviceToHost, st.stream()));
@@ -286,9 +253,8 @@ int clc_find_chessboard(clc_handle* h, const clc_chess_options* copt, const clc_
   const int64_t* off_dev = st.in(offsets.data(), offsets.size());
   float* out_dev = st.out(corners, 2 * M);
   double* strength_dev = st.out_opt(strength, M);
-  CLC_TRY(st.status(who));
   // (a NaN start comes back as it is: an image without a board keeps its NaN corners)
-  CLC_TRY(clc_corner_subpix_device(h, sopt, img_dev, width, height, pitch, n_images, starts_dev, off_dev, out_dev, nullptr, nullptr, strength_dev));
+  enqueue_subpix_refinement(st, *sopt, img_dev, width, height, pitch, n_images, starts_dev, off_dev, 0, M, out_dev, nullptr, nullptr, strength_dev);
   return st.finish(who);
 }
 
@@ -319,7 +285,7 @@ int clc_find_chessboard_device(clc_handle* h, const clc_chess_options* copt, con
   if (n_images == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
   Staging st(h);
-  CLC_TRY(find_on_device(who, h, st, o, tol, sopt, images_dev, width, height, pitch, n_images, cols, rows, corners_dev, found_dev, strength_dev));
+  find_on_device(st, o, tol, sopt, images_dev, width, height, pitch, n_images, cols, rows, corners_dev, found_dev, strength_dev);
   return st.finish(who);
 }
 
@@ -339,8 +305,7 @@ int clc_find_chessboard_gpu(clc_handle* h, const clc_chess_options* copt, const 
   float* corners_dev = st.out(corners, 2 * M);
   int32_t* found_dev = st.out(found, n_images);
   double* strength_dev = st.out_opt(strength, M);
-  CLC_TRY(st.status(who));
-  CLC_TRY(find_on_device(who, h, st, o, tol, sopt, img_dev, width, height, pitch, n_images, cols, rows, corners_dev, found_dev, strength_dev));
+  find_on_device(st, o, tol, sopt, img_dev, width, height, pitch, n_images, cols, rows, corners_dev, found_dev, strength_dev);
   return st.finish(who);
 }
 

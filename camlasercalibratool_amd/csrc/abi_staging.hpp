@@ -1,5 +1,7 @@
 // abi_staging.hpp — the device memory of ONE call of the C-ABI: the uploads of its host arrays, its scratch, and the copies back
-// (abi_campose.hip, abi_joint.hip, abi_camcal.hip, abi_guidance.hip; the assemble and sweep forms of abi_frontend.hip).  Host code only: _build.csrc_sha16() does not cover this file.
+// (abi_camcal.hip, abi_guidance.hip, the assemble and sweep forms of abi_frontend.hip; abi_campose.hip through abi_lift.hpp; the units
+// of the joint problems through abi_jointcall.hpp; those of the image front end, abi_subpix.hip, abi_chess.hip and abi_tags.hip,
+// through abi_imagecall.hpp).  Host code only: _build.csrc_sha16() does not cover this file.
 //
 // A host-array form is: checks, one in / out / inout line per array, the pair's device-side function, finish().  The _device form is:
 // checks, the same function, finish().  That function takes device pointers and takes its scratch from the Staging it is given, so
@@ -9,6 +11,7 @@
 #include "clc_abi_internal.hpp"
 
 #include <chrono>
+#include <memory>
 #include <vector>
 
 namespace clc_abi {
@@ -40,6 +43,14 @@ class Staging {
     if (d && count > 0) err_ = hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, h_->stream);
     return d;
   }
+  // The same for a small array that the call builds inside a helper: this object keeps the vector until it dies, so the copy's source
+  // outlives finish()'s synchronise whatever scope built it.
+  template <class T>
+  const T* in_owned(std::vector<T> host) {
+    auto kept = std::make_shared<const std::vector<T>>(std::move(host));
+    owned_.push_back(kept);
+    return in(kept->data(), kept->size());
+  }
   // A block whose first `count` elements finish() copies to host.
   template <class T>
   T* out(T* host, size_t count) {
@@ -67,7 +78,7 @@ class Staging {
     if (err_ == hipSuccess) err_ = e;
   }
   void launched() { check(hipGetLastError()); }
-  // CLC_OK, or the held error reported (no synchronise): for a call whose device-side function ends in a synchronise of its own
+  // CLC_OK, or the held error reported (no synchronise): for a call that reads something back and waits ahead of its finish()
   int status(const char* who) const { return err_ == hipSuccess ? CLC_OK : fail(CLC_ERR_HIP, who, err_); }
   // The recorded copies back, then the call's ONE synchronise.  Nothing is enqueued or waited for once an error is held.
   int finish(const char* who) {
@@ -85,6 +96,7 @@ class Staging {
   hipError_t err_ = hipSuccess;
   std::vector<DevPool::Block> blocks_;
   std::vector<Back> back_;
+  std::vector<std::shared_ptr<const void>> owned_;
 };
 
 using Clock = std::chrono::steady_clock;
@@ -95,12 +107,5 @@ inline void stamp_solve_ms(clc_summary* summaries, size_t n, Clock::time_point t
   const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
   for (size_t k = 0; k < n; ++k) summaries[k].solve_ms = ms;
 }
-
-// K25's detection on device arrays (abi_chess.hip: its checks with the defaults filled in, and its enqueue: per chunk of 170 images the
-// counters to zero, one workgroup per tile, one wave per image), for the unit that builds on its candidates (abi_tags.hip).
-int chess_detection_checks(const char* who, const clc_chess_options* in, int32_t width, int32_t height, int64_t pitch, size_t n_images,
-                           clc_chess_options* o);
-void enqueue_chess_detection(Staging& st, const clc_chess_options& o, const uint8_t* images, int32_t width, int32_t height, int64_t pitch,
-                             size_t n_images, float* cand_xy, int32_t* cand_r5, int32_t* count, int32_t* count_raw, int32_t* status);
 
 }  // namespace clc_abi

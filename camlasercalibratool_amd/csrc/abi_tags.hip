@@ -3,7 +3,7 @@
 // A unit of its own, held to its own register figures (tests/test_tags_resources.py).
 // (one of the translation units of the C-ABI; see clc_abi_internal.hpp)
 #include "abi_drive.hpp"
-#include "abi_staging.hpp"
+#include "abi_imagecall.hpp"
 #include "clc_tags.hpp"
 
 using namespace clc_abi;
@@ -12,8 +12,8 @@ namespace {
 
 namespace tg = clc::tags;
 
-// Images per launch of the edge and decode kernels, as K25 chunks its own: the edge lists of one launch stay below 10 MiB.
-constexpr size_t kChunkImages = 170;
+// (images per launch of the edge and decode kernels: kChessChunkImages, as K25 chunks its own; the edge lists of one launch stay
+// below 10 MiB)
 constexpr size_t kPointLaunchImages = (size_t)1 << 20;
 
 struct Checked {
@@ -51,35 +51,31 @@ int tag_checks(const char* who, bool required, const clc_tag_family* f, const cl
     dflt.max_per_image = tg::MAX_CAND;
     copt = &dflt;
   }
-  CLC_TRY(chess_detection_checks(who, copt, width, height, pitch, n_images, &out->c));
-  if (sopt && (sopt->win_x < 1 || sopt->win_x > CLC_SUBPIX_MAX_WIN || sopt->win_y < 1 || sopt->win_y > CLC_SUBPIX_MAX_WIN || sopt->max_iter < 1 ||
-               sopt->max_iter > 100 || !(std::isfinite(sopt->eps) && sopt->eps >= 0.0) || sopt->reserved != 0))
-    return fail(CLC_ERR_INVALID_ARG, (w + ": the refinement options are not valid (clc_corner_subpix)").c_str());
+  CLC_TRY(chess_checks(who, true, copt, width, height, pitch, n_images, &out->c));
+  CLC_TRY(refinement_checks(who, sopt, (uint64_t)n_images * 4 * (uint64_t)cols * (uint64_t)rows));
   if (!required) return fail(CLC_ERR_INVALID_ARG, (w + ": bad argument").c_str());
   return CLC_OK;
 }
 
-// Detection, edges, quads and decode, and with sopt the refinement, on device arrays, nothing read back in between.  With sopt the
-// call ends in clc_corner_subpix_device's synchronise; without it nothing has been waited for yet.
-int tags_on_device(const char* who, clc_handle* h, Staging& st, const Checked& o, const clc_tag_family& f, const clc_subpix_options* sopt,
-                   const uint8_t* img_dev, int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows,
-                   float* corners_dev, int32_t* hamming_dev, int32_t* count_dev, int32_t* status_dev, int32_t* n_quads_dev,
-                   int32_t* n_foreign_dev, int32_t* n_dropped_dev, double* strength_dev) {
-  const size_t stride = (size_t)o.c.max_per_image, T = (size_t)cols * (size_t)rows, chunk = std::min(n_images, kChunkImages);
+// Detection, edges, quads and decode, and with sopt the refinement, on device arrays, all enqueued on the caller's st: nothing is read
+// back in between and nothing is waited for here.
+void tags_on_device(Staging& st, const Checked& o, const clc_tag_family& f, const clc_subpix_options* sopt, const uint8_t* img_dev,
+                    int32_t width, int32_t height, int64_t pitch, size_t n_images, int32_t cols, int32_t rows, float* corners_dev,
+                    int32_t* hamming_dev, int32_t* count_dev, int32_t* status_dev, int32_t* n_quads_dev, int32_t* n_foreign_dev,
+                    int32_t* n_dropped_dev, double* strength_dev) {
+  const size_t stride = (size_t)o.c.max_per_image, T = (size_t)cols * (size_t)rows, chunk = std::min(n_images, kChessChunkImages);
   const uint64_t* codes_dev = st.in(f.codes, (size_t)f.n_codes);
   float* xy_dev = st.scratch<float>(2 * n_images * stride);
   int32_t* cnt_dev = st.scratch<int32_t>(n_images);
   int32_t* cst_dev = st.scratch<int32_t>(n_images);
   int32_t* edges_dev = st.scratch<int32_t>(chunk * stride * (size_t)tg::EDGE_INTS);
-  std::vector<int64_t> offsets;
-  int64_t* off_dev = nullptr;
-  if (sopt) {
-    offsets.resize(n_images + 1);
+  const int64_t* off_dev = nullptr;
+  if (sopt) {  // every image has 4 T corners
+    std::vector<int64_t> offsets(n_images + 1);
     for (size_t i = 0; i <= n_images; ++i) offsets[i] = (int64_t)(i * 4 * T);
-    off_dev = st.in(offsets.data(), offsets.size());
+    off_dev = st.in_owned(std::move(offsets));
   }
-  CLC_TRY(st.status(who));
-  enqueue_chess_detection(st, o.c, img_dev, width, height, pitch, n_images, xy_dev, nullptr, cnt_dev, nullptr, cst_dev);
+  if (st.ok()) enqueue_chess(st, o.c, img_dev, width, height, pitch, n_images, xy_dev, nullptr, cnt_dev, nullptr, cst_dev);
   tg::TagArgs a{};
   a.width = width; a.height = height; a.stride = (int32_t)stride; a.d = f.side; a.b = f.border; a.n_codes = f.n_codes;
   a.max_hamming = f.max_hamming; a.min_side = o.t.min_side_px; a.max_side = o.t.max_side_px ? o.t.max_side_px : std::min(width, height);
@@ -100,10 +96,10 @@ int tags_on_device(const char* who, clc_handle* h, Staging& st, const Checked& o
     hipLaunchKernelGGL(tg::tag_decode_kernel, dim3((unsigned)n), dim3(tg::LANES), 0, st.stream(), a);
     st.launched();
   }
-  CLC_TRY(st.status(who));
-  if (!sopt) return CLC_OK;
   // (a NaN start comes back as it is: a tag not seen keeps its NaN corners)
-  return clc_corner_subpix_device(h, sopt, img_dev, width, height, pitch, n_images, corners_dev, off_dev, corners_dev, nullptr, nullptr, strength_dev);
+  if (sopt && st.ok())
+    enqueue_subpix_refinement(st, *sopt, img_dev, width, height, pitch, n_images, corners_dev, off_dev, 0, n_images * 4 * T, corners_dev, nullptr,
+                              nullptr, strength_dev);
 }
 
 }  // namespace
@@ -142,9 +138,8 @@ int clc_tag_grid(clc_handle* h, const clc_tag_family* family, const clc_tag_opti
   int32_t* foreign_dev = st.out_opt(n_foreign, n_images);
   int32_t* dropped_dev = st.out_opt(n_edges_dropped, n_images);
   double* strength_dev = st.out_opt(strength, n_images * T * 4);
-  CLC_TRY(st.status(who));
-  CLC_TRY(tags_on_device(who, h, st, o, *family, sopt, img_dev, width, height, pitch, n_images, cols, rows, corners_dev, hamming_dev, count_dev,
-                         status_dev, quads_dev, foreign_dev, dropped_dev, strength_dev));
+  tags_on_device(st, o, *family, sopt, img_dev, width, height, pitch, n_images, cols, rows, corners_dev, hamming_dev, count_dev, status_dev,
+                 quads_dev, foreign_dev, dropped_dev, strength_dev);
   return st.finish(who);
 }
 
@@ -161,8 +156,8 @@ int clc_tag_grid_device(clc_handle* h, const clc_tag_family* family, const clc_t
   if (n_images == 0) return CLC_OK;
   CLC_HIP(hipSetDevice(h->device));
   Staging st(h);
-  CLC_TRY(tags_on_device(who, h, st, o, *family, sopt, images_dev, width, height, pitch, n_images, cols, rows, corners_dev, hamming_dev, count_dev,
-                         status_dev, n_quads_dev, n_foreign_dev, n_edges_dropped_dev, strength_dev));
+  tags_on_device(st, o, *family, sopt, images_dev, width, height, pitch, n_images, cols, rows, corners_dev, hamming_dev, count_dev, status_dev,
+                 n_quads_dev, n_foreign_dev, n_edges_dropped_dev, strength_dev);
   return st.finish(who);
 }
 

@@ -99,6 +99,16 @@ class TagFamily:
         return cls(kept, side, border, max_hamming)
 
 
+def _images_arg(who: str, images: np.ndarray, width: Optional[int]):
+    """The images of a host-array call of the image front end -> (the uint8 array [n, height, pitch], its four C arguments: the pointer,
+    width (the pitch unless given), height, pitch)."""
+    img = np.ascontiguousarray(images, dtype=np.uint8)
+    if img.ndim != 3:
+        raise ValueError("%s: images must be [n, height, pitch]" % who)
+    return img, (img.ctypes.data_as(C.c_void_p), C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]),
+                 C.c_int64(img.shape[2]))
+
+
 def chessboard_order(cand_xy: np.ndarray, count: np.ndarray, cols: int, rows: int, status: Optional[np.ndarray] = None,
                      options: Optional[ChessOrderOptions] = None) -> dict:
     """clc_chessboard_order (K25; host code: no Solver, no device): cand_xy [n, stride, 2] and count [n] as Solver.chess_corners returns
@@ -967,9 +977,7 @@ class Solver:
         [M, 2] float32 start pixels grouped per image by the CSR offsets [n + 1] (absolute rows of corners_px).
         -> dict(corners [M, 2] float32, status [M] int32 (CLC_SUBPIX_*), iterations [M] int32, strength [M]); rows outside
         [offsets[0], offsets[n]) come back as they went in, with status -99, iterations 0 and strength NaN."""
-        img = np.ascontiguousarray(images, dtype=np.uint8)
-        if img.ndim != 3:
-            raise ValueError("corner_subpix: images must be [n, height, pitch]")
+        img, img_args = _images_arg("corner_subpix", images, width)
         cp = np.ascontiguousarray(corners_px, dtype=np.float32).reshape(-1, 2)
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(off) - 1
@@ -979,9 +987,7 @@ class Solver:
         st = np.full(len(cp), -99, dtype=np.int32); it = np.zeros(len(cp), dtype=np.int32); lam = np.full(len(cp), np.nan)
         V = lambda a: a.ctypes.data_as(C.c_void_p)
         o = C.byref(options) if options is not None else None
-        check(self._L.clc_corner_subpix(self._h, o, V(img), C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]),
-                                        C.c_int64(img.shape[2]), C.c_size_t(n), V(cp), V(off), V(out), V(st), V(it), V(lam)),
-              "clc_corner_subpix")
+        check(self._L.clc_corner_subpix(self._h, o, *img_args, C.c_size_t(n), V(cp), V(off), V(out), V(st), V(it), V(lam)), "clc_corner_subpix")
         return dict(corners=out, status=st, iterations=it, strength=lam)
 
     def corner_subpix_device(self, images_ptr: int, width: int, height: int, pitch: int, n_images: int, corners_ptr: int, offsets_ptr: int,
@@ -999,16 +1005,13 @@ class Solver:
         """clc_chess_corners (K25): images uint8 [n, H, W], or [n, H, pitch] with width= given -> dict(xy [n, stride, 2] float32 integer
         pixels ordered by (-R5, y, x), NaN in the unused slots; r5 [n, stride] int32; count [n]; count_raw [n]; status [n]: 1, or -2
         where the image has more than 4096 raw candidates), stride = options.max_per_image."""
-        img = np.ascontiguousarray(images, dtype=np.uint8)
-        if img.ndim != 3:
-            raise ValueError("chess_corners: images must be [n, height, pitch]")
+        img, img_args = _images_arg("chess_corners", images, width)
         o = options if options is not None else _capi.default_chess_options()
         n, stride = img.shape[0], max(int(o.max_per_image), 1)
         xy = np.full((n, stride, 2), -7.0, np.float32); r5 = np.full((n, stride), -7, np.int32)
         cnt = np.full(n, -7, np.int32); raw = np.full(n, -7, np.int32); st = np.full(n, -99, np.int32)
         V = lambda a: a.ctypes.data_as(C.c_void_p)
-        check(self._L.clc_chess_corners(self._h, C.byref(o), V(img), C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]),
-                                        C.c_int64(img.shape[2]), C.c_size_t(n), V(xy), V(r5), V(cnt), V(raw), V(st)), "clc_chess_corners")
+        check(self._L.clc_chess_corners(self._h, C.byref(o), *img_args, C.c_size_t(n), V(xy), V(r5), V(cnt), V(raw), V(st)), "clc_chess_corners")
         return dict(xy=xy, r5=r5, count=cnt, count_raw=raw, status=st)
 
     def chess_corners_device(self, images_ptr: int, width: int, height: int, pitch: int, n_images: int, xy_ptr: int, count_ptr: int,
@@ -1029,16 +1032,13 @@ class Solver:
         and nothing read back between the stages; the same results."""
         if ordering not in ("host", "device"):
             raise ValueError("find_chessboard: ordering must be 'host' or 'device'")
-        img = np.ascontiguousarray(images, dtype=np.uint8)
-        if img.ndim != 3:
-            raise ValueError("find_chessboard: images must be [n, height, pitch]")
+        img, img_args = _images_arg("find_chessboard", images, width)
         n, per = img.shape[0], max(int(cols) * int(rows), 1)
         corners = np.full((n, per, 2), np.nan, np.float32); found = np.zeros(n, np.int32); lam = np.full((n, per), np.nan)
         V = lambda a: a.ctypes.data_as(C.c_void_p)
         ref = lambda o: C.byref(o) if o is not None else None
         name = "clc_find_chessboard" if ordering == "host" else "clc_find_chessboard_gpu"
-        check(getattr(self._L, name)(self._h, ref(chess_options), ref(order_options), ref(subpix_options), V(img),
-                                     C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]), C.c_int64(img.shape[2]),
+        check(getattr(self._L, name)(self._h, ref(chess_options), ref(order_options), ref(subpix_options), *img_args,
                                      C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), V(corners), V(found), V(lam)), name)
         return dict(corners=corners, found=found.astype(bool), strength=lam)
 
@@ -1073,9 +1073,7 @@ class Solver:
         id = row cols + col -> dict(corners [n, cols rows, 4, 2] float32, NaN for a tag not seen, integer pixels or with subpix_options
         refined (K24); hamming [n, cols rows], -1 not seen; count [n]; status [n]: 1, or -2 where the detection overflowed; n_quads,
         n_foreign, n_edges_dropped [n]; strength [n, cols rows, 4])."""
-        img = np.ascontiguousarray(images, dtype=np.uint8)
-        if img.ndim != 3:
-            raise ValueError("tag_grid: images must be [n, height, pitch]")
+        img, img_args = _images_arg("tag_grid", images, width)
         n, T = img.shape[0], max(int(cols) * int(rows), 1)
         r = dict(corners=np.full((n, T, 4, 2), -7.0, np.float32), hamming=np.full((n, T), -7, np.int32), count=np.full(n, -7, np.int32),
                  status=np.full(n, -99, np.int32), n_quads=np.full(n, -7, np.int32), n_foreign=np.full(n, -7, np.int32),
@@ -1083,8 +1081,7 @@ class Solver:
         V = lambda a: a.ctypes.data_as(C.c_void_p)
         ref = lambda o: C.byref(o) if o is not None else None
         fam = family.c_struct()
-        check(self._L.clc_tag_grid(self._h, C.byref(fam), ref(tag_options), ref(chess_options), ref(subpix_options), V(img),
-                                   C.c_int32(img.shape[2] if width is None else width), C.c_int32(img.shape[1]), C.c_int64(img.shape[2]),
+        check(self._L.clc_tag_grid(self._h, C.byref(fam), ref(tag_options), ref(chess_options), ref(subpix_options), *img_args,
                                    C.c_size_t(n), C.c_int32(cols), C.c_int32(rows), V(r["corners"]), V(r["hamming"]), V(r["count"]), V(r["status"]),
                                    V(r["n_quads"]), V(r["n_foreign"]), V(r["n_edges_dropped"]), V(r["strength"])), "clc_tag_grid")
         return r

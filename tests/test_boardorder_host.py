@@ -185,6 +185,9 @@ def test_find_refusals(name):
     assert "width and height" in msg
     code, msg = call(small, bad_order, bad_subpix, img, 16, 5, 4, corners, found)
     assert "tol" in msg
+    # every field of the refinement options, the order of two refusals, the corner count: the rows all composite forms share
+    import imagecall_refusals
+    imagecall_refusals.check_composite_refusals(L, name)
 
 
 def test_sanitized_standalone_program(tmp_path):

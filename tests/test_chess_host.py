@@ -312,6 +312,9 @@ def test_refusals_of_arguments():
                        ((None, None, None, img, 16, 5, 4, corners, None), "bad argument"), ((None, None, None, img, 16, 5, 4, corners, found), "bad argument")]:
         code, msg = call(*args)
         assert code == -1 and msg.startswith("clc_find_chessboard:") and text in msg, (code, msg, text)
+    # every field of the refinement options, the order of two refusals, the corner count: the rows all composite forms share
+    import imagecall_refusals
+    imagecall_refusals.check_composite_refusals(L, "clc_find_chessboard")
 
 
 @pytest.mark.parametrize("program,needle", [("chessorder_main.cpp", "boards found 30"), ("chess_sanitize_main.cpp", "candidates ")])

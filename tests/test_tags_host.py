@@ -256,6 +256,9 @@ def test_refusals_of_arguments(name):
         code, msg = tag_call(L, name, **kw)
         assert code == -1 and msg.startswith(name + ":") and text in msg, (kw, code, msg, text)
     assert tag_call(L, name, fam=fam(), n=0, images=False, arrays=False)[0] == -1  # no image, but no handle either
+    # every field of the refinement options, the order of two refusals, the corner count: the rows all composite forms share
+    import imagecall_refusals
+    imagecall_refusals.check_composite_refusals(L, name)
     V = C.c_void_p
     for args, text in [((None, None, 1, 0, 2, 0.05, 0.3, None, None, V(8)), "cols and rows"), ((None, None, 1, 2, 2, 0.0, 0.3, None, None, V(8)), "tag_size"),
                        ((None, None, 1, 2, 2, 0.05, -0.1, None, None, V(8)), "tag_spacing"), ((None, None, 1, 2, 2, float("nan"), 0.3, None, None, V(8)), "tag_size"),
